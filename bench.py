@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec, boat race 5x5, 65 536 environments per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds
+what takes runs of its own: the untimed per-launch pass and the measured write ceiling
+(`roofline.per_launch_ms`, `measured_write_ceiling_gbs`), the CPU baselines, the other
+games, play() mode and the deferred rows.  `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy (float32, a fixed seeded sample of the environments).
 
 With N > 1 (and no WORLD_SIZE in the environment) this process starts N child
 ranks itself - `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -119,6 +125,13 @@ def parse_args(argv=None):
                  help='environments per GPU (default: the BASELINE config)')
   p.add_argument('--frames', type=int, default=100,
                  help='Engine.play() frames per launch (episode length)')
+  p.add_argument('--full', action='store_true',
+                 help='also the measurements beside the headline: the per-launch pass and the '
+                      'write ceiling, the CPU baselines, the other games, play() mode and the '
+                      'deferred rows (--no-cpu-baseline / --no-extras leave parts of it out)')
+  p.add_argument('--dump-outputs', default=None, metavar='DIR',
+                 help='after the timed steps, write what the last one computed as DIR/<name>.npy '
+                      '(float32; at most 64 MB, a fixed seeded sample of the environments)')
   p.add_argument('--no-cpu-baseline', action='store_true')
   p.add_argument('--no-group', action='store_true',
                  help='N = 1 only, for A/B measurements: no process group (the episode-return '
@@ -285,6 +298,64 @@ def short_row(value, ms_per_step, roof, cpu):
       'n/a' if not cpu else '{:.3g}/{}c'.format(cpu['value'], cpu['cores']))
 
 
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
+DUMP_SEED = 20240601           # which environments (and, past the limit, frames) are written
+
+
+def dumpable_streams(out, T, B):
+  """The output streams of a rollout dict a caller reads per frame and environment, by their
+  shapes, checked on the host: [T, B, ...] observations / boards, [..., T, B] per-frame streams
+  (reward, discount, done, perf, the one-cell and wide tiers' trace).  Anything else - the shape
+  tier's flat scratch buffer, say - is not an output of that kind and is left out."""
+  import torch
+  streams = {}
+  for name, v in out.items():
+    if not isinstance(v, torch.Tensor):
+      continue
+    if name in ('obs', 'board'):
+      if v.dim() >= 2 and tuple(v.shape[:2]) == (T, B):
+        streams[name] = (v, 1, 0)              # (tensor, environment axis, frame axis)
+    elif v.dim() >= 2 and tuple(v.shape[-2:]) == (T, B):
+      streams[name] = (v, v.dim() - 1, v.dim() - 2)
+  return streams
+
+
+def sample_outputs(out, ret, T, B, limit=DUMP_LIMIT, seed=DUMP_SEED):
+  """What one T-frame rollout of B environments returned, on the host as float32 arrays: every
+  stream `dumpable_streams` keeps, at a fixed seeded sample of environments (all of them when
+  they fit; past the limit for one environment, a sample of frames too), the episode return of
+  every environment (`ret`, [B]), and the sample's indices.  Deterministic for the same T and B."""
+  import numpy as np
+  import torch
+  streams = dumpable_streams(out, T, B)
+  arrays = {}
+  if ret is not None and tuple(ret.shape) == (B,):
+    arrays['episode_return'] = ret.detach().float().cpu().numpy()
+  per_frame_env = sum(4 * v.numel() // (T * B) for v, _, _ in streams.values())
+  budget = limit - sum(a.nbytes for a in arrays.values()) - 8 * (B + T)
+  rng = np.random.RandomState(seed)
+  n_env = max(1, min(B, budget // max(1, per_frame_env * T)))
+  envs = np.arange(B) if n_env == B else np.sort(rng.choice(B, n_env, replace=False))
+  n_frames = T if per_frame_env * T <= budget else max(1, budget // per_frame_env)
+  frames = np.arange(T) if n_frames == T else np.sort(rng.choice(T, n_frames, replace=False))
+  assert envs.max() < B and frames.max() < T      # (every index in range before any device sees it)
+  for name, (v, e_axis, t_axis) in streams.items():
+    e = torch.from_numpy(envs).to(v.device)
+    t = torch.from_numpy(frames).to(v.device)
+    arrays[name] = v.index_select(e_axis, e).index_select(t_axis, t).float().cpu().numpy()
+  arrays['sample_env_index'] = envs.astype(np.float64)
+  arrays['sample_frame_index'] = frames.astype(np.float64)
+  assert sum(a.nbytes for a in arrays.values()) <= limit, {k: a.nbytes for k, a in arrays.items()}
+  return arrays
+
+
+def write_outputs(directory, arrays):
+  import numpy as np
+  os.makedirs(directory, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(directory, name + '.npy'), a)
+
+
 # ------------------------------------------------------------ CPU baselines
 
 def cpu_baseline(game_name, frames, seconds, batch=65536):
@@ -385,14 +456,17 @@ def kernel_names(fused, split, B=None, T=None):
 
 
 def measure_rollout(game_name, B, T, steps, warmup, device, rank, dist, gather_every,
-                    standin=None, deferred=False, with_log=False, gather_at=2.0 / 3.0):
+                    standin=None, deferred=False, with_log=False, gather_at=2.0 / 3.0,
+                    full=True, dump=False):
   """Warm up, then time exactly `steps` rollout launches.  Returns a dict.
 
   Wall clock: perf_counter around the timed region, bracketed by synchronize +
   barrier on both sides.  Kernel time: ONE pair of HIP events on the launch stream
   around the same `steps` launches (mean per launch, inter-launch gaps included), so
-  the timed region carries no per-launch event packets.  A second, untimed pass of
-  the same launches with an event pair per launch gives the median / min / max.
+  the timed region carries no per-launch event packets.  With `full`, a second, untimed
+  pass of the same launches with an event pair per launch gives the median / min / max,
+  and the write ceiling is measured over the observation buffer.  With `dump`, what the
+  last timed launch returned is copied to the host (`sample_outputs`) before anything else.
   """
   import numpy as np
   import torch
@@ -573,8 +647,12 @@ def measure_rollout(game_name, B, T, steps, warmup, device, rank, dist, gather_e
                 gather_every=gather_every if log is not None else None,
                 mean_return=float(out['reward'].sum(0).mean())
                 if out['reward'] is not None else None)
+  # (off the clock and after the window's own bookkeeping, so that the line reads the same with
+  # and without it; before the per-launch pass, which reuses the buffers)
+  result['dumped'] = sample_outputs(out, fused.ret, T, B) if dump else None
   if on_gpu:
     result['kernel_ms'] = ev0.elapsed_time(ev1) / steps
+  if on_gpu and full:
     # untimed second pass: one event pair per launch
     starts = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
     stops = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
@@ -761,8 +839,11 @@ def run_rank(args):
   T = args.frames
   m = measure_rollout(args.game, B, T, args.steps, args.warmup, device, rank, dist,
                       args.gather_every, standin, args.deferred,
-                      with_log=True, gather_at=args.gather_at)
+                      with_log=True, gather_at=args.gather_at, full=args.full,
+                      dump=bool(args.dump_outputs) and rank == 0)
   fused, elapsed = m['fused'], m['elapsed']
+  if m['dumped'] is not None:
+    write_outputs(args.dump_outputs, m['dumped'])
 
   gathered_ok = None
   if m['log'] is not None:
@@ -885,9 +966,11 @@ def run_rank(args):
       line['config']['library_settings'] = _hip.config_string()
     if standin is None:
       line['roofline'] = roofline(args.game, B, T, fused, m['kernel_ms'],
-                                  m['per_launch_ms'], m.get('ceiling'))
-      line['config']['launch_ms_median'] = m['per_launch_ms']['median']
-    solo = world == 1 and standin is None and not args.force_dist
+                                  m.get('per_launch_ms'), m.get('ceiling'))
+      if args.full:
+        line['config']['launch_ms_median'] = m['per_launch_ms']['median']
+    # (a plain run stops here: what follows takes runs of its own and needs --full)
+    solo = world == 1 and standin is None and not args.force_dist and args.full
     if affinity_before is not None:
       os.sched_setaffinity(0, affinity_before)      # the CPU baselines below use every core
     if solo and not args.no_cpu_baseline and args.game not in NO_C_ORACLE:

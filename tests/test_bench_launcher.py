@@ -144,6 +144,59 @@ def test_more_gpus_than_the_node_has_fails_fast_with_a_clear_message():
   assert not r.stdout.strip()
 
 
+def _tier_buffers(tier, T, B, L=3, H=4, W=5, pitch=None):
+  """Output dicts shaped as each tier's rollout_buffers() makes them (campx_amd/fused.py, wide.py,
+  shapes.py), filled with distinct values."""
+  import torch
+  pitch = pitch or B
+  g = torch.Generator().manual_seed(1)
+
+  def rows(dtype, *lead):
+    return torch.randint(0, 100, lead + (T, pitch), generator=g).to(dtype)[..., :B]
+  out = dict(obs=torch.randint(0, 2, (T, B, L, H, W), generator=g).to(torch.int8), board=None,
+             reward=rows(torch.float32), discount=rows(torch.float32), done=rows(torch.uint8))
+  if tier == 'one_cell':
+    out.update(perf=rows(torch.int8), trace=rows(torch.uint8, 1))
+  elif tier == 'wide':
+    out.update(perf=None, trace=rows(torch.int16, 2))
+  else:                                  # shape tier: the frame-major path's flat int64 scratch
+    out.update(perf=None, trace=torch.randint(0, 1 << 40, (777,), generator=g))
+  return out
+
+
+def test_dumped_outputs_of_every_tier_are_its_per_frame_streams():
+  """`--dump-outputs`: the [T, B, ...] / [..., T, B] streams of every tier at a seeded sample of
+  environments, under the size limit; a buffer of any other shape (the shape tier's scratch) is
+  left out, and no index is ever out of range - also where fewer environments fit than there are
+  frames, and where not even one environment's frames fit."""
+  import numpy as np
+  import torch
+  sys.path.insert(0, REPO)
+  import bench
+  T, B = 40, 64
+  for tier, names in (('one_cell', {'obs', 'reward', 'discount', 'done', 'perf', 'trace'}),
+                      ('wide', {'obs', 'reward', 'discount', 'done', 'trace'}),
+                      ('shape', {'obs', 'reward', 'discount', 'done'})):
+    out = _tier_buffers(tier, T, B, pitch=B + 16 if tier == 'one_cell' else None)
+    ret = torch.arange(B, dtype=torch.float32)
+    for limit, all_frames in ((1 << 30, True), (200 << 10, True), (8 << 10, False)):
+      a = bench.sample_outputs(out, ret, T, B, limit=limit)
+      assert set(a) == names | {'episode_return', 'sample_env_index', 'sample_frame_index'}, tier
+      assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+      assert sum(v.nbytes for v in a.values()) <= limit
+      envs, frames = a['sample_env_index'].astype(int), a['sample_frame_index'].astype(int)
+      assert (len(frames) == T) is all_frames and (len(envs) == B) is (limit == 1 << 30)
+      assert len(envs) < T or limit == 1 << 30       # (the case of fewer environments than frames)
+      assert np.array_equal(a['episode_return'], ret.numpy())
+      pick = np.ix_(frames, envs)
+      assert np.array_equal(a['obs'], out['obs'].numpy()[pick].astype(np.float32))
+      for k in names - {'obs'}:
+        v = out[k].numpy()
+        assert np.array_equal(a[k], v[(Ellipsis,) + pick].astype(np.float32)), (tier, k)
+      again = bench.sample_outputs(out, ret, T, B, limit=limit)
+      assert all(np.array_equal(again[k], a[k]) for k in a)
+
+
 # ------------------------------------------------------------------------------- GPU
 
 import pytest  # noqa: E402
@@ -234,3 +287,37 @@ def test_one_rccl_rank_through_the_real_launcher():
   assert g[0]['done_when_launches_ended'] is (cfg['gather_exposed_us_max'] == 0.0)
   # the closing barrier is off the clock: the step time is the kernels' plus the host's share
   assert line["ms_per_step"] < 1.05 * line["roofline"]["kernel_ms"], (w, g)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('game', ['boat_race', 'maze16', 'hello_world', 'coin_field'])
+def test_dump_outputs_of_a_plain_run(game, tmp_path):
+  """`bench.py --dump-outputs` on each tier at its bench batch: what the last timed step
+  returned, the same in two runs (a frame without a reward reads NaN on the shape tier, as the
+  reference's None), every stream at the sampled environments and frames."""
+  import numpy as np
+  args = ['--gpus', '1', '--game', game, '--steps', '2', '--warmup', '1', '--no-group']
+  dumps = []
+  for k in range(2):
+    r = _run(args + ['--dump-outputs', str(tmp_path / str(k))])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+    assert line['steps'] == 2 and line['ms_per_step'] > 0
+    d = tmp_path / str(k)
+    dumps.append({f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))})
+  a, b = dumps
+  assert set(a) == set(b) and all(np.array_equal(a[k], b[k], equal_nan=True) for k in a)
+  assert {'obs', 'discount', 'done', 'episode_return', 'sample_env_index'} <= set(a)
+  assert sum(v.nbytes for v in a.values()) <= 64 << 20
+  n_frames, n_envs = len(a['sample_frame_index']), len(a['sample_env_index'])
+  assert a['obs'].shape[:2] == (n_frames, n_envs) and a['episode_return'].shape == (_bench_batch(game),)
+  for k in ('reward', 'discount', 'done', 'perf', 'trace'):
+    if k in a:
+      assert a[k].shape[-2:] == (n_frames, n_envs), k
+  assert not np.isnan(a['episode_return']).any()
+
+
+def _bench_batch(game):
+  sys.path.insert(0, REPO)
+  import bench
+  return bench.WORKLOADS[game][1]

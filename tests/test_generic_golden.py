@@ -150,18 +150,18 @@ def test_boat_race_transition_table(golden):
 
 @pytest.mark.skipif(not os.path.isdir('/root/reference/examples'),
                     reason='reference tree not present (GPU box)')
-def test_unmodified_reference_boat_race_runs_on_this_engine(golden):
+def test_unmodified_reference_boat_race_runs_on_this_engine(golden, tmp_path):
   """`examples/boat_race.py` imported AS IS (from /root/reference) against this
   repo's `campx` alias package: same frames as the reference engine produced."""
   gold = golden('boat_race')
-  np.save('/tmp/_campx_actions.npy', gold['actions'][:, :3])
+  np.save(tmp_path / 'actions.npy', gold['actions'][:, :3])
   code = r'''
 import sys, numpy as np, torch
 sys.path.insert(0, %r)                      # this repo: `campx` -> campx_amd
 sys.path.append('/root/reference/examples')  # boat_race.py only
 import campx, boat_race
 assert campx.__file__.startswith(%r)
-acts = np.load('/tmp/_campx_actions.npy')
+acts = np.load(%r)
 boards, rewards = [], []
 for n in range(acts.shape[1]):
     game, obs, r, d = boat_race.make_game()
@@ -170,12 +170,13 @@ for n in range(acts.shape[1]):
         a = torch.zeros(5); a[int(acts[t, n])] = 1
         obs, r, d = game.play(a)
         boards.append(obs.board.numpy().copy()); rewards.append(float(r))
-np.save('/tmp/_campx_boards.npy', np.array(boards)); np.save('/tmp/_campx_rewards.npy', np.array(rewards))
-''' % (REPO, REPO)
+np.save(%r, np.array(boards)); np.save(%r, np.array(rewards))
+''' % (REPO, REPO, str(tmp_path / 'actions.npy'),
+       str(tmp_path / 'boards.npy'), str(tmp_path / 'rewards.npy'))
   subprocess.run([sys.executable, '-c', code], check=True)
   T = gold['actions'].shape[0]
-  boards = np.load('/tmp/_campx_boards.npy').reshape(3, T, 5, 5)
-  rewards = np.load('/tmp/_campx_rewards.npy').reshape(3, T)
+  boards = np.load(tmp_path / 'boards.npy').reshape(3, T, 5, 5)
+  rewards = np.load(tmp_path / 'rewards.npy').reshape(3, T)
   for n in range(3):
     assert np.array_equal(boards[n], gold['board'][1:, n])
     assert np.array_equal(rewards[n], gold['reward'][:, n])

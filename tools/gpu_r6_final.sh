@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 timeout 2700 python -m pytest tests -m gpu -q --maxfail=10 > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -8 $O/pytest.log | cut -c1-300
 for i in $(seq 1 $n); do
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_$i.log 2>$O/bench_$i.err
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_$i.log 2>$O/bench_$i.err
   python3 - <<PY
 import json
 d = json.loads(open('$O/bench_$i.log').read().strip().splitlines()[-1])

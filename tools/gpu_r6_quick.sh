@@ -9,7 +9,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 timeout 300 python __graft_entry__.py smoke > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 timeout 2400 python -m pytest $* -m gpu -q --maxfail=10 > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -30 $O/pytest.log | cut -c1-400
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.log 2>$O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.log 2>$O/bench.err; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.loads(open('$O/bench.log').read().strip().splitlines()[-1])

@@ -20,7 +20,7 @@ print(json.dumps({k: v for k, v in d['roofline'].items() if 'note' not in k}))
 PY
 grep BENCH_DETAILS $O/bench.err | cut -c1-600
 for i in 1 2 3; do
-  timeout 300 python bench.py --game hello_world --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-group 2>/dev/null | python3 -c "
+  timeout 300 python bench.py --full --game hello_world --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-group 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('HELLO ms_per_step %.4f kernel_ms %.4f median %.4f min %.4f frac %.4f ceiling %s' % (d['ms_per_step'], r['kernel_ms'], r['per_launch_ms']['median'], r['per_launch_ms']['min'], r['frac'], r['measured_write_ceiling_gbs']))"

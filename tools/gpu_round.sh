@@ -13,7 +13,7 @@ timeout 900 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/
 timeout 300 python bench.py --gpus 1 --force-dist --no-cpu-baseline --no-extras > $O/bench_dist.log 2>&1; echo "bench_dist rc=$?"; tail -1 $O/bench_dist.log
 for v in "$@"; do
   for g in boat_race sokoban wall_world; do
-    CAMPX_LIB=build/variants/$v/libcampx_hip.so timeout 300 python bench.py --game $g --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/var_${v}_$g.log 2>&1
+    CAMPX_LIB=build/variants/$v/libcampx_hip.so timeout 300 python bench.py --full --game $g --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/var_${v}_$g.log 2>&1
     echo "variant $v $g rc=$? $(tail -1 $O/var_${v}_$g.log | python3 -c 'import sys,json
 try:
   d=json.loads(sys.stdin.read()); r=d["roofline"]; print("ms_per_step=%.4f kernel_ms=%.4f median=%.4f frac=%.3f" % (d["ms_per_step"], r["kernel_ms"], r["per_launch_ms"]["median"], r["frac"]))

@@ -10,8 +10,10 @@ tag=$1; shift
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
+repo=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
-bench="python3 $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-extras $*"
+# (--full: tools/make_traffic.py counts the untimed per-launch pass among the profiled launches)
+bench="python3 $repo/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-extras $*"
 timeout 900 rocprofv3 --kernel-trace --stats -d $out -o trace -- $bench > $out/trace.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD -d $out -o pmc_insts -- $bench > $out/pmc_insts.log 2>&1
 timeout 900 rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE -d $out -o pmc_wait -- $bench > $out/pmc_wait.log 2>&1
