@@ -31,6 +31,8 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_spec_size', 'campx_wide_spec_validate', 'campx_wide_tables_bytes',
            'campx_wide_tables_build', 'campx_wide_reset_launch', 'campx_wide_rollout_launch',
            'campx_wide_rules_size', 'campx_wide_enumerate_launch',
+           'campx_wide_update_launch', 'campx_render_gather_launch',
+           'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_check_actions_launch',
            'campx_onehot_to_ids_launch', 'campx_config_set', 'campx_config_get',
            'campx_config_string', 'campx_write_probe_launch', 'campx_strerror',
@@ -59,6 +61,17 @@ class CampxFlowState(ctypes.Structure):
   rollouts, in the caller's (host) memory."""
   _fields_ = [('tag', ctypes.c_int64), ('B', ctypes.c_int64), ('T', ctypes.c_int64),
               ('pitch', ctypes.c_int64), ('n_dyn', ctypes.c_int64), ('block', ctypes.c_int64)]
+
+
+class CampxGather(ctypes.Structure):
+  """include/campx_hip.h: one request to render sampled (frame, environment) pairs of a trace."""
+  _fields_ = [('trace', ctypes.c_void_p), ('n_planes', ctypes.c_int64), ('T', ctypes.c_int64),
+              ('pitch', ctypes.c_int64), ('plane', ctypes.c_int64),
+              ('t_idx', ctypes.c_void_p), ('e_idx', ctypes.c_void_p),
+              ('idx64', ctypes.c_int32), ('obs_format', ctypes.c_int32), ('N', ctypes.c_int64),
+              ('obs', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
+              ('bad_flag', ctypes.c_void_p), ('streaming', ctypes.c_int32),
+              ('reserved', ctypes.c_int32)]
 
 
 ERR_FLOW_TIMEOUT = 1
@@ -139,6 +152,16 @@ def _load():
   lib.campx_wide_rules_size.argtypes = []
   lib.campx_wide_enumerate_launch.restype = i32
   lib.campx_wide_enumerate_launch.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp]
+  gather_p = ctypes.POINTER(CampxGather)
+  lib.campx_wide_update_launch.restype = i32
+  lib.campx_wide_update_launch.argtypes = [wide_p, vp, CampxState, vp, CampxOutputs, i64, i32,
+                                           i32, vp]
+  lib.campx_render_gather_launch.restype = i32
+  lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
+  lib.campx_wide_render_gather_launch.restype = i32
+  lib.campx_wide_render_gather_launch.argtypes = [wide_p, vp, gather_p, i64, vp]
+  lib.campx_render_gather_plan.restype = i32
+  lib.campx_render_gather_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_check_actions_launch.restype = i32
   lib.campx_check_actions_launch.argtypes = [vp, i64, vp, vp]
   lib.campx_onehot_to_ids_launch.restype = i32
@@ -187,7 +210,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
-            'onehot_to_ids', 'check_actions')
+            'wide_update', 'render_gather', 'wide_render_gather', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

@@ -600,6 +600,20 @@ int32_t launch_render(const CampxSpec& s, const CampxSpec* spec_dev, const uint8
                       int8_t* dst, int64_t B, int32_t T, int64_t plane_rows, int64_t pitch,
                       bool is_board, int fmt, hipStream_t stream);
 
+
+// k_gather.hip: sampled (frame, environment) pairs of a stored trace rendered into a minibatch
+struct GatherPlan {
+  uint32_t m, sh1, sh2;   // exact n / R for 32-bit n
+  uint32_t total;         // N * R
+  uint32_t shift;         // from the first (memory-aligned) window's start to the output's
+  uint32_t grid;          // workgroups (a multiple of 8)
+};
+GatherPlan gather_plan(int64_t N, int64_t R, int fmt, uint64_t dst_addr);
+int32_t gather_check(const CampxGather* g, int64_t B, int64_t R, int64_t n_planes, int entry_bytes);
+int32_t launch_gather_from(const RenderSource& src, const CampxGather& g, int64_t B, hipStream_t stream);
+// k_wide.hip
+RenderSource wide_render_source(const CampxWideSpec& s, const void* tables_dev);
+
 }  // namespace campx_impl
 
 #endif  // CAMPX_COMMON_HIP_H_

@@ -12,6 +12,8 @@
 //   campx::update_render            update of one rollout + render of the one before it
 //   campx::shape_rollout            the shape tier (Hello World): reset / step / rollout
 //   campx::wide_rollout             the wide tier (boards above 128 cells): reset / step / rollout
+//   campx::wide_update              the wide tier's update pass alone (trace-only rollouts)
+//   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -727,6 +729,153 @@ void wide_rollout(const Tensor& spec_host, const Tensor& tables, Tensor& state, 
              "campx_wide_rollout_launch");
 }
 
+// Wide tier, the update pass alone (campx_wide_update_launch): campx::wide_rollout's T-frame form
+// without observations.
+void wide_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                 const OptTensor& ret, const Tensor& actions, const OptTensor& reward,
+                 const OptTensor& discount, const OptTensor& step_done, const OptTensor& perf,
+                 Tensor& trace, const OptTensor& bad_count, const OptTensor& bad_flag,
+                 bool reset_first) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1,
+              "campx::wide_update: state must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = state.device();
+  const int64_t B = state.size(0), K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+  want(state, "state", at::kInt, dev, {B});
+  want(done, "done", at::kByte, dev, {B});
+  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
+  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  TORCH_CHECK(actions.dim() == 2, "campx::wide_update: actions must be int8 [T, B]");
+  const int64_t T = actions.size(0);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_update: bad frame count");
+  want(actions, "actions", at::kChar, dev, {T, B});
+  int64_t pitch = 0;
+  TORCH_CHECK(trace.device() == dev && trace.scalar_type() == at::kShort && trace.dim() == 3 &&
+                  trace.size(0) == K && trace.size(1) == T && trace.size(2) == B &&
+                  (B == 1 || trace.stride(2) == 1),
+              "campx: trace must be int16 [", K, ", ", T, ", ", B, "] on ", dev, ", contiguous within a row");
+  if (T > 1) pitch = trace.stride(1);
+  else if (K > 1) pitch = trace.stride(0);
+  TORCH_CHECK(pitch == 0 || (pitch >= B && (K == 1 || trace.stride(0) == T * pitch)),
+              "campx: trace rows must be >= B apart and its planes T * pitch apart");
+  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, dev, T, B, pitch);
+  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, dev, T, B, pitch);
+  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, dev, T, B, pitch);
+  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, dev, T, B, pitch);
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  CampxOutputs out{};
+  out.scalar_pitch = pitch;
+  out.reward = opt_ptr<float>(reward);
+  out.discount = opt_ptr<float>(discount);
+  out.done = opt_ptr<uint8_t>(step_done);
+  out.perf = opt_ptr<int8_t>(perf);
+  out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
+  out.bad_count = opt_ptr<int32_t>(bad_count);
+  out.bad_flag = flag_ptr(bad_flag, dev);
+  CampxState st{reinterpret_cast<int8_t*>(state.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
+                opt_ptr<float>(ret), nullptr};
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_wide_update_launch(hs, tables.data_ptr(), st,
+                                    reinterpret_cast<const int8_t*>(actions.data_ptr()), out, B,
+                                    (int32_t)T, reset_first ? 1 : 0,
+                                    c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_update_launch");
+}
+
+// Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
+// campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
+// t_idx[i], environment e_idx[i] of `trace` [planes, T', B] - any T', rows and planes as far apart
+// as the strides say (a view of a padded buffer, a ring of several rollouts).  Requests past the
+// kernel's 32-bit bound go as several launches of a multiple of 16 rows each.
+template <typename Launch>
+void gather_rows(const char* what, const Tensor& trace, at::ScalarType entry, int64_t planes,
+                 int64_t row_bytes, const Tensor& t_idx, const Tensor& e_idx, Tensor& obs,
+                 const OptTensor& bad_count, const OptTensor& bad_flag, bool streaming,
+                 c10::IntArrayRef frame, Launch launch) {
+  TORCH_CHECK(trace.device().is_cuda(), what, ": trace must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = trace.device();
+  TORCH_CHECK(trace.scalar_type() == entry && trace.dim() == 3 && trace.size(0) == planes &&
+                  trace.size(1) >= 1 && trace.size(2) >= 1 && (trace.size(2) == 1 || trace.stride(2) == 1),
+              what, ": trace must be ", entry, " [", planes, ", T, B], contiguous within a row");
+  const int64_t T = trace.size(1), B = trace.size(2);
+  const int64_t pitch = T > 1 ? trace.stride(1) : B;
+  const int64_t plane = planes > 1 ? trace.stride(0) : T * pitch;
+  TORCH_CHECK(pitch >= B && plane >= T * pitch, what, ": trace rows must be >= B apart and its "
+              "planes >= T * pitch apart");
+  TORCH_CHECK(t_idx.dim() == 1 && t_idx.size(0) >= 1 && t_idx.device() == dev && t_idx.is_contiguous() &&
+                  (t_idx.scalar_type() == at::kLong || t_idx.scalar_type() == at::kInt),
+              what, ": t_idx must be a contiguous int64 or int32 [N] tensor on ", dev);
+  const int64_t N = t_idx.size(0);
+  want(e_idx, "e_idx", t_idx.scalar_type(), dev, {N});
+  std::vector<int64_t> shape{N};
+  shape.insert(shape.end(), frame.begin(), frame.end());
+  want(obs, "obs", obs.scalar_type(), dev, shape);
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  CampxGather g{};
+  g.trace = trace.data_ptr();
+  g.n_planes = planes;
+  g.T = T;
+  g.pitch = pitch;
+  g.plane = plane;
+  g.idx64 = t_idx.scalar_type() == at::kLong ? 1 : 0;
+  g.obs_format = obs_format_of(obs);
+  g.bad_count = opt_ptr<int32_t>(bad_count);
+  g.bad_flag = flag_ptr(bad_flag, dev);
+  g.streaming = streaming ? 1 : 0;
+  const int64_t idx_bytes = g.idx64 ? 8 : 4, elem = obs.element_size();
+  const int64_t most = (((1ll << 32) - 65536 - 1) / row_bytes) & ~(int64_t)15;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  void* stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  for (int64_t n0 = 0; n0 < N; n0 += most) {
+    g.N = N - n0 < most ? N - n0 : most;
+    g.t_idx = static_cast<const char*>(t_idx.data_ptr()) + n0 * idx_bytes;
+    g.e_idx = static_cast<const char*>(e_idx.data_ptr()) + n0 * idx_bytes;
+    g.obs = static_cast<char*>(obs.data_ptr()) + n0 * row_bytes * elem;
+    check_ok(launch(&g, B, stream), what);
+  }
+}
+
+void render_gather(const Tensor& spec_host, const Tensor& spec_dev, const Tensor& trace,
+                   const Tensor& t_idx, const Tensor& e_idx, Tensor& obs, const OptTensor& bad_count,
+                   const OptTensor& bad_flag, bool streaming) {
+  const CampxSpec* hs = host_spec(spec_host);
+  TORCH_CHECK(spec_dev.device() == trace.device() && spec_dev.scalar_type() == at::kByte &&
+                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)sizeof(CampxSpec),
+              "campx: spec_dev must be the CampxSpec blob as a uint8 tensor on ", trace.device());
+  const CampxSpec* ds = reinterpret_cast<const CampxSpec*>(spec_dev.data_ptr());
+  gather_rows("campx::render_gather", trace, at::kByte, hs->n_dyn,
+              (int64_t)hs->n_layers * hs->rows * hs->cols, t_idx, e_idx, obs, bad_count, bad_flag,
+              streaming, {hs->n_layers, hs->rows, hs->cols},
+              [&](const CampxGather* g, int64_t B, void* stream) {
+                return campx_render_gather_launch(hs, ds, g, B, stream);
+              });
+}
+
+void wide_render_gather(const Tensor& spec_host, const Tensor& tables, const Tensor& trace,
+                        const Tensor& t_idx, const Tensor& e_idx, Tensor& obs,
+                        const OptTensor& bad_count, const OptTensor& bad_flag, bool streaming) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(tables.device() == trace.device() && tables.scalar_type() == at::kByte &&
+                  tables.is_contiguous() && tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", trace.device());
+  const int64_t K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+  const void* blob = tables.data_ptr();
+  gather_rows("campx::wide_render_gather", trace, at::kShort, K,
+              (int64_t)hs->n_layers * hs->rows * hs->cols, t_idx, e_idx, obs, bad_count, bad_flag,
+              streaming, {hs->n_layers, hs->rows, hs->cols},
+              [&](const CampxGather* g, int64_t B, void* stream) {
+                return campx_wide_render_gather_launch(hs, blob, g, B, stream);
+              });
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -790,6 +939,11 @@ void wide_rollout_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const Opt
                        const OptTensor&, Tensor&, const OptTensor&, const OptTensor&,
                        const OptTensor&, const OptTensor&, const OptTensor&, Tensor&,
                        const OptTensor&, const OptTensor&, bool) {}
+void wide_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const Tensor&,
+                      const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&, Tensor&,
+                      const OptTensor&, const OptTensor&, bool) {}
+void render_gather_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
+                        Tensor&, const OptTensor&, const OptTensor&, bool) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
 void check_actions_meta(const Tensor&, Tensor&) {}
 
@@ -861,6 +1015,17 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(c!)? ret, Tensor? actions, Tensor(d!) obs, Tensor(e!)? board, Tensor(f!)? reward, "
       "Tensor(g!)? discount, Tensor(h!)? step_done, Tensor(i!)? perf, Tensor(j!) trace, "
       "Tensor(k!)? bad_count, Tensor(l!)? bad_flag, bool reset_first) -> ()");
+  m.def(
+      "wide_update(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor actions, Tensor(d!)? reward, Tensor(e!)? discount, "
+      "Tensor(f!)? step_done, Tensor(g!)? perf, Tensor(h!) trace, Tensor(i!)? bad_count, "
+      "Tensor(j!)? bad_flag, bool reset_first) -> ()");
+  m.def(
+      "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
+      "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
+  m.def(
+      "wide_render_gather(Tensor spec_host, Tensor tables, Tensor trace, Tensor t_idx, Tensor e_idx, "
+      "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -875,13 +1040,17 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("update_render", &update_render);
   m.impl("shape_rollout", &shape_rollout);
   m.impl("wide_rollout", &wide_rollout);
+  m.impl("wide_update", &wide_update);
+  m.impl("render_gather", &render_gather);
+  m.impl("wide_render_gather", &wide_render_gather);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }
 
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
-                           "wide_rollout", "onehot_to_ids", "check_actions"})
+                           "wide_rollout", "wide_update", "render_gather", "wide_render_gather", "onehot_to_ids",
+                           "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
@@ -895,6 +1064,9 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("update_render", &update_render_meta);
   m.impl("shape_rollout", &shape_rollout_meta);
   m.impl("wide_rollout", &wide_rollout_meta);
+  m.impl("wide_update", &wide_update_meta);
+  m.impl("render_gather", &render_gather_meta);
+  m.impl("wide_render_gather", &render_gather_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);
   m.impl("check_actions", &check_actions_meta);
 }

@@ -1169,6 +1169,68 @@ int32_t campx_wide_rollout_launch(const CampxWideSpec* s, const void* tables_dev
   return CAMPX_OK;
 }
 
+// The update pass alone: what campx_wide_rollout_launch() runs in front of its render(s), in one
+// launch however long the rollout (nothing reads the trace back, so nothing is cut in chunks).
+int32_t campx_wide_update_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
+                                 const int8_t* actions, CampxOutputs out, int64_t B, int32_t T,
+                                 int32_t reset_first, void* stream) {
+  if (!s || !tables_dev || !st.pos || !st.done || !actions || !out.trace || B <= 0 || T <= 0)
+    return CAMPX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(out.trace) & 1) || (reinterpret_cast<uintptr_t>(st.pos) & 3))
+    return CAMPX_EINVAL;
+  if (out.scalar_pitch && out.scalar_pitch < B) return CAMPX_EINVAL;
+  const int32_t v = wide_validate_plain(s);
+  if (v != CAMPX_OK) return v;
+  if (out.perf && !s->has_perf) return CAMPX_EINVAL;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const WideLayout w = wide_layout(*s);
+  WideParams wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.n_states = s->n_states;
+  wp.n_dyn = w.n_planes;
+  wp.discounts[0] = 1.0f;
+  for (int i = 1; i < 16; ++i) wp.discounts[i] = s->discount_list[i];
+  wp.has_dcodes = s->any_dcode;
+  wp.plane = (int64_t)T * row_pitch(out, B);
+  const char* blob = static_cast<const char*>(tables_dev);
+  const uint2* entries = reinterpret_cast<const uint2*>(blob);
+  const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
+  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
+  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
+  const size_t want = (size_t)(w.cells_off) + (size_t)s->n_states * sizeof(u32x4) +
+                      (out.perf ? (size_t)w.n_entries : 0);
+  const bool in_lds = want <= (size_t)knob(K_WIDE_LDS_MAX);
+  const size_t lds = in_lds ? want : 0;
+  const dim3 grid((unsigned)((B + kWideThreads - 1) / kWideThreads));
+  out.obs = nullptr;
+  out.board = nullptr;
+#define CAMPX_WIDE_LAUNCH(LDS, PERF)                                                              \
+  do {                                                                                            \
+    CAMPX_ALLOW_LDS((wide_update_kernel<LDS, PERF>), lds);                                        \
+    hipLaunchKernelGGL((wide_update_kernel<LDS, PERF>), grid, dim3(kWideThreads), lds, hs, wp,    \
+                       entries, cells, perf, state, st, actions, out, B, T, reset_first);         \
+  } while (0)
+  if (in_lds && out.perf) CAMPX_WIDE_LAUNCH(true, true);
+  else if (in_lds) CAMPX_WIDE_LAUNCH(true, false);
+  else if (out.perf) CAMPX_WIDE_LAUNCH(false, true);
+  else CAMPX_WIDE_LAUNCH(false, false);
+#undef CAMPX_WIDE_LAUNCH
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+}
+
+int32_t campx_wide_render_gather_launch(const CampxWideSpec* s, const void* tables_dev,
+                                        const CampxGather* g, int64_t B, void* stream) {
+  if (!s || !tables_dev) return CAMPX_EINVAL;
+  const int32_t v = wide_validate_plain(s);
+  if (v != CAMPX_OK) return v;
+  const WideLayout w = wide_layout(*s);
+  const int64_t R = (int64_t)s->n_layers * s->rows * s->cols;
+  const int32_t rc = gather_check(g, B, R, w.n_planes, 2);
+  if (rc != CAMPX_OK) return rc;
+  return launch_gather_from(wide_render_source(*s, tables_dev), *g, B, static_cast<hipStream_t>(stream));
+}
+
 int32_t campx_wide_rules_size(void) { return (int32_t)sizeof(CampxWideRules); }
 
 int32_t campx_wide_enumerate_launch(const CampxWideRules* r, const uint16_t* cells_in, int64_t N,

@@ -431,6 +431,32 @@ class Engine(object):
                          'been through its_showtime()')
     return self._fused.rollout_buffers(T, **kwargs)
 
+  def rollout_trace(self, actions, reset_first=False, out=None):
+    """Batched tiers only: T frames of update pass and nothing else - `rollout()`'s dict without
+    'obs' / 'board'.  The trace is the stored trajectory; `render_frames()` materialises the
+    transitions a minibatch samples.  See `fused.FusedGame.rollout_trace` (the shape tier raises
+    NotImplementedError)."""
+    if self._fused is None:
+      raise RuntimeError('rollout_trace() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.rollout_trace(actions, reset_first=reset_first, out=out)
+
+  def rollout_trace_buffers(self, T):
+    """Batched tiers only: the dict of `rollout_trace(out=...)`, allocated once."""
+    if self._fused is None:
+      raise RuntimeError('rollout_trace_buffers() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.rollout_trace_buffers(T)
+
+  def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
+    """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
+    `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See
+    `fused.FusedGame.render_frames` (the shape tier raises NotImplementedError)."""
+    if self._fused is None:
+      raise RuntimeError('render_frames() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.render_frames(trace, t_idx, e_idx, obs_dtype=obs_dtype, out=out)
+
   def rollout_deferred(self, actions, out, reset_first=False, actions_ready=False):
     """Fused tiers only: T frames whose observations may arrive with the NEXT call - for action
     streams that do not wait for them.  Returns the previous call's buffers, complete; see

@@ -61,6 +61,13 @@ FORCE_SPLIT = SPLIT_ROLLOUT   # kept for callers that toggled it: same as SPLIT_
 PAD_ROWS = True
 
 _OBS_DTYPES = (torch.int8, torch.float16, torch.bfloat16)
+# render_frames(): whether the gather kernel's stores bypass the caches like a rollout's
+# (`sc0 sc1 nt`) or are plain ones.  Measured (tools/bench_gather.py, profiles/r07_gather.txt; boat
+# race, plain / streaming): int8 the same at every size (1 048 576 rows: 3.30 / 3.26 TB/s), bf16
+# 1.46 / 1.62 TB/s at 65 536 rows and 2.69 / 4.00 at 1 048 576 - streaming is never measurably slower, so it is
+# the default.  (What a consumer that reads a small minibatch back at once gains from plain stores
+# was not measured: NOTES.md R7.)
+GATHER_STREAMING = True
 
 
 def _ptr(t):
@@ -187,6 +194,7 @@ class FusedGame(object):
     # host memory (include/campx_hip.h CampxOutputs.error_flag), looked at after EVERY launch
     self._err_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._err_flag_view = self._err_flag.numpy()
+    self._init_gather()
     self._deferred = None      # rollout_deferred(): the dict whose observations are still owed
     self._deferred_rendered = False    # ... unless that rollout was run whole (no shared launch)
     self._shared_launch = {}   # T -> whether campx_update_render_launch shares one launch
@@ -200,13 +208,36 @@ class FusedGame(object):
     layers = {ch: obs[:, i] for i, ch in enumerate(self.chars)}
     return Observation(board=board, layers=layers, layered_board=obs)
 
-  def _raise_bad(self):
+  def _init_gather(self):
+    """render_frames()'s bookkeeping of indices out of range: a device counter and a flag in
+    pinned host memory, as for bad actions."""
+    self._bad_idx = torch.zeros((1,), dtype=torch.int32, device=self.device)
+    self._bad_idx_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
+    self._bad_idx_flag_view = self._bad_idx_flag.numpy()
+
+  def _take_bad_indices(self):
+    n = int(self._bad_idx.item())      # synchronises: we are about to raise anyway
+    self._bad_idx.zero_()
+    self._bad_idx_flag_view[0] = 0
+    return n
+
+  def _raise_bad(self, indices=False):
+    """One ValueError for everything the kernels counted: action ids outside 0..4 and - when their
+    flag is up, or `indices` - rows of render_frames() outside the trace.  Both counters are read
+    before either is cleared, so neither is lost to the other's error."""
     n = int(self._bad.item())          # synchronises: we are about to raise anyway
+    rows = self._take_bad_indices() if indices or self._bad_idx_flag_view[0] else 0
     self._bad.zero_()
     self._bad_flag_view[0] = 0
+    what = []
     if n:
-      raise ValueError('{} action ids are outside 0..{} (or came from rows that are not '
-                       'exactly one-hot)'.format(n, gamespec.N_ACTIONS - 1))
+      what.append('{} action ids are outside 0..{} (or came from rows that are not '
+                  'exactly one-hot)'.format(n, gamespec.N_ACTIONS - 1))
+    if rows:
+      what.append('{} rows of render_frames() named a frame or an environment outside the '
+                  'trace (they were rendered from the nearest one inside)'.format(rows))
+    if what:
+      raise ValueError('; '.join(what))
 
   def check_actions(self):
     """Synchronise and raise ValueError if any consumed action id was outside 0..4 (and
@@ -214,7 +245,7 @@ class FusedGame(object):
     definitive for every rollout issued)."""
     torch.cuda.synchronize(self.device)
     self.check_ok()
-    self._raise_bad()
+    self._raise_bad(indices=True)
 
   def check_ok(self):
     """Raise RuntimeError if a launch reported, through the error word, that it could not do what
@@ -241,7 +272,7 @@ class FusedGame(object):
     mode = self.validate_actions
     if mode == 'sync':
       self._raise_bad()
-    elif mode and self._bad_flag_view[0]:
+    elif mode and (self._bad_flag_view[0] or self._bad_idx_flag_view[0]):
       self._raise_bad()
 
   def _action_ids(self, actions, expect):
@@ -525,6 +556,126 @@ class FusedGame(object):
     self.check_ok()
     if validate:
       self._after_launch()
+    return out
+
+  # ------------------------------------------------- the trace as a stored trajectory
+
+  def _trace_only_refusal(self):
+    """Why this game has no trace-only rollouts (None: it has)."""
+    if not self.uses_table:
+      return ('the update pass of this game is not tabulated (it runs the rule interpreter: '
+              'fused.COMPILE_TABLE is off, or its table would be too large)')
+    return None
+
+  def rollout_trace_buffers(self, T):
+    """Allocate the dict of `rollout_trace(out=...)` once: `rollout_buffers(T)` without 'obs' /
+    'board' - same shapes, dtypes and row padding."""
+    B, dev = self.batch, self.device
+    pitch = (B + 15) // 16 * 16 if PAD_ROWS else B
+
+    def rows(dtype, *lead):
+      return torch.empty(lead + (T, pitch), dtype=dtype, device=dev)[..., :B]
+    return dict(
+        reward=rows(torch.float32) if self.any_reward else None,
+        discount=rows(torch.float32),
+        done=rows(torch.uint8),
+        perf=rows(torch.int8) if self.has_perf else None,
+        trace=rows(torch.uint8, self.n_dyn))
+
+  def _rollout_trace_op(self, ids, out, validate, reset_first):
+    self._update(self._spec_host, self._spec_dev, self.pos, self.done, self.ret, self._pair_table,
+                 ids, out['reward'], out['discount'], out['done'], out['perf'], out['trace'],
+                 self._bad if validate else None, self._bad_flag if validate else None,
+                 bool(reset_first))
+
+  def rollout_trace(self, actions, reset_first=False, out=None):
+    """T frames of update pass and nothing else: the rollout stops at the trace.
+
+    What `rollout()` returns without 'obs' / 'board' - 'trace', 'reward', 'discount', 'done',
+    'perf', same shapes, dtypes and row padding - and the same state afterwards (`ret`, `frame`,
+    bad-action accounting).  The trace is a complete description of every frame at about a
+    hundredth of the observations' size: keep it (several rollouts' traces concatenate along the
+    frame axis) and have `render_frames()` materialise the transitions a minibatch samples.
+    `out`: a dict from `rollout_trace_buffers(T)`, overwritten.
+    """
+    refusal = self._trace_only_refusal()
+    if refusal:
+      raise ValueError('rollout_trace(): ' + refusal)
+    T = int(actions.shape[0])
+    if T < 1:
+      raise ValueError('a rollout needs at least one frame: actions [T, B] with T >= 1')
+    if (torch.is_tensor(actions) and actions.dtype == torch.int8
+        and actions.device == self.device and actions.shape == (T, self.batch)
+        and actions.is_contiguous()):
+      ids = actions
+    else:
+      ids = self._action_ids(actions, (T, self.batch))
+    if out is None:
+      out = self.rollout_trace_buffers(T)
+    validate = self.validate_actions
+    self._aux_in_sync = False
+    self._rollout_trace_op(ids, out, validate, reset_first)
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if validate:
+      self._after_launch()
+    return out
+
+  def _gather_op(self, trace, t_idx, e_idx, out):
+    _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,
+                           self._bad_idx, self._bad_idx_flag, GATHER_STREAMING)
+
+  _trace_dtype = torch.uint8
+
+  def _trace_planes(self):
+    return self.n_dyn
+
+  def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
+    """The observations of sampled transitions, rendered from a trace: `[N, L, H, W]`.
+
+    Row i is bit for bit what `rollout()` wrote, or would have written, at
+    `obs[t_idx[i], e_idx[i]]` of the rollout(s) whose trace this is.
+
+    Args:
+      trace: a trace tensor of this game, `[planes, T', B]` - from `rollout_trace()`, from
+          `rollout()`, or several of them concatenated along T'.  Views of padded buffers are
+          fine: the row pitch is taken from the strides.
+      t_idx, e_idx: integer tensors `[N]` (int64 or int32), on the device: frame and environment
+          of each row.  Indices outside the trace are clamped on the device and counted; like bad
+          actions they raise ValueError lazily - from a later call, or from `check_actions()` -
+          because this call does not synchronise.
+      obs_dtype: torch.int8 (0 / 1), torch.float16 or torch.bfloat16 (0.0 / 1.0).
+      out: a `[N, L, H, W]` tensor of that dtype to write into (the call is then capturable in a
+          HIP graph).
+    """
+    L, H, W = self.n_layers, self.rows, self.cols
+    if L * H * W < 16:
+      raise ValueError('render_frames(): rows of {} bytes are below the 16 the render kernels need'
+                       .format(L * H * W))
+    planes = self._trace_planes()
+    if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.dtype != self._trace_dtype
+        or trace.shape[0] != planes or trace.shape[2] != self.batch or trace.device != self.device):
+      raise ValueError('trace must be a {} [{}, T, {}] tensor of this game on {}'.format(
+          self._trace_dtype, planes, self.batch, self.device))
+    t_idx, e_idx = torch.as_tensor(t_idx), torch.as_tensor(e_idx)
+    if t_idx.dim() != 1 or t_idx.shape != e_idx.shape or t_idx.numel() < 1:
+      raise ValueError('t_idx and e_idx must be integer tensors [N] of one length N >= 1')
+    if t_idx.dtype not in (torch.int32, torch.int64) or e_idx.dtype != t_idx.dtype:
+      raise ValueError('t_idx and e_idx must both be int64 or both int32')
+    t_idx = t_idx.to(self.device).contiguous()
+    e_idx = e_idx.to(self.device).contiguous()
+    N = int(t_idx.numel())
+    if out is None:
+      if obs_dtype not in _OBS_DTYPES:
+        raise ValueError('obs_dtype must be torch.int8, float16 or bfloat16')
+      out = torch.empty((N, L, H, W), dtype=obs_dtype, device=self.device)
+    elif tuple(out.shape) != (N, L, H, W) or out.dtype not in _OBS_DTYPES or not out.is_contiguous():
+      raise ValueError('out must be a contiguous int8 / float16 / bfloat16 [N, L, H, W] tensor')
+    self._gather_op(trace, t_idx, e_idx, out)
+    if self.validate_actions == 'sync':
+      self._raise_bad(indices=True)
+    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
+      self._raise_bad()
     return out
 
   def rollout_deferred(self, actions, out, reset_first=False, actions_ready=False):

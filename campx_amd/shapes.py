@@ -173,6 +173,21 @@ class ShapeGame(object):
     from .play_graph import PlayGraph
     return PlayGraph(self, n_frames, policy=policy, record_obs=record_obs)
 
+  def _no_stored_trace(self, method):
+    raise NotImplementedError(
+        '{}() is not offered by the shape tier: its trace is the things\' offsets plus trail '
+        'keyframes every fourth frame, not a self-contained description of each frame'
+        .format(method))
+
+  def rollout_trace_buffers(self, T):
+    self._no_stored_trace('rollout_trace_buffers')
+
+  def rollout_trace(self, actions, reset_first=False, out=None):
+    self._no_stored_trace('rollout_trace')
+
+  def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
+    self._no_stored_trace('render_frames')
+
   def rollout_buffers(self, T, keep_obs=True, want_board=False, obs_dtype=torch.int8,
                       share=None):
     if obs_dtype not in (torch.int8, torch.float16, torch.bfloat16):

@@ -94,6 +94,10 @@ class WideGame(fused.FusedGame):
     self.frame = -1
     self._observation_cache = self._observation(self._obs, self._board)
     self._wide = _hip.ops.wide_rollout.default
+    # (no launch of this tier raises the error word; check_ok() / check_actions() read it all the same)
+    self._err_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
+    self._err_flag_view = self._err_flag.numpy()
+    self._init_gather()
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -139,6 +143,29 @@ class WideGame(fused.FusedGame):
     out = super(WideGame, self).rollout_buffers(T, keep_obs, want_board, obs_dtype, share)
     out['trace'] = self._trace_rows(T)
     return out
+
+  def rollout_trace_buffers(self, T):
+    out = super(WideGame, self).rollout_trace_buffers(T)
+    out['trace'] = self._trace_rows(T)
+    return out
+
+  def _trace_only_refusal(self):
+    return None
+
+  def _rollout_trace_op(self, ids, out, validate, reset_first):
+    _hip.ops.wide_update(self._spec_host, self._tables, self.state, self.done, self.ret, ids,
+                         out['reward'], out['discount'], out['done'], out['perf'], out['trace'],
+                         self._bad if validate else None, self._bad_flag if validate else None,
+                         bool(reset_first))
+
+  _trace_dtype = torch.int16
+
+  def _trace_planes(self):
+    return self._n_planes
+
+  def _gather_op(self, trace, t_idx, e_idx, out):
+    _hip.ops.wide_render_gather(self._spec_host, self._tables, trace, t_idx, e_idx, out,
+                                self._bad_idx, self._bad_idx_flag, fused.GATHER_STREAMING)
 
   def rollout_deferred(self, actions, out, reset_first=False, actions_ready=False):
     """`FusedGame.rollout_deferred` for this tier, which has no shared launch: the rollout is

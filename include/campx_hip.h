@@ -675,6 +675,64 @@ int32_t campx_wide_rollout_launch(const CampxWideSpec* spec_host, const void* ta
                                   CampxState state, const int8_t* actions, CampxOutputs out,
                                   int64_t B, int32_t T, int32_t reset_first, void* stream);
 
+/*
+ * ---- The trace as a stored trajectory ------------------------------------------------
+ * A rollout's trace is a complete description of every frame (CampxOutputs.trace: one byte per
+ * moving thing, frame and environment in the one-cell tier; 16 bits, plus one plane for a piece
+ * mask or a scenery variant, in the state-table tier) at a hundredth of the observations' size.
+ * A caller that trains from a replay buffer keeps traces and has the observations of the
+ * transitions it samples rendered on demand.  No reference counterpart: the reference renders
+ * every frame as it plays it (campx/engine.py:295-324).
+ *
+ *   campx_update_launch (above) / campx_wide_update_launch
+ *       the update pass of T frames and nothing else: state, trace, per-frame scalars.
+ *   campx_render_gather_launch / campx_wide_render_gather_launch
+ *       row i of `obs` = the observation of frame t_idx[i], environment e_idx[i] of `trace`,
+ *       bit for bit what a rollout writes for that frame and environment.
+ */
+typedef struct CampxGather {
+  const void* trace;    /* DEVICE [n_planes][T][pitch] entries: uint8 (one-cell tier), uint16
+                           (state-table tier, 2-byte aligned).  Any number of rollouts' traces
+                           one after the other along T. */
+  int64_t n_planes;     /* must be the game's: n_dyn, + 1 with a piece mask or scenery variants */
+  int64_t T;            /* frames the trace holds */
+  int64_t pitch;        /* entries from one frame's row to the next (>= B) */
+  int64_t plane;        /* entries from one plane to the next (>= T * pitch) */
+  const void* t_idx;    /* DEVICE [N] frame of row i ... */
+  const void* e_idx;    /* ... and its environment; int32, or int64 with idx64 != 0.  An index
+                           outside 0..T-1 / 0..B-1 is clamped on the device (nothing is read out of
+                           bounds; the row shows the clamped frame) and counted. */
+  int32_t idx64;
+  int32_t obs_format;   /* CAMPX_OBS_INT8 / _F16 / _BF16 */
+  int64_t N;            /* rows; N * L*rows*cols must stay below 2^32 - 2^16 (larger requests:
+                           several calls, each of a multiple of 16 rows) */
+  void* obs;            /* DEVICE [N][L][rows][cols], 16-byte aligned */
+  int32_t* bad_count;   /* optional device int32: += rows with an index out of range */
+  int32_t* bad_flag;    /* optional, as CampxOutputs.bad_flag: set to 1 when there was one */
+  int32_t streaming;    /* != 0: the stores bypass the caches (`sc0 sc1 nt`, the rollout's
+                           store); 0: plain stores - a minibatch is usually read again at once */
+  int32_t reserved;
+} CampxGather;
+
+/* Asynchronous on `stream`, no synchronisation, no library state; every argument is checked
+ * before anything is launched (CAMPX_EINVAL: NULL, N <= 0, misaligned `obs`, pitch < B, a plane
+ * count that is not the game's, N * row bytes past the bound above, rows below 16 bytes). */
+int32_t campx_render_gather_launch(const CampxSpec* spec_host, const CampxSpec* spec_dev,
+                                   const CampxGather* gather, int64_t B, void* stream);
+int32_t campx_wide_render_gather_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                        const CampxGather* gather, int64_t B, void* stream);
+/* campx_wide_rollout_launch()'s arguments; out.obs / out.board are ignored (may be NULL), the
+ * variant or mask plane of the trace is written exactly as in a full rollout. */
+int32_t campx_wide_update_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                 CampxState state, const int8_t* actions, CampxOutputs out,
+                                 int64_t B, int32_t T, int32_t reset_first, void* stream);
+/* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
+ * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
+ * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
+ * workgroups; image bytes of a wave's window; waves per workgroup. */
+int32_t campx_render_gather_plan(int64_t N, int32_t R, int32_t obs_format, uint64_t dst_addr,
+                                 int64_t* plan_out);
+
 /* *bad_count (device int32, caller-zeroed) += number of ids outside 0..4 in
  * actions[0..n). */
 int32_t campx_check_actions_launch(const int8_t* actions, int64_t n, int32_t* bad_count,
