@@ -31,7 +31,8 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_spec_size', 'campx_wide_spec_validate', 'campx_wide_tables_bytes',
            'campx_wide_tables_build', 'campx_wide_reset_launch', 'campx_wide_rollout_launch',
            'campx_wide_rules_size', 'campx_wide_enumerate_launch',
-           'campx_wide_update_launch', 'campx_render_gather_launch',
+           'campx_wide_update_launch', 'campx_wide_policy_update_launch',
+           'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_check_actions_launch',
            'campx_onehot_to_ids_launch', 'campx_config_set', 'campx_config_get',
@@ -156,6 +157,9 @@ def _load():
   lib.campx_wide_update_launch.restype = i32
   lib.campx_wide_update_launch.argtypes = [wide_p, vp, CampxState, vp, CampxOutputs, i64, i32,
                                            i32, vp]
+  lib.campx_wide_policy_update_launch.restype = i32
+  lib.campx_wide_policy_update_launch.argtypes = [wide_p, vp, CampxState, vp, ctypes.c_uint64, i64,
+                                                  CampxOutputs, vp, vp, i64, i32, i32, vp]
   lib.campx_render_gather_launch.restype = i32
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
@@ -210,7 +214,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'render_gather', 'wide_render_gather', 'onehot_to_ids', 'check_actions')
+            'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

@@ -613,6 +613,16 @@ int32_t gather_check(const CampxGather* g, int64_t B, int64_t R, int64_t n_plane
 int32_t launch_gather_from(const RenderSource& src, const CampxGather& g, int64_t B, hipStream_t stream);
 // k_wide.hip
 RenderSource wide_render_source(const CampxWideSpec& s, const void* tables_dev);
+// where the parts of the state-table blob are (campx_wide_tables_build() lays it out)
+struct WideLayout {
+  int64_t n_entries, cells_off, perf_off, rot_obs_off, rot_board_off, pieces_off, total;
+  int pitch_obs, pitch_board;
+  int n_variants;          // sets of rotations (1: the scenery never changes)
+  int n_planes;            // planes of the trace: the things, plus the variant's when there are several,
+                           // or the mask of the pieces that show
+};
+WideLayout wide_layout(const CampxWideSpec& s);
+int32_t wide_validate_plain(const CampxWideSpec* s);
 
 }  // namespace campx_impl
 

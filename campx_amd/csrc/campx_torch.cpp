@@ -13,6 +13,8 @@
 //   campx::shape_rollout            the shape tier (Hello World): reset / step / rollout
 //   campx::wide_rollout             the wide tier (boards above 128 cells): reset / step / rollout
 //   campx::wide_update              the wide tier's update pass alone (trace-only rollouts)
+//   campx::wide_policy_update       the same with every frame's action sampled on the device from a
+//                                   policy over the game's states (closed-loop rollouts)
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
@@ -787,6 +789,69 @@ void wide_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, T
            "campx_wide_update_launch");
 }
 
+// Wide tier, closed loop (campx_wide_policy_update_launch): campx::wide_update with the action
+// stream replaced by `policy` float32 [n_states, 5]; the actions taken and - optionally - the rows
+// they were sampled from come back as streams of the call's row pitch.  T is the trace's.
+void wide_policy_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                        const OptTensor& ret, const Tensor& policy, int64_t seed, int64_t first_frame,
+                        const OptTensor& reward, const OptTensor& discount,
+                        const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
+                        Tensor& actions_out, const OptTensor& states_out, const OptTensor& bad_count,
+                        const OptTensor& bad_flag, bool reset_first) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1,
+              "campx::wide_policy_update: state must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = state.device();
+  const int64_t B = state.size(0), K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+  want(state, "state", at::kInt, dev, {B});
+  want(done, "done", at::kByte, dev, {B});
+  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
+  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want(policy, "policy", at::kFloat, dev, {(int64_t)hs->n_states, (int64_t)CAMPX_N_ACTIONS});
+  TORCH_CHECK(first_frame >= 0, "campx::wide_policy_update: first_frame must be >= 0");
+  TORCH_CHECK(trace.dim() == 3, "campx::wide_policy_update: trace must be int16 [K, T, B]");
+  const int64_t T = trace.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_policy_update: bad frame count");
+  int64_t pitch = 0;
+  TORCH_CHECK(trace.device() == dev && trace.scalar_type() == at::kShort && trace.size(0) == K &&
+                  trace.size(2) == B && (B == 1 || trace.stride(2) == 1),
+              "campx: trace must be int16 [", K, ", ", T, ", ", B, "] on ", dev, ", contiguous within a row");
+  if (T > 1) pitch = trace.stride(1);
+  else if (K > 1) pitch = trace.stride(0);
+  TORCH_CHECK(pitch == 0 || (pitch >= B && (K == 1 || trace.stride(0) == T * pitch)),
+              "campx: trace rows must be >= B apart and its planes T * pitch apart");
+  want_rows(actions_out, "actions_out", at::kChar, dev, T, B, pitch);
+  if (states_out.has_value()) want_rows(*states_out, "states_out", at::kInt, dev, T, B, pitch);
+  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, dev, T, B, pitch);
+  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, dev, T, B, pitch);
+  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, dev, T, B, pitch);
+  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, dev, T, B, pitch);
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  CampxOutputs out{};
+  out.scalar_pitch = pitch;
+  out.reward = opt_ptr<float>(reward);
+  out.discount = opt_ptr<float>(discount);
+  out.done = opt_ptr<uint8_t>(step_done);
+  out.perf = opt_ptr<int8_t>(perf);
+  out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
+  out.bad_count = opt_ptr<int32_t>(bad_count);
+  out.bad_flag = flag_ptr(bad_flag, dev);
+  CampxState st{reinterpret_cast<int8_t*>(state.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
+                opt_ptr<float>(ret), nullptr};
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_wide_policy_update_launch(
+               hs, tables.data_ptr(), st, reinterpret_cast<const float*>(policy.data_ptr()),
+               (uint64_t)seed, first_frame, out, reinterpret_cast<int8_t*>(actions_out.data_ptr()),
+               opt_ptr<int32_t>(states_out), B, (int32_t)T, reset_first ? 1 : 0,
+               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_policy_update_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` [planes, T', B] - any T', rows and planes as far apart
@@ -942,6 +1007,10 @@ void wide_rollout_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const Opt
 void wide_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const Tensor&,
                       const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&, Tensor&,
                       const OptTensor&, const OptTensor&, bool) {}
+void wide_policy_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&,
+                             const Tensor&, int64_t, int64_t, const OptTensor&, const OptTensor&,
+                             const OptTensor&, const OptTensor&, Tensor&, Tensor&, const OptTensor&,
+                             const OptTensor&, const OptTensor&, bool) {}
 void render_gather_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                         Tensor&, const OptTensor&, const OptTensor&, bool) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
@@ -1021,6 +1090,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(f!)? step_done, Tensor(g!)? perf, Tensor(h!) trace, Tensor(i!)? bad_count, "
       "Tensor(j!)? bad_flag, bool reset_first) -> ()");
   m.def(
+      "wide_policy_update(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor policy, int seed, int first_frame, Tensor(d!)? reward, "
+      "Tensor(e!)? discount, Tensor(f!)? step_done, Tensor(g!)? perf, Tensor(h!) trace, "
+      "Tensor(i!) actions_out, Tensor(j!)? states_out, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, "
+      "bool reset_first) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1041,6 +1116,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("shape_rollout", &shape_rollout);
   m.impl("wide_rollout", &wide_rollout);
   m.impl("wide_update", &wide_update);
+  m.impl("wide_policy_update", &wide_policy_update);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("onehot_to_ids", &onehot_to_ids);
@@ -1049,7 +1125,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
-                           "wide_rollout", "wide_update", "render_gather", "wide_render_gather", "onehot_to_ids",
+                           "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "onehot_to_ids",
                            "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
@@ -1065,6 +1141,7 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("shape_rollout", &shape_rollout_meta);
   m.impl("wide_rollout", &wide_rollout_meta);
   m.impl("wide_update", &wide_update_meta);
+  m.impl("wide_policy_update", &wide_policy_update_meta);
   m.impl("render_gather", &render_gather_meta);
   m.impl("wide_render_gather", &render_gather_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);

@@ -496,14 +496,7 @@ __global__ void wide_reset_kernel(const u32x4* __restrict__ cells, int32_t K, in
 
 // ---- the table blob: [entries uint2 x 5S, padded to 16][cells 8 x uint16 x S][perf int8 x 5S, padded to 16]
 // [rot_obs][rot_board][pieces: 16 words for the layered rows, 16 for the flat board]
-struct WideLayout {
-  int64_t n_entries, cells_off, perf_off, rot_obs_off, rot_board_off, pieces_off, total;
-  int pitch_obs, pitch_board;
-  int n_variants;          // sets of rotations (1: the scenery never changes)
-  int n_planes;            // planes of the trace: the things, plus the variant's when there are several,
-                           // or the mask of the pieces that show
-};
-
+// (struct WideLayout: campx_common.hip.h - k_policy.hip reads the same blob)
 static int wide_variants(const CampxWideSpec& s) { return s.n_variants > 1 ? s.n_variants : 1; }
 
 WideLayout wide_layout(const CampxWideSpec& s) {

@@ -102,6 +102,7 @@ class Engine(object):
     self._device = device
     self._fused = None
     self._action_set = None
+    self._state_table = False
 
   # ---------------------------------------------------------------- set-up
 
@@ -209,6 +210,18 @@ class Engine(object):
       raise ValueError('exactly 5 actions are needed')
     self._action_set = actions
 
+  def use_state_table(self):
+    """Build addition, batched engines, set-up time only: run this game from its STATE table
+    (`wide.WideGame`) whatever tier `its_showtime()` would pick for it.  The state-table tier is
+    where a frame's state index is everything a policy can read, so it is the tier that offers
+    closed-loop rollouts (`rollout_policy()`); a small game such as the boat race, which runs on
+    the one-cell tier by default, takes them after this call.  The game is enumerated on the
+    device where `its_showtime()` does that today and tabulated on the host otherwise, rule
+    classes included; a game that cannot be tabulated raises `tabulate.TabulationError` from
+    `its_showtime()`.  Without the call nothing changes."""
+    self._not_during_showtime('use_state_table')
+    self._state_table = True
+
   def update_group(self, group_name):
     """Entities added from now on belong to update group `group_name`."""
     self._not_during_showtime('update_group')
@@ -295,7 +308,13 @@ class Engine(object):
       n_movers = 0
       if big and gamespec.is_rule_game(self) and not gamespec.is_shape_rule_game(self):
         n_movers = sum(1 for e in gamespec.describe(self).entities if e.moves)
-      if n_movers >= 2:
+      if self._state_table and n_movers < 2:
+        # use_state_table(): the tabulator gets the game whatever it is made of - the rule classes
+        # are ordinary Python classes too - and its refusal is the answer
+        from . import chance, recognise, tabulate
+        with chance.forbidden(tabulate.TabulationError):
+          traced = tabulate.trace(self, actions=recognise.detect_actions(self))
+      elif n_movers >= 2:
         # a multi-mover rule game above 128 cells: millions of reachable states, enumerated by
         # the rules themselves on the device (the host tabulator below spends a frame of Python
         # per state and action); the wide tier runs the table
@@ -356,7 +375,7 @@ class Engine(object):
 
     if self._batch is not None:
       from . import fused
-      if traced is not None and traced.dense_reason is not None:
+      if traced is not None and (traced.dense_reason is not None or self._state_table):
         # (more than 128 cells, or more tracked values than the cell-indexed tables take:
         # the game runs from its state table)
         from . import wide
@@ -447,6 +466,23 @@ class Engine(object):
       raise RuntimeError('rollout_trace_buffers() needs a batched Engine (batch=B) that has '
                          'been through its_showtime()')
     return self._fused.rollout_trace_buffers(T)
+
+  def rollout_policy(self, policy, T, **kwargs):
+    """State-table tier only: T frames in one launch with every action sampled on the device from
+    `policy`, float32 `[n_states, 5]` weights per state - `rollout_trace()`'s dict plus 'actions'
+    and 'states'.  See `wide.WideGame.rollout_policy`; the other batched tiers raise
+    NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('rollout_policy() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.rollout_policy(policy, T, **kwargs)
+
+  def rollout_policy_buffers(self, T, want_states=True):
+    """State-table tier only: the dict of `rollout_policy(out=...)`, allocated once."""
+    if self._fused is None:
+      raise RuntimeError('rollout_policy_buffers() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.rollout_policy_buffers(T, want_states=want_states)
 
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs

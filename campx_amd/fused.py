@@ -221,18 +221,29 @@ class FusedGame(object):
     self._bad_idx_flag_view[0] = 0
     return n
 
+  def _take_bad_policy_rows(self):
+    """Environment-frames of rollout_policy() that met a bad policy row (the state-table tier
+    counts them beside the bad action ids, under the same flag); 0 on the other tiers."""
+    return 0
+
   def _raise_bad(self, indices=False):
-    """One ValueError for everything the kernels counted: action ids outside 0..4 and - when their
-    flag is up, or `indices` - rows of render_frames() outside the trace.  Both counters are read
-    before either is cleared, so neither is lost to the other's error."""
+    """One ValueError for everything the kernels counted: action ids outside 0..4, bad policy rows
+    met by rollout_policy() and - when their flag is up, or `indices` - rows of render_frames()
+    outside the trace.  Every counter is read before any is cleared, so none is lost to another's
+    error."""
     n = int(self._bad.item())          # synchronises: we are about to raise anyway
     rows = self._take_bad_indices() if indices or self._bad_idx_flag_view[0] else 0
+    policy_rows = self._take_bad_policy_rows()
     self._bad.zero_()
     self._bad_flag_view[0] = 0
     what = []
     if n:
       what.append('{} action ids are outside 0..{} (or came from rows that are not '
                   'exactly one-hot)'.format(n, gamespec.N_ACTIONS - 1))
+    if policy_rows:
+      what.append('{} environment-frames of rollout_policy() met bad policy rows (a weight that is '
+                  'negative or NaN, or a sum that is not a positive finite number); they took '
+                  'action {}'.format(policy_rows, gamespec.N_ACTIONS - 1))
     if rows:
       what.append('{} rows of render_frames() named a frame or an environment outside the '
                   'trace (they were rendered from the nearest one inside)'.format(rows))
@@ -620,6 +631,20 @@ class FusedGame(object):
     if validate:
       self._after_launch()
     return out
+
+  def _no_policy_rollouts(self, method):
+    raise NotImplementedError(
+        '{}() is offered by the state-table tier only, where a frame\'s state index is everything '
+        'a policy can read: call Engine.use_state_table() before its_showtime() to run this game '
+        'from its state table'.format(method))
+
+  def rollout_policy_buffers(self, T, want_states=True):
+    self._no_policy_rollouts('rollout_policy_buffers')
+
+  def rollout_policy(self, policy, T, seed=0, first_frame=None, reset_first=False, out=None,
+                     want_states=True):
+    """Closed-loop rollouts (`wide.WideGame.rollout_policy`): the state-table tier only."""
+    self._no_policy_rollouts('rollout_policy')
 
   def _gather_op(self, trace, t_idx, e_idx, out):
     _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,

@@ -179,6 +179,19 @@ class ShapeGame(object):
         'keyframes every fourth frame, not a self-contained description of each frame'
         .format(method))
 
+  def _no_policy_rollouts(self, method):
+    raise NotImplementedError(
+        '{}() is offered by the state-table tier only, where a frame\'s state index is everything '
+        'a policy can read (Engine.use_state_table() puts a game that can be tabulated there; the '
+        'shape tier\'s games of translating multi-cell things cannot)'.format(method))
+
+  def rollout_policy_buffers(self, T, want_states=True):
+    self._no_policy_rollouts('rollout_policy_buffers')
+
+  def rollout_policy(self, policy, T, seed=0, first_frame=None, reset_first=False, out=None,
+                     want_states=True):
+    self._no_policy_rollouts('rollout_policy')
+
   def rollout_trace_buffers(self, T):
     self._no_stored_trace('rollout_trace_buffers')
 

@@ -88,6 +88,9 @@ class WideGame(fused.FusedGame):
     self._perf_arg = self.perf if self.has_perf else None
     self._bad = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._onehot_bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    # environment-frames of rollout_policy() that met a bad policy row (raised with the bad ids)
+    self._bad_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._policy_frame = 0            # absolute frame the next rollout_policy() continues at
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._bad_flag_view = self._bad_flag.numpy()
     self.validate_actions = True
@@ -157,6 +160,99 @@ class WideGame(fused.FusedGame):
                          out['reward'], out['discount'], out['done'], out['perf'], out['trace'],
                          self._bad if validate else None, self._bad_flag if validate else None,
                          bool(reset_first))
+
+  # ------------------------------------------------------------ closed-loop rollouts
+
+  @property
+  def n_states(self):
+    """States of the game's table: the rows of a `rollout_policy()` policy."""
+    return int(self.spec.n_states)
+
+  def _take_bad_policy_rows(self):
+    n = int(self._bad_rows.item())
+    self._bad_rows.zero_()
+    return n
+
+  def rollout_policy_buffers(self, T, want_states=True):
+    """Allocate the dict of `rollout_policy(out=...)` once: `rollout_trace_buffers(T)` plus
+    'actions' int8 [T, B] and - `want_states` - 'states' int32 [T, B], rows padded alike."""
+    out = self.rollout_trace_buffers(T)
+    B = self.batch
+    pitch = (B + 15) // 16 * 16 if fused.PAD_ROWS else B
+    out['actions'] = torch.empty((T, pitch), dtype=torch.int8, device=self.device)[..., :B]
+    if want_states:
+      out['states'] = torch.empty((T, pitch), dtype=torch.int32, device=self.device)[..., :B]
+    return out
+
+  def rollout_policy(self, policy, T, seed=0, first_frame=None, reset_first=False, out=None,
+                     want_states=True):
+    """T frames of update pass in ONE launch, every action sampled on the device from `policy`:
+    the closed-loop form of `rollout_trace()`.
+
+    `policy` is a contiguous float32 `[n_states, 5]` tensor on the game's device: row s holds the
+    weights of the five actions in state s (a tabular softmax policy, an epsilon-greedy Q-table,
+    a network evaluated once on the game's states).  Weights need not be normalised; an action of
+    weight exactly 0 is never taken; a one-hot row is a deterministic policy.  A tensor that
+    requires grad is used through `.detach()`.  The row read is that of the state the frame
+    starts from - row 0 for an environment whose episode ended on the frame before.
+
+    Sampling (include/campx_hip.h has the rule in full) is counter-based: environment e at
+    absolute frame f draws word f & 3 of the Philox4x32-10 block of key `seed`, counter
+    (e, f >> 2).  `first_frame=None` continues a per-game frame counter - 0 at construction,
+    advanced by T with every call - so that two calls of T1 and T2 frames sample what one call of
+    T1 + T2 does; an explicit `first_frame` is used as given and sets the counter to
+    `first_frame + T`.
+
+    Returns `rollout_trace()`'s dict - 'trace', 'reward', 'discount', 'done', 'perf', same
+    shapes, dtypes and row padding - plus 'actions' int8 [T, B], the actions taken, and with
+    `want_states` 'states' int32 [T, B], the row each was sampled from.  For a learner
+    `log pi = torch.log(p[out['states'].long(), out['actions'].long()])` with
+    `p = policy / policy.sum(1, keepdim=True)` (differentiable in whatever `policy` was computed
+    from).  `render_frames()` on 'trace', or `rollout(out['actions'])` from the same start, gives
+    the observations.  `frame`, `ret` and the lazy error accounting are `rollout_trace()`'s: a
+    row with a negative or NaN weight, or whose sum is not a positive finite number, makes the
+    environment-frames that meet it take action 4 and raises ValueError - with their count -
+    from this call or a later one, or from `check_actions()`.
+    `out`: a dict from `rollout_policy_buffers(T, want_states)`, overwritten.
+    """
+    S = self.n_states
+    if (not torch.is_tensor(policy) or policy.dtype != torch.float32 or policy.dim() != 2
+        or tuple(policy.shape) != (S, gamespec.N_ACTIONS) or policy.device != self.device
+        or not policy.is_contiguous()):
+      got = ('{} {} on {}'.format(policy.dtype, list(policy.shape), policy.device)
+             if torch.is_tensor(policy) else type(policy).__name__)
+      raise ValueError('policy must be a contiguous float32 [{}, {}] tensor (n_states x actions) '
+                       'on {}, got {}'.format(S, gamespec.N_ACTIONS, self.device, got))
+    T = int(T)
+    if T < 1:
+      raise ValueError('a rollout needs at least one frame: T >= 1')
+    first = self._policy_frame if first_frame is None else int(first_frame)
+    if first < 0 or first + T >= 1 << 63:
+      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
+    seed = int(seed) & ((1 << 64) - 1)
+    if out is None:
+      out = self.rollout_policy_buffers(T, want_states)
+    else:
+      rows = [out.get('actions')] + ([out.get('states')] if want_states else [])
+      trace = out.get('trace')
+      if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.shape[1] != T
+          or any(not torch.is_tensor(r) or tuple(r.shape) != (T, self.batch)
+                 or (T > 1 and r.stride(0) != trace.stride(1)) for r in rows)):
+        raise ValueError('out must be a dict from rollout_policy_buffers({}, want_states={}) of '
+                         'this game ({} environments)'.format(T, bool(want_states), self.batch))
+    validate = self.validate_actions
+    _hip.ops.wide_policy_update(
+        self._spec_host, self._tables, self.state, self.done, self.ret, policy.detach(),
+        seed - (1 << 64) if seed >= 1 << 63 else seed, first, out['reward'], out['discount'],
+        out['done'], out['perf'], out['trace'], out['actions'],
+        out.get('states') if want_states else None, self._bad_rows if validate else None,
+        self._bad_flag if validate else None, bool(reset_first))
+    self._policy_frame = first + T
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if validate:
+      self._after_launch()
+    return out
 
   _trace_dtype = torch.int16
 

@@ -726,6 +726,41 @@ int32_t campx_wide_render_gather_launch(const CampxWideSpec* spec_host, const vo
 int32_t campx_wide_update_launch(const CampxWideSpec* spec_host, const void* tables_dev,
                                  CampxState state, const int8_t* actions, CampxOutputs out,
                                  int64_t B, int32_t T, int32_t reset_first, void* stream);
+/*
+ * ---- Closed-loop rollouts: actions sampled on the device from a per-state policy -------------
+ * campx_wide_update_launch() with the action stream replaced by a policy over the game's states,
+ * `policy` DEVICE float32 [n_states][5] (4-byte aligned): weights, not necessarily normalised.
+ * The whole T-frame episode, sampling included, is one launch (csrc/k_policy.hip).  No reference
+ * counterpart: the reference's drivers run their policy on the host, frame by frame
+ * (examples/reinforce.py:136-149).
+ *
+ * The sampling rule.  For environment e and absolute frame f = first_frame + t:
+ *   - one Philox4x32-10 block per environment and group of four frames: key (seed & 0xffffffff,
+ *     seed >> 32), counter (e, g & 0xffffffff, g >> 32, 0) with g = f >> 2, multipliers
+ *     0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85; frame f takes output
+ *     word f & 3, x;
+ *   - u = float(x >> 8) * 2^-24 (exact, in [0, 1));
+ *   - with w[0..4] the row of the state the frame STARTS from (row 0 for an environment whose
+ *     episode ended on the frame before): c0 = w0, c1 = c0 + w1, c2 = c1 + w2, c3 = c2 + w3,
+ *     c4 = c3 + w4, f32 sums in this order; r = u * c4, one f32 multiply;
+ *     action = (r >= c0) + (r >= c1) + (r >= c2) + (r >= c3).
+ * An action of weight exactly 0 is never taken; a one-hot row is a deterministic policy.  A row
+ * with a negative or NaN weight, or whose c4 is not a positive finite number, is BAD: the
+ * environment-frame that meets it takes action 4 and is counted into out.bad_count / out.bad_flag,
+ * as an action id outside 0..4 is.
+ *
+ * Writes what campx_wide_update_launch() writes (state, trace with every plane, the per-frame
+ * scalars, same row pitch), plus `actions_out` DEVICE int8 [T][pitch] - the actions taken - and,
+ * unless NULL, `states_out` DEVICE int32 [T][pitch] (4-byte aligned): the row each frame sampled
+ * from.  CAMPX_EINVAL: NULL, B <= 0 or above 2^32 - 1, T <= 0, first_frame < 0 or
+ * first_frame + T past 2^63 - 1, misaligned pointers, pitch < B, out.perf for a game without.
+ * Asynchronous on `stream`, no synchronisation, no library state.
+ */
+int32_t campx_wide_policy_update_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                        CampxState state, const float* policy, uint64_t seed,
+                                        int64_t first_frame, CampxOutputs out, int8_t* actions_out,
+                                        int32_t* states_out, int64_t B, int32_t T,
+                                        int32_t reset_first, void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
