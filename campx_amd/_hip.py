@@ -34,6 +34,8 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_update_launch', 'campx_wide_policy_update_launch',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
+           'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
+           'campx_returns_launch',
            'campx_check_actions_launch',
            'campx_onehot_to_ids_launch', 'campx_config_set', 'campx_config_get',
            'campx_config_string', 'campx_write_probe_launch', 'campx_strerror',
@@ -73,6 +75,17 @@ class CampxGather(ctypes.Structure):
               ('obs', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
               ('bad_flag', ctypes.c_void_p), ('streaming', ctypes.c_int32),
               ('reserved', ctypes.c_int32)]
+
+
+class CampxReturns(ctypes.Structure):
+  """include/campx_hip.h: the streams of one campx_returns_launch() call."""
+  _fields_ = [('reward', ctypes.c_void_p), ('done', ctypes.c_void_p), ('discount', ctypes.c_void_p),
+              ('values', ctypes.c_void_p), ('bootstrap', ctypes.c_void_p),
+              ('returns', ctypes.c_void_p), ('advantages', ctypes.c_void_p),
+              ('reward_pitch', ctypes.c_int64), ('done_pitch', ctypes.c_int64),
+              ('discount_pitch', ctypes.c_int64), ('values_pitch', ctypes.c_int64),
+              ('returns_pitch', ctypes.c_int64), ('advantages_pitch', ctypes.c_int64),
+              ('gamma', ctypes.c_float), ('lam', ctypes.c_float)]
 
 
 ERR_FLOW_TIMEOUT = 1
@@ -164,6 +177,13 @@ def _load():
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
   lib.campx_wide_render_gather_launch.argtypes = [wide_p, vp, gather_p, i64, vp]
+  lib.campx_wide_render_states_scratch_bytes.restype = i64
+  lib.campx_wide_render_states_scratch_bytes.argtypes = [wide_p, i64]
+  lib.campx_wide_render_states_launch.restype = i32
+  lib.campx_wide_render_states_launch.argtypes = [wide_p, vp, vp, i32, i64, vp, i32, vp, i64, vp, vp,
+                                                  vp]
+  lib.campx_returns_launch.restype = i32
+  lib.campx_returns_launch.argtypes = [ctypes.POINTER(CampxReturns), i64, i32, vp]
   lib.campx_render_gather_plan.restype = i32
   lib.campx_render_gather_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_check_actions_launch.restype = i32
@@ -214,7 +234,8 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'onehot_to_ids', 'check_actions')
+            'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'wide_render_states',
+            'returns', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

@@ -16,6 +16,8 @@
 //   campx::wide_policy_update       the same with every frame's action sampled on the device from a
 //                                   policy over the game's states (closed-loop rollouts)
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
+//   campx::wide_render_states       the observations of given states of a state-table game
+//   campx::returns                  discounted returns / GAE advantages of a rollout's streams
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -37,6 +39,7 @@
 #include <ATen/core/Tensor.h>
 #include <ATen/core/dispatch/Dispatcher.h>
 #include <ATen/core/stack.h>
+#include <ATen/ops/empty.h>
 #include <c10/core/impl/LocalDispatchKeySet.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -941,6 +944,103 @@ void wide_render_gather(const Tensor& spec_host, const Tensor& tables, const Ten
               });
 }
 
+// Wide tier: the observations of the states `state_ids` int32 / int64 [N] (None: all of them, row
+// i is state i) as `obs` [N, L, H, W] (campx_wide_render_states_launch).  `scratch`: the one-frame
+// trace the launch writes, any contiguous tensor of campx_wide_render_states_scratch_bytes() on
+// the device; None: allocated here (a caller that captures the op into a graph brings its own).
+void wide_render_states(const Tensor& spec_host, const Tensor& tables, const OptTensor& state_ids,
+                        Tensor& obs, const OptTensor& scratch, const OptTensor& bad_count,
+                        const OptTensor& bad_flag) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(tables.device().is_cuda(), "campx::wide_render_states: tables must be on a HIP device "
+              "(no CPU implementation)");
+  const c10::Device dev = tables.device();
+  TORCH_CHECK(tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  TORCH_CHECK(obs.dim() == 4 && obs.size(0) >= 1, "campx::wide_render_states: obs must be [N, L, H, W]");
+  const int64_t N = obs.size(0);
+  want(obs, "obs", obs.scalar_type(), dev, {N, hs->n_layers, hs->rows, hs->cols});
+  const int32_t format = obs_format_of(obs);
+  if (state_ids.has_value()) {
+    TORCH_CHECK(state_ids->scalar_type() == at::kLong || state_ids->scalar_type() == at::kInt,
+                "campx::wide_render_states: state_ids must be int64 or int32");
+    want(*state_ids, "state_ids", state_ids->scalar_type(), dev, {N});
+  }
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  const int64_t need = campx_wide_render_states_scratch_bytes(hs, N);
+  TORCH_CHECK(need > 0, "campx::wide_render_states: bad spec or row count");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  Tensor trace;
+  if (scratch.has_value()) {
+    TORCH_CHECK(scratch->device() == dev && scratch->is_contiguous() && (int64_t)scratch->nbytes() >= need,
+                "campx::wide_render_states: scratch must be a contiguous tensor of at least ", need,
+                " bytes on ", dev);
+    trace = *scratch;
+  } else {
+    trace = at::empty({need}, obs.options().dtype(at::kByte));
+  }
+  check_ok(campx_wide_render_states_launch(
+               hs, tables.data_ptr(), state_ids.has_value() ? state_ids->data_ptr() : nullptr,
+               state_ids.has_value() && state_ids->scalar_type() == at::kLong ? 1 : 0, N,
+               obs.data_ptr(), format, trace.data_ptr(), (int64_t)trace.nbytes(),
+               opt_ptr<int32_t>(bad_count), flag_ptr(bad_flag, dev),
+               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_render_states_launch");
+}
+
+// Discounted returns and GAE advantages of [T, B] streams (campx_returns_launch): every stream
+// contiguous within a row, rows any pitch >= B apart, each stream its own.
+void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTensor& discount,
+             const OptTensor& values, const OptTensor& bootstrap, double lam, Tensor& returns_out,
+             const OptTensor& advantages) {
+  TORCH_CHECK(reward.device().is_cuda() && reward.dim() == 2,
+              "campx::returns: reward must be a float32 [T, B] tensor on a HIP device (no CPU "
+              "implementation)");
+  const c10::Device dev = reward.device();
+  const int64_t T = reward.size(0), B = reward.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::returns: bad shape [", T, ", ", B, "]");
+  TORCH_CHECK(values.has_value() == advantages.has_value(),
+              "campx::returns: values and advantages come together");
+  auto rows = [&](const Tensor& t, const char* name, at::ScalarType dtype) -> int64_t {
+    TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
+    TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
+                t.scalar_type());
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
+                " must have shape [", T, ", ", B, "], it has ", t.sizes());
+    TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
+    TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
+                ", below its ", B, " columns");
+    return T == 1 ? B : t.stride(0);
+  };
+  CampxReturns r{};
+  r.reward_pitch = rows(reward, "reward", at::kFloat);
+  r.done_pitch = rows(done, "done", at::kByte);
+  if (discount.has_value()) r.discount_pitch = rows(*discount, "discount", at::kFloat);
+  if (values.has_value()) {
+    r.values_pitch = rows(*values, "values", at::kFloat);
+    r.advantages_pitch = rows(*advantages, "advantages", at::kFloat);
+  }
+  r.returns_pitch = rows(returns_out, "returns", at::kFloat);
+  if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, dev, {B});
+  r.reward = reinterpret_cast<const float*>(reward.data_ptr());
+  r.done = reinterpret_cast<const uint8_t*>(done.data_ptr());
+  r.discount = opt_ptr<const float>(discount);
+  r.values = opt_ptr<const float>(values);
+  r.bootstrap = opt_ptr<const float>(bootstrap);
+  r.returns = reinterpret_cast<float*>(returns_out.data_ptr());
+  r.advantages = opt_ptr<float>(advantages);
+  r.gamma = (float)gamma;
+  r.lam = (float)lam;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_returns_launch(&r, B, (int32_t)T,
+                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_returns_launch");
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -1013,6 +1113,10 @@ void wide_policy_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, con
                              const OptTensor&, const OptTensor&, bool) {}
 void render_gather_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
                         Tensor&, const OptTensor&, const OptTensor&, bool) {}
+void wide_render_states_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&,
+                             const OptTensor&, const OptTensor&) {}
+void returns_meta(const Tensor&, const Tensor&, double, const OptTensor&, const OptTensor&,
+                  const OptTensor&, double, Tensor&, const OptTensor&) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
 void check_actions_meta(const Tensor&, Tensor&) {}
 
@@ -1101,6 +1205,12 @@ TORCH_LIBRARY(campx, m) {
   m.def(
       "wide_render_gather(Tensor spec_host, Tensor tables, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
+  m.def(
+      "wide_render_states(Tensor spec_host, Tensor tables, Tensor? state_ids, Tensor(a!) obs, "
+      "Tensor(b!)? scratch, Tensor(c!)? bad_count, Tensor(d!)? bad_flag) -> ()");
+  m.def(
+      "returns(Tensor reward, Tensor done, float gamma, Tensor? discount, Tensor? values, "
+      "Tensor? bootstrap, float lam, Tensor(a!) returns, Tensor(b!)? advantages) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -1119,14 +1229,16 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_policy_update", &wide_policy_update);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
+  m.impl("wide_render_states", &wide_render_states);
+  m.impl("returns", &returns);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }
 
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
-                           "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "onehot_to_ids",
-                           "check_actions"})
+                           "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
+                           "returns", "onehot_to_ids", "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
@@ -1144,6 +1256,8 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("wide_policy_update", &wide_policy_update_meta);
   m.impl("render_gather", &render_gather_meta);
   m.impl("wide_render_gather", &render_gather_meta);
+  m.impl("wide_render_states", &wide_render_states_meta);
+  m.impl("returns", &returns_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);
   m.impl("check_actions", &check_actions_meta);
 }

@@ -484,6 +484,17 @@ class Engine(object):
                          'been through its_showtime()')
     return self._fused.rollout_policy_buffers(T, want_states=want_states)
 
+  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
+    """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
+    game's table (None: all of them), bit for bit what `play()` / `rollout()` show for an
+    environment in that state - what a network evaluated once per state is evaluated on.  See
+    `wide.WideGame.render_states`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('render_states() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.render_states(state_ids, obs_dtype=obs_dtype, out=out)
+
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
     `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See

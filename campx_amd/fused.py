@@ -226,6 +226,11 @@ class FusedGame(object):
     counts them beside the bad action ids, under the same flag); 0 on the other tiers."""
     return 0
 
+  def _take_bad_state_ids(self):
+    """Ids of render_states() outside the game's table (the state-table tier counts them under the
+    flag of render_frames()'s rows); 0 on the other tiers."""
+    return 0
+
   def _raise_bad(self, indices=False):
     """One ValueError for everything the kernels counted: action ids outside 0..4, bad policy rows
     met by rollout_policy() and - when their flag is up, or `indices` - rows of render_frames()
@@ -234,6 +239,7 @@ class FusedGame(object):
     n = int(self._bad.item())          # synchronises: we are about to raise anyway
     rows = self._take_bad_indices() if indices or self._bad_idx_flag_view[0] else 0
     policy_rows = self._take_bad_policy_rows()
+    state_ids = self._take_bad_state_ids()
     self._bad.zero_()
     self._bad_flag_view[0] = 0
     what = []
@@ -247,6 +253,9 @@ class FusedGame(object):
     if rows:
       what.append('{} rows of render_frames() named a frame or an environment outside the '
                   'trace (they were rendered from the nearest one inside)'.format(rows))
+    if state_ids:
+      what.append('{} state ids of render_states() are outside the game\'s table (they were '
+                  'rendered as state 0)'.format(state_ids))
     if what:
       raise ValueError('; '.join(what))
 
@@ -645,6 +654,10 @@ class FusedGame(object):
                      want_states=True):
     """Closed-loop rollouts (`wide.WideGame.rollout_policy`): the state-table tier only."""
     self._no_policy_rollouts('rollout_policy')
+
+  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
+    """Observations by state index (`wide.WideGame.render_states`): the state-table tier only."""
+    self._no_policy_rollouts('render_states')
 
   def _gather_op(self, trace, t_idx, e_idx, out):
     _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,

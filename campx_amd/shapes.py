@@ -192,6 +192,9 @@ class ShapeGame(object):
                      want_states=True):
     self._no_policy_rollouts('rollout_policy')
 
+  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
+    self._no_policy_rollouts('render_states')
+
   def rollout_trace_buffers(self, T):
     self._no_stored_trace('rollout_trace_buffers')
 

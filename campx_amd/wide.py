@@ -91,6 +91,11 @@ class WideGame(fused.FusedGame):
     # environment-frames of rollout_policy() that met a bad policy row (raised with the bad ids)
     self._bad_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._policy_frame = 0            # absolute frame the next rollout_policy() continues at
+    # ids of render_states() outside the table (raised with the rows of render_frames(), under
+    # their flag), and the one-frame trace of its out= calls: the last block is the largest; the
+    # smaller ones before it stay alive, a captured graph may still write into them
+    self._bad_state_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._states_scratch = []
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._bad_flag_view = self._bad_flag.numpy()
     self.validate_actions = True
@@ -252,6 +257,69 @@ class WideGame(fused.FusedGame):
     self.check_ok()
     if validate:
       self._after_launch()
+    return out
+
+  # ------------------------------------------------------------ observations by state
+
+  def _take_bad_state_ids(self):
+    n = int(self._bad_state_ids.item())
+    self._bad_state_ids.zero_()
+    return n
+
+  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
+    """The observations of states of the game's table, `[N, L, H, W]`: what a network that is
+    evaluated once per state - the policy of `rollout_policy()`, a critic - is evaluated on.
+
+    Row i is bit for bit the observation `play()` / `rollout()` show for an environment that is
+    in state `state_ids[i]`.  State 0 is the reset state: row 0 of `render_states()` is the
+    `its_showtime()` frame.  With `out = rollout_policy(...)`, `render_states(out['states'][t])`
+    are the observations frame t's actions were sampled from, and `render_states(game.state)`
+    the ones the rollout ended in.
+
+    Args:
+      state_ids: int32 or int64 `[N]` on the game's device, N >= 1; None: all states,
+          `arange(n_states)`.  Ids outside `[0, n_states)` are rendered as state 0 and counted on
+          the device; like bad actions they raise ValueError lazily - from a later call, or from
+          `check_actions()` - because this call does not synchronise.
+      obs_dtype: torch.int8 (0 / 1), torch.float16 or torch.bfloat16 (0.0 / 1.0).
+      out: a contiguous `[N, L, H, W]` tensor of such a dtype to write into.  The call is then
+          capturable in a HIP graph (no allocation, no host synchronisation: its scratch is kept
+          with the game).
+    """
+    L, H, W = self.n_layers, self.rows, self.cols
+    if state_ids is None:
+      ids, N = None, self.n_states
+    else:
+      ids = state_ids
+      if (not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1
+          or ids.numel() < 1 or ids.device != self.device):
+        got = ('{} {} on {}'.format(ids.dtype, list(ids.shape), ids.device)
+               if torch.is_tensor(ids) else type(ids).__name__)
+        raise ValueError('state_ids must be an int32 or int64 [N] tensor on {}, N >= 1 (or None for '
+                         'all {} states), got {}'.format(self.device, self.n_states, got))
+      ids = ids.contiguous()
+      N = int(ids.numel())
+    scratch = None
+    if out is None:
+      if obs_dtype not in fused._OBS_DTYPES:
+        raise ValueError('obs_dtype must be torch.int8, float16 or bfloat16')
+      out = torch.empty((N, L, H, W), dtype=obs_dtype, device=self.device)
+    else:
+      if (not torch.is_tensor(out) or tuple(out.shape) != (N, L, H, W)
+          or out.dtype not in fused._OBS_DTYPES or not out.is_contiguous()
+          or out.device != self.device):
+        raise ValueError('out must be a contiguous int8 / float16 / bfloat16 [{}, {}, {}, {}] tensor '
+                         'on {}'.format(N, L, H, W, self.device))
+      need = int(_hip.lib.campx_wide_render_states_scratch_bytes(ctypes.byref(self.spec), N))
+      if not self._states_scratch or self._states_scratch[-1].numel() < need:
+        self._states_scratch.append(torch.empty((need,), dtype=torch.uint8, device=self.device))
+      scratch = self._states_scratch[-1]
+    _hip.ops.wide_render_states(self._spec_host, self._tables, ids, out, scratch,
+                                self._bad_state_ids, self._bad_idx_flag)
+    if self.validate_actions == 'sync':
+      self._raise_bad(indices=True)
+    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
+      self._raise_bad()
     return out
 
   _trace_dtype = torch.int16

@@ -761,6 +761,68 @@ int32_t campx_wide_policy_update_launch(const CampxWideSpec* spec_host, const vo
                                         int64_t first_frame, CampxOutputs out, int8_t* actions_out,
                                         int32_t* states_out, int64_t B, int32_t T,
                                         int32_t reset_first, void* stream);
+/*
+ * ---- Observations by state index --------------------------------------------------------------
+ * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
+ * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
+ * in state state_ids[i] of the game's table: what a network evaluated once per state - the policy
+ * of campx_wide_policy_update_launch(), a critic - is evaluated on.  State 0 is the reset state.
+ * `state_ids` DEVICE int32 [N] (`ids64` = 0) or int64 [N] (`ids64` = 1); NULL: row i is state i.
+ * An id outside [0, n_states) is rendered as state 0 and counted into *bad_count (device int32,
+ * caller-zeroed, may be NULL); *bad_flag (device or mapped pinned int32, may be NULL) is set to 1.
+ *
+ * One small launch writes the states' trace entries - the rows of the table's `state_cells` -
+ * as a one-frame trace of N environments into `scratch` (DEVICE, 16-byte aligned, caller-owned,
+ * at least campx_wide_render_states_scratch_bytes(spec, N) bytes; its contents mean nothing
+ * afterwards); the rollout's render kernel then renders it (csrc/k_states.hip), in as many
+ * launches as keep rows x row bytes of each below 2^32 - 65536.  N is not bounded by that.
+ * CAMPX_EINVAL: NULL, N <= 0, misaligned pointers, a bad `obs_format`, too small a scratch.
+ * Asynchronous on `stream`, no synchronisation, no allocation, no library state.
+ */
+int64_t campx_wide_render_states_scratch_bytes(const CampxWideSpec* spec_host, int64_t N);
+int32_t campx_wide_render_states_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                        const void* state_ids, int32_t ids64, int64_t N, void* obs,
+                                        int32_t obs_format, void* scratch, int64_t scratch_bytes,
+                                        int32_t* bad_count, int32_t* bad_flag, void* stream);
+/*
+ * ---- Discounted returns and GAE advantages of a rollout, episode-aware ------------------------
+ * One backward pass over the [T][B] streams of any tier's rollout, in one launch
+ * (csrc/k_returns.hip).  Rollouts rebuild a finished environment in-kernel, so an episode may end
+ * anywhere inside one: nothing is carried across a frame whose `done` is set.  No reference
+ * counterpart: the reference's drivers play one episode at a time and sum on the host
+ * (examples/reinforce.py:96-99, examples/actor_critic.py:120-123).
+ *
+ * The rule.  f32 throughout, every operation rounded on its own (no fused multiply-add), so that
+ * a float32 restatement is bit-exact.  Per environment e, for t = T-1 down to 0:
+ *     r      = isnan(reward[t]) ? 0 : reward[t]          (NaN: the frame had no reward)
+ *     c      = gamma * discount[t]                       (gamma when `discount` is NULL)
+ *     G_next = t == T-1 ? bootstrap[e] : G[t+1]          (0 when `bootstrap` is NULL)
+ *     G[t]   = done[t] ? r : r + c * G_next
+ * and with `values` (the critic at the state each frame STARTS in):
+ *     v_next = t == T-1 ? bootstrap[e] : values[t+1]
+ *     delta  = (done[t] ? r : r + c * v_next) - values[t]
+ *     A[t]   = done[t] ? delta : delta + (c * lam) * A_next        (A_next = 0 past the last frame)
+ * G goes to `returns`, A to `advantages`.
+ *
+ * Every stream is DEVICE memory, rows contiguous, frame t's row `*_pitch` elements after frame
+ * t-1's (>= B; the padded rows of the rollout buffers are fine, each stream may have its own).
+ * `values` and `advantages` are both given or both NULL; `discount` and `bootstrap` (float32 [B])
+ * may be NULL.  CAMPX_EINVAL: NULL where it is not allowed, B <= 0, T <= 0, a pitch below B,
+ * float pointers that are not 4-byte aligned, gamma or lam not finite.
+ * Asynchronous on `stream`, no synchronisation, no library state.
+ */
+typedef struct CampxReturns {
+  const float* reward;        /* [T][reward_pitch] */
+  const uint8_t* done;        /* [T][done_pitch] */
+  const float* discount;      /* [T][discount_pitch], or NULL */
+  const float* values;        /* [T][values_pitch], or NULL */
+  const float* bootstrap;     /* [B], or NULL */
+  float* returns;             /* [T][returns_pitch] */
+  float* advantages;          /* [T][advantages_pitch]; NULL exactly when `values` is */
+  int64_t reward_pitch, done_pitch, discount_pitch, values_pitch, returns_pitch, advantages_pitch;
+  float gamma, lam;
+} CampxReturns;
+int32_t campx_returns_launch(const CampxReturns* returns, int64_t B, int32_t T, void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
