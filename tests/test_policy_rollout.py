@@ -13,7 +13,10 @@ The games:
                 on its state table by `use_state_table()`: 5 044 states, two planes.  Its table
                 (entries, trace entries and thresholds: 76 bytes per state, 383 KB) is past the
                 144 KiB that are staged in LDS, so it takes `wide_policy_update_kernel<false, ..>`,
-                which reads table and weights through L1 / L2.  The other three take the LDS path.
+                which reads table and weights through L1 / L2.  The others take the LDS path;
+  * variants    tests/random_pickups.py definition 12 (test_render_states.py's), a tide that turns
+                the whole floor: the scenery comes in VARIANTS, and which one shows is the trace's
+                second plane (two planes, no discount codes: the K = 2 plain chunks, in LDS).
 """
 
 import re
@@ -26,7 +29,7 @@ import policy_reference as ref
 
 pytestmark = pytest.mark.gpu
 
-GAMES = ['maze', 'boat_race', 'pickups', 'porter']
+GAMES = ['maze', 'boat_race', 'pickups', 'porter', 'variants']
 PORTER_BIG = ['############', '#P         #', '# X    #   #', '#      #   #', '#   ####   #',
               '#          #', '#      G   #', '#   #      #', '#   #      #', '############']
 
@@ -43,6 +46,9 @@ def _engine(name, B):
   if name == 'pickups':
     import random_pickups
     return random_pickups.builder(random_pickups.definitions()[3])(batch=B, device='cuda')
+  if name == 'variants':
+    import random_pickups
+    return random_pickups.builder(random_pickups.definitions()[12])(batch=B, device='cuda')
   import lanes_probes
   game = lanes_probes.ascii_art_to_game(
       PORTER_BIG, what_lies_beneath=' ', sprites={'P': lanes_probes.Porter},
@@ -58,6 +64,8 @@ def _game(name, B):
   game = _engine(name, B)
   game.its_showtime()
   assert isinstance(game.fused, wide.WideGame), type(game.fused)
+  if name == 'variants':
+    assert game.fused.spec.n_variants > 1 and game.fused._n_planes == game.fused.n_dyn + 1
   return game
 
 
