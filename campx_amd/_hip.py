@@ -36,6 +36,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
            'campx_returns_launch',
+           'campx_state_sums_launch', 'campx_state_sums_plan', 'campx_table_lookup_launch',
            'campx_check_actions_launch',
            'campx_onehot_to_ids_launch', 'campx_config_set', 'campx_config_get',
            'campx_config_string', 'campx_write_probe_launch', 'campx_strerror',
@@ -87,6 +88,30 @@ class CampxReturns(ctypes.Structure):
               ('returns_pitch', ctypes.c_int64), ('advantages_pitch', ctypes.c_int64),
               ('gamma', ctypes.c_float), ('lam', ctypes.c_float)]
 
+
+class CampxStateSums(ctypes.Structure):
+  """include/campx_hip.h: the streams and accumulators of one campx_state_sums_launch() call."""
+  _fields_ = [('states', ctypes.c_void_p), ('actions', ctypes.c_void_p),
+              ('values', ctypes.c_void_p * 4),
+              ('states_pitch', ctypes.c_int64), ('actions_pitch', ctypes.c_int64),
+              ('values_pitch', ctypes.c_int64 * 4), ('n_states', ctypes.c_int64),
+              ('n_actions', ctypes.c_int32), ('n_values', ctypes.c_int32),
+              ('frac_bits', ctypes.c_int32), ('accumulate', ctypes.c_int32),
+              ('path', ctypes.c_int32), ('reserved', ctypes.c_int32),
+              ('acc', ctypes.c_void_p), ('skipped', ctypes.c_void_p), ('clamped', ctypes.c_void_p)]
+
+
+class CampxTableLookup(ctypes.Structure):
+  """include/campx_hip.h: one campx_table_lookup_launch() call."""
+  _fields_ = [('table', ctypes.c_void_p), ('states', ctypes.c_void_p), ('actions', ctypes.c_void_p),
+              ('out', ctypes.c_void_p), ('states_pitch', ctypes.c_int64),
+              ('actions_pitch', ctypes.c_int64), ('out_pitch', ctypes.c_int64),
+              ('n_states', ctypes.c_int64), ('n_actions', ctypes.c_int32),
+              ('reserved', ctypes.c_int32), ('bad_count', ctypes.c_void_p)]
+
+
+SUMS_MAX_VALUES = 4
+SUMS_LDS_BUDGET = 49152
 
 ERR_FLOW_TIMEOUT = 1
 
@@ -184,6 +209,12 @@ def _load():
                                                   vp]
   lib.campx_returns_launch.restype = i32
   lib.campx_returns_launch.argtypes = [ctypes.POINTER(CampxReturns), i64, i32, vp]
+  lib.campx_state_sums_launch.restype = i32
+  lib.campx_state_sums_launch.argtypes = [ctypes.POINTER(CampxStateSums), i64, i32, vp]
+  lib.campx_state_sums_plan.restype = i32
+  lib.campx_state_sums_plan.argtypes = [i64, i32, i32, i64, i32, i32, i32, ctypes.POINTER(i64)]
+  lib.campx_table_lookup_launch.restype = i32
+  lib.campx_table_lookup_launch.argtypes = [ctypes.POINTER(CampxTableLookup), i64, i32, vp]
   lib.campx_render_gather_plan.restype = i32
   lib.campx_render_gather_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_check_actions_launch.restype = i32
@@ -235,7 +266,7 @@ def _load_ops():
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'wide_render_states',
-            'returns', 'onehot_to_ids', 'check_actions')
+            'returns', 'state_sums', 'table_lookup', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

@@ -18,6 +18,8 @@
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::returns                  discounted returns / GAE advantages of a rollout's streams
+//   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
+//   campx::table_lookup             table[states, actions] of a rollout's streams
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -1041,6 +1043,105 @@ void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTe
            "campx_returns_launch");
 }
 
+// A [T, B] stream of the two ops below: contiguous within a row, rows any pitch >= B apart.
+int64_t stream_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
+                    int64_t T, int64_t B) {
+  TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
+  TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
+              t.scalar_type());
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
+              " must have shape [", T, ", ", B, "], it has ", t.sizes());
+  TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
+  TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
+              ", below its ", B, " columns");
+  return T == 1 ? B : t.stride(0);
+}
+
+// Per-(state, action) fixed-point sums of [T, B] streams (campx_state_sums_launch): `raw` int64
+// [1 + K, n_states * n_actions] in any shape that is contiguous, the counters int64 of one element.
+void state_sums(const Tensor& states, const OptTensor& actions, at::TensorList values,
+                int64_t n_states, int64_t n_actions, int64_t frac_bits, bool accumulate,
+                int64_t path, Tensor& raw, Tensor& skipped, Tensor& clamped) {
+  TORCH_CHECK(states.device().is_cuda() && states.dim() == 2,
+              "campx::state_sums: states must be an int32 [T, B] tensor on a HIP device (no CPU "
+              "implementation)");
+  const c10::Device dev = states.device();
+  const int64_t T = states.size(0), B = states.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::state_sums: bad shape [", T, ", ", B, "]");
+  const int64_t K = (int64_t)values.size();
+  TORCH_CHECK(K <= CAMPX_SUMS_MAX_VALUES, "campx::state_sums: at most ", CAMPX_SUMS_MAX_VALUES,
+              " value streams, got ", K);
+  TORCH_CHECK(n_states >= 1 && n_states <= 0x7fffffff && n_actions >= 1 && n_actions <= 128 &&
+                  frac_bits >= 0 && frac_bits <= 62 && path >= 0 && path <= 2,
+              "campx::state_sums: bad n_states / n_actions / frac_bits / path");
+  CampxStateSums s{};
+  s.states_pitch = stream_rows(states, "states", at::kInt, dev, T, B);
+  if (actions.has_value()) s.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
+  for (int64_t k = 0; k < K; ++k) {
+    s.values_pitch[k] = stream_rows(values[k], "values", at::kFloat, dev, T, B);
+    s.values[k] = reinterpret_cast<const float*>(values[k].data_ptr());
+  }
+  TORCH_CHECK(raw.device() == dev && raw.scalar_type() == at::kLong && raw.is_contiguous() &&
+                  raw.numel() == (K + 1) * n_states * n_actions,
+              "campx::state_sums: raw must be a contiguous int64 tensor of ", K + 1, " x ", n_states,
+              " x ", n_actions, " elements on ", dev);
+  for (const Tensor* c : {&skipped, &clamped})
+    TORCH_CHECK(c->device() == dev && c->scalar_type() == at::kLong && c->numel() == 1,
+                "campx::state_sums: skipped and clamped must be int64 tensors of one element on ", dev);
+  s.states = reinterpret_cast<const int32_t*>(states.data_ptr());
+  s.actions = opt_ptr<const int8_t>(actions);
+  s.n_states = n_states;
+  s.n_actions = (int32_t)n_actions;
+  s.n_values = (int32_t)K;
+  s.frac_bits = (int32_t)frac_bits;
+  s.accumulate = accumulate ? 1 : 0;
+  s.path = (int32_t)path;
+  s.acc = reinterpret_cast<int64_t*>(raw.data_ptr());
+  s.skipped = reinterpret_cast<int64_t*>(skipped.data_ptr());
+  s.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_state_sums_launch(&s, B, (int32_t)T,
+                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_state_sums_launch");
+}
+
+// out[t, e] = table[states[t, e] * n_actions + actions[t, e]] (campx_table_lookup_launch); `table`
+// float32 [n_states] without actions, [n_states, n_actions] with.
+void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& actions, Tensor& out,
+                  const OptTensor& bad_count) {
+  TORCH_CHECK(states.device().is_cuda() && states.dim() == 2,
+              "campx::table_lookup: states must be an int32 [T, B] tensor on a HIP device (no CPU "
+              "implementation)");
+  const c10::Device dev = states.device();
+  const int64_t T = states.size(0), B = states.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::table_lookup: bad shape [", T, ", ", B, "]");
+  TORCH_CHECK(table.device() == dev && table.scalar_type() == at::kFloat && table.is_contiguous() &&
+                  table.dim() == (actions.has_value() ? 2 : 1) && table.numel() >= 1,
+              "campx::table_lookup: table must be a contiguous float32 [n_states",
+              actions.has_value() ? ", n_actions" : "", "] tensor on ", dev);
+  const int64_t S = table.size(0), A = actions.has_value() ? table.size(1) : 1;
+  TORCH_CHECK(S <= 0x7fffffff && A <= 128, "campx::table_lookup: table too large: ", table.sizes());
+  CampxTableLookup l{};
+  l.states_pitch = stream_rows(states, "states", at::kInt, dev, T, B);
+  if (actions.has_value()) l.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
+  l.out_pitch = stream_rows(out, "out", at::kFloat, dev, T, B);
+  if (bad_count.has_value())
+    TORCH_CHECK(bad_count->device() == dev && bad_count->scalar_type() == at::kLong &&
+                    bad_count->numel() == 1,
+                "campx::table_lookup: bad_count must be an int64 tensor of one element on ", dev);
+  l.table = reinterpret_cast<const float*>(table.data_ptr());
+  l.states = reinterpret_cast<const int32_t*>(states.data_ptr());
+  l.actions = opt_ptr<const int8_t>(actions);
+  l.out = reinterpret_cast<float*>(out.data_ptr());
+  l.n_states = S;
+  l.n_actions = (int32_t)A;
+  l.bad_count = opt_ptr<int64_t>(bad_count);
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_table_lookup_launch(&l, B, (int32_t)T,
+                                     c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_table_lookup_launch");
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -1117,6 +1218,9 @@ void wide_render_states_meta(const Tensor&, const Tensor&, const OptTensor&, Ten
                              const OptTensor&, const OptTensor&) {}
 void returns_meta(const Tensor&, const Tensor&, double, const OptTensor&, const OptTensor&,
                   const OptTensor&, double, Tensor&, const OptTensor&) {}
+void state_sums_meta(const Tensor&, const OptTensor&, at::TensorList, int64_t, int64_t, int64_t, bool,
+                     int64_t, Tensor&, Tensor&, Tensor&) {}
+void table_lookup_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
 void check_actions_meta(const Tensor&, Tensor&) {}
 
@@ -1211,6 +1315,13 @@ TORCH_LIBRARY(campx, m) {
   m.def(
       "returns(Tensor reward, Tensor done, float gamma, Tensor? discount, Tensor? values, "
       "Tensor? bootstrap, float lam, Tensor(a!) returns, Tensor(b!)? advantages) -> ()");
+  m.def(
+      "state_sums(Tensor states, Tensor? actions, Tensor[] values, int n_states, int n_actions, "
+      "int frac_bits, bool accumulate, int path, Tensor(a!) raw, Tensor(b!) skipped, "
+      "Tensor(c!) clamped) -> ()");
+  m.def(
+      "table_lookup(Tensor table, Tensor states, Tensor? actions, Tensor(a!) out, "
+      "Tensor(b!)? bad_count) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -1231,6 +1342,8 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);
   m.impl("returns", &returns);
+  m.impl("state_sums", &state_sums);
+  m.impl("table_lookup", &table_lookup);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }
@@ -1238,7 +1351,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
                            "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
-                           "returns", "onehot_to_ids", "check_actions"})
+                           "returns", "state_sums", "table_lookup", "onehot_to_ids", "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
@@ -1258,6 +1371,8 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("wide_render_gather", &render_gather_meta);
   m.impl("wide_render_states", &wide_render_states_meta);
   m.impl("returns", &returns_meta);
+  m.impl("state_sums", &state_sums_meta);
+  m.impl("table_lookup", &table_lookup_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);
   m.impl("check_actions", &check_actions_meta);
 }

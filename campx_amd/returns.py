@@ -13,6 +13,13 @@ is tier-agnostic: it takes the `[T, B]` streams of `rollout()`, `rollout_trace()
 
 The rule is in include/campx_hip.h next to the sampling rule; tests/returns_reference.py restates
 it in numpy float32, bit for bit.  No CPU path.
+
+The learner's half of such an episode is here too.  Everything a tabular loss needs from the
+`[T, B]` streams is a sum per (state, action): `sum_by_state()` is that reduction in one launch, in
+64-bit fixed point - order-independent, so bitwise reproducible - and `table_lookup()` is the
+`table[states, actions]` gather without the two int64 copies of the streams, differentiable in the
+table through `sum_by_state()` (csrc/k_sums.hip, `campx::state_sums`, `campx::table_lookup`;
+tests/state_sums_reference.py restates the rule in numpy).
 """
 
 import math
@@ -104,3 +111,184 @@ def discounted_returns(reward, done, gamma, discount=None, values=None, bootstra
   _hip.ops.returns(reward, done, float(gamma), discount, values, bootstrap, float(lam),
                    out['returns'], out['advantages'] if values is not None else None)
   return out if set(out) == set(want) else {k: out[k] for k in want}
+
+
+# ------------------------------------------------------------------ per-state sums and lookups
+
+def _sums_streams(states, actions, fn):
+  """Checks the index streams of `sum_by_state()` / `table_lookup()`; returns (T, B, device)."""
+  _rows(states, 'states', torch.int32, None, None, None)
+  T, B = int(states.shape[0]), int(states.shape[1])
+  device = states.device
+  if device.type != 'cuda':
+    raise ValueError('states must be on a HIP device, it is on {} (there is no CPU path)'.format(device))
+  if T > 0x7fffffff or B > 1 << 31:
+    raise ValueError('{}: [T, B] = {} is too large'.format(fn, [T, B]))
+  if actions is not None:
+    _rows(actions, 'actions', torch.int8, T, B, device)
+  return T, B, device
+
+
+def _count_arg(x, name, low, high):
+  if isinstance(x, bool) or not isinstance(x, int) or not low <= x <= high:
+    raise ValueError('{} must be an integer in [{}, {}], got {!r}'.format(name, low, high, x))
+  return x
+
+
+def sums_limits(T, B):
+  """(n2, largest frac_bits) of the fixed-point rule for N = T * B frames: n2 = ceil(log2(N)),
+  a value is clamped to +-2^(62 - n2) quanta and frac_bits may be at most 62 - n2."""
+  n2 = (int(T) * int(B) - 1).bit_length()
+  return n2, 62 - n2
+
+
+def sum_by_state(states, actions=None, values=(), n_states=None, n_actions=5, frac_bits=24,
+                 accumulate=False, out=None, path=0):
+  """Count and sum `[T, B]` streams per (state, action) - or per state - in one launch.
+
+  The rule (include/campx_hip.h), in 64-bit fixed point so that the result does not depend on the
+  order of the additions and is bitwise reproducible.  With f = `frac_bits` and N = T * B:
+
+      n2    = ceil(log2(N))                     lim = 2^(62 - n2); f <= 62 - n2 is required
+      q     = llrint(double(x) * 2^f)           round to nearest even; the product is exact
+      q     = 0, counted in 'clamped'           if x is NaN
+      q     = +-lim, counted in 'clamped'       if |double(x) * 2^f| > lim (+-Inf included)
+      bin   = states[t, e] * n_actions + actions[t, e]      (n_actions = 1 without `actions`)
+      raw[0][bin]     += 1
+      raw[1 + k][bin] += q_k                    for each of the K value streams
+
+  A frame whose state is outside [0, n_states) or whose action is outside [0, n_actions) adds
+  nothing and is counted in 'skipped' (its values are not looked at).  N additions of at most lim
+  cannot overflow an int64.  Without clamping, sums[k] is within count * 2^-(f + 1) of the exact sum.
+
+  Args:
+    states: int32 `[T, B]`, e.g. `rollout_policy()`'s 'states'.
+    actions: int8 `[T, B]` ('actions'), or None: sums per state, results without the action axis.
+    values: up to 4 float32 `[T, B]` streams (returns, advantages, their squares ...).  A stream
+        that requires grad is used through `.detach()`.
+    n_states: rows of the table the states index (`Engine.n_states`), 1 .. 2^31 - 1.
+    n_actions: 1 .. 128; ignored (1) when `actions` is None.
+    frac_bits: f above, 0 .. 62 - n2.
+    accumulate: add onto `out` instead of overwriting it: several rollouts reduced into one step
+        (the no-overflow bound holds per call).  Needs `out`.
+    out: a dict with 'raw' int64 `[K + 1, n_states, n_actions]` (`[K + 1, n_states]` without
+        actions), contiguous, and 'skipped' and 'clamped', int64 tensors of one element; the call
+        allocates nothing the accumulators need and is capturable in a HIP graph.
+    path: 0 lets the library choose where the accumulators live, 1 forces LDS (ValueError when
+        they do not fit), 2 global memory.  By the rule, no bit of the result depends on it.
+
+  Every `[T, B]` tensor lives on one HIP device with `stride(1) == 1` and any row pitch >= B, each
+  its own.  Returns a dict: 'count' int64 `[n_states, n_actions]` (a view of raw[0]), 'sums'
+  float64 `[K, n_states, n_actions]` = raw[1:] * 2^-f, 'raw' the accumulators themselves, 'skipped'
+  and 'clamped' device int64 scalars - reading them is the caller's synchronisation.  Argument
+  errors raise ValueError before anything is launched.  No CPU path.
+  """
+  T, B, device = _sums_streams(states, actions, 'sum_by_state')
+  if not isinstance(values, (tuple, list)):
+    raise ValueError('values must be a tuple of float32 [T, B] tensors, got {}'.format(type(values).__name__))
+  K = len(values)
+  if K > _hip.SUMS_MAX_VALUES:
+    raise ValueError('at most {} value streams, got {}'.format(_hip.SUMS_MAX_VALUES, K))
+  for k, v in enumerate(values):
+    _rows(v, 'values[{}]'.format(k), torch.float32, T, B, device)
+  values = [v.detach() for v in values]
+  S = _count_arg(n_states, 'n_states', 1, 0x7fffffff)
+  A = 1 if actions is None else _count_arg(n_actions, 'n_actions', 1, 128)
+  n2, most = sums_limits(T, B)
+  _count_arg(frac_bits, 'frac_bits (N = T * B = {}, n2 = {})'.format(T * B, n2), 0, most)
+  _count_arg(path, 'path', 0, 2)
+  if path == 1 and S * A * (K + 1) * 8 > _hip.SUMS_LDS_BUDGET:
+    raise ValueError('path=1: {} accumulators of 8 bytes do not fit the LDS budget of {} bytes'.format(
+        S * A * (K + 1), _hip.SUMS_LDS_BUDGET))
+  shape = (K + 1, S) + (() if actions is None else (A,))
+  if out is None:
+    if accumulate:
+      raise ValueError('accumulate=True adds onto out: pass the dict of an earlier call')
+    counters = torch.empty((2,), dtype=torch.int64, device=device)
+    out = {'raw': torch.empty(shape, dtype=torch.int64, device=device),
+           'skipped': counters[0], 'clamped': counters[1]}
+  else:
+    if not isinstance(out, dict):
+      raise ValueError("out must be a dict: 'raw' int64 {}, 'skipped' and 'clamped' int64 scalars".format(
+          list(shape)))
+    raw = out.get('raw')
+    if (not torch.is_tensor(raw) or raw.dtype != torch.int64 or tuple(raw.shape) != shape
+        or raw.device != device or not raw.is_contiguous()):
+      raise ValueError("out['raw'] must be a contiguous int64 {} tensor on {}, got {}".format(
+          list(shape), device,
+          '{} {} on {}'.format(raw.dtype, list(raw.shape), raw.device) if torch.is_tensor(raw)
+          else type(raw).__name__))
+    for k in ('skipped', 'clamped'):
+      c = out.get(k)
+      if (not torch.is_tensor(c) or c.dtype != torch.int64 or c.numel() != 1 or c.device != device):
+        raise ValueError("out['{}'] must be an int64 tensor of one element on {}".format(k, device))
+  raw = out['raw']
+  _hip.ops.state_sums(states, actions, values, S, A, int(frac_bits), bool(accumulate), int(path),
+                      raw, out['skipped'], out['clamped'])
+  return {'count': raw[0], 'sums': raw[1:].double() * 2.0 ** -frac_bits, 'raw': raw,
+          'skipped': out['skipped'].view(()), 'clamped': out['clamped'].view(())}
+
+
+class _TableLookup(torch.autograd.Function):
+  """`table_lookup()`: the forward is campx::table_lookup, the backward one `sum_by_state()`."""
+
+  @staticmethod
+  def forward(ctx, table, states, actions, bad_count):
+    T, B = states.shape
+    x = torch.empty((T, B), dtype=torch.float32, device=states.device)
+    _hip.ops.table_lookup(table.detach(), states, actions, x, bad_count)
+    ctx.save_for_backward(states, *(() if actions is None else (actions,)))
+    ctx.table_shape = tuple(table.shape)
+    return x
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    if not ctx.needs_input_grad[0]:
+      return None, None, None, None
+    states = ctx.saved_tensors[0]
+    actions = ctx.saved_tensors[1] if len(ctx.saved_tensors) > 1 else None
+    T, B = states.shape
+    grad_out = grad_out.detach()
+    if grad_out.dtype != torch.float32:
+      grad_out = grad_out.float()
+    if (B > 1 and grad_out.stride(1) != 1) or (T > 1 and grad_out.stride(0) < B):
+      grad_out = grad_out.contiguous()             # (a broadcast gradient: `x.sum().backward()`)
+    S = ctx.table_shape[0]
+    A = ctx.table_shape[1] if actions is not None else 1
+    sums = sum_by_state(states, actions, values=(grad_out,), n_states=S, n_actions=A,
+                        frac_bits=min(24, sums_limits(T, B)[1]))
+    return sums['sums'][0].float(), None, None, None
+
+
+def table_lookup(table, states, actions=None, bad_count=None):
+  """`table[states, actions]` of a rollout's streams as they are: float32 `[T, B]`, one launch.
+
+  `x[t, e] = table[states[t, e], actions[t, e]]` (`table[states[t, e]]` when `actions` is None),
+  what `table[states.long(), actions.long()]` computes, without the two int64 copies of the
+  streams.  Differentiable in `table`: the backward is
+  `sum_by_state(states, actions, values=(grad_out,))['sums'][0].float()` - the per-bin sum of the
+  incoming gradient by `sum_by_state()`'s fixed-point rule (frac_bits 24), bitwise reproducible,
+  where the advanced index accumulates float32 in arrival order.
+
+  Args:
+    table: float32 `[n_states, n_actions]` (n_actions <= 128), or `[n_states]` when `actions` is
+        None; contiguous, on the streams' device.
+    states: int32 `[T, B]`; actions: int8 `[T, B]` or None - `stride(1) == 1`, any row pitch >= B.
+    bad_count: an int64 tensor of one element on the device, or None.  A frame whose state or
+        action is out of range gets 0.0 (and no gradient) and is added to it.
+
+  Argument errors raise ValueError before anything is launched.  No CPU path.
+  """
+  T, B, device = _sums_streams(states, actions, 'table_lookup')
+  want_dim = 1 if actions is None else 2
+  if (not torch.is_tensor(table) or table.dtype != torch.float32 or table.dim() != want_dim
+      or table.device != device or not table.is_contiguous() or table.numel() < 1
+      or table.shape[0] > 0x7fffffff or (want_dim == 2 and table.shape[1] > 128)):
+    raise ValueError('table must be a contiguous float32 {} tensor on {}, got {}'.format(
+        '[n_states]' if actions is None else '[n_states, n_actions <= 128]', device,
+        '{} {} on {}'.format(table.dtype, list(table.shape), table.device) if torch.is_tensor(table)
+        else type(table).__name__))
+  if bad_count is not None and (not torch.is_tensor(bad_count) or bad_count.dtype != torch.int64
+                                or bad_count.numel() != 1 or bad_count.device != device):
+    raise ValueError('bad_count must be an int64 tensor of one element on {}'.format(device))
+  return _TableLookup.apply(table, states, actions, bad_count)

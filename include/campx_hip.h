@@ -823,6 +823,106 @@ typedef struct CampxReturns {
   float gamma, lam;
 } CampxReturns;
 int32_t campx_returns_launch(const CampxReturns* returns, int64_t B, int32_t T, void* stream);
+/*
+ * ---- Per-state sums of a rollout's streams: the learner's gradient in one launch -------------
+ * Everything a tabular loss needs from the [T][B] streams of a rollout is a sum per (state,
+ * action): the gradient of  sum_t f(table[s_t, a_t]) * w_t  with respect to `table` is
+ * f'(table[s, a]) * (sum of w_t over the frames with s_t = s, a_t = a); a squared critic loss
+ * needs n_s, sum G and sum G^2 per state.  One reduction (csrc/k_sums.hip) over the streams as the
+ * rollout wrote them - int32 states, int8 actions, padded rows - gives those sums, for any tier.
+ * No reference counterpart.
+ *
+ * The rule.  Sums are accumulated in 64-bit FIXED POINT, so the result does not depend on the
+ * order of the additions and is bitwise reproducible (float atomics are not).  For a value stream
+ * x (float32), frac_bits = f and N = T * B:
+ *     n2    = ceil(log2(N))                     (0 for N = 1)
+ *     lim   = 2^(62 - n2)                       in quantised units; 62 - n2 - f >= 0 is required
+ *     d     = double(x) * 2^f                   (exact in double)
+ *     q     = llrint(d)                         round to nearest, ties to even
+ *     q     = 0, counted in `clamped`           if x is NaN
+ *     q     = +lim / -lim, counted in `clamped` if |d| > lim   (+Inf / -Inf included)
+ *     bin   = states[t][e] * n_actions + actions[t][e]     (n_actions = 1 and no action stream
+ *                                                           when `actions` is NULL)
+ *     acc[0][bin]     += 1
+ *     acc[1 + k][bin] += q_k                    for each of the K = n_values value streams
+ * A frame whose state is outside [0, n_states) or whose action is outside [0, n_actions) adds
+ * nothing anywhere and is counted in `skipped`; its values are not looked at (so they are never
+ * counted in `clamped`).  N additions of magnitude at most lim cannot overflow an int64, so every
+ * kernel structure that performs these additions - in any order, with any privatisation -
+ * produces the same 64-bit integers.  The float value of a sum is acc * 2^-f; each contribution was
+ * rounded once, by at most half a quantum: |sum - exact| <= acc[0][bin] * 2^-(f+1) without clamping.
+ * tests/state_sums_reference.py restates the rule in numpy.
+ *
+ * Streams are DEVICE memory, rows contiguous, frame t's row `*_pitch` elements after frame t-1's
+ * (>= B, each stream its own).  `acc` is DEVICE int64 [1 + n_values][n_states * n_actions],
+ * 8-byte aligned; `skipped` and `clamped` are DEVICE int64 scalars, 8-byte aligned.  Unless
+ * `accumulate` is set the three are zeroed first, by one kernel on `stream` (the call stays
+ * capturable, and a captured graph holds kernel nodes only); with `accumulate` the call adds onto them - the no-overflow bound above then holds
+ * per call, and keeping the total of several calls inside an int64 is the caller's business.
+ *
+ * Two accumulation paths, `path`: 1 = the accumulators live in LDS - `copies` of them, selected by
+ * lane, so that the lanes of a wave that land in one bin do not all queue on one LDS address -
+ * take 64-bit LDS atomic adds, and each workgroup ends by folding its copies and adding its
+ * non-zero bins to `acc` with global 64-bit atomics; 2 = every lane adds straight into `acc` with
+ * no-return global 64-bit atomics (tables too large for LDS; contention is low there).
+ * 0 = chosen by arithmetic: the LDS path when the accumulators fit and a workgroup's flush
+ * (bins x planes atomics) is small against the frames it reduces, else global.  By the rule the
+ * choice cannot change a bit of the result.
+ *
+ * campx_state_sums_plan() is that arithmetic, pure host code (nothing is launched): plan_out[8] =
+ * the path taken (1 / 2); copies (1 on the global path); workgroups along B; workgroups along T;
+ * frames per workgroup; dynamic LDS bytes (0 on the global path); n2; 62 - n2.  CAMPX_EINVAL:
+ * n_states < 1 or above 2^31 - 1, n_actions outside 1..128, n_values outside 0..4, B <= 0 or above
+ * 2^31, T <= 0, frac_bits < 0 or 62 - n2 - frac_bits < 0, a `path` outside 0..2, path 1 for
+ * accumulators that do not fit LDS.  campx_state_sums_launch() returns CAMPX_EINVAL for the same
+ * and for: NULL where it is not allowed (`actions` may be NULL exactly when n_actions == 1 is
+ * meant without an action stream; values[k] for k >= n_values are ignored), misaligned pointers,
+ * a pitch below B.  Asynchronous on `stream`, no synchronisation, no library state.
+ */
+#define CAMPX_SUMS_MAX_VALUES 4
+#define CAMPX_SUMS_LDS_BUDGET 49152   /* bytes of LDS accumulators (all copies) a workgroup may hold */
+typedef struct CampxStateSums {
+  const int32_t* states;      /* [T][states_pitch] */
+  const int8_t* actions;      /* [T][actions_pitch], or NULL */
+  const float* values[CAMPX_SUMS_MAX_VALUES];     /* each [T][values_pitch[k]] */
+  int64_t states_pitch, actions_pitch, values_pitch[CAMPX_SUMS_MAX_VALUES];
+  int64_t n_states;
+  int32_t n_actions;
+  int32_t n_values;           /* K */
+  int32_t frac_bits;
+  int32_t accumulate;         /* != 0: add onto acc / skipped / clamped */
+  int32_t path;               /* 0 = by arithmetic, 1 = LDS, 2 = global */
+  int32_t reserved;
+  int64_t* acc;               /* [1 + K][n_states * n_actions]; plane 0 is the count */
+  int64_t* skipped;
+  int64_t* clamped;
+} CampxStateSums;
+int32_t campx_state_sums_launch(const CampxStateSums* sums, int64_t B, int32_t T, void* stream);
+int32_t campx_state_sums_plan(int64_t n_states, int32_t n_actions, int32_t n_values, int64_t B,
+                              int32_t T, int32_t frac_bits, int32_t path, int64_t* plan_out);
+/*
+ * out[t][e] = table[states[t][e] * n_actions + actions[t][e]], float32 (csrc/k_sums.hip): what a
+ * learner otherwise writes as two int64 copies of the streams and an advanced index.  Same stream
+ * types and pitches as above (`actions` NULL: n_actions = 1); `table` DEVICE float32
+ * [n_states * n_actions], staged in LDS when it fits and is small against the frames a workgroup
+ * looks up, read through the caches otherwise.  A frame whose state or action is out of range
+ * gets 0.0 and is counted into *bad_count (DEVICE int64, 8-byte aligned, added to, may be NULL).
+ * CAMPX_EINVAL: NULL, bad sizes as above, misaligned pointers, a pitch below B.  Asynchronous on
+ * `stream`, no synchronisation, no library state.
+ */
+typedef struct CampxTableLookup {
+  const float* table;         /* [n_states * n_actions] */
+  const int32_t* states;      /* [T][states_pitch] */
+  const int8_t* actions;      /* [T][actions_pitch], or NULL */
+  float* out;                 /* [T][out_pitch] */
+  int64_t states_pitch, actions_pitch, out_pitch;
+  int64_t n_states;
+  int32_t n_actions;
+  int32_t reserved;
+  int64_t* bad_count;
+} CampxTableLookup;
+int32_t campx_table_lookup_launch(const CampxTableLookup* lookup, int64_t B, int32_t T,
+                                  void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
