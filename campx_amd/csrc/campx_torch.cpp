@@ -20,6 +20,7 @@
 //   campx::returns                  discounted returns / GAE advantages of a rollout's streams
 //   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
 //   campx::table_lookup             table[states, actions] of a rollout's streams
+//   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -1142,6 +1143,50 @@ void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& ac
            "campx_table_lookup_launch");
 }
 
+// Sweeps of the Bellman backup over the state table (campx_wide_sweeps_launch): `policy` float32
+// [n_states, 5] for the value of a policy, None for value iteration; as many sweeps as `residual`
+// has elements.  `values_in` may be `values_out`.
+void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor& policy,
+                 const OptTensor& reward, double gamma, const Tensor& values_in, Tensor& values_out,
+                 const OptTensor& scratch, const OptTensor& q, const OptTensor& greedy,
+                 Tensor& residual, const OptTensor& bad_rows, const OptTensor& bad_flag,
+                 int64_t path) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(values_out.device().is_cuda(),
+              "campx::wide_sweeps: values_out must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = values_out.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  if (policy.has_value()) want(*policy, "policy", at::kFloat, dev, {S, A});
+  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
+  want(values_in, "values_in", at::kFloat, dev, {S});
+  want(values_out, "values_out", at::kFloat, dev, {S});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, {S});
+  if (q.has_value()) want(*q, "q", at::kFloat, dev, {S, A});
+  if (greedy.has_value()) want(*greedy, "greedy", at::kChar, dev, {S});
+  TORCH_CHECK(residual.device() == dev && residual.scalar_type() == at::kFloat && residual.dim() == 1 &&
+                  residual.is_contiguous() && residual.numel() >= 1 && residual.numel() <= (1 << 20),
+              "campx::wide_sweeps: residual must be a contiguous float32 [sweeps] tensor on ", dev,
+              ", 1 <= sweeps <= 2^20");
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_sweeps: path must be 0, 1 or 2");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_wide_sweeps_launch(
+               hs, tables.data_ptr(), opt_ptr<const float>(policy), opt_ptr<const float>(reward),
+               (float)gamma, reinterpret_cast<const float*>(values_in.data_ptr()),
+               reinterpret_cast<float*>(values_out.data_ptr()), opt_ptr<float>(scratch),
+               opt_ptr<float>(q), opt_ptr<int8_t>(greedy),
+               reinterpret_cast<float*>(residual.data_ptr()), opt_ptr<int32_t>(bad_rows),
+               flag_ptr(bad_flag, dev), (int32_t)residual.numel(), (int32_t)path,
+               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_sweeps_launch");
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -1221,6 +1266,9 @@ void returns_meta(const Tensor&, const Tensor&, double, const OptTensor&, const 
 void state_sums_meta(const Tensor&, const OptTensor&, at::TensorList, int64_t, int64_t, int64_t, bool,
                      int64_t, Tensor&, Tensor&, Tensor&) {}
 void table_lookup_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&) {}
+void wide_sweeps_meta(const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, double,
+                      const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
+                      Tensor&, const OptTensor&, const OptTensor&, int64_t) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
 void check_actions_meta(const Tensor&, Tensor&) {}
 
@@ -1322,6 +1370,11 @@ TORCH_LIBRARY(campx, m) {
   m.def(
       "table_lookup(Tensor table, Tensor states, Tensor? actions, Tensor(a!) out, "
       "Tensor(b!)? bad_count) -> ()");
+  m.def(
+      "wide_sweeps(Tensor spec_host, Tensor tables, Tensor? policy, Tensor? reward, float gamma, "
+      "Tensor values_in, Tensor(a!) values_out, Tensor(b!)? scratch, Tensor(c!)? q, "
+      "Tensor(d!)? greedy, Tensor(e!) residual, Tensor(f!)? bad_rows, Tensor(g!)? bad_flag, "
+      "int path) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -1344,6 +1397,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("returns", &returns);
   m.impl("state_sums", &state_sums);
   m.impl("table_lookup", &table_lookup);
+  m.impl("wide_sweeps", &wide_sweeps);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }
@@ -1351,7 +1405,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
                            "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
-                           "returns", "state_sums", "table_lookup", "onehot_to_ids", "check_actions"})
+                           "returns", "state_sums", "table_lookup", "wide_sweeps", "onehot_to_ids", "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
@@ -1373,6 +1427,7 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("returns", &returns_meta);
   m.impl("state_sums", &state_sums_meta);
   m.impl("table_lookup", &table_lookup_meta);
+  m.impl("wide_sweeps", &wide_sweeps_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);
   m.impl("check_actions", &check_actions_meta);
 }

@@ -495,6 +495,33 @@ class Engine(object):
                          'been through its_showtime()')
     return self._fused.render_states(state_ids, obs_dtype=obs_dtype, out=out)
 
+  def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
+    """State-table tier only: the exact value of `policy`, float32 `[n_states, 5]` weights per
+    state, after `sweeps` Jacobi sweeps of the Bellman backup over the game's table - 'values',
+    'q', 'residual', 'sweeps'.  See `wide.WideGame.evaluate_policy`; the other batched tiers raise
+    NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('evaluate_policy() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.evaluate_policy(policy, gamma, sweeps, **kwargs)
+
+  def value_iteration(self, gamma, sweeps, **kwargs):
+    """State-table tier only: `sweeps` sweeps of value iteration over the game's table - 'values',
+    'q', 'greedy', 'residual', 'sweeps'.  See `wide.WideGame.value_iteration`; the other batched
+    tiers raise NotImplementedError."""
+    if self._fused is None:
+      raise RuntimeError('value_iteration() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.value_iteration(gamma, sweeps, **kwargs)
+
+  def table_arrays(self):
+    """State-table tier only: the game's table as device tensors `[n_states, 5]` - 'next_state',
+    'reward', 'done', 'discount', 'perf'.  See `wide.WideGame.table_arrays`."""
+    if self._fused is None:
+      raise RuntimeError('table_arrays() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.table_arrays()
+
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
     `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See

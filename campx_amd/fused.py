@@ -226,6 +226,11 @@ class FusedGame(object):
     counts them beside the bad action ids, under the same flag); 0 on the other tiers."""
     return 0
 
+  def _take_bad_plan_rows(self):
+    """Bad rows of the policies given to evaluate_policy() (the state-table tier counts them under
+    the flag of the bad action ids); 0 on the other tiers."""
+    return 0
+
   def _take_bad_state_ids(self):
     """Ids of render_states() outside the game's table (the state-table tier counts them under the
     flag of render_frames()'s rows); 0 on the other tiers."""
@@ -240,6 +245,7 @@ class FusedGame(object):
     rows = self._take_bad_indices() if indices or self._bad_idx_flag_view[0] else 0
     policy_rows = self._take_bad_policy_rows()
     state_ids = self._take_bad_state_ids()
+    plan_rows = self._take_bad_plan_rows()
     self._bad.zero_()
     self._bad_flag_view[0] = 0
     what = []
@@ -256,6 +262,10 @@ class FusedGame(object):
     if state_ids:
       what.append('{} state ids of render_states() are outside the game\'s table (they were '
                   'rendered as state 0)'.format(state_ids))
+    if plan_rows:
+      what.append('{} rows of the policy given to evaluate_policy() are bad (a weight that is '
+                  'negative or NaN, or a sum that is not a positive finite number); they were '
+                  'evaluated as taking action {}'.format(plan_rows, gamespec.N_ACTIONS - 1))
     if what:
       raise ValueError('; '.join(what))
 
@@ -658,6 +668,18 @@ class FusedGame(object):
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """Observations by state index (`wide.WideGame.render_states`): the state-table tier only."""
     self._no_policy_rollouts('render_states')
+
+  def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
+    """Exact policy evaluation (`wide.WideGame.evaluate_policy`): the state-table tier only."""
+    self._no_policy_rollouts('evaluate_policy')
+
+  def value_iteration(self, gamma, sweeps, **kwargs):
+    """Value iteration (`wide.WideGame.value_iteration`): the state-table tier only."""
+    self._no_policy_rollouts('value_iteration')
+
+  def table_arrays(self):
+    """The game's table as tensors (`wide.WideGame.table_arrays`): the state-table tier only."""
+    self._no_policy_rollouts('table_arrays')
 
   def _gather_op(self, trace, t_idx, e_idx, out):
     _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,

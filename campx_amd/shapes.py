@@ -195,6 +195,15 @@ class ShapeGame(object):
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     self._no_policy_rollouts('render_states')
 
+  def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
+    self._no_policy_rollouts('evaluate_policy')
+
+  def value_iteration(self, gamma, sweeps, **kwargs):
+    self._no_policy_rollouts('value_iteration')
+
+  def table_arrays(self):
+    self._no_policy_rollouts('table_arrays')
+
   def rollout_trace_buffers(self, T):
     self._no_stored_trace('rollout_trace_buffers')
 

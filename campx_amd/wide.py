@@ -16,6 +16,7 @@ device raises.
 """
 
 import ctypes
+import math
 
 import torch
 
@@ -91,6 +92,8 @@ class WideGame(fused.FusedGame):
     # environment-frames of rollout_policy() that met a bad policy row (raised with the bad ids)
     self._bad_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._policy_frame = 0            # absolute frame the next rollout_policy() continues at
+    # bad rows of the policies given to evaluate_policy() (raised under the same flag)
+    self._bad_plan_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     # ids of render_states() outside the table (raised with the rows of render_frames(), under
     # their flag), and the one-frame trace of its out= calls: the last block is the largest; the
     # smaller ones before it stay alive, a captured graph may still write into them
@@ -178,6 +181,16 @@ class WideGame(fused.FusedGame):
     self._bad_rows.zero_()
     return n
 
+  def _check_policy(self, policy):
+    S = self.n_states
+    if (not torch.is_tensor(policy) or policy.dtype != torch.float32 or policy.dim() != 2
+        or tuple(policy.shape) != (S, gamespec.N_ACTIONS) or policy.device != self.device
+        or not policy.is_contiguous()):
+      got = ('{} {} on {}'.format(policy.dtype, list(policy.shape), policy.device)
+             if torch.is_tensor(policy) else type(policy).__name__)
+      raise ValueError('policy must be a contiguous float32 [{}, {}] tensor (n_states x actions) '
+                       'on {}, got {}'.format(S, gamespec.N_ACTIONS, self.device, got))
+
   def rollout_policy_buffers(self, T, want_states=True):
     """Allocate the dict of `rollout_policy(out=...)` once: `rollout_trace_buffers(T)` plus
     'actions' int8 [T, B] and - `want_states` - 'states' int32 [T, B], rows padded alike."""
@@ -220,14 +233,7 @@ class WideGame(fused.FusedGame):
     from this call or a later one, or from `check_actions()`.
     `out`: a dict from `rollout_policy_buffers(T, want_states)`, overwritten.
     """
-    S = self.n_states
-    if (not torch.is_tensor(policy) or policy.dtype != torch.float32 or policy.dim() != 2
-        or tuple(policy.shape) != (S, gamespec.N_ACTIONS) or policy.device != self.device
-        or not policy.is_contiguous()):
-      got = ('{} {} on {}'.format(policy.dtype, list(policy.shape), policy.device)
-             if torch.is_tensor(policy) else type(policy).__name__)
-      raise ValueError('policy must be a contiguous float32 [{}, {}] tensor (n_states x actions) '
-                       'on {}, got {}'.format(S, gamespec.N_ACTIONS, self.device, got))
+    self._check_policy(policy)
     T = int(T)
     if T < 1:
       raise ValueError('a rollout needs at least one frame: T >= 1')
@@ -258,6 +264,190 @@ class WideGame(fused.FusedGame):
     if validate:
       self._after_launch()
     return out
+
+  # ------------------------------------------------------------ planning on the table
+
+  def _take_bad_plan_rows(self):
+    n = int(self._bad_plan_rows.item())
+    self._bad_plan_rows.zero_()
+    return n
+
+  def table_arrays(self):
+    """The game's table - its complete, deterministic MDP - decoded from the blob the kernels
+    walk, as device tensors `[n_states, 5]`, each entry as a rollout reports the frame that takes
+    action a in state s: 'next_state' int32, 'reward' float32 (NaN = None), 'done' uint8,
+    'discount' float32, 'perf' int8 (zeros for a game without hidden performance)."""
+    S, A = self.n_states, gamespec.N_ACTIONS
+    n = S * A
+    entries = self._tables[:n * 8].view(torch.int32).view(S, A, 2)
+    word = entries[..., 1]
+    done = (word >> 24) & 1
+    code = ((word >> 25) & 15).long()
+    listed = torch.tensor([float(x) for x in self.spec.discount_list], dtype=torch.float32,
+                          device=self.device)
+    plain = torch.where(done != 0, torch.zeros((), device=self.device),
+                        torch.ones((), device=self.device))
+    if self.has_perf:
+      perf_off = (n * 8 + 15) // 16 * 16 + S * 16      # past the entries and the states' cells
+      perf = self._tables[perf_off:perf_off + n].view(torch.int8).view(S, A).clone()
+    else:
+      perf = torch.zeros((S, A), dtype=torch.int8, device=self.device)
+    return {'next_state': (word & 0xffffff).contiguous(),
+            'reward': entries[..., 0].contiguous().view(torch.float32),
+            'done': done.to(torch.uint8),
+            'discount': torch.where(code != 0, listed[code], plain),
+            'perf': perf}
+
+  def sweep_buffers(self, sweeps, want_q=True, greedy=True):
+    """Allocate the dict of `evaluate_policy(out=...)` (`greedy=False`) or
+    `value_iteration(out=...)` once: 'values' float32 [S], 'residual' float32 [sweeps], 'scratch'
+    float32 [S] (the second value vector of the one-launch-per-sweep path), with `want_q` 'q'
+    float32 [S, 5] and with `greedy` 'greedy' int8 [S]."""
+    S, dev = self.n_states, self.device
+    out = {'values': torch.zeros((S,), dtype=torch.float32, device=dev),
+           'residual': torch.zeros((int(sweeps),), dtype=torch.float32, device=dev),
+           'scratch': torch.zeros((S,), dtype=torch.float32, device=dev)}
+    if want_q:
+      out['q'] = torch.zeros((S, gamespec.N_ACTIONS), dtype=torch.float32, device=dev)
+    if greedy:
+      out['greedy'] = torch.zeros((S,), dtype=torch.int8, device=dev)
+    return out
+
+  def _sweeps(self, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path):
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    greedy = policy is None
+
+    def tensor_ok(t, dtype, shape):
+      return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape
+              and t.device == dev and t.is_contiguous())
+
+    if (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
+        or abs(gamma) > torch.finfo(torch.float32).max):
+      raise ValueError('gamma must be a finite number (as a float32), got {!r}'.format(gamma))
+    if isinstance(sweeps, bool) or not isinstance(sweeps, int) or not 1 <= sweeps <= 1 << 20:
+      raise ValueError('sweeps must be an int, 1 <= sweeps <= 2^20, got {!r}'.format(sweeps))
+    if values is not None and not tensor_ok(values, torch.float32, (S,)):
+      raise ValueError('values must be a contiguous float32 [{}] tensor (n_states) on {}, or '
+                       'None for zeros'.format(S, dev))
+    if reward is not None and not tensor_ok(reward, torch.float32, (S, A)):
+      raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
+                       '{}, or None for the table\'s own'.format(S, A, dev))
+    if tol is not None and (isinstance(tol, bool) or not isinstance(tol, (int, float))
+                            or not math.isfinite(tol) or tol < 0):
+      raise ValueError('tol must be a finite number >= 0 or None, got {!r}'.format(tol))
+    if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
+      raise ValueError('check_every must be an int >= 1, got {!r}'.format(check_every))
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    plan = (ctypes.c_int64 * 4)()
+    if _hip.lib.campx_wide_sweeps_plan(S, 0 if greedy else 1, 0 if reward is None else 1,
+                                       _hip.config_get('wide_lds_max'), path, plan) != 0:
+      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
+                       '(library setting wide_lds_max); use path=0 or path=2'.format(S))
+    want = [('values', torch.float32, (S,)), ('residual', torch.float32, (sweeps,))]
+    if plan[0] == 2:
+      want.append(('scratch', torch.float32, (S,)))
+    if want_q:
+      want.append(('q', torch.float32, (S, A)))
+    if greedy:
+      want.append(('greedy', torch.int8, (S,)))
+    if out is None:
+      out = self.sweep_buffers(sweeps, want_q, greedy)
+    else:
+      if not isinstance(out, dict) or any(not tensor_ok(out.get(k), d, sh) for k, d, sh in want):
+        raise ValueError('out must be a dict from sweep_buffers({}, want_q={}, greedy={}) of this '
+                         'game: {}'.format(sweeps, bool(want_q), greedy,
+                                           ', '.join('{!r} {} {}'.format(k, d, list(sh)) for k, d, sh in want)))
+      if values is not None and out.get('scratch') is not None and \
+          values.data_ptr() == out['scratch'].data_ptr():
+        raise ValueError('values must not be out[\'scratch\']')
+    if reward is not None:
+      reward = reward.detach()
+    v_out = out['values']
+    if values is None:
+      v_out.zero_()
+      v_in = v_out
+    else:
+      v_in = values.detach()
+    residual = out['residual']
+    validate = self.validate_actions
+    ran = 0
+    while ran < sweeps:
+      n = sweeps - ran if tol is None else min(check_every, sweeps - ran)
+      count = validate and ran == 0 and not greedy        # bad rows: once per call
+      _hip.ops.wide_sweeps(self._spec_host, self._tables, policy, reward, float(gamma), v_in, v_out,
+                           out.get('scratch'), out['q'] if want_q else None,
+                           out['greedy'] if greedy else None, residual[ran:ran + n],
+                           self._bad_plan_rows if count else None,
+                           self._bad_flag if count else None, path)
+      ran += n
+      v_in = v_out
+      if tol is not None and bool((residual[ran - n:ran] <= tol).any()):     # (synchronises)
+        break
+    if validate:
+      self._after_launch()
+    res = {'values': v_out, 'residual': residual[:ran], 'sweeps': ran}
+    if want_q:
+      res['q'] = out['q']
+    if greedy:
+      res['greedy'] = out['greedy']
+    return res
+
+  def evaluate_policy(self, policy, gamma, sweeps, values=None, reward=None, want_q=True, tol=None,
+                      check_every=32, out=None, path=0):
+    """The exact value of `policy` on the game's table: `sweeps` Jacobi sweeps of
+
+        q[s, a] = r[s, a]                              if (s, a) ends the episode
+                = r[s, a] + (gamma * D[s, a]) * v[next[s, a]]        otherwise
+        v'[s]   = sum_a w[s, a] * q[s, a] / sum_a w[s, a]
+
+    on the device (csrc/k_plan.hip, `campx::wide_sweeps`), where `rollout_policy()` can only sample
+    it.  r, next and D - the frame's discount - are the table's, as `table_arrays()` shows them; a
+    reward of None counts as 0.  float32 with every operation rounded on its own, sums in action
+    order (include/campx_hip.h has the rule in full; tests/planning_reference.py restates it bit
+    for bit), so the result does not depend on how the sweeps were run.
+
+    Args:
+      policy: what `rollout_policy()` takes, checked the same way: contiguous float32
+          `[n_states, 5]` weights.  A bad row (a negative or NaN weight, a sum that is not a
+          positive finite number) is evaluated as taking action 4 - as the sampler plays it - and
+          raises ValueError with the count of such rows, lazily like bad actions: from
+          `check_actions()` or a later call, under `validate_actions='sync'` from this one.
+      gamma: the discount factor, a finite float.
+      sweeps: how many sweeps to run, 1 .. 2^20.
+      values: float32 `[n_states]` to start from, or None for zeros.  Running n sweeps and then m
+          more from the 'values' of the first call equals n + m sweeps, bit for bit.
+      reward: float32 `[n_states, 5]` to use instead of the table's rewards (NaN counts as 0):
+          `table_arrays()['perf'].float()` gives a policy's exact hidden performance.
+      want_q: also return 'q'.
+      tol: None - the call never synchronises - or a residual to stop at: sweeps then run in blocks
+          of `check_every`, the host reads each block's residuals once and stops after the first
+          block that holds one <= tol.  The values are those of a plain call of 'sweeps' sweeps.
+      out: a dict from `sweep_buffers(sweeps, want_q, greedy=False)`, overwritten; with `out` and
+          `tol=None` the call allocates nothing and is capturable in a HIP graph.
+      path: 0 - all sweeps in one launch by one workgroup that holds the table in LDS whenever it
+          fits there, else one launch per sweep; 1 / 2 force either (1 raises ValueError for a
+          table that does not fit).  Every path gives the same bits.
+
+    Returns a dict: 'values' float32 `[n_states]`; 'q' float32 `[n_states, 5]` (with `want_q`) -
+    the backup of the last sweep, so that 'values' is exactly its reduction; 'residual' float32
+    `[sweeps run]`, per sweep the largest |v_k[s] - v_{k-1}[s]| (NaN if any difference is);
+    'sweeps' int, the sweeps run.  Argument errors raise ValueError before anything is launched.
+    """
+    self._check_policy(policy)
+    return self._sweeps(policy.detach(), gamma, sweeps, values, reward, want_q,
+                        tol, check_every, out, path)
+
+  def value_iteration(self, gamma, sweeps, values=None, reward=None, want_q=True, tol=None,
+                      check_every=32, out=None, path=0):
+    """`sweeps` sweeps of value iteration on the game's table: `evaluate_policy()` with
+    `v'[s] = max_a q[s, a]` in place of the policy's average.  Same arguments (`out` from
+    `sweep_buffers(sweeps, want_q)`), same result plus 'greedy' int8 `[n_states]`: per state the
+    lowest action that attains the maximum of the returned q.  A one-hot policy built from it -
+    `torch.nn.functional.one_hot(res['greedy'].long(), 5).float()` - is what `rollout_policy()`
+    and `evaluate_policy()` take."""
+    return self._sweeps(None, gamma, sweeps, values, reward, want_q, tol,
+                        check_every, out, path)
 
   # ------------------------------------------------------------ observations by state
 

@@ -923,6 +923,73 @@ typedef struct CampxTableLookup {
 } CampxTableLookup;
 int32_t campx_table_lookup_launch(const CampxTableLookup* lookup, int64_t B, int32_t T,
                                   void* stream);
+/*
+ * ---- Exact policy evaluation and value iteration on the state table ---------------------------
+ * The blob campx_wide_policy_update_launch() walks is the game's complete deterministic MDP:
+ * (state, action) -> next state, reward, done, discount code.  Sweeps of the Bellman backup over
+ * it give the exact value of a policy and the optimal values, where the rollouts above can only
+ * sample them (csrc/k_plan.hip).  No reference counterpart.
+ *
+ * The rule.  f32 throughout, every operation rounded on its own (no fused multiply-add), the one
+ * division IEEE-rounded, so that a float32 restatement is bit-exact (tests/planning_reference.py
+ * is one, in numpy).  For entry (s, a) of the table:
+ *     n = its next state
+ *     r = its reward, NaN ("None") counted as 0; with `reward_override` (DEVICE float32
+ *         [n_states][5]) that array's element instead, NaN still counted as 0
+ *     d = its done bit
+ *     D = the frame's discount as a rollout reports it: discount_list[code], or - code 0 - 0.0
+ *         when d is set and 1.0 otherwise
+ *     c = gamma * D
+ *     q[s][a] = d ? r : r + c * v[n]        (nothing is carried across an episode's end: the cut
+ *                                            and the operation order of campx_returns_launch())
+ * Policy reduction (`policy` DEVICE float32 [n_states][5], the weights
+ * campx_wide_policy_update_launch() samples from), with w = policy[s]:
+ *     c4    = (((w0 + w1) + w2) + w3) + w4                          (the sampler's own total)
+ *     v'[s] = (((((w0*q0) + w1*q1) + w2*q2) + w3*q3) + w4*q4) / c4
+ * A row that the sampler calls BAD - a negative or NaN weight, a c4 that is not a positive finite
+ * number - takes action 4 as it does there: v'[s] = q[s][4].  Such rows are counted into
+ * *bad_rows (DEVICE int32, added to, may be NULL) once per call, and *bad_flag (device or mapped
+ * pinned int32, may be NULL) is set to 1.
+ * Greedy reduction (`policy` NULL): v'[s] = max over a of q[s][a], found as  best = q0; for a = 1
+ * .. 4: if (q[a] > best) best = q[a]  - so the greedy action is the lowest a attaining it.
+ *
+ * Sweeps are Jacobi.  With v_0 = `v_in`, for k = 1 .. n_sweeps:
+ *     q_k = the backup of v_{k-1}        v_k = the reduction of q_k
+ *     residual[k-1] = the float whose bit pattern is the largest, over s, of the bit patterns of
+ *                     |v_k[s] - v_{k-1}[s]|   (a maximum of integers: order-independent; a NaN
+ *                     difference wins it and shows as NaN)
+ * `v_out` = v_n; `q` (DEVICE float32 [n_states][5], may be NULL) = q_n, so that v_out is exactly
+ * the reduction of the returned q; `greedy` (DEVICE int8 [n_states], may be NULL) = the greedy
+ * action of q_n (4 in every row under a policy).  n sweeps and then m more from the v_out of the
+ * first call are n + m sweeps, bit for bit.
+ *
+ * Two paths, `path`: 1 = one workgroup stages the entries, two value vectors and the policy in
+ * LDS and runs all n_sweeps in ONE launch, a workgroup barrier between sweeps; 2 = one launch per
+ * sweep, a lane per state, between `v_out` and `scratch` (DEVICE float32 [n_states], needed on
+ * this path only), after one small kernel that zeroes `residual`; the launches follow each other
+ * on `stream`, a sweep boundary is a kernel boundary.  0 = path 1 whenever the table fits the
+ * library setting wide_lds_max.  By the rule the choice cannot change a bit of any result.
+ * `v_in` may be `v_out`; otherwise `v_in` is left as it is.
+ *
+ * campx_wide_sweeps_plan() is the choice as host-only arithmetic (nothing is launched):
+ * plan_out[4] = the path taken (1 / 2); dynamic LDS bytes (0 on path 2); threads of a workgroup;
+ * workgroups of a sweep.  `policy` is 1 for the policy reduction and 0 for the greedy one;
+ * `has_override` is accepted for completeness - the staged entry holds the reward the sweeps use,
+ * wherever it came from, so an override takes no LDS of its own.  CAMPX_EINVAL: n_states outside
+ * 1 .. CAMPX_WIDE_MAX_STATES, a flag that is not 0 / 1, wide_lds_max < 0, a `path` outside 0..2,
+ * path 1 for a table that does not fit.  campx_wide_sweeps_launch() returns CAMPX_EINVAL for the
+ * same and for: NULL where it is not allowed, pointers that are not 4-byte aligned, n_sweeps
+ * outside 1 .. 2^20, a gamma that is not finite, `v_in` and `v_out` that overlap without being
+ * equal, on path 2 a `scratch` that is NULL or overlaps either.  Asynchronous on `stream`, no
+ * synchronisation, no allocation, no library state.
+ */
+int32_t campx_wide_sweeps_plan(int64_t n_states, int32_t policy, int32_t has_override,
+                               int64_t wide_lds_max, int32_t path, int64_t* plan_out);
+int32_t campx_wide_sweeps_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                 const float* policy, const float* reward_override, float gamma,
+                                 const float* v_in, float* v_out, float* scratch, float* q,
+                                 int8_t* greedy, float* residual, int32_t* bad_rows,
+                                 int32_t* bad_flag, int32_t n_sweeps, int32_t path, void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
