@@ -21,6 +21,7 @@
 //   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
 //   campx::table_lookup             table[states, actions] of a rollout's streams
 //   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
+//   campx::wide_visit               exact state visitation of a policy over the state table
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -1187,6 +1188,52 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
            "campx_wide_sweeps_launch");
 }
 
+// Exact state visitation of a policy over the state table (campx_wide_visit_launch): as many
+// frames as `finished` has elements, from `start` (int64 [n_states] units of 2^-38; None: one
+// environment in state 0), which may be `final_mass`.
+void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& policy,
+                const OptTensor& start, bool restart, Tensor& visits, Tensor& finished,
+                Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
+                const OptTensor& scratch, const OptTensor& bad_rows, const OptTensor& bad_flag,
+                int64_t path) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(visits.device().is_cuda(),
+              "campx::wide_visit: visits must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = visits.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want(policy, "policy", at::kFloat, dev, {S, A});
+  if (start.has_value()) want(*start, "start", at::kLong, dev, {S});
+  want(visits, "visits", at::kLong, dev, {S, A});
+  TORCH_CHECK(finished.device() == dev && finished.scalar_type() == at::kLong && finished.dim() == 1 &&
+                  finished.is_contiguous() && finished.numel() >= 1 && finished.numel() <= (1 << 20),
+              "campx::wide_visit: finished must be a contiguous int64 [frames] tensor on ", dev,
+              ", 1 <= frames <= 2^20");
+  const int64_t T = finished.numel();
+  want(final_mass, "final_mass", at::kLong, dev, {S});
+  if (per_frame.has_value()) want(*per_frame, "per_frame", at::kLong, dev, {T + 1, S});
+  want(counts, "counts", at::kInt, dev, {S, A});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, {S});
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_visit: path must be 0, 1 or 2");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_wide_visit_launch(
+               hs, tables.data_ptr(), reinterpret_cast<const float*>(policy.data_ptr()),
+               opt_ptr<const int64_t>(start), restart ? 1 : 0, (int32_t)T,
+               reinterpret_cast<int64_t*>(visits.data_ptr()),
+               reinterpret_cast<int64_t*>(finished.data_ptr()),
+               reinterpret_cast<int64_t*>(final_mass.data_ptr()), opt_ptr<int64_t>(per_frame),
+               reinterpret_cast<int32_t*>(counts.data_ptr()), opt_ptr<int64_t>(scratch),
+               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path,
+               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_visit_launch");
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -1269,6 +1316,9 @@ void table_lookup_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, 
 void wide_sweeps_meta(const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, double,
                       const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
                       Tensor&, const OptTensor&, const OptTensor&, int64_t) {}
+void wide_visit_meta(const Tensor&, const Tensor&, const Tensor&, const OptTensor&, bool, Tensor&,
+                     Tensor&, Tensor&, const OptTensor&, Tensor&, const OptTensor&, const OptTensor&,
+                     const OptTensor&, int64_t) {}
 void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
 void check_actions_meta(const Tensor&, Tensor&) {}
 
@@ -1375,6 +1425,11 @@ TORCH_LIBRARY(campx, m) {
       "Tensor values_in, Tensor(a!) values_out, Tensor(b!)? scratch, Tensor(c!)? q, "
       "Tensor(d!)? greedy, Tensor(e!) residual, Tensor(f!)? bad_rows, Tensor(g!)? bad_flag, "
       "int path) -> ()");
+  m.def(
+      "wide_visit(Tensor spec_host, Tensor tables, Tensor policy, Tensor? start, bool restart, "
+      "Tensor(a!) visits, Tensor(b!) finished, Tensor(c!) final_mass, Tensor(d!)? per_frame, "
+      "Tensor(e!) counts, Tensor(f!)? scratch, Tensor(g!)? bad_rows, Tensor(h!)? bad_flag, "
+      "int path) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -1398,6 +1453,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("state_sums", &state_sums);
   m.impl("table_lookup", &table_lookup);
   m.impl("wide_sweeps", &wide_sweeps);
+  m.impl("wide_visit", &wide_visit);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }
@@ -1405,7 +1461,8 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
                            "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
-                           "returns", "state_sums", "table_lookup", "wide_sweeps", "onehot_to_ids", "check_actions"})
+                           "returns", "state_sums", "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids",
+                           "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
@@ -1428,6 +1485,7 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("state_sums", &state_sums_meta);
   m.impl("table_lookup", &table_lookup_meta);
   m.impl("wide_sweeps", &wide_sweeps_meta);
+  m.impl("wide_visit", &wide_visit_meta);
   m.impl("onehot_to_ids", &onehot_to_ids_meta);
   m.impl("check_actions", &check_actions_meta);
 }

@@ -1,0 +1,449 @@
+// k_visit.hip - exact state visitation of a policy on a game's state table: the FORWARD half of
+// the deterministic MDP that k_plan.hip sweeps backwards.  Given the weights rollout_policy()
+// samples from, how much probability sits in each state at each frame and how often each
+// (state, action) is taken - what rollout_policy() + sum_by_state() can only estimate.
+//
+// The rule (include/campx_hip.h has it in full; tests/visitation_reference.py restates it in
+// numpy): mass is an int64 in units of 2^-38.  Per state, N_i = how many of the sampler's 2^24
+// values u play an action <= i, found by bisection on the sampler's own f32 product and
+// comparison; a state's mass m splits into x_a = y_a - y_{a-1}, y_i = floor(m * N_i / 2^24), which
+// sums to m exactly; x_a moves to the entry's next state, or - an entry that ends the episode -
+// is counted into finished[t] and, with `restart`, moves to state 0.  Every addition is an integer
+// addition: the scatter gives the same bits whatever order the lanes arrive in, so both paths
+// below, a continued call and the numpy restatement agree bit for bit.
+//
+// visit_counts_kernel     a lane per state: the bisection, `counts`, the bad rows; on the global
+//     path also the two mass buffers the first frame starts from and the zeroes of `finished`.
+// visit_lds_kernel        one workgroup holds the entries' next / done words, N and two mass
+//     vectors in LDS and runs ALL frames of the call, one __syncthreads() per frame; scatters are
+//     64-bit LDS atomic adds; `visits` stays in the registers of the lane that owns the state.
+// visit_frame_kernel      one launch per frame, a lane per state; scatters are no-return 64-bit
+//     global atomic adds; the mass that ends an episode is summed across the wave first, so that
+//     finished[t] and state 0 take one atomic per wave; the lane that reads d[s] clears it, so
+//     that the buffer is zero when it is the target of the frame after next.
+// plan_visit() chooses; campx_wide_visit_plan() shows the choice to a test without a GPU.
+
+#include "campx_common.hip.h"
+
+#include <math.h>
+
+namespace campx_impl {
+
+typedef unsigned long long u64;
+
+constexpr int kVisitLdsThreads = 1024;     // at most; a multiple of 64 that covers the states
+constexpr int kVisitPerLane = 3;           // states a lane of the LDS workgroup owns, at most
+constexpr int kVisitThreads = 256;         // global path, and the counts
+constexpr int64_t kVisitLdsHeader = 64;    // the two slots of finished[t]
+constexpr int32_t kVisitMaxFrames = 1 << 20;
+constexpr uint32_t kVisitWords = 1u << 24; // the sampler's values u
+
+struct VisitPlan {
+  int32_t path;            // 1 LDS, 2 global
+  int32_t threads;         // of a workgroup
+  int64_t grid;            // workgroups of a frame
+  int64_t lds_bytes;
+  int32_t off_n, off_d0, off_d1;     // byte offsets into the dynamic LDS
+};
+
+static inline int64_t visit_up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+
+// The LDS a table of S states takes: header, the entries' second words [5][S] x 4 bytes, N [4][S]
+// x 4 bytes and two mass vectors [S] x 8 bytes - 52 bytes per state.  A lane keeps the visits of
+// the states it owns in registers, kVisitPerLane of them at most.
+static inline int32_t plan_visit(int64_t S, int64_t lds_max, int32_t path, VisitPlan* p) {
+  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || lds_max < 0 || path < 0 || path > 2) return CAMPX_EINVAL;
+  memset(p, 0, sizeof(*p));
+  int64_t at = kVisitLdsHeader + visit_up16(S * CAMPX_N_ACTIONS * 4);
+  p->off_n = (int32_t)at;
+  at += visit_up16(S * 4 * 4);
+  p->off_d0 = (int32_t)at;
+  at += visit_up16(S * 8);
+  p->off_d1 = (int32_t)at;
+  at += visit_up16(S * 8);
+  const bool fits = at <= lds_max && S <= (int64_t)kVisitLdsThreads * kVisitPerLane;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  if (path == 1 || (path == 0 && fits)) {
+    p->path = 1;
+    const int64_t t = (S + 63) / 64 * 64;
+    p->threads = (int32_t)(t > kVisitLdsThreads ? kVisitLdsThreads : t);
+    p->grid = 1;
+    p->lds_bytes = at;
+  } else {
+    p->path = 2;
+    p->threads = kVisitThreads;
+    p->grid = (S + kVisitThreads - 1) / kVisitThreads;
+    p->lds_bytes = 0;
+    p->off_n = p->off_d0 = p->off_d1 = 0;
+  }
+  return CAMPX_OK;
+}
+
+// policy_thresholds() of k_policy.hip, restated: the sampler's thresholds of a row, a bad row's
+// {-1, -1, -1, -1, 0}.
+__device__ __forceinline__ void row_thresholds(const float* w, float (&c)[5]) {
+  const float w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+  c[0] = w0;
+  c[1] = c[0] + w1;
+  c[2] = c[1] + w2;
+  c[3] = c[2] + w3;
+  c[4] = c[3] + w4;
+  const bool good = w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f && w3 >= 0.0f && w4 >= 0.0f &&
+                    c[4] > 0.0f && c[4] < INFINITY;
+  if (!good) {
+    c[0] = c[1] = c[2] = c[3] = -1.0f;
+    c[4] = 0.0f;
+  }
+}
+
+// The smallest u in 0 .. 2^24 whose product reaches the threshold (2^24: none does): the
+// sampler's own multiply and comparison, which are monotone in u.  25 steps halve 2^24 + 1
+// candidates down to one.
+__device__ __forceinline__ uint32_t first_word_reaching(float threshold, float c4) {
+  uint32_t lo = 0, hi = kVisitWords;
+#pragma unroll 1
+  for (int step = 0; step < 25; ++step) {
+    const uint32_t mid = (lo + hi) >> 1;
+    const float u = (float)mid * 5.9604644775390625e-8f;     // 2^-24: exact
+    const float r = u * c4;
+    const bool ok = r >= threshold;
+    hi = ok ? mid : hi;
+    lo = ok ? lo : mid + 1;
+  }
+  return hi;
+}
+
+// y_i = floor(m * n / 2^24) for 0 <= m < 2^62, n <= 2^24, without overflow.
+__device__ __forceinline__ u64 share(u64 m, uint32_t n) {
+  return (m >> 24) * n + (((m & 0xffffffull) * n) >> 24);
+}
+
+// x[a]: the mass each action takes, from the counts of the row.
+__device__ __forceinline__ void split_mass(u64 m, const uint32_t (&n)[4], u64 (&x)[5]) {
+  const u64 y0 = share(m, n[0]), y1 = share(m, n[1]), y2 = share(m, n[2]), y3 = share(m, n[3]);
+  x[0] = y0;
+  x[1] = y1 - y0;
+  x[2] = y2 - y1;
+  x[3] = y3 - y2;
+  x[4] = m - y3;
+}
+
+__device__ __forceinline__ u64 wave_sum(u64 v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+    v += ((u64)hi << 32) | lo;
+  }
+  return v;
+}
+
+__device__ __forceinline__ void lds_add(u64* p, u64 v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ void global_add(u64* p, u64 v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// `counts` and the bad rows of every state; with `d_first` (global path) also the mass the first
+// frame reads - `start`, or one environment in state 0 -, zeroes where it scatters to, and the
+// zeroes of finished[0 .. n_frames).  Each lane touches element s of each vector only, and reads
+// start[s] before it writes, so `start` may be either buffer.
+__global__ __launch_bounds__(kVisitThreads) void visit_counts_kernel(
+    int32_t S, const float* __restrict__ policy, int32_t* __restrict__ counts, const u64* start,
+    u64* d_first, u64* d_second, u64* __restrict__ finished, int32_t n_frames,
+    int32_t* __restrict__ bad_rows, int32_t* __restrict__ bad_flag) {
+  const int first = (int)(blockIdx.x * kVisitThreads + threadIdx.x);
+  if (d_first) {
+    const int step = (int)(gridDim.x * kVisitThreads);
+    for (int i = first; i < n_frames; i += step) finished[i] = 0;
+  }
+  const int s = first;
+  if (s >= S) return;
+  float c[5];
+  row_thresholds(policy + (int64_t)s * CAMPX_N_ACTIONS, c);
+  uint32_t before = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t n = first_word_reaching(c[i], c[4]);
+    counts[s * CAMPX_N_ACTIONS + i] = (int32_t)(n - before);
+    before = n;
+  }
+  counts[s * CAMPX_N_ACTIONS + 4] = (int32_t)(kVisitWords - before);
+  if (d_first) {
+    const u64 m = start ? start[s] : (s == 0 ? (1ull << CAMPX_VISIT_FRAC_BITS) : 0ull);
+    d_second[s] = 0;
+    d_first[s] = m;
+  }
+  if (c[4] == 0.0f) {
+    if (bad_rows) atomicAdd(bad_rows, 1);
+    if (bad_flag) __hip_atomic_store(bad_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+struct VisitParams {
+  int32_t S, n_frames, restart;
+  int32_t off_n, off_d0, off_d1;
+};
+
+// Where an entry leads.  (A next state outside the table cannot come out of
+// campx_wide_tables_build(); it adds to state 0 rather than past the vector.)
+__device__ __forceinline__ uint32_t target_of(uint32_t word, uint32_t S) {
+  const uint32_t next = word & 0xffffffu;
+  return next < S ? next : 0u;
+}
+
+__global__ __launch_bounds__(kVisitLdsThreads) void visit_lds_kernel(
+    VisitParams vp, const uint2* __restrict__ g_entries, const int32_t* __restrict__ g_counts,
+    const u64* start, u64* __restrict__ visits, u64* __restrict__ finished, u64* final_out,
+    u64* __restrict__ per_frame) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_visit[];
+  u64* fin = reinterpret_cast<u64*>(lds_visit);                              // [2]: frame t uses t & 1
+  uint32_t* ent = reinterpret_cast<uint32_t*>(lds_visit + kVisitLdsHeader);  // [5][S]
+  uint32_t* cum = reinterpret_cast<uint32_t*>(lds_visit + vp.off_n);         // [4][S]
+  u64* cur = reinterpret_cast<u64*>(lds_visit + vp.off_d0);
+  u64* nxt = reinterpret_cast<u64*>(lds_visit + vp.off_d1);
+  const int S = vp.S, nt = (int)blockDim.x, tid = (int)threadIdx.x;
+  for (int i = tid; i < S * CAMPX_N_ACTIONS; i += nt) {
+    const int s = i / CAMPX_N_ACTIONS, a = i - s * CAMPX_N_ACTIONS;
+    ent[a * S + s] = g_entries[i].y;
+  }
+  for (int s = tid; s < S; s += nt) {
+    uint32_t n = 0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      n += (uint32_t)g_counts[s * CAMPX_N_ACTIONS + a];
+      cum[a * S + s] = n;
+    }
+    cur[s] = start ? start[s] : (s == 0 ? (1ull << CAMPX_VISIT_FRAC_BITS) : 0ull);
+    nxt[s] = 0;
+  }
+  if (tid < 2) fin[tid] = 0;
+  __syncthreads();
+
+  u64 acc[kVisitPerLane][5];
+#pragma unroll
+  for (int j = 0; j < kVisitPerLane; ++j)
+#pragma unroll
+    for (int a = 0; a < 5; ++a) acc[j][a] = 0;
+
+  for (int t = 0; t < vp.n_frames; ++t) {
+    u64 over = 0;
+#pragma unroll
+    for (int j = 0; j < kVisitPerLane; ++j) {
+      const int s = tid + j * nt;
+      if (s < S) {
+        const u64 m = cur[s];
+        if (per_frame) per_frame[(int64_t)t * S + s] = m;
+        if (m) {
+          cur[s] = 0;            // the target of frame t + 1: nobody else touches it in frame t
+          uint32_t n[4], e[5];
+          u64 x[5];
+#pragma unroll
+          for (int a = 0; a < 4; ++a) n[a] = cum[a * S + s];
+#pragma unroll
+          for (int a = 0; a < 5; ++a) e[a] = ent[a * S + s];
+          split_mass(m, n, x);
+#pragma unroll
+          for (int a = 0; a < 5; ++a) {
+            acc[j][a] += x[a];
+            if (x[a]) {
+              if ((e[a] >> 24) & 1u) over += x[a];
+              else lds_add(&nxt[target_of(e[a], (uint32_t)S)], x[a]);
+            }
+          }
+        }
+      }
+    }
+    over = wave_sum(over);
+    if ((tid & 63) == 0 && over) {
+      lds_add(&fin[t & 1], over);
+      if (vp.restart) lds_add(&nxt[0], over);
+    }
+    __syncthreads();               // d_{t+1} and finished[t] are complete; d_t is all zero
+    if (tid == 0) {
+      finished[t] = fin[t & 1];
+      fin[t & 1] = 0;              // (used again by frame t + 2, past the next barrier)
+    }
+    u64* swap = cur;
+    cur = nxt;
+    nxt = swap;
+  }
+#pragma unroll
+  for (int j = 0; j < kVisitPerLane; ++j) {
+    const int s = tid + j * nt;
+    if (s < S) {
+      const u64 m = cur[s];
+      final_out[s] = m;
+      if (per_frame) per_frame[(int64_t)vp.n_frames * S + s] = m;
+#pragma unroll
+      for (int a = 0; a < 5; ++a) visits[s * CAMPX_N_ACTIONS + a] = acc[j][a];
+    }
+  }
+}
+
+// One frame.  `src` is d_t and is left all zero, `dst` - zero when the launch starts, but for what
+// the workgroups of this launch have added - becomes d_{t+1}.  `first`: visits are written, not
+// added to.  `row`: per_frame[t], or NULL.
+__global__ __launch_bounds__(kVisitThreads) void visit_frame_kernel(
+    int32_t S, int32_t restart, int32_t first, const uint2* __restrict__ entries,
+    const int32_t* __restrict__ counts, u64* src, u64* dst, u64* __restrict__ visits,
+    u64* __restrict__ finished_t, u64* __restrict__ row) {
+  const int s = (int)(blockIdx.x * kVisitThreads + threadIdx.x);
+  u64 over = 0;
+  if (s < S) {
+    const u64 m = src[s];
+    if (row) row[s] = m;
+    u64 x[5] = {0, 0, 0, 0, 0};
+    if (m) {
+      src[s] = 0;                  // the target of the frame after next
+      uint32_t n[4], word[5];
+      const int at = s * CAMPX_N_ACTIONS;
+#pragma unroll
+      for (int a = 0; a < 5; ++a) word[a] = entries[at + a].y;
+      uint32_t sum = 0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        sum += (uint32_t)counts[at + a];
+        n[a] = sum;
+      }
+      split_mass(m, n, x);
+#pragma unroll
+      for (int a = 0; a < 5; ++a) {
+        if (x[a]) {
+          if ((word[a] >> 24) & 1u) over += x[a];
+          else global_add(&dst[target_of(word[a], (uint32_t)S)], x[a]);
+        }
+      }
+    }
+    if (first) {
+#pragma unroll
+      for (int a = 0; a < 5; ++a) visits[(int64_t)s * CAMPX_N_ACTIONS + a] = x[a];
+    } else if (m) {
+#pragma unroll
+      for (int a = 0; a < 5; ++a) visits[(int64_t)s * CAMPX_N_ACTIONS + a] += x[a];
+    }
+  }
+  // every lane of the wave is here: the mass that ended an episode goes out once per wave
+  over = wave_sum(over);
+  if ((threadIdx.x & 63) == 0 && over) {
+    global_add(finished_t, over);
+    if (restart) global_add(&dst[0], over);
+  }
+}
+
+// per_frame[n_frames] = d_T, which the last frame left in `final`.
+__global__ __launch_bounds__(kVisitThreads) void visit_last_row_kernel(
+    int32_t S, const u64* __restrict__ final_in, u64* __restrict__ row) {
+  const int s = (int)(blockIdx.x * kVisitThreads + threadIdx.x);
+  if (s < S) row[s] = final_in[s];
+}
+
+static bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
+// [a, a + S) and [b, b + S) share an element
+static bool overlap8(const void* a, const void* b, int64_t S) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t n = (uintptr_t)S * sizeof(int64_t);
+  return x < y ? y - x < n : x - y < n;
+}
+
+}  // namespace campx_impl
+
+using namespace campx_impl;
+
+extern "C" {
+
+int32_t campx_wide_visit_plan(int64_t n_states, int64_t wide_lds_max, int32_t path,
+                              int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  VisitPlan p;
+  const int32_t e = plan_visit(n_states, wide_lds_max, path, &p);
+  if (e != CAMPX_OK) return e;
+  plan_out[0] = p.path;
+  plan_out[1] = p.lds_bytes;
+  plan_out[2] = p.threads;
+  plan_out[3] = p.grid;
+  return CAMPX_OK;
+}
+
+int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, const float* policy,
+                                const int64_t* start, int32_t restart, int32_t n_frames,
+                                int64_t* visits, int64_t* finished, int64_t* final_mass,
+                                int64_t* per_frame, int32_t* counts, int64_t* scratch,
+                                int32_t* bad_rows, int32_t* bad_flag, int32_t path, void* stream) {
+  if (!s || !tables_dev || !policy || !visits || !finished || !final_mass || !counts)
+    return CAMPX_EINVAL;
+  if (n_frames < 1 || n_frames > kVisitMaxFrames || (restart & ~1)) return CAMPX_EINVAL;
+  if (!aligned_to(tables_dev, 8) || !aligned_to(policy, 4) || !aligned_to(start, 8) ||
+      !aligned_to(visits, 8) || !aligned_to(finished, 8) || !aligned_to(final_mass, 8) ||
+      !aligned_to(per_frame, 8) || !aligned_to(counts, 4) || !aligned_to(scratch, 8) ||
+      !aligned_to(bad_rows, 4) || !aligned_to(bad_flag, 4))
+    return CAMPX_EINVAL;
+  const int32_t v = wide_validate_plain(s);
+  if (v != CAMPX_OK) return v;
+  const int64_t S = s->n_states;
+  VisitPlan plan;
+  const int32_t e = plan_visit(S, knob(K_WIDE_LDS_MAX), path, &plan);
+  if (e != CAMPX_OK) return e;
+  // the mass to start from and the mass to leave are one vector or two apart
+  if (start && start != final_mass && overlap8(start, final_mass, S)) return CAMPX_EINVAL;
+  if (plan.path == 2 &&
+      (!scratch || overlap8(scratch, final_mass, S) || (start && overlap8(scratch, start, S))))
+    return CAMPX_EINVAL;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const uint2* entries = reinterpret_cast<const uint2*>(tables_dev);
+  const u64* d_start = reinterpret_cast<const u64*>(start);
+  u64* d_visits = reinterpret_cast<u64*>(visits);
+  u64* d_finished = reinterpret_cast<u64*>(finished);
+  u64* d_final = reinterpret_cast<u64*>(final_mass);
+  u64* d_rows = reinterpret_cast<u64*>(per_frame);
+  u64* d_scratch = reinterpret_cast<u64*>(scratch);
+  const dim3 per_state((unsigned)((S + kVisitThreads - 1) / kVisitThreads));
+  // Frame k of n scatters into `final` when n - k is even and into the scratch vector when it is
+  // odd, so that the last one leaves d_T in `final`; frame 1 reads the other of the two.
+  u64* src = (n_frames & 1) ? d_scratch : d_final;
+  u64* dst = (n_frames & 1) ? d_final : d_scratch;
+  const bool global = plan.path == 2;
+  hipLaunchKernelGGL(visit_counts_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S, policy,
+                     counts, d_start, global ? src : nullptr, global ? dst : nullptr, d_finished,
+                     n_frames, bad_rows, bad_flag);
+  const hipError_t pe = hipGetLastError();
+  if (pe != hipSuccess) return hip_failed(pe);
+  if (!global) {
+    VisitParams vp;
+    memset(&vp, 0, sizeof(vp));
+    vp.S = (int32_t)S;
+    vp.n_frames = n_frames;
+    vp.restart = restart;
+    vp.off_n = plan.off_n;
+    vp.off_d0 = plan.off_d0;
+    vp.off_d1 = plan.off_d1;
+    CAMPX_ALLOW_LDS(visit_lds_kernel, (size_t)plan.lds_bytes);
+    hipLaunchKernelGGL(visit_lds_kernel, dim3(1), dim3((unsigned)plan.threads),
+                       (size_t)plan.lds_bytes, hs, vp, entries, counts, d_start, d_visits,
+                       d_finished, d_final, d_rows);
+    const hipError_t le = hipGetLastError();
+    return le == hipSuccess ? CAMPX_OK : hip_failed(le);
+  }
+  for (int32_t k = 1; k <= n_frames; ++k) {
+    hipLaunchKernelGGL(visit_frame_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S, restart,
+                       (int32_t)(k == 1), entries, counts, src, dst, d_visits, d_finished + (k - 1),
+                       d_rows ? d_rows + (int64_t)(k - 1) * S : nullptr);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return hip_failed(le);
+    u64* swap = src;
+    src = dst;
+    dst = swap;
+  }
+  if (d_rows) {
+    hipLaunchKernelGGL(visit_last_row_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S,
+                       d_final, d_rows + (int64_t)n_frames * S);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return hip_failed(le);
+  }
+  return CAMPX_OK;
+}
+
+}  // extern "C"

@@ -522,6 +522,25 @@ class Engine(object):
                          'been through its_showtime()')
     return self._fused.table_arrays()
 
+  def state_visitation(self, policy, frames, **kwargs):
+    """State-table tier only: the exact visitation of `policy`, float32 `[n_states, 5]` weights per
+    state, over `frames` frames of the game's table, in int64 units of 2^-38 - 'visits', 'finished',
+    'final', 'per_frame', 'counts', 'probs', 'unit'.  See `wide.WideGame.state_visitation`; the
+    other batched tiers raise NotImplementedError (`use_state_table()` before `its_showtime()`
+    puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('state_visitation() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.state_visitation(policy, frames, **kwargs)
+
+  def visitation_buffers(self, frames, want_frames=False):
+    """State-table tier only: the dict of `state_visitation(out=...)`.  See
+    `wide.WideGame.visitation_buffers`."""
+    if self._fused is None:
+      raise RuntimeError('visitation_buffers() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.visitation_buffers(frames, want_frames)
+
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
     `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See

@@ -231,6 +231,11 @@ class FusedGame(object):
     the flag of the bad action ids); 0 on the other tiers."""
     return 0
 
+  def _take_bad_visit_rows(self):
+    """Bad rows of the policies given to state_visitation() (the state-table tier counts them under
+    the flag of the bad action ids); 0 on the other tiers."""
+    return 0
+
   def _take_bad_state_ids(self):
     """Ids of render_states() outside the game's table (the state-table tier counts them under the
     flag of render_frames()'s rows); 0 on the other tiers."""
@@ -246,6 +251,7 @@ class FusedGame(object):
     policy_rows = self._take_bad_policy_rows()
     state_ids = self._take_bad_state_ids()
     plan_rows = self._take_bad_plan_rows()
+    visit_rows = self._take_bad_visit_rows()
     self._bad.zero_()
     self._bad_flag_view[0] = 0
     what = []
@@ -266,6 +272,10 @@ class FusedGame(object):
       what.append('{} rows of the policy given to evaluate_policy() are bad (a weight that is '
                   'negative or NaN, or a sum that is not a positive finite number); they were '
                   'evaluated as taking action {}'.format(plan_rows, gamespec.N_ACTIONS - 1))
+    if visit_rows:
+      what.append('{} rows of the policy given to state_visitation() are bad (a weight that is '
+                  'negative or NaN, or a sum that is not a positive finite number); all their mass '
+                  'took action {}'.format(visit_rows, gamespec.N_ACTIONS - 1))
     if what:
       raise ValueError('; '.join(what))
 
@@ -680,6 +690,14 @@ class FusedGame(object):
   def table_arrays(self):
     """The game's table as tensors (`wide.WideGame.table_arrays`): the state-table tier only."""
     self._no_policy_rollouts('table_arrays')
+
+  def state_visitation(self, policy, frames, **kwargs):
+    """Exact state visitation (`wide.WideGame.state_visitation`): the state-table tier only."""
+    self._no_policy_rollouts('state_visitation')
+
+  def visitation_buffers(self, frames, want_frames=False):
+    """The buffers of `state_visitation(out=...)`: the state-table tier only."""
+    self._no_policy_rollouts('visitation_buffers')
 
   def _gather_op(self, trace, t_idx, e_idx, out):
     _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,

@@ -204,6 +204,12 @@ class ShapeGame(object):
   def table_arrays(self):
     self._no_policy_rollouts('table_arrays')
 
+  def state_visitation(self, policy, frames, **kwargs):
+    self._no_policy_rollouts('state_visitation')
+
+  def visitation_buffers(self, frames, want_frames=False):
+    self._no_policy_rollouts('visitation_buffers')
+
   def rollout_trace_buffers(self, T):
     self._no_stored_trace('rollout_trace_buffers')
 

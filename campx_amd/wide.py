@@ -94,6 +94,8 @@ class WideGame(fused.FusedGame):
     self._policy_frame = 0            # absolute frame the next rollout_policy() continues at
     # bad rows of the policies given to evaluate_policy() (raised under the same flag)
     self._bad_plan_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    # bad rows of the policies given to state_visitation() (raised under the same flag)
+    self._bad_visit_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     # ids of render_states() outside the table (raised with the rows of render_frames(), under
     # their flag), and the one-frame trace of its out= calls: the last block is the largest; the
     # smaller ones before it stay alive, a captured graph may still write into them
@@ -448,6 +450,147 @@ class WideGame(fused.FusedGame):
     and `evaluate_policy()` take."""
     return self._sweeps(None, gamma, sweeps, values, reward, want_q, tol,
                         check_every, out, path)
+
+  # ------------------------------------------------------------ exact visitation on the table
+
+  VISIT_UNIT = 1 << 38             # one environment, in the int64 units of state_visitation()
+
+  def _take_bad_visit_rows(self):
+    n = int(self._bad_visit_rows.item())
+    self._bad_visit_rows.zero_()
+    return n
+
+  def visitation_buffers(self, frames, want_frames=False):
+    """Allocate the dict of `state_visitation(out=...)` once: 'visits' int64 [S, 5], 'finished'
+    int64 [frames], 'final' int64 [S], 'counts' int32 [S, 5], 'scratch' int64 [S] (the second mass
+    vector of the one-launch-per-frame path) and - `want_frames` - 'per_frame' int64
+    [frames + 1, S]."""
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    frames = int(frames)
+    out = {'visits': torch.zeros((S, A), dtype=torch.int64, device=dev),
+           'finished': torch.zeros((frames,), dtype=torch.int64, device=dev),
+           'final': torch.zeros((S,), dtype=torch.int64, device=dev),
+           'counts': torch.zeros((S, A), dtype=torch.int32, device=dev),
+           'scratch': torch.zeros((S,), dtype=torch.int64, device=dev)}
+    if want_frames:
+      out['per_frame'] = torch.zeros((frames + 1, S), dtype=torch.int64, device=dev)
+    return out
+
+  def state_visitation(self, policy, frames, start=None, restart=True, want_frames=False, out=None,
+                       path=0):
+    """The exact visitation of `policy` on the game's table: how much probability sits in each
+    state at each of `frames` frames, and how often each (state, action) is taken - what
+    `rollout_policy()` followed by `returns.sum_by_state()` estimates with sampling noise, computed
+    from the table on the device (csrc/k_visit.hip, `campx::wide_visit`).
+
+    Mass is an int64 in units of 2^-38: one environment is 'unit' = 2^38.  Per state the sampler's
+    2^24 equally likely values are counted into the five actions exactly as `rollout_policy()`
+    plays them ('counts'); a state's mass m goes to its actions as `floor(m * N / 2^24)`
+    differences, which sum to m to the last unit; an action's share moves to the entry's next state
+    or - an entry that ends the episode - is counted into 'finished' and, with `restart`, moves to
+    state 0 as a rollout's environment does.  Only integers are added, so the result does not
+    depend on how the kernels ran (include/campx_hip.h has the rule in full;
+    tests/visitation_reference.py restates it bit for bit).
+
+    Args:
+      policy: what `rollout_policy()` takes, checked the same way: contiguous float32
+          `[n_states, 5]` weights.  A bad row (a negative or NaN weight, a sum that is not a
+          positive finite number) sends all its mass to action 4 - as the sampler plays it - and
+          raises ValueError with the count of such rows, lazily like `evaluate_policy()`'s: from
+          `check_actions()` or a later call, under `validate_actions='sync'` from this one.
+      frames: how many frames to run, 1 .. 2^20.
+      start: where the mass starts.  None: one environment in state 0.  An int64 `[n_states]`
+          tensor in units - every entry >= 0, the total at most 2^38 -, typically the 'final' of an
+          earlier call: n frames and then m more from it equal n + m frames bit for bit, 'visits'
+          and 'finished' adding up.  A float tensor `[n_states]` of probabilities - finite, >= 0,
+          summing to 1 within 1e-4 - is quantised HERE, not by the kernels: every entry times 2^38
+          rounded down, the units that are then missing from 2^38 given to the largest entry, so
+          that the total is exactly 2^38.  `start` is validated eagerly (a few synchronising
+          reads: this call is planning, not a hot loop).
+      restart: True - mass whose episode ends starts over in state 0, the total stays put, as in a
+          rollout of fixed length; False - it leaves, and 'finished' is what left at each frame.
+      want_frames: also return 'per_frame'.
+      out: a dict from `visitation_buffers(frames, want_frames)`, overwritten; 'final' may be the
+          `start` of the call.
+      path: 0 - all frames in one launch by one workgroup that holds the table in LDS whenever it
+          fits there, else one launch per frame; 1 / 2 force either (1 raises ValueError for a
+          table that does not fit).  Every path gives the same bits.
+
+    Returns a dict: 'visits' int64 `[n_states, 5]`, the mass that took action a in state s, summed
+    over the frames (`B * visits / 2^38` is the expectation of `sum_by_state()`'s count for B
+    environments); 'finished' int64 `[frames]`, the mass whose episode ended at each frame; 'final'
+    int64 `[n_states]`, the mass per state after the last frame; 'per_frame' int64
+    `[frames + 1, n_states]` (with `want_frames`), the mass per state before each frame and after
+    the last; 'counts' int32 `[n_states, 5]`, rows summing to 2^24; 'probs' float64
+    `[n_states, 5]` = counts / 2^24, the exact probability with which `rollout_policy()` takes a
+    in s - what `log pi` should be built from; 'unit' = 2^38.  Argument errors raise ValueError
+    before anything is launched.
+    """
+    self._check_policy(policy)
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    unit = self.VISIT_UNIT
+
+    def tensor_ok(t, dtype, shape):
+      return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape
+              and t.device == dev and t.is_contiguous())
+
+    if isinstance(frames, bool) or not isinstance(frames, int) or not 1 <= frames <= 1 << 20:
+      raise ValueError('frames must be an int, 1 <= frames <= 2^20, got {!r}'.format(frames))
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    plan = (ctypes.c_int64 * 4)()
+    if _hip.lib.campx_wide_visit_plan(S, _hip.config_get('wide_lds_max'), path, plan) != 0:
+      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
+                       '(library setting wide_lds_max); use path=0 or path=2'.format(S))
+    if start is not None:
+      if (not torch.is_tensor(start) or tuple(start.shape) != (S,) or start.device != dev
+          or not (start.dtype == torch.int64 or start.is_floating_point())):
+        raise ValueError('start must be None, an int64 [{0}] tensor of units of 2^-38 or a float '
+                         '[{0}] tensor of probabilities, on {1}'.format(S, dev))
+      start = start.detach()
+      if start.dtype == torch.int64:
+        if not start.is_contiguous():
+          raise ValueError('an int64 start must be contiguous')
+        if bool((start < 0).any()) or int(start.sum()) > unit or int(start.max()) > unit:
+          raise ValueError('an int64 start must hold entries >= 0 that total at most 2^38')
+      else:
+        p = start.double()
+        if not bool(torch.isfinite(p).all()) or bool((p < 0).any()) or abs(float(p.sum()) - 1.0) > 1e-4:
+          raise ValueError('a float start must hold finite probabilities >= 0 that sum to 1 (within 1e-4)')
+        start = torch.floor(p * float(unit)).long()
+        largest = int(torch.argmax(p))
+        start[largest] += unit - int(start.sum())
+        if int(start[largest]) < 0:
+          raise ValueError('a float start sums to more than 1 by more than its largest entry')
+    want = [('visits', torch.int64, (S, A)), ('finished', torch.int64, (frames,)),
+            ('final', torch.int64, (S,)), ('counts', torch.int32, (S, A))]
+    if plan[0] == 2:
+      want.append(('scratch', torch.int64, (S,)))
+    if want_frames:
+      want.append(('per_frame', torch.int64, (frames + 1, S)))
+    if out is None:
+      out = self.visitation_buffers(frames, want_frames)
+    else:
+      if not isinstance(out, dict) or any(not tensor_ok(out.get(k), d, sh) for k, d, sh in want):
+        raise ValueError('out must be a dict from visitation_buffers({}, want_frames={}) of this '
+                         'game: {}'.format(frames, bool(want_frames),
+                                           ', '.join('{!r} {} {}'.format(k, d, list(sh)) for k, d, sh in want)))
+      if start is not None and out.get('scratch') is not None and \
+          start.data_ptr() == out['scratch'].data_ptr():
+        raise ValueError('start must not be out[\'scratch\']')
+    validate = self.validate_actions
+    _hip.ops.wide_visit(self._spec_host, self._tables, policy.detach(), start, bool(restart),
+                        out['visits'], out['finished'], out['final'],
+                        out['per_frame'] if want_frames else None, out['counts'], out.get('scratch'),
+                        self._bad_visit_rows if validate else None,
+                        self._bad_flag if validate else None, path)
+    if validate:
+      self._after_launch()
+    res = {'visits': out['visits'], 'finished': out['finished'], 'final': out['final'],
+           'counts': out['counts'], 'probs': out['counts'].double() / float(1 << 24), 'unit': unit}
+    if want_frames:
+      res['per_frame'] = out['per_frame']
+    return res
 
   # ------------------------------------------------------------ observations by state
 

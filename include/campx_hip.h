@@ -990,6 +990,78 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* spec_host, const void* tab
                                  const float* v_in, float* v_out, float* scratch, float* q,
                                  int8_t* greedy, float* residual, int32_t* bad_rows,
                                  int32_t* bad_flag, int32_t n_sweeps, int32_t path, void* stream);
+/*
+ * ---- Exact state visitation of a policy on the state table ------------------------------------
+ * The forward half of the same MDP: given the weights campx_wide_policy_update_launch() samples
+ * from, how much probability sits in each state at each frame and how often each (state, action)
+ * is taken - exactly, where a rollout followed by campx_state_sums_launch() estimates it
+ * (csrc/k_visit.hip).  No reference counterpart.
+ *
+ * Mass is an int64 in units of 2^-CAMPX_VISIT_FRAC_BITS; one environment is 2^38.  Every addition
+ * below is an integer addition, so no result depends on the order a kernel adds in: both paths, a
+ * continued call and a numpy restatement (tests/visitation_reference.py) agree bit for bit.
+ *
+ * 1. The exact action counts of a row.  For w = policy[s] (DEVICE float32 [n_states][5]) take the
+ *    sampler's thresholds c0 = w0, c1 = c0 + w1, c2 = c1 + w2, c3 = c2 + w3, c4 = c3 + w4 (f32, in
+ *    that order); a BAD row - a negative or NaN weight, a c4 that is not a positive finite number
+ *    - has {-1, -1, -1, -1, 0}, as there.  For i = 0 .. 3, N[s][i] is the number of 24-bit values
+ *    u in 0 .. 2^24 - 1 whose sampled action is at most i: the smallest u with
+ *        float(u) * 2^-24 * c4 >= c_i
+ *    (the sampler's own f32 multiply - float(u) * 2^-24 is exact - and its own comparison), 2^24
+ *    if there is none.  The product is monotone in u: 25 bisection steps (lo = 0, hi = 2^24; mid =
+ *    (lo + hi) >> 1; reached ? hi = mid : lo = mid + 1) find it.  A bad row has N = {0, 0, 0, 0}:
+ *    all its mass takes action 4, as the sampler plays it; bad rows are counted into *bad_rows
+ *    (DEVICE int32, added to, may be NULL) once per call and *bad_flag (device or mapped pinned
+ *    int32, may be NULL) is set to 1.  N[s][4] = 2^24.
+ *    counts[s][a] = N[s][a] - N[s][a-1] (N[s][-1] = 0), DEVICE int32 [n_states][5], an output:
+ *    every row sums to 2^24, and counts / 2^24 is the exact probability with which the sampler
+ *    takes a in s.
+ * 2. Splitting a state's mass m, 0 <= m < 2^62.  For i = 0 .. 4
+ *        y_i = (m >> 24) * N_i + (((m & 0xffffff) * N_i) >> 24)
+ *    which is floor(m * N_i / 2^24) exactly and cannot overflow; y_4 = m.  x_a = y_a - y_{a-1},
+ *    y_{-1} = 0: every x_a >= 0 and they sum to m exactly.
+ * 3. One frame, from d_t to d_{t+1} (zero before the frame): for every state s with mass d_t[s]
+ *    and every action a,  visits[s][a] += x_a;  if the entry of (s, a) ends the episode,
+ *    finished[t] += x_a and - with `restart` - d_{t+1}[0] += x_a (the rollout's `from = done ? 0 :
+ *    now`; without `restart` the mass leaves); otherwise d_{t+1}[next state of (s, a)] += x_a.
+ *    Rewards, discount codes and the hidden performance play no part.
+ * 4. n_frames frames from d_0 = `start` (DEVICE int64 [n_states], every entry >= 0, total <=
+ *    2^38; NULL: 2^38 in state 0).  Outputs, all DEVICE, all overwritten: `visits` int64
+ *    [n_states][5], summed over the frames of this call (below 2^58); `finished` int64 [n_frames];
+ *    `final` int64 [n_states] = d_n; `per_frame` int64 [n_frames + 1][n_states] = d_0 .. d_n (may
+ *    be NULL); `counts`.  n frames and then m more from the `final` of the first call are n + m
+ *    frames bit for bit; their `visits` and `finished` add up.  `start` may be `final`; otherwise
+ *    it is left as it is.
+ *
+ * Two paths, `path`: 1 = after the kernel that makes `counts`, one workgroup stages the entries, N
+ * and two mass vectors in LDS and runs all n_frames in ONE launch, a workgroup barrier between
+ * frames, the scatter by 64-bit LDS atomic adds; 2 = one launch per frame, a lane per state, the
+ * scatter by 64-bit global atomic adds between `final` and `scratch` (DEVICE int64 [n_states],
+ * needed on this path only; left all zero), a frame boundary is a kernel boundary.  0 = path 1
+ * whenever the table fits the library setting wide_lds_max (52 bytes per state and a header) and
+ * has at most 3 072 states.  By the rule the choice cannot change a bit of any result.
+ *
+ * campx_wide_visit_plan() is the choice as host-only arithmetic (nothing is launched):
+ * plan_out[4] = the path taken (1 / 2); dynamic LDS bytes (0 on path 2); threads of a workgroup;
+ * workgroups of a frame.  CAMPX_EINVAL: n_states outside 1 .. CAMPX_WIDE_MAX_STATES, wide_lds_max
+ * < 0, a `path` outside 0 .. 2, path 1 for a table that does not fit.
+ * campx_wide_visit_launch() returns CAMPX_EINVAL, before anything is launched, for the same and
+ * for: NULL where it is not allowed (`start`, `per_frame`, `bad_rows`, `bad_flag` may be; `scratch`
+ * on path 1), pointers that are not aligned (8 bytes for the int64 arrays and the tables, 4 for the
+ * others), n_frames outside 1 .. 2^20, a `restart` that is not 0 / 1, `final` overlapping `start`
+ * without being equal to it, on path 2 a `scratch` that overlaps either.  The contents of `start`
+ * are the caller's to keep within the bounds above (the kernels do not look).  Asynchronous on
+ * `stream`, no synchronisation, no allocation, no library state.
+ */
+#define CAMPX_VISIT_FRAC_BITS 38
+int32_t campx_wide_visit_plan(int64_t n_states, int64_t wide_lds_max, int32_t path,
+                              int64_t* plan_out);
+int32_t campx_wide_visit_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                const float* policy, const int64_t* start, int32_t restart,
+                                int32_t n_frames, int64_t* visits, int64_t* finished,
+                                int64_t* final_mass, int64_t* per_frame, int32_t* counts,
+                                int64_t* scratch, int32_t* bad_rows, int32_t* bad_flag,
+                                int32_t path, void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
