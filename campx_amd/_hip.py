@@ -35,6 +35,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
+           'campx_wide_render_windows_launch', 'campx_wide_render_windows_plan',
            'campx_returns_launch',
            'campx_state_sums_launch', 'campx_state_sums_plan', 'campx_table_lookup_launch',
            'campx_wide_sweeps_plan', 'campx_wide_sweeps_launch',
@@ -78,6 +79,24 @@ class CampxGather(ctypes.Structure):
               ('obs', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
               ('bad_flag', ctypes.c_void_p), ('streaming', ctypes.c_int32),
               ('reserved', ctypes.c_int32)]
+
+
+class CampxWindows(ctypes.Structure):
+  """include/campx_hip.h: one request to render observation windows."""
+  _fields_ = [('source', ctypes.c_int32), ('idx64', ctypes.c_int32), ('trace', ctypes.c_void_p),
+              ('n_planes', ctypes.c_int64), ('T', ctypes.c_int64), ('pitch', ctypes.c_int64),
+              ('plane', ctypes.c_int64), ('t_idx', ctypes.c_void_p), ('e_idx', ctypes.c_void_p),
+              ('state_ids', ctypes.c_void_p), ('N', ctypes.c_int64),
+              ('h', ctypes.c_int32), ('w', ctypes.c_int32), ('anchor', ctypes.c_int32),
+              ('thing', ctypes.c_int32), ('r0', ctypes.c_int32), ('c0', ctypes.c_int32),
+              ('pad_layer', ctypes.c_int32), ('obs_format', ctypes.c_int32),
+              ('obs', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
+              ('bad_flag', ctypes.c_void_p), ('streaming', ctypes.c_int32),
+              ('reserved', ctypes.c_int32)]
+
+
+WINDOWS_PAIRS, WINDOWS_TRACE, WINDOWS_STATES = 0, 1, 2
+WINDOW_ON_THING, WINDOW_FIXED = 0, 1
 
 
 class CampxReturns(ctypes.Structure):
@@ -209,6 +228,10 @@ def _load():
   lib.campx_wide_render_states_launch.restype = i32
   lib.campx_wide_render_states_launch.argtypes = [wide_p, vp, vp, i32, i64, vp, i32, vp, i64, vp, vp,
                                                   vp]
+  lib.campx_wide_render_windows_launch.restype = i32
+  lib.campx_wide_render_windows_launch.argtypes = [wide_p, vp, vp, ctypes.POINTER(CampxWindows), i64, vp]
+  lib.campx_wide_render_windows_plan.restype = i32
+  lib.campx_wide_render_windows_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_returns_launch.restype = i32
   lib.campx_returns_launch.argtypes = [ctypes.POINTER(CampxReturns), i64, i32, vp]
   lib.campx_state_sums_launch.restype = i32
@@ -278,7 +301,7 @@ def _load_ops():
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'wide_render_states',
-            'returns', 'state_sums', 'table_lookup', 'wide_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
+            'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

@@ -17,6 +17,7 @@
 //                                   policy over the game's states (closed-loop rollouts)
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
+//   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
 //   campx::returns                  discounted returns / GAE advantages of a rollout's streams
 //   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
 //   campx::table_lookup             table[states, actions] of a rollout's streams
@@ -996,6 +997,103 @@ void wide_render_states(const Tensor& spec_host, const Tensor& tables, const Opt
            "campx_wide_render_states_launch");
 }
 
+// Wide tier: observation windows (campx_wide_render_windows_launch; include/campx_hip.h has the
+// rule).  `source` 0: rows (t_idx[i], e_idx[i]) of `trace`, `obs` [N, L, h, w]; 1: the whole trace,
+// `obs` [T, B, L, h, w]; 2: the states `t_idx` of the table (None: all of them, row i is state i),
+// `obs` [N, L, h, w].  `thing` >= 0: egocentric on that plane; -1: fixed at (r0, c0).
+// `layer_of_cell`: uint8 [max(n_variants, 1), 1024] on the device.
+void wide_render_windows(const Tensor& spec_host, const Tensor& tables, const Tensor& layer_of_cell,
+                         int64_t source, const OptTensor& trace, const OptTensor& t_idx,
+                         const OptTensor& e_idx, Tensor& obs, int64_t h, int64_t w, int64_t thing,
+                         int64_t r0, int64_t c0, int64_t pad_layer, const OptTensor& bad_count,
+                         const OptTensor& bad_flag, bool streaming) {
+  const char* what = "campx::wide_render_windows";
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
+              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
+  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  TORCH_CHECK(tables.device().is_cuda(), what, ": tables must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = tables.device();
+  TORCH_CHECK(tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  const int64_t V = hs->n_variants > 1 ? hs->n_variants : 1;
+  want(layer_of_cell, "layer_of_cell", at::kByte, dev, {V, CAMPX_WIDE_MAX_CELLS});
+  TORCH_CHECK(source >= CAMPX_WINDOWS_PAIRS && source <= CAMPX_WINDOWS_STATES, what, ": source must be 0, 1 or 2");
+  TORCH_CHECK(h >= 1 && w >= 1 && h <= 2 * hs->rows - 1 && w <= 2 * hs->cols - 1, what,
+              ": a window of ", h, " x ", w, " on a board of ", hs->rows, " x ", hs->cols);
+  const int64_t L = hs->n_layers;
+  CampxWindows q{};
+  q.source = (int32_t)source;
+  int64_t B = 1;
+  if (source != CAMPX_WINDOWS_STATES) {
+    TORCH_CHECK(trace.has_value(), what, ": this source needs a trace");
+    const int64_t K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+    TORCH_CHECK(trace->device() == dev && trace->scalar_type() == at::kShort && trace->dim() == 3 &&
+                    trace->size(0) == K && trace->size(1) >= 1 && trace->size(2) >= 1 &&
+                    (trace->size(2) == 1 || trace->stride(2) == 1),
+                what, ": trace must be int16 [", K, ", T, B] on ", dev, ", contiguous within a row");
+    const int64_t T = trace->size(1);
+    B = trace->size(2);
+    q.trace = trace->data_ptr();
+    q.n_planes = K;
+    q.T = T;
+    q.pitch = T > 1 ? trace->stride(1) : B;
+    q.plane = K > 1 ? trace->stride(0) : T * q.pitch;
+    TORCH_CHECK(q.pitch >= B && q.plane >= T * q.pitch, what, ": trace rows must be >= B apart and its "
+                "planes >= T * pitch apart");
+  }
+  if (source == CAMPX_WINDOWS_PAIRS) {
+    TORCH_CHECK(t_idx.has_value() && e_idx.has_value(), what, ": sampled pairs need t_idx and e_idx");
+    TORCH_CHECK(t_idx->dim() == 1 && t_idx->size(0) >= 1 && t_idx->device() == dev && t_idx->is_contiguous() &&
+                    (t_idx->scalar_type() == at::kLong || t_idx->scalar_type() == at::kInt),
+                what, ": t_idx must be a contiguous int64 or int32 [N] tensor on ", dev);
+    q.N = t_idx->size(0);
+    want(*e_idx, "e_idx", t_idx->scalar_type(), dev, {q.N});
+    q.t_idx = t_idx->data_ptr();
+    q.e_idx = e_idx->data_ptr();
+    q.idx64 = t_idx->scalar_type() == at::kLong ? 1 : 0;
+    want(obs, "obs", obs.scalar_type(), dev, {q.N, L, h, w});
+  } else if (source == CAMPX_WINDOWS_TRACE) {
+    q.N = q.T * B;
+    want(obs, "obs", obs.scalar_type(), dev, {q.T, B, L, h, w});
+  } else {
+    TORCH_CHECK(obs.dim() == 4 && obs.size(0) >= 1, what, ": obs must be [N, L, h, w]");
+    q.N = obs.size(0);
+    want(obs, "obs", obs.scalar_type(), dev, {q.N, L, h, w});
+    if (t_idx.has_value()) {
+      TORCH_CHECK(t_idx->scalar_type() == at::kLong || t_idx->scalar_type() == at::kInt,
+                  what, ": state ids must be int64 or int32");
+      want(*t_idx, "state_ids", t_idx->scalar_type(), dev, {q.N});
+      q.state_ids = t_idx->data_ptr();
+      q.idx64 = t_idx->scalar_type() == at::kLong ? 1 : 0;
+    }
+  }
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  q.h = (int32_t)h;
+  q.w = (int32_t)w;
+  q.anchor = thing >= 0 ? CAMPX_WINDOW_ON_THING : CAMPX_WINDOW_FIXED;
+  q.thing = (int32_t)(thing >= 0 ? thing : 0);
+  TORCH_CHECK(thing < hs->n_dyn, what, ": thing ", thing, " of ", hs->n_dyn);
+  TORCH_CHECK(thing >= 0 || (r0 >= -255 && r0 <= 255 && c0 >= -255 && c0 <= 255), what,
+              ": a fixed window's corner must be within -255 .. 255");
+  q.r0 = (int32_t)r0;
+  q.c0 = (int32_t)c0;
+  TORCH_CHECK(pad_layer >= -1 && pad_layer < L, what, ": pad layer ", pad_layer, " of ", L);
+  q.pad_layer = (int32_t)pad_layer;
+  q.obs_format = obs_format_of(obs);
+  q.obs = obs.data_ptr();
+  q.bad_count = opt_ptr<int32_t>(bad_count);
+  q.bad_flag = flag_ptr(bad_flag, dev);
+  q.streaming = streaming ? 1 : 0;
+  TORCH_CHECK(q.N <= ((1ll << 32) - 65536 - 1) / (L * h * w), what, ": ", q.N, " rows of ", L * h * w,
+              " elements are past what one call addresses (2^32 - 65536 - 1): split the request");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  check_ok(campx_wide_render_windows_launch(hs, tables.data_ptr(), layer_of_cell.data_ptr(), &q, B,
+                                            c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+           "campx_wide_render_windows_launch");
+}
+
 // Discounted returns and GAE advantages of [T, B] streams (campx_returns_launch): every stream
 // contiguous within a row, rows any pitch >= B apart, each stream its own.
 void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTensor& discount,
@@ -1308,6 +1406,9 @@ void render_gather_meta(const Tensor&, const Tensor&, const Tensor&, const Tenso
                         Tensor&, const OptTensor&, const OptTensor&, bool) {}
 void wide_render_states_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&,
                              const OptTensor&, const OptTensor&) {}
+void wide_render_windows_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, const OptTensor&,
+                              const OptTensor&, const OptTensor&, Tensor&, int64_t, int64_t, int64_t,
+                              int64_t, int64_t, int64_t, const OptTensor&, const OptTensor&, bool) {}
 void returns_meta(const Tensor&, const Tensor&, double, const OptTensor&, const OptTensor&,
                   const OptTensor&, double, Tensor&, const OptTensor&) {}
 void state_sums_meta(const Tensor&, const OptTensor&, at::TensorList, int64_t, int64_t, int64_t, bool,
@@ -1411,6 +1512,10 @@ TORCH_LIBRARY(campx, m) {
       "wide_render_states(Tensor spec_host, Tensor tables, Tensor? state_ids, Tensor(a!) obs, "
       "Tensor(b!)? scratch, Tensor(c!)? bad_count, Tensor(d!)? bad_flag) -> ()");
   m.def(
+      "wide_render_windows(Tensor spec_host, Tensor tables, Tensor layer_of_cell, int source, "
+      "Tensor? trace, Tensor? t_idx, Tensor? e_idx, Tensor(a!) obs, int h, int w, int thing, int r0, "
+      "int c0, int pad_layer, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
+  m.def(
       "returns(Tensor reward, Tensor done, float gamma, Tensor? discount, Tensor? values, "
       "Tensor? bootstrap, float lam, Tensor(a!) returns, Tensor(b!)? advantages) -> ()");
   m.def(
@@ -1449,6 +1554,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);
+  m.impl("wide_render_windows", &wide_render_windows);
   m.impl("returns", &returns);
   m.impl("state_sums", &state_sums);
   m.impl("table_lookup", &table_lookup);
@@ -1461,7 +1567,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
   for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
                            "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
-                           "returns", "state_sums", "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids",
+                           "wide_render_windows", "returns", "state_sums", "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids",
                            "check_actions"})
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
@@ -1481,6 +1587,7 @@ TORCH_LIBRARY_IMPL(campx, Meta, m) {
   m.impl("render_gather", &render_gather_meta);
   m.impl("wide_render_gather", &render_gather_meta);
   m.impl("wide_render_states", &wide_render_states_meta);
+  m.impl("wide_render_windows", &wide_render_windows_meta);
   m.impl("returns", &returns_meta);
   m.impl("state_sums", &state_sums_meta);
   m.impl("table_lookup", &table_lookup_meta);

@@ -495,6 +495,37 @@ class Engine(object):
                          'been through its_showtime()')
     return self._fused.render_states(state_ids, obs_dtype=obs_dtype, out=out)
 
+  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
+    """State-table tier only: `[N, L, h, w]`, `render_frames()` of the pairs `(t_idx[i], e_idx[i])`
+    cropped to a `campx_amd.windows.Window` - egocentric on a tracked thing or fixed on the board -
+    without the full observations being written.  See `wide.WideGame.render_frame_windows`; the
+    other batched tiers raise NotImplementedError (`use_state_table()` before `its_showtime()`
+    puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('render_frame_windows() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.render_frame_windows(trace, t_idx, e_idx, window, obs_dtype=obs_dtype, out=out)
+
+  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
+    """State-table tier only: `[T, B, L, h, w]`, the windows of every frame of a trace.  See
+    `wide.WideGame.render_trace_windows`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('render_trace_windows() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.render_trace_windows(trace, window, obs_dtype=obs_dtype, out=out)
+
+  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
+    """State-table tier only: `[N, L, h, w]`, `render_states()` of the states `state_ids` (None:
+    all of them) cropped to a `campx_amd.windows.Window` - what a network that sees only the
+    agent's surroundings is evaluated on, once per state.  See
+    `wide.WideGame.render_state_windows`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    if self._fused is None:
+      raise RuntimeError('render_state_windows() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()')
+    return self._fused.render_state_windows(window, state_ids, obs_dtype=obs_dtype, out=out)
+
   def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
     """State-table tier only: the exact value of `policy`, float32 `[n_states, 5]` weights per
     state, after `sweeps` Jacobi sweeps of the Bellman backup over the game's table - 'values',

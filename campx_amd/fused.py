@@ -241,6 +241,12 @@ class FusedGame(object):
     flag of render_frames()'s rows); 0 on the other tiers."""
     return 0
 
+  def _take_bad_windows(self):
+    """(rows of render_frame_windows() outside the trace, state ids of render_state_windows()
+    outside the table): the state-table tier counts them under the flag of render_frames()'s rows;
+    (0, 0) on the other tiers."""
+    return 0, 0
+
   def _raise_bad(self, indices=False):
     """One ValueError for everything the kernels counted: action ids outside 0..4, bad policy rows
     met by rollout_policy() and - when their flag is up, or `indices` - rows of render_frames()
@@ -252,6 +258,7 @@ class FusedGame(object):
     state_ids = self._take_bad_state_ids()
     plan_rows = self._take_bad_plan_rows()
     visit_rows = self._take_bad_visit_rows()
+    window_rows, window_ids = self._take_bad_windows()
     self._bad.zero_()
     self._bad_flag_view[0] = 0
     what = []
@@ -276,6 +283,12 @@ class FusedGame(object):
       what.append('{} rows of the policy given to state_visitation() are bad (a weight that is '
                   'negative or NaN, or a sum that is not a positive finite number); all their mass '
                   'took action {}'.format(visit_rows, gamespec.N_ACTIONS - 1))
+    if window_rows:
+      what.append('{} rows of render_frame_windows() named a frame or an environment outside the '
+                  'trace (their windows were rendered from the nearest one inside)'.format(window_rows))
+    if window_ids:
+      what.append('{} state ids of render_state_windows() are outside the game\'s table (their '
+                  'windows were rendered as state 0\'s)'.format(window_ids))
     if what:
       raise ValueError('; '.join(what))
 
@@ -678,6 +691,18 @@ class FusedGame(object):
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """Observations by state index (`wide.WideGame.render_states`): the state-table tier only."""
     self._no_policy_rollouts('render_states')
+
+  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
+    """Observation windows (`wide.WideGame.render_frame_windows`): the state-table tier only."""
+    self._no_policy_rollouts('render_frame_windows')
+
+  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
+    """Observation windows (`wide.WideGame.render_trace_windows`): the state-table tier only."""
+    self._no_policy_rollouts('render_trace_windows')
+
+  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
+    """Observation windows (`wide.WideGame.render_state_windows`): the state-table tier only."""
+    self._no_policy_rollouts('render_state_windows')
 
   def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
     """Exact policy evaluation (`wide.WideGame.evaluate_policy`): the state-table tier only."""

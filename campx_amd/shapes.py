@@ -195,6 +195,15 @@ class ShapeGame(object):
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     self._no_policy_rollouts('render_states')
 
+  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
+    self._no_stored_trace('render_frame_windows')
+
+  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
+    self._no_stored_trace('render_trace_windows')
+
+  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
+    self._no_policy_rollouts('render_state_windows')
+
   def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
     self._no_policy_rollouts('evaluate_policy')
 

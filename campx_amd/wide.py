@@ -101,6 +101,11 @@ class WideGame(fused.FusedGame):
     # smaller ones before it stay alive, a captured graph may still write into them
     self._bad_state_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._states_scratch = []
+    # the same two of the window calls, counted apart so that the error says where they came from
+    self._bad_window_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_window_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._layer_of_cell = None        # the window kernel's scenery table
+    self._window_table()
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._bad_flag_view = self._bad_flag.numpy()
     self.validate_actions = True
@@ -654,6 +659,145 @@ class WideGame(fused.FusedGame):
     elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
       self._raise_bad()
     return out
+
+  # ------------------------------------------------------------ observation windows
+
+  def _take_bad_windows(self):
+    rows, ids = int(self._bad_window_rows.item()), int(self._bad_window_ids.item())
+    self._bad_window_rows.zero_()
+    self._bad_window_ids.zero_()
+    return rows, ids
+
+  def _window_table(self):
+    """uint8 [variants, 1024] on the device: the scenery's layer per cell of each variant, from
+    the host arrays the game keeps (the table blob is not touched).  The scenery's row is one-hot
+    per cell - campx_wide_tables_build() sets exactly the byte of this layer - so the layer is all
+    the window kernel needs of it."""
+    if self._layer_of_cell is None:
+      import numpy as np
+      HW = self.rows * self.cols
+      tops = self._arrays.get('variant_top_layer')
+      if self.spec.n_variants > 1 and tops is not None:
+        tops = np.asarray(tops, np.uint8).reshape(int(self.spec.n_variants), HW)
+      else:
+        tops = np.frombuffer(bytes(bytearray(self.spec.static_top_layer)), np.uint8)[:HW].reshape(1, HW)
+      table = np.zeros((tops.shape[0], 1024), np.uint8)
+      table[:, :HW] = tops
+      self._layer_of_cell = torch.from_numpy(table).to(self.device)
+    return self._layer_of_cell
+
+  def _windows(self, method, source, window, trace, t_idx, e_idx, shape, obs_dtype, out):
+    from . import windows
+    if not isinstance(window, windows.Window):
+      raise ValueError('{}(): window must be a campx_amd.windows.Window, got {}'.format(
+          method, type(window).__name__))
+    where = window.resolve(self.chars, self.spec)
+    shape = tuple(shape) + (self.n_layers, window.height, window.width)
+    rows = 1
+    for n in shape[:-3]:
+      rows *= n
+    if rows * self.n_layers * window.height * window.width > (1 << 32) - 65536 - 1:
+      raise ValueError('{}(): {} rows of {} x {} x {} elements are past what one call addresses '
+                       '(2^32 - 65536 - 1 elements): split the request'.format(
+                           method, rows, self.n_layers, window.height, window.width))
+    if out is None:
+      if obs_dtype not in fused._OBS_DTYPES:
+        raise ValueError('obs_dtype must be torch.int8, float16 or bfloat16')
+      out = torch.empty(shape, dtype=obs_dtype, device=self.device)
+    elif (not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype not in fused._OBS_DTYPES
+          or not out.is_contiguous() or out.device != self.device):
+      raise ValueError('out must be a contiguous int8 / float16 / bfloat16 {} tensor on {}'.format(
+          list(shape), self.device))
+    _hip.ops.wide_render_windows(
+        self._spec_host, self._tables, self._window_table(), source, trace, t_idx, e_idx, out,
+        window.height, window.width, where.thing, where.r0, where.c0, where.pad_layer,
+        self._bad_window_ids if source == _hip.WINDOWS_STATES else self._bad_window_rows,
+        self._bad_idx_flag, fused.GATHER_STREAMING)
+    if self.validate_actions == 'sync':
+      self._raise_bad(indices=True)
+    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
+      self._raise_bad()
+    return out
+
+  def _check_window_trace(self, trace):
+    planes = self._n_planes
+    if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.dtype != torch.int16
+        or trace.shape[0] != planes or trace.shape[2] != self.batch or trace.device != self.device):
+      raise ValueError('trace must be a {} [{}, T, {}] tensor of this game on {}'.format(
+          torch.int16, planes, self.batch, self.device))
+
+  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
+    """Windows of the observations of sampled transitions, `[N, L, h, w]`: `render_frames()`
+    cropped to what `window` shows, without the full observations being written.
+
+    Row i is bit for bit `render_frames(trace, t_idx, e_idx)[i]` cut to the `h x w` cells whose
+    top-left cell is `(row - h // 2, col - w // 2)` of the tracked thing's cell in that frame -
+    or the window's fixed corner -, with cells off the board 0, or 1 in the layer of the window's
+    `pad` character (include/campx_hip.h has the rule; `campx_amd.windows.Window`).  A thing that
+    is hidden still centres its window where its trace entry says it is.
+
+    Args:
+      trace, t_idx, e_idx: as for `render_frames()`; indices outside the trace are clamped on the
+          device, counted, and raise ValueError lazily - from a later call or `check_actions()` -
+          in a message that names this call.
+      window: a `campx_amd.windows.Window`.
+      obs_dtype: torch.int8 (0 / 1), torch.float16 or torch.bfloat16 (0.0 / 1.0).
+      out: a contiguous `[N, L, h, w]` tensor of such a dtype to write into.  The call then
+          allocates nothing and does not synchronise: it is capturable in a HIP graph.
+    """
+    self._check_window_trace(trace)
+    t_idx, e_idx = torch.as_tensor(t_idx), torch.as_tensor(e_idx)
+    if t_idx.dim() != 1 or t_idx.shape != e_idx.shape or t_idx.numel() < 1:
+      raise ValueError('t_idx and e_idx must be integer tensors [N] of one length N >= 1')
+    if t_idx.dtype not in (torch.int32, torch.int64) or e_idx.dtype != t_idx.dtype:
+      raise ValueError('t_idx and e_idx must both be int64 or both int32')
+    t_idx = t_idx.to(self.device).contiguous()
+    e_idx = e_idx.to(self.device).contiguous()
+    return self._windows('render_frame_windows', _hip.WINDOWS_PAIRS, window, trace, t_idx, e_idx,
+                         (int(t_idx.numel()),), obs_dtype, out)
+
+  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
+    """Windows of EVERY frame of a trace, `[T, B, L, h, w]`: `render_frame_windows()` of
+    `(t, e)` for all t and e, without index tensors.  `trace` may be a view of a padded buffer, as
+    `rollout_policy()` returns it.  `out`: a contiguous `[T, B, L, h, w]` tensor to write into
+    (the call is then capturable in a HIP graph)."""
+    self._check_window_trace(trace)
+    return self._windows('render_trace_windows', _hip.WINDOWS_TRACE, window, trace, None, None,
+                         (int(trace.shape[1]), self.batch), obs_dtype, out)
+
+  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
+    """Windows of the observations of states of the game's table, `[N, L, h, w]`:
+    `render_states()` cropped to what `window` shows.  The window round the agent is a function of
+    the state, so a network that sees only the window is still a per-state table: evaluate it on
+    `render_state_windows(window)` once and hand the result to `rollout_policy()`.
+
+    Row i is bit for bit the window of `render_states(state_ids)[i]`; the states' entries are
+    read from the table directly, no scratch trace is kept.  Row 0 of all states is the window of
+    the `its_showtime()` frame.
+
+    Args:
+      window: a `campx_amd.windows.Window`.
+      state_ids: int32 or int64 `[N]` on the game's device, N >= 1; None: all states.  Ids outside
+          `[0, n_states)` are rendered as state 0, counted, and raise ValueError lazily, in a
+          message that names this call.
+      obs_dtype: torch.int8 (0 / 1), torch.float16 or torch.bfloat16 (0.0 / 1.0).
+      out: a contiguous `[N, L, h, w]` tensor of such a dtype to write into (no allocation, no
+          synchronisation: capturable in a HIP graph).
+    """
+    if state_ids is None:
+      ids, N = None, self.n_states
+    else:
+      ids = state_ids
+      if (not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1
+          or ids.numel() < 1 or ids.device != self.device):
+        got = ('{} {} on {}'.format(ids.dtype, list(ids.shape), ids.device)
+               if torch.is_tensor(ids) else type(ids).__name__)
+        raise ValueError('state_ids must be an int32 or int64 [N] tensor on {}, N >= 1 (or None for '
+                         'all {} states), got {}'.format(self.device, self.n_states, got))
+      ids = ids.contiguous()
+      N = int(ids.numel())
+    return self._windows('render_state_windows', _hip.WINDOWS_STATES, window, None, ids, None,
+                         (N,), obs_dtype, out)
 
   _trace_dtype = torch.int16
 

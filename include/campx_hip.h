@@ -785,6 +785,84 @@ int32_t campx_wide_render_states_launch(const CampxWideSpec* spec_host, const vo
                                         int32_t obs_format, void* scratch, int64_t scratch_bytes,
                                         int32_t* bad_count, int32_t* bad_flag, void* stream);
 /*
+ * ---- Observation windows: egocentric or fixed crops, rendered without the full observation ----
+ * A learner on a large board rarely wants the whole board: it wants what the agent sees.  Row i of
+ * `obs` DEVICE [N][L][h][w] is a WINDOW of the observation that campx_wide_render_gather_launch() /
+ * campx_wide_render_states_launch() write for the same row - `full[i]`, [L][H][W] - computed from
+ * the row's trace entries without `full` ever being written (csrc/k_window.hip).  No reference
+ * counterpart: the reference has no croppers.
+ *
+ * The rule.  A window is (h, w, anchor, pad).  Let (r0, c0) be the board coordinates of the
+ * window's top-left cell:
+ *   - CAMPX_WINDOW_ON_THING, egocentric on thing k: cell = entry_k & 0x3ff, where entry_k is the
+ *     row's trace entry in plane k, clamped to H*W - 1; (cy, cx) = divmod(cell, W);
+ *     r0 = cy - h / 2, c0 = cx - w / 2 (integer division).  The `shows` bit is NOT consulted: a
+ *     hidden thing centres the window where its entry says it is.
+ *   - CAMPX_WINDOW_FIXED: (r0, c0) is given; either may be negative (each within -255 .. 255).
+ * Then
+ *     obs[i][l][y][x] = full[i][l][r0 + y][c0 + x]      where that cell is on the board,
+ *                     = (l == pad_layer) ? 1 : 0        off the board (pad_layer -1: 0 everywhere).
+ * Formats are int8 0 / 1, f16 (0x3C00) and bf16 (0x3F80), as everywhere else.  By definition a
+ * window is a crop of the full observation.
+ *
+ * Where a row's entries come from (`source`):
+ *   CAMPX_WINDOWS_PAIRS   t_idx[i] * pitch + e_idx[i] into each plane of `trace`: CampxGather's
+ *                         addressing - int32 or int64 indices, clamped, bad ones counted.
+ *   CAMPX_WINDOWS_TRACE   no index arrays: row i is frame i / B, environment i % B; N = T * B and
+ *                         `obs` is [T][B][L][h][w].
+ *   CAMPX_WINDOWS_STATES  the entries of state state_ids[i] of the table blob, read directly (no
+ *                         scratch trace); NULL: row i is state i.  An id outside [0, n_states) is
+ *                         rendered as state 0 and counted.
+ * `layer_of_cell` DEVICE uint8 [max(n_variants, 1)][CAMPX_WIDE_MAX_CELLS], 16-byte aligned: the
+ * scenery's layer per cell of each variant (CampxWideSpec.static_top_layer /
+ * variant_top_layer), cells past rows * cols padded with anything.  The caller builds it; the
+ * table blob is not changed.
+ */
+#define CAMPX_WINDOWS_PAIRS 0
+#define CAMPX_WINDOWS_TRACE 1
+#define CAMPX_WINDOWS_STATES 2
+#define CAMPX_WINDOW_ON_THING 0
+#define CAMPX_WINDOW_FIXED 1
+
+typedef struct CampxWindows {
+  int32_t source;       /* CAMPX_WINDOWS_PAIRS / _TRACE / _STATES */
+  int32_t idx64;        /* t_idx / e_idx / state_ids are int64 (else int32) */
+  const void* trace;    /* PAIRS, TRACE: DEVICE uint16 [n_planes][T][pitch], as CampxGather.trace */
+  int64_t n_planes;     /* must be the game's */
+  int64_t T;            /* frames the trace holds */
+  int64_t pitch;        /* entries from one frame's row to the next (>= B) */
+  int64_t plane;        /* entries from one plane to the next (>= T * pitch) */
+  const void* t_idx;    /* PAIRS: DEVICE [N] frame of row i ... */
+  const void* e_idx;    /* ... and its environment */
+  const void* state_ids; /* STATES: DEVICE [N], or NULL for 0 .. N-1 */
+  int64_t N;            /* rows; N * L*h*w at most 2^32 - 65536 - 1 */
+  int32_t h, w;         /* 1 <= h <= 2*rows - 1, 1 <= w <= 2*cols - 1, L*h*w >= 16 */
+  int32_t anchor;       /* CAMPX_WINDOW_ON_THING / _FIXED */
+  int32_t thing;        /* ON_THING: the plane that centres the window, < n_dyn */
+  int32_t r0, c0;       /* FIXED: the top-left cell */
+  int32_t pad_layer;    /* the layer set off the board, or -1 */
+  int32_t obs_format;   /* CAMPX_OBS_INT8 / _F16 / _BF16 */
+  void* obs;            /* DEVICE [N][L][h][w], 16-byte aligned */
+  int32_t* bad_count;   /* optional device int32: += rows with an index or id out of range */
+  int32_t* bad_flag;    /* optional, as CampxOutputs.bad_flag */
+  int32_t streaming;    /* as CampxGather.streaming */
+  int32_t reserved;
+} CampxWindows;
+
+/* Asynchronous on `stream`, no synchronisation, no allocation, no library state.  Every argument
+ * is checked before anything touches a device.  CAMPX_EINVAL: a NULL or misaligned pointer; h < 1,
+ * w < 1, h > 2*rows - 1 or w > 2*cols - 1; L*h*w < 16; N <= 0 or N * L*h*w above
+ * 2^32 - 65536 - 1; a thing plane >= n_dyn; a pad layer >= L; a fixed corner outside -255 .. 255;
+ * a trace geometry that campx_wide_render_gather_launch() refuses (pitch < B, a plane count that
+ * is not the game's, planes closer than T * pitch); TRACE with N != T * B. */
+int32_t campx_wide_render_windows_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                         const void* layer_of_cell, const CampxWindows* windows,
+                                         int64_t B, void* stream);
+/* The launch arithmetic of the above, host only: campx_render_gather_plan()'s eight numbers for
+ * rows of Rw = L*h*w elements (16 .. 16 * 253 * 253). */
+int32_t campx_wide_render_windows_plan(int64_t N, int32_t Rw, int32_t obs_format, uint64_t dst_addr,
+                                       int64_t* plan_out);
+/*
  * ---- Discounted returns and GAE advantages of a rollout, episode-aware ------------------------
  * One backward pass over the [T][B] streams of any tier's rollout, in one launch
  * (csrc/k_returns.hip).  Rollouts rebuild a finished environment in-kernel, so an episode may end
