@@ -299,7 +299,7 @@ def _load_ops():
 
 
 ops = _load_ops()
-OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'shape_rollout', 'wide_rollout',
+OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
 

@@ -9,6 +9,7 @@
 //   campx::step     one Engine.play() frame for B environments
 //   campx::rollout  T consecutive frames in one launch
 //   campx::update / campx::render   the two kernels of a rollout as separate ops
+//   campx::rollout_pipelined        the two of them over two streams, in one dispatch
 //   campx::update_render            update of one rollout + render of the one before it
 //   campx::shape_rollout            the shape tier (Hello World): reset / step / rollout
 //   campx::wide_rollout             the wide tier (boards above 128 cells): reset / step / rollout
@@ -29,7 +30,7 @@
 // place (declared mutable in the schema, so functionalization and torch.compile see
 // the writes); the work is enqueued on torch's CURRENT HIP stream of the tensors'
 // device and nothing synchronises.  Registered for the CUDA dispatch key (= HIP on
-// ROCm) and Meta (shape-free no-op, which is also the fake-tensor implementation).
+// ROCm) and Meta (one boxed no-op for every op, which is also the fake-tensor implementation).
 // There is deliberately no CPU kernel: calling these with CPU state raises.
 // An ADInplaceOrView kernel (one boxed function, registered for every op) bumps the version
 // counter of every tensor an op writes, so that autograd refuses a backward pass through a
@@ -39,7 +40,8 @@
 // types below are torch's own names for that arrangement.)
 //
 // The ops only unpack tensors into the C ABI of include/campx_hip.h; all kernels
-// live in csrc/k_*.hip.
+// live in csrc/k_*.hip.  Each contract a tensor has to meet is one helper in the first part of
+// this file; the ops below them say which of their arguments meets which.
 
 #include <ATen/core/Tensor.h>
 #include <ATen/core/dispatch/Dispatcher.h>
@@ -54,8 +56,8 @@
 #include <map>
 #include <mutex>
 #include <optional>
+#include <string>
 #include <unordered_map>
-#include <vector>
 
 #include "campx_hip.h"
 
@@ -63,6 +65,12 @@ namespace {
 
 using at::Tensor;
 using OptTensor = std::optional<Tensor>;
+using DeviceGuard = c10::hip::HIPGuardMasqueradingAsCUDA;
+
+const OptTensor kNone;
+
+// torch's current stream of the current device (ask under the op's DeviceGuard)
+hipStream_t current_stream() { return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(); }
 
 void check_ok(int32_t rc, const char* what) {
   TORCH_CHECK(rc == CAMPX_OK, what, " failed: ", campx_strerror(rc), " (code ", rc, ", hipError ",
@@ -77,29 +85,84 @@ const CampxSpec* host_spec(const Tensor& spec_host) {
   return reinterpret_cast<const CampxSpec*>(spec_host.data_ptr());
 }
 
-void want(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
-          c10::IntArrayRef shape) {
+// The spec struct `type` of the other tiers in host memory ...
+const void* host_blob(const Tensor& spec_host, size_t bytes, const char* type) {
+  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
+                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)bytes,
+              "campx: spec_host must be the ", type, " blob as a CPU uint8 tensor");
+  return spec_host.data_ptr();
+}
+
+const CampxWideSpec* wide_spec(const Tensor& spec_host) {
+  return static_cast<const CampxWideSpec*>(host_blob(spec_host, sizeof(CampxWideSpec), "CampxWideSpec"));
+}
+
+// ... and a spec struct's copy on the device.
+const void* dev_blob(const Tensor& spec_dev, size_t bytes, const char* type, const c10::Device& dev) {
+  TORCH_CHECK(spec_dev.device() == dev && spec_dev.scalar_type() == at::kByte &&
+                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)bytes,
+              "campx: spec_dev must be the ", type, " blob as a uint8 tensor on ", dev);
+  return spec_dev.data_ptr();
+}
+
+const CampxSpec* dev_spec(const Tensor& spec_dev, const c10::Device& dev) {
+  return static_cast<const CampxSpec*>(dev_blob(spec_dev, sizeof(CampxSpec), "CampxSpec", dev));
+}
+
+// The device blob campx_wide_tables_build() filled for the state-table game `hs`.
+void want_wide_tables(const Tensor& tables, const CampxWideSpec* hs, const c10::Device& dev) {
+  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
+                  tables.numel() == campx_wide_tables_bytes(hs),
+              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+}
+
+// Planes of a state-table game's trace: the things, plus the scenery's variant when it has
+// several - or the mask of its pieces that show (the library's rule, csrc/k_wide.hip).
+inline int64_t wide_planes(const CampxWideSpec* hs) {
+  return hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+}
+
+void want_on(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev) {
   TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
   TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
               t.scalar_type());
+}
+
+void want(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
+          c10::IntArrayRef shape) {
+  want_on(t, name, dtype, dev);
   TORCH_CHECK(t.is_contiguous(), "campx: ", name, " must be contiguous");
   TORCH_CHECK(t.sizes() == shape, "campx: ", name, " must have shape ", shape, ", it has ",
               t.sizes());
 }
 
-// The per-frame scalar streams [T, B] and the trace [K, T, B] may be PADDED: contiguous
-// within a row, rows `pitch` >= B elements apart, the same pitch for every stream of a call
-// (the planes of the trace then T * pitch apart).  rollout_buffers() pads to a multiple of
+// A [T, B] stream: contiguous within a row, its rows as far apart as stride(0) says.
+void want_row_stream(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
+                     int64_t T, int64_t B) {
+  want_on(t, name, dtype, dev);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
+              " must have shape [", T, ", ", B, "], it has ", t.sizes());
+  TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
+}
+
+// ... of campx::returns / state_sums / table_lookup: rows any pitch >= B apart, each stream its
+// own; returns the pitch.
+int64_t stream_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
+                    int64_t T, int64_t B) {
+  want_row_stream(t, name, dtype, dev, T, B);
+  TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
+              ", below its ", B, " columns");
+  return T == 1 ? B : t.stride(0);
+}
+
+// ... of a rollout.  The per-frame scalar streams [T, B] and the trace [K, T, B] may be PADDED:
+// contiguous within a row, rows `pitch` >= B elements apart, the same pitch for every stream of a
+// call (the planes of the trace then T * pitch apart).  rollout_buffers() pads to a multiple of
 // 16 when the batch size is not one, so that every row starts aligned
 // (CampxOutputs.scalar_pitch).  `pitch` is 0 until the first stream has been seen.
 void want_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
                int64_t T, int64_t B, int64_t& pitch) {
-  TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
-  TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
-              t.scalar_type());
-  TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
-              " must have shape [", T, ", ", B, "], it has ", t.sizes());
-  TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
+  want_row_stream(t, name, dtype, dev, T, B);
   if (T == 1) {
     // One row: its own pitch is never used, but the call's pitch (taken from the planes of the
     // trace, want_trace() runs first) decides whether the update kernels store the row's last
@@ -120,21 +183,57 @@ void want_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c1
   pitch = p;
 }
 
+const char* entry_name(at::ScalarType entry) { return entry == at::kByte ? "uint8" : "int16"; }
+
+// The trace a rollout writes: `entry` uint8 (one-cell tiers) or int16 (state-table tier),
+// [K, T, B] - or, `frames` false, the one frame [K, B] - padded like the streams above.
 // (call it before want_rows: with one frame only the planes of the trace tell the pitch)
-void want_trace(const Tensor& t, const c10::Device& dev, int64_t K, int64_t T, int64_t B,
-                int64_t& pitch) {
-  TORCH_CHECK(t.device() == dev && t.scalar_type() == at::kByte && t.dim() == 3 &&
-                  t.size(0) == K && t.size(1) == T && t.size(2) == B,
-              "campx: trace must be uint8 [", K, ", ", T, ", ", B, "] on ", dev);
-  TORCH_CHECK(B == 1 || t.stride(2) == 1, "campx: trace must be contiguous within a row");
+void want_trace(const Tensor& t, at::ScalarType entry, const c10::Device& dev, int64_t K, int64_t T,
+                int64_t B, int64_t& pitch, bool frames = true) {
+  const bool shaped = frames ? t.dim() == 3 && t.size(0) == K && t.size(1) == T && t.size(2) == B
+                             : t.dim() == 2 && t.size(0) == K && t.size(1) == B;
+  TORCH_CHECK(t.device() == dev && t.scalar_type() == entry && shaped, "campx: trace must be ",
+              entry_name(entry), " [", K, ", ", frames ? c10::str(T, ", ") : std::string(), B,
+              "] on ", dev);
+  TORCH_CHECK(B == 1 || t.stride(frames ? 2 : 1) == 1, "campx: trace must be contiguous within a row");
   int64_t p = pitch;
-  if (T > 1) p = t.stride(1);
+  if (frames && T > 1) p = t.stride(1);
   else if (K > 1) p = t.stride(0);
   if (p == 0) return;            // one frame, one plane: nothing to tell
-  TORCH_CHECK(p >= B && (pitch == 0 || p == pitch) && (K == 1 || t.stride(0) == T * p),
+  TORCH_CHECK(p >= B && (pitch == 0 || p == pitch) && (K == 1 || !frames || t.stride(0) == T * p),
               "campx: trace must have the row pitch of the other per-frame streams and planes "
               "T * pitch apart");
   pitch = p;
+}
+
+// A STORED trace, as the gather and window ops read it: [planes, T', B] of any T', rows and
+// planes as far apart as the strides say (a view of a padded buffer, a ring of several rollouts).
+struct StoredTrace {
+  int64_t T, B, pitch, plane;
+};
+
+StoredTrace want_stored_trace(const char* what, const Tensor& t, at::ScalarType entry,
+                              const c10::Device& dev, int64_t planes) {
+  TORCH_CHECK(t.device() == dev && t.scalar_type() == entry && t.dim() == 3 && t.size(0) == planes &&
+                  t.size(1) >= 1 && t.size(2) >= 1 && (t.size(2) == 1 || t.stride(2) == 1),
+              what, ": trace must be ", entry_name(entry), " [", planes, ", T, B] on ", dev,
+              ", contiguous within a row");
+  StoredTrace s{t.size(1), t.size(2), 0, 0};
+  s.pitch = s.T > 1 ? t.stride(1) : s.B;
+  s.plane = planes > 1 ? t.stride(0) : s.T * s.pitch;
+  TORCH_CHECK(s.pitch >= s.B && s.plane >= s.T * s.pitch, what, ": trace rows must be >= B apart and its "
+              "planes >= T * pitch apart");
+  return s;
+}
+
+// The sampled (frame, environment) pairs of those ops: two index tensors [N] of one integer
+// type; returns N.
+int64_t want_pairs(const char* what, const Tensor& t_idx, const Tensor& e_idx, const c10::Device& dev) {
+  TORCH_CHECK(t_idx.dim() == 1 && t_idx.size(0) >= 1 && t_idx.device() == dev && t_idx.is_contiguous() &&
+                  (t_idx.scalar_type() == at::kLong || t_idx.scalar_type() == at::kInt),
+              what, ": t_idx must be a contiguous int64 or int32 [N] tensor on ", dev);
+  want(e_idx, "e_idx", t_idx.scalar_type(), dev, {t_idx.size(0)});
+  return t_idx.size(0);
 }
 
 template <typename T>
@@ -158,6 +257,75 @@ int32_t* flag_ptr(const OptTensor& t, const c10::Device& dev) {
   return static_cast<int32_t*>(mapped);
 }
 
+// The stream half of CampxOutputs: the optional per-frame streams of a call - [T, B] of the
+// call's row pitch (want_trace() comes first) or, `frames` false, [B] of its one frame - and the
+// bad-action counter and flag.  (`out.trace` is the caller's.)
+void want_streams(CampxOutputs& out, const c10::Device& dev, int64_t T, int64_t B, int64_t pitch,
+                  bool frames, const OptTensor& reward, const OptTensor& discount,
+                  const OptTensor& step_done, const OptTensor& perf, const OptTensor& bad_count,
+                  const OptTensor& bad_flag) {
+  const struct { const OptTensor& t; const char* name; at::ScalarType dtype; } streams[] = {
+      {reward, "reward", at::kFloat}, {discount, "discount", at::kFloat},
+      {step_done, "step_done", at::kByte}, {perf, "perf", at::kChar}};
+  for (const auto& s : streams) {
+    if (!s.t.has_value()) continue;
+    if (frames) want_rows(*s.t, s.name, s.dtype, dev, T, B, pitch);
+    else want(*s.t, s.name, s.dtype, dev, {B});
+  }
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  out.scalar_pitch = pitch;
+  out.reward = opt_ptr<float>(reward);
+  out.discount = opt_ptr<float>(discount);
+  out.done = opt_ptr<uint8_t>(step_done);
+  out.perf = opt_ptr<int8_t>(perf);
+  out.bad_count = opt_ptr<int32_t>(bad_count);
+  out.bad_flag = flag_ptr(bad_flag, dev);
+}
+
+int32_t obs_format_of(const Tensor& obs) {
+  switch (obs.scalar_type()) {
+    case at::kChar: return CAMPX_OBS_INT8;
+    case at::kHalf: return CAMPX_OBS_F16;
+    case at::kBFloat16: return CAMPX_OBS_BF16;
+    default: TORCH_CHECK(false, "campx: obs must be int8, float16 or bfloat16, it is ", obs.scalar_type());
+  }
+  return 0;
+}
+
+// The observation half of CampxOutputs: `obs` (int8, or f16 / bf16 for a policy network) and the
+// optional int8 `board`, each [T, B, ...] - every frame kept - or [B, ...] - one frame buffer,
+// overwritten: the last frame.  kOne: the op has one frame; kEvery: it keeps them all; kAsGiven:
+// each tensor's rank says which - `alike`, the wide tier's rule, the same for both (names the op).
+enum class Frames { kOne, kEvery, kAsGiven };
+
+void want_frames(CampxOutputs& out, const c10::Device& dev, Frames frames, int64_t T, int64_t B,
+                 int64_t L, int64_t H, int64_t W, const Tensor& obs, const OptTensor& board,
+                 const char* obs_name = "obs", const char* alike = nullptr) {
+  out.obs_format = obs_format_of(obs);
+  const bool keep = frames == Frames::kEvery || (frames == Frames::kAsGiven && obs.dim() == 5);
+  if (keep) want(obs, obs_name, obs.scalar_type(), dev, {T, B, L, H, W});
+  else want(obs, obs_name, obs.scalar_type(), dev, {B, L, H, W});
+  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
+  out.obs_t_stride = keep ? B * L * H * W : 0;
+  if (!board.has_value()) return;
+  const bool bkeep = frames == Frames::kEvery || (frames == Frames::kAsGiven && board->dim() == 4);
+  TORCH_CHECK(!alike || bkeep == keep, alike,
+              ": obs and board must both keep every frame or both the last");
+  if (bkeep) want(*board, "board", at::kChar, dev, {T, B, H, W});
+  else want(*board, "board", at::kChar, dev, {B, H, W});
+  out.board = reinterpret_cast<int8_t*>(board->data_ptr());
+  out.board_t_stride = bkeep ? B * H * W : 0;
+}
+
+// An action stream int8 [T, B]; returns T.
+int64_t want_actions(const char* what, const Tensor& actions, const c10::Device& dev, int64_t B) {
+  TORCH_CHECK(actions.dim() == 2, what, ": actions must be int8 [T, B]");
+  want(actions, "actions", at::kChar, dev, {actions.size(0), B});
+  return actions.size(0);
+}
+
+const int8_t* ids(const Tensor& actions) { return reinterpret_cast<const int8_t*>(actions.data_ptr()); }
+
 struct Game {
   const CampxSpec* spec_host;
   const CampxSpec* spec_dev;
@@ -177,35 +345,55 @@ Game unpack_game(const Tensor& spec_host, const Tensor& spec_dev, const Tensor& 
   want(pos, "pos", at::kChar, dev, {2 * K, B});
   want(done, "done", at::kByte, dev, {B});
   if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
-  TORCH_CHECK(spec_dev.device() == dev && spec_dev.scalar_type() == at::kByte &&
-                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)sizeof(CampxSpec),
-              "campx: spec_dev must be the CampxSpec blob as a uint8 tensor on ", dev);
+  const CampxSpec* ds = dev_spec(spec_dev, dev);
   if (pair_table.has_value())
     TORCH_CHECK(pair_table->device() == dev && pair_table->is_contiguous() &&
                     pair_table->nbytes() == (size_t)campx_pair_table_bytes(hs),
                 "campx: pair_table has the wrong size or device");
-  Game g{hs,
-         reinterpret_cast<const CampxSpec*>(spec_dev.data_ptr()),
-         CampxState{reinterpret_cast<int8_t*>(pos.data_ptr()),
-                    reinterpret_cast<uint8_t*>(done.data_ptr()), opt_ptr<float>(ret),
-                    pair_table.has_value() ? pair_table->data_ptr() : nullptr},
-         dev,
-         B,
-         K,
-         hs->n_layers,
-         hs->rows,
-         hs->cols};
-  return g;
+  return Game{hs,
+              ds,
+              CampxState{reinterpret_cast<int8_t*>(pos.data_ptr()),
+                         reinterpret_cast<uint8_t*>(done.data_ptr()), opt_ptr<float>(ret),
+                         pair_table.has_value() ? pair_table->data_ptr() : nullptr},
+              dev,
+              B,
+              K,
+              hs->n_layers,
+              hs->rows,
+              hs->cols};
 }
 
-int32_t obs_format_of(const Tensor& obs) {
-  switch (obs.scalar_type()) {
-    case at::kChar: return CAMPX_OBS_INT8;
-    case at::kHalf: return CAMPX_OBS_F16;
-    case at::kBFloat16: return CAMPX_OBS_BF16;
-    default: TORCH_CHECK(false, "campx: obs must be int8, float16 or bfloat16, it is ", obs.scalar_type());
-  }
-  return 0;
+// The same for a state-table game (wide tier): `tables` the device blob campx_wide_tables_build()
+// filled, `state` int32 [B] the environments' state indices, K the planes of its trace.
+struct WideGame {
+  const CampxWideSpec* hs;
+  const void* tables;
+  CampxState state;
+  c10::Device dev;
+  int64_t B, K, L, H, W;
+};
+
+WideGame unpack_wide(const char* what, const Tensor& spec_host, const Tensor& tables,
+                     const Tensor& state, const Tensor& done, const OptTensor& ret) {
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1, what,
+              ": state must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = state.device();
+  const int64_t B = state.size(0);
+  want(state, "state", at::kInt, dev, {B});
+  want(done, "done", at::kByte, dev, {B});
+  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
+  want_wide_tables(tables, hs, dev);
+  return WideGame{hs,
+                  tables.data_ptr(),
+                  CampxState{reinterpret_cast<int8_t*>(state.data_ptr()),
+                             reinterpret_cast<uint8_t*>(done.data_ptr()), opt_ptr<float>(ret), nullptr},
+                  dev,
+                  B,
+                  wide_planes(hs),
+                  hs->n_layers,
+                  hs->rows,
+                  hs->cols};
 }
 
 void reset(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tensor& done,
@@ -216,9 +404,8 @@ void reset(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tensor&
   CampxOutputs out{};
   out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
   out.board = opt_ptr<int8_t>(board);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  check_ok(campx_reset_launch(g.spec_host, g.spec_dev, g.state, out, g.B,
-                              c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_reset_launch(g.spec_host, g.spec_dev, g.state, out, g.B, current_stream()),
            "campx_reset_launch");
 }
 
@@ -229,43 +416,14 @@ void rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tenso
              const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
              const OptTensor& scratch, const OptTensor& scratch_state, const OptTensor& error_flag) {
   const Game g = unpack_game(spec_host, spec_dev, pos, done, ret, pair_table);
-  TORCH_CHECK(actions.dim() == 2, "campx::rollout: actions must be int8 [T, B]");
-  const int64_t T = actions.size(0);
+  const int64_t T = want_actions("campx::rollout", actions, g.dev, g.B);
   TORCH_CHECK(T <= 0x7fffffff, "campx::rollout: too many frames");
-  want(actions, "actions", at::kChar, g.dev, {T, g.B});
   CampxOutputs out{};
-  out.obs_format = obs_format_of(obs);
-  const bool keep = obs.dim() == 5;  // every frame kept, else one frame buffer overwritten
-  if (keep)
-    want(obs, "obs", obs.scalar_type(), g.dev, {T, g.B, g.L, g.H, g.W});
-  else
-    want(obs, "obs", obs.scalar_type(), g.dev, {g.B, g.L, g.H, g.W});
-  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  out.obs_t_stride = keep ? g.B * g.L * g.H * g.W : 0;
-  if (board.has_value()) {
-    if (board->dim() == 4) {
-      want(*board, "board", at::kChar, g.dev, {T, g.B, g.H, g.W});
-      out.board_t_stride = g.B * g.H * g.W;
-    } else {
-      want(*board, "board", at::kChar, g.dev, {g.B, g.H, g.W});
-    }
-    out.board = opt_ptr<int8_t>(board);
-  }
+  want_frames(out, g.dev, Frames::kAsGiven, T, g.B, g.L, g.H, g.W, obs, board);
   int64_t pitch = 0;
-  if (trace.has_value()) want_trace(*trace, g.dev, g.K, T, g.B, pitch);
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, g.dev, T, g.B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, g.dev, T, g.B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, g.dev, T, g.B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, g.dev, T, g.B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
-  out.scalar_pitch = pitch;
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  if (trace.has_value()) want_trace(*trace, at::kByte, g.dev, g.K, T, g.B, pitch);
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = opt_ptr<uint8_t>(trace);
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, g.dev);
   if (scratch.has_value()) {   // CampxOutputs.overlap_ctl: zeroed once by its owner
     // (how many bytes each user of it needs is the library's check: too small a block only
     // means the launch takes another path)
@@ -286,10 +444,9 @@ void rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tenso
     }
   }
   out.error_flag = flag_ptr(error_flag, g.dev);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  check_ok(campx_rollout_launch(g.spec_host, g.spec_dev, g.state, reinterpret_cast<const int8_t*>(actions.data_ptr()),
-                                out, g.B, (int32_t)T, reset_first ? 1 : 0,
-                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_rollout_launch(g.spec_host, g.spec_dev, g.state, ids(actions), out, g.B, (int32_t)T,
+                                reset_first ? 1 : 0, current_stream()),
            "campx_rollout_launch");
 }
 
@@ -301,31 +458,16 @@ void update(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tensor
             const OptTensor& perf, Tensor& trace, const OptTensor& bad_count,
             const OptTensor& bad_flag, bool reset_first) {
   const Game g = unpack_game(spec_host, spec_dev, pos, done, ret, pair_table);
-  TORCH_CHECK(actions.dim() == 2, "campx::update: actions must be int8 [T, B]");
-  const int64_t T = actions.size(0);
+  const int64_t T = want_actions("campx::update", actions, g.dev, g.B);
   TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::update: bad frame count");
-  want(actions, "actions", at::kChar, g.dev, {T, g.B});
   int64_t pitch = 0;
-  want_trace(trace, g.dev, g.K, T, g.B, pitch);
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, g.dev, T, g.B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, g.dev, T, g.B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, g.dev, T, g.B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, g.dev, T, g.B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
+  want_trace(trace, at::kByte, g.dev, g.K, T, g.B, pitch);
   CampxOutputs out{};
-  out.scalar_pitch = pitch;
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, g.dev);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  check_ok(campx_update_launch(g.spec_host, g.spec_dev, g.state,
-                               reinterpret_cast<const int8_t*>(actions.data_ptr()), out, g.B,
-                               (int32_t)T, reset_first ? 1 : 0,
-                               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_update_launch(g.spec_host, g.spec_dev, g.state, ids(actions), out, g.B, (int32_t)T,
+                               reset_first ? 1 : 0, current_stream()),
            "campx_update_launch");
 }
 
@@ -335,28 +477,13 @@ void render(const Tensor& spec_host, const Tensor& spec_dev, const Tensor& trace
   TORCH_CHECK(trace.device().is_cuda() && trace.dim() == 3, "campx::render: trace must be a HIP uint8 [K, T, B] tensor");
   const c10::Device dev = trace.device();
   const int64_t K = hs->n_dyn, T = trace.size(1), B = trace.size(2);
-  int64_t pitch = 0;
-  want_trace(trace, dev, K, T, B, pitch);
-  TORCH_CHECK(spec_dev.device() == dev && spec_dev.scalar_type() == at::kByte &&
-                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)sizeof(CampxSpec),
-              "campx: spec_dev must be the CampxSpec blob as a uint8 tensor on ", dev);
   CampxOutputs out{};
-  out.scalar_pitch = pitch;
-  out.obs_format = obs_format_of(obs);
-  want(obs, "obs", obs.scalar_type(), dev, {T, B, hs->n_layers, hs->rows, hs->cols});
-  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  out.obs_t_stride = B * hs->n_layers * hs->rows * hs->cols;
-  if (board.has_value()) {
-    want(*board, "board", at::kChar, dev, {T, B, hs->rows, hs->cols});
-    out.board = opt_ptr<int8_t>(board);
-    out.board_t_stride = B * hs->rows * hs->cols;
-  }
+  want_trace(trace, at::kByte, dev, K, T, B, out.scalar_pitch);
+  const CampxSpec* ds = dev_spec(spec_dev, dev);
+  want_frames(out, dev, Frames::kEvery, T, B, hs->n_layers, hs->rows, hs->cols, obs, board);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_render_launch(hs, reinterpret_cast<const CampxSpec*>(spec_dev.data_ptr()), out, B,
-                               (int32_t)T,
-                               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
-           "campx_render_launch");
+  const DeviceGuard guard(dev);
+  check_ok(campx_render_launch(hs, ds, out, B, (int32_t)T, current_stream()), "campx_render_launch");
 }
 
 // A rollout over TWO streams (fused.py rollout(pipelined=True), in C++ since round 5): the update
@@ -403,40 +530,19 @@ void rollout_pipelined(const Tensor& spec_host, const Tensor& spec_dev, Tensor& 
                        Tensor& trace, const OptTensor& bad_count, const OptTensor& bad_flag,
                        bool reset_first, bool resync) {
   const Game g = unpack_game(spec_host, spec_dev, pos, done, ret, pair_table);
-  TORCH_CHECK(actions.dim() == 2, "campx::rollout_pipelined: actions must be int8 [T, B]");
-  const int64_t T = actions.size(0);
+  const int64_t T = want_actions("campx::rollout_pipelined", actions, g.dev, g.B);
   TORCH_CHECK(T >= 1 && T <= 65535, "campx::rollout_pipelined: 1 to 65535 frames");
-  want(actions, "actions", at::kChar, g.dev, {T, g.B});
   int64_t pitch = 0;
-  want_trace(trace, g.dev, g.K, T, g.B, pitch);
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, g.dev, T, g.B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, g.dev, T, g.B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, g.dev, T, g.B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, g.dev, T, g.B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
+  want_trace(trace, at::kByte, g.dev, g.K, T, g.B, pitch);
   CampxOutputs upd{};
-  upd.scalar_pitch = pitch;
-  upd.reward = opt_ptr<float>(reward);
-  upd.discount = opt_ptr<float>(discount);
-  upd.done = opt_ptr<uint8_t>(step_done);
-  upd.perf = opt_ptr<int8_t>(perf);
+  want_streams(upd, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   upd.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  upd.bad_count = opt_ptr<int32_t>(bad_count);
-  upd.bad_flag = flag_ptr(bad_flag, g.dev);
   CampxOutputs ren{};
   ren.scalar_pitch = pitch;
-  ren.obs_format = obs_format_of(obs);
-  want(obs, "obs", obs.scalar_type(), g.dev, {T, g.B, g.L, g.H, g.W});
-  ren.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  ren.obs_t_stride = g.B * g.L * g.H * g.W;
-  if (board.has_value()) {
-    want(*board, "board", at::kChar, g.dev, {T, g.B, g.H, g.W});
-    ren.board = opt_ptr<int8_t>(board);
-    ren.board_t_stride = g.B * g.H * g.W;
-  }
+  want_frames(ren, g.dev, Frames::kEvery, T, g.B, g.L, g.H, g.W, obs, board);
   ren.trace = upd.trace;
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  hipStream_t main = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const DeviceGuard guard(g.dev);
+  hipStream_t main = current_stream();
   PipeStreams& p = pipe_streams(g.dev.index());
   std::lock_guard<std::mutex> one_at_a_time(p.busy);
   if (resync) {       // everything issued on the caller's stream so far, renders included
@@ -456,8 +562,7 @@ void rollout_pipelined(const Tensor& spec_host, const Tensor& spec_dev, Tensor& 
   }
   hipEvent_t reader = p.readers[upd.trace];      // (by value: the map may rehash)
   if (reader && !resync) hip_ok(hipStreamWaitEvent(p.side, reader, 0), "hipStreamWaitEvent");
-  check_ok(campx_update_launch(g.spec_host, g.spec_dev, g.state,
-                               reinterpret_cast<const int8_t*>(actions.data_ptr()), upd, g.B, (int32_t)T,
+  check_ok(campx_update_launch(g.spec_host, g.spec_dev, g.state, ids(actions), upd, g.B, (int32_t)T,
                                reset_first ? 1 : 0, p.side),
            "campx_update_launch");
   hip_ok(hipEventRecord(p.updated, p.side), "hipEventRecord");
@@ -479,41 +584,21 @@ void update_render(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos,
                    const OptTensor& bad_flag, bool reset_first, const Tensor& prev_trace,
                    Tensor& prev_obs) {
   const Game g = unpack_game(spec_host, spec_dev, pos, done, ret, pair_table);
-  TORCH_CHECK(actions.dim() == 2, "campx::update_render: actions must be int8 [T, B]");
-  const int64_t T = actions.size(0);
+  const int64_t T = want_actions("campx::update_render", actions, g.dev, g.B);
   TORCH_CHECK(T >= 1 && T <= 65535, "campx::update_render: 1 to 65535 frames");
-  want(actions, "actions", at::kChar, g.dev, {T, g.B});
-  int64_t pitch = 0, prev_pitch = 0;
-  want_trace(trace, g.dev, g.K, T, g.B, pitch);
-  want_trace(prev_trace, g.dev, g.K, T, g.B, prev_pitch);
+  int64_t pitch = 0;
+  CampxOutputs out{}, prev{};
+  want_trace(trace, at::kByte, g.dev, g.K, T, g.B, pitch);
+  want_trace(prev_trace, at::kByte, g.dev, g.K, T, g.B, prev.scalar_pitch);
   TORCH_CHECK(prev_trace.data_ptr() != trace.data_ptr(),
               "campx::update_render: the two rollouts need a trace buffer each");
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, g.dev, T, g.B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, g.dev, T, g.B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, g.dev, T, g.B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, g.dev, T, g.B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
-  CampxOutputs out{};
-  out.scalar_pitch = pitch;
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, g.dev);
-  CampxOutputs prev{};
-  prev.scalar_pitch = prev_pitch;
-  prev.obs_format = obs_format_of(prev_obs);
-  want(prev_obs, "prev_obs", prev_obs.scalar_type(), g.dev, {T, g.B, g.L, g.H, g.W});
-  prev.obs = reinterpret_cast<int8_t*>(prev_obs.data_ptr());
-  prev.obs_t_stride = g.B * g.L * g.H * g.W;
+  want_frames(prev, g.dev, Frames::kEvery, T, g.B, g.L, g.H, g.W, prev_obs, kNone, "prev_obs");
   prev.trace = reinterpret_cast<uint8_t*>(prev_trace.data_ptr());
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  check_ok(campx_update_render_launch(g.spec_host, g.spec_dev, g.state,
-                                      reinterpret_cast<const int8_t*>(actions.data_ptr()), out, prev,
-                                      g.B, (int32_t)T, reset_first ? 1 : 0,
-                                      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_update_render_launch(g.spec_host, g.spec_dev, g.state, ids(actions), out, prev, g.B,
+                                      (int32_t)T, reset_first ? 1 : 0, current_stream()),
            "campx_update_render_launch");
 }
 
@@ -525,28 +610,12 @@ void step(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos, Tensor& 
           const OptTensor& bad_flag) {
   const Game g = unpack_game(spec_host, spec_dev, pos, done, ret, pair_table);
   want(actions, "actions", at::kChar, g.dev, {g.B});
-  const int32_t format = obs_format_of(obs);   // int8, or f16 / bf16 for a policy network
-  want(obs, "obs", obs.scalar_type(), g.dev, {g.B, g.L, g.H, g.W});
-  if (board.has_value()) want(*board, "board", at::kChar, g.dev, {g.B, g.H, g.W});
-  if (reward.has_value()) want(*reward, "reward", at::kFloat, g.dev, {g.B});
-  if (discount.has_value()) want(*discount, "discount", at::kFloat, g.dev, {g.B});
-  if (step_done.has_value()) want(*step_done, "step_done", at::kByte, g.dev, {g.B});
-  if (perf.has_value()) want(*perf, "perf", at::kChar, g.dev, {g.B});
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
   CampxOutputs out{};
-  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  out.obs_format = format;
-  out.board = opt_ptr<int8_t>(board);
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, g.dev);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(g.dev);
-  check_ok(campx_rollout_launch(g.spec_host, g.spec_dev, g.state,
-                                reinterpret_cast<const int8_t*>(actions.data_ptr()), out, g.B, 1, 0,
-                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  want_frames(out, g.dev, Frames::kOne, 1, g.B, g.L, g.H, g.W, obs, board);
+  want_streams(out, g.dev, 1, g.B, 0, false, reward, discount, step_done, perf, bad_count, bad_flag);
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_rollout_launch(g.spec_host, g.spec_dev, g.state, ids(actions), out, g.B, 1, 0,
+                                current_stream()),
            "campx_rollout_launch");
 }
 
@@ -558,10 +627,8 @@ void shape_rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos,
                    const OptTensor& discount, const OptTensor& step_done,
                    const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
                    bool emit_first, const OptTensor& trace, const OptTensor& tables) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxShapeSpec),
-              "campx: spec_host must be the CampxShapeSpec blob as a CPU uint8 tensor");
-  const CampxShapeSpec* hs = reinterpret_cast<const CampxShapeSpec*>(spec_host.data_ptr());
+  const CampxShapeSpec* hs = static_cast<const CampxShapeSpec*>(
+      host_blob(spec_host, sizeof(CampxShapeSpec), "CampxShapeSpec"));
   TORCH_CHECK(pos.device().is_cuda() && pos.dim() == 2,
               "campx::shape_rollout: state must be on a HIP device (no CPU implementation)");
   const c10::Device dev = pos.device();
@@ -570,9 +637,8 @@ void shape_rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos,
   want(done, "done", at::kByte, dev, {B});
   if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
   if (backdrop_state.has_value()) want(*backdrop_state, "backdrop_state", at::kChar, dev, {B, H * W});
-  TORCH_CHECK(spec_dev.device() == dev && spec_dev.scalar_type() == at::kByte &&
-                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)sizeof(CampxShapeSpec),
-              "campx: spec_dev must be the CampxShapeSpec blob as a uint8 tensor on ", dev);
+  const CampxShapeSpec* ds = static_cast<const CampxShapeSpec*>(
+      dev_blob(spec_dev, sizeof(CampxShapeSpec), "CampxShapeSpec", dev));
   int64_t T = 0;
   bool frames = false;  // outputs carry a leading frame axis
   if (actions.has_value()) {
@@ -582,29 +648,13 @@ void shape_rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos,
     else want(*actions, "actions", at::kChar, dev, {B});
   }
   CampxOutputs out{};
-  auto shape = [&](std::initializer_list<int64_t> tail) {
-    std::vector<int64_t> v;
-    if (frames) v.push_back(T);
-    v.push_back(B);
-    v.insert(v.end(), tail);
-    return v;
-  };
-  const bool keep = frames && obs.dim() == 5;
-  out.obs_format = obs_format_of(obs);       // int8, or f16 / bf16 for a policy network
-  if (keep || !frames) want(obs, "obs", obs.scalar_type(), dev, shape({L, H, W}));
-  else want(obs, "obs", obs.scalar_type(), dev, {B, L, H, W});
-  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  out.obs_t_stride = keep ? B * L * H * W : 0;
-  if (board.has_value()) {
-    const bool bkeep = frames && board->dim() == 4;
-    if (bkeep) want(*board, "board", at::kChar, dev, {T, B, H, W});
-    else want(*board, "board", at::kChar, dev, {B, H, W});
-    out.board = opt_ptr<int8_t>(board);
-    out.board_t_stride = bkeep ? B * H * W : 0;
-  }
-  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, shape({}));
-  if (discount.has_value()) want(*discount, "discount", at::kFloat, dev, shape({}));
-  if (step_done.has_value()) want(*step_done, "step_done", at::kByte, dev, shape({}));
+  want_frames(out, dev, frames ? Frames::kAsGiven : Frames::kOne, T, B, L, H, W, obs, board);
+  // (this tier's streams are contiguous: [T, B] with a frame axis, else [B])
+  const int64_t scalars[2] = {T, B};
+  const c10::IntArrayRef shape(scalars + (frames ? 0 : 1), frames ? 2 : 1);
+  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, shape);
+  if (discount.has_value()) want(*discount, "discount", at::kFloat, dev, shape);
+  if (step_done.has_value()) want(*step_done, "step_done", at::kByte, dev, shape);
   if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
   out.reward = opt_ptr<float>(reward);
   out.discount = opt_ptr<float>(discount);
@@ -627,115 +677,52 @@ void shape_rollout(const Tensor& spec_host, const Tensor& spec_dev, Tensor& pos,
   }
   CampxState state{reinterpret_cast<int8_t*>(pos.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
                    opt_ptr<float>(ret), nullptr};
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_shape_rollout_launch(
-               hs, reinterpret_cast<const CampxShapeSpec*>(spec_dev.data_ptr()), tables_dev, state,
-               opt_ptr<int8_t>(backdrop_state), opt_ptr<int8_t>(actions), out, B, (int32_t)T,
-               reset_first ? 1 : 0, emit_first ? 1 : 0,
-               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(dev);
+  check_ok(campx_shape_rollout_launch(hs, ds, tables_dev, state, opt_ptr<int8_t>(backdrop_state),
+                                      opt_ptr<int8_t>(actions), out, B, (int32_t)T,
+                                      reset_first ? 1 : 0, emit_first ? 1 : 0, current_stream()),
            "campx_shape_rollout_launch");
 }
 
 // Wide tier (state-table games: boards above 128 cells, include/campx_hip.h): reset
 // (actions = None), one frame (actions [B], outputs [B...]) or T frames (actions [T, B])
-// through one op.  `tables`: the device blob campx_wide_tables_build() filled.  `state`:
-// int32 [B], the environments' state indices.  `trace`: int16 [K, B] / [K, T, B] (rows may be
-// padded like the other per-frame streams).  With T frames, `obs` is [T, B, L, H, W] (every
-// frame) or [B, L, H, W] (the last one).
+// through one op.  `trace`: int16 [K, B] / [K, T, B] (rows may be padded like the other
+// per-frame streams).  With T frames, `obs` is [T, B, L, H, W] (every frame) or [B, L, H, W]
+// (the last one).
 void wide_rollout(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
                   const OptTensor& ret, const OptTensor& actions, Tensor& obs, const OptTensor& board,
                   const OptTensor& reward, const OptTensor& discount, const OptTensor& step_done,
                   const OptTensor& perf, Tensor& trace, const OptTensor& bad_count,
                   const OptTensor& bad_flag, bool reset_first) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
-  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1,
-              "campx::wide_rollout: state must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = state.device();
-  // (planes of the trace: the things, plus the scenery's variant when it has several - or the mask
-  // of its pieces that show)
-  const int64_t B = state.size(0), K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0), L = hs->n_layers, H = hs->rows,
-                W = hs->cols;
-  want(state, "state", at::kInt, dev, {B});
-  want(done, "done", at::kByte, dev, {B});
-  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
-  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  const char* what = "campx::wide_rollout";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
   int64_t T = 0;
   bool frames = false;
   if (actions.has_value()) {
     frames = actions->dim() == 2;
     T = frames ? actions->size(0) : 1;
-    if (frames) want(*actions, "actions", at::kChar, dev, {T, B});
-    else want(*actions, "actions", at::kChar, dev, {B});
-    TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_rollout: bad frame count");
+    if (frames) want(*actions, "actions", at::kChar, g.dev, {T, g.B});
+    else want(*actions, "actions", at::kChar, g.dev, {g.B});
+    TORCH_CHECK(T >= 1 && T <= 0x7fffffff, what, ": bad frame count");
   }
   CampxOutputs out{};
   int64_t pitch = 0;
-  // the trace first: with one frame only its planes tell the row pitch
-  TORCH_CHECK(trace.device() == dev && trace.scalar_type() == at::kShort,
-              "campx: trace must be an int16 tensor on ", dev);
-  if (frames) {
-    TORCH_CHECK(trace.dim() == 3 && trace.size(0) == K && trace.size(1) == T && trace.size(2) == B &&
-                    (B == 1 || trace.stride(2) == 1),
-                "campx: trace must be int16 [", K, ", ", T, ", ", B, "], contiguous within a row");
-    if (T > 1) pitch = trace.stride(1);
-    else if (K > 1) pitch = trace.stride(0);
-    TORCH_CHECK(pitch == 0 || (pitch >= B && (K == 1 || trace.stride(0) == T * pitch)),
-                "campx: trace rows must be >= B apart and its planes T * pitch apart");
-  } else {
-    TORCH_CHECK(trace.dim() == 2 && trace.size(0) == K && trace.size(1) == B &&
-                    (B == 1 || trace.stride(1) == 1),
-                "campx: trace must be int16 [", K, ", ", B, "], contiguous within a row");
-    if (K > 1) pitch = trace.stride(0);
-    TORCH_CHECK(pitch == 0 || pitch >= B, "campx: trace rows must be >= B apart");
-  }
-  auto stream_of = [&](const OptTensor& t, const char* name, at::ScalarType dtype) {
-    if (!t.has_value()) return;
-    if (frames) want_rows(*t, name, dtype, dev, T, B, pitch);
-    else want(*t, name, dtype, dev, {B});
-  };
-  stream_of(reward, "reward", at::kFloat);
-  stream_of(discount, "discount", at::kFloat);
-  stream_of(step_done, "step_done", at::kByte);
-  stream_of(perf, "perf", at::kChar);
-  out.scalar_pitch = pitch;
-  out.obs_format = obs_format_of(obs);
-  const bool keep = frames && obs.dim() == 5;
-  if (keep) want(obs, "obs", obs.scalar_type(), dev, {T, B, L, H, W});
-  else want(obs, "obs", obs.scalar_type(), dev, {B, L, H, W});
-  out.obs = reinterpret_cast<int8_t*>(obs.data_ptr());
-  out.obs_t_stride = (keep || !frames) ? B * L * H * W : 0;
-  if (board.has_value()) {
-    const bool bkeep = frames && board->dim() == 4;
-    TORCH_CHECK(bkeep == keep, "campx::wide_rollout: obs and board must both keep every frame or both the last");
-    if (bkeep) want(*board, "board", at::kChar, dev, {T, B, H, W});
-    else want(*board, "board", at::kChar, dev, {B, H, W});
-    out.board = opt_ptr<int8_t>(board);
-    out.board_t_stride = (bkeep || !frames) ? B * H * W : 0;
-  }
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  want_trace(trace, at::kShort, g.dev, g.K, T, g.B, pitch, frames);
+  want_streams(out, g.dev, T, g.B, pitch, frames, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, dev);
-  CampxState st{reinterpret_cast<int8_t*>(state.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
-                opt_ptr<float>(ret), nullptr};
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  void* stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  want_frames(out, g.dev, frames ? Frames::kAsGiven : Frames::kOne, T, g.B, g.L, g.H, g.W, obs, board,
+              "obs", what);
+  if (!frames) {   // (one frame: to the library, every frame kept)
+    out.obs_t_stride = g.B * g.L * g.H * g.W;
+    if (board.has_value()) out.board_t_stride = g.B * g.H * g.W;
+  }
+  const DeviceGuard guard(g.dev);
   if (!actions.has_value())
-    check_ok(campx_wide_reset_launch(hs, tables.data_ptr(), st, out, B, stream),
+    check_ok(campx_wide_reset_launch(g.hs, g.tables, g.state, out, g.B, current_stream()),
              "campx_wide_reset_launch");
   else
-    check_ok(campx_wide_rollout_launch(hs, tables.data_ptr(), st,
-                                       reinterpret_cast<const int8_t*>(actions->data_ptr()), out, B,
-                                       (int32_t)T, reset_first ? 1 : 0, stream),
+    check_ok(campx_wide_rollout_launch(g.hs, g.tables, g.state, ids(*actions), out, g.B, (int32_t)T,
+                                       reset_first ? 1 : 0, current_stream()),
              "campx_wide_rollout_launch");
 }
 
@@ -746,54 +733,17 @@ void wide_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, T
                  const OptTensor& discount, const OptTensor& step_done, const OptTensor& perf,
                  Tensor& trace, const OptTensor& bad_count, const OptTensor& bad_flag,
                  bool reset_first) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
-  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1,
-              "campx::wide_update: state must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = state.device();
-  const int64_t B = state.size(0), K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
-  want(state, "state", at::kInt, dev, {B});
-  want(done, "done", at::kByte, dev, {B});
-  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
-  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
-  TORCH_CHECK(actions.dim() == 2, "campx::wide_update: actions must be int8 [T, B]");
-  const int64_t T = actions.size(0);
+  const WideGame g = unpack_wide("campx::wide_update", spec_host, tables, state, done, ret);
+  const int64_t T = want_actions("campx::wide_update", actions, g.dev, g.B);
   TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_update: bad frame count");
-  want(actions, "actions", at::kChar, dev, {T, B});
   int64_t pitch = 0;
-  TORCH_CHECK(trace.device() == dev && trace.scalar_type() == at::kShort && trace.dim() == 3 &&
-                  trace.size(0) == K && trace.size(1) == T && trace.size(2) == B &&
-                  (B == 1 || trace.stride(2) == 1),
-              "campx: trace must be int16 [", K, ", ", T, ", ", B, "] on ", dev, ", contiguous within a row");
-  if (T > 1) pitch = trace.stride(1);
-  else if (K > 1) pitch = trace.stride(0);
-  TORCH_CHECK(pitch == 0 || (pitch >= B && (K == 1 || trace.stride(0) == T * pitch)),
-              "campx: trace rows must be >= B apart and its planes T * pitch apart");
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, dev, T, B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, dev, T, B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, dev, T, B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, dev, T, B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  want_trace(trace, at::kShort, g.dev, g.K, T, g.B, pitch);
   CampxOutputs out{};
-  out.scalar_pitch = pitch;
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, dev);
-  CampxState st{reinterpret_cast<int8_t*>(state.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
-                opt_ptr<float>(ret), nullptr};
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_wide_update_launch(hs, tables.data_ptr(), st,
-                                    reinterpret_cast<const int8_t*>(actions.data_ptr()), out, B,
-                                    (int32_t)T, reset_first ? 1 : 0,
-                                    c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_update_launch(g.hs, g.tables, g.state, ids(actions), out, g.B, (int32_t)T,
+                                    reset_first ? 1 : 0, current_stream()),
            "campx_wide_update_launch");
 }
 
@@ -806,110 +756,62 @@ void wide_policy_update(const Tensor& spec_host, const Tensor& tables, Tensor& s
                         const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
                         Tensor& actions_out, const OptTensor& states_out, const OptTensor& bad_count,
                         const OptTensor& bad_flag, bool reset_first) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
-  TORCH_CHECK(state.device().is_cuda() && state.dim() == 1,
-              "campx::wide_policy_update: state must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = state.device();
-  const int64_t B = state.size(0), K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
-  want(state, "state", at::kInt, dev, {B});
-  want(done, "done", at::kByte, dev, {B});
-  if (ret.has_value()) want(*ret, "ret", at::kFloat, dev, {B});
-  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
-  want(policy, "policy", at::kFloat, dev, {(int64_t)hs->n_states, (int64_t)CAMPX_N_ACTIONS});
+  const WideGame g = unpack_wide("campx::wide_policy_update", spec_host, tables, state, done, ret);
+  want(policy, "policy", at::kFloat, g.dev, {(int64_t)g.hs->n_states, (int64_t)CAMPX_N_ACTIONS});
   TORCH_CHECK(first_frame >= 0, "campx::wide_policy_update: first_frame must be >= 0");
   TORCH_CHECK(trace.dim() == 3, "campx::wide_policy_update: trace must be int16 [K, T, B]");
   const int64_t T = trace.size(1);
   TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_policy_update: bad frame count");
   int64_t pitch = 0;
-  TORCH_CHECK(trace.device() == dev && trace.scalar_type() == at::kShort && trace.size(0) == K &&
-                  trace.size(2) == B && (B == 1 || trace.stride(2) == 1),
-              "campx: trace must be int16 [", K, ", ", T, ", ", B, "] on ", dev, ", contiguous within a row");
-  if (T > 1) pitch = trace.stride(1);
-  else if (K > 1) pitch = trace.stride(0);
-  TORCH_CHECK(pitch == 0 || (pitch >= B && (K == 1 || trace.stride(0) == T * pitch)),
-              "campx: trace rows must be >= B apart and its planes T * pitch apart");
-  want_rows(actions_out, "actions_out", at::kChar, dev, T, B, pitch);
-  if (states_out.has_value()) want_rows(*states_out, "states_out", at::kInt, dev, T, B, pitch);
-  if (reward.has_value()) want_rows(*reward, "reward", at::kFloat, dev, T, B, pitch);
-  if (discount.has_value()) want_rows(*discount, "discount", at::kFloat, dev, T, B, pitch);
-  if (step_done.has_value()) want_rows(*step_done, "step_done", at::kByte, dev, T, B, pitch);
-  if (perf.has_value()) want_rows(*perf, "perf", at::kChar, dev, T, B, pitch);
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
+  want_trace(trace, at::kShort, g.dev, g.K, T, g.B, pitch);
+  want_rows(actions_out, "actions_out", at::kChar, g.dev, T, g.B, pitch);
+  if (states_out.has_value()) want_rows(*states_out, "states_out", at::kInt, g.dev, T, g.B, pitch);
   CampxOutputs out{};
-  out.scalar_pitch = pitch;
-  out.reward = opt_ptr<float>(reward);
-  out.discount = opt_ptr<float>(discount);
-  out.done = opt_ptr<uint8_t>(step_done);
-  out.perf = opt_ptr<int8_t>(perf);
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  out.bad_count = opt_ptr<int32_t>(bad_count);
-  out.bad_flag = flag_ptr(bad_flag, dev);
-  CampxState st{reinterpret_cast<int8_t*>(state.data_ptr()), reinterpret_cast<uint8_t*>(done.data_ptr()),
-                opt_ptr<float>(ret), nullptr};
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(g.dev);
   check_ok(campx_wide_policy_update_launch(
-               hs, tables.data_ptr(), st, reinterpret_cast<const float*>(policy.data_ptr()),
+               g.hs, g.tables, g.state, reinterpret_cast<const float*>(policy.data_ptr()),
                (uint64_t)seed, first_frame, out, reinterpret_cast<int8_t*>(actions_out.data_ptr()),
-               opt_ptr<int32_t>(states_out), B, (int32_t)T, reset_first ? 1 : 0,
-               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+               opt_ptr<int32_t>(states_out), g.B, (int32_t)T, reset_first ? 1 : 0, current_stream()),
            "campx_wide_policy_update_launch");
 }
 
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
-// t_idx[i], environment e_idx[i] of `trace` [planes, T', B] - any T', rows and planes as far apart
-// as the strides say (a view of a padded buffer, a ring of several rollouts).  Requests past the
+// t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
 // kernel's 32-bit bound go as several launches of a multiple of 16 rows each.
 template <typename Launch>
 void gather_rows(const char* what, const Tensor& trace, at::ScalarType entry, int64_t planes,
-                 int64_t row_bytes, const Tensor& t_idx, const Tensor& e_idx, Tensor& obs,
-                 const OptTensor& bad_count, const OptTensor& bad_flag, bool streaming,
-                 c10::IntArrayRef frame, Launch launch) {
+                 int64_t L, int64_t H, int64_t W, const Tensor& t_idx, const Tensor& e_idx, Tensor& obs,
+                 const OptTensor& bad_count, const OptTensor& bad_flag, bool streaming, Launch launch) {
   TORCH_CHECK(trace.device().is_cuda(), what, ": trace must be on a HIP device (no CPU implementation)");
   const c10::Device dev = trace.device();
-  TORCH_CHECK(trace.scalar_type() == entry && trace.dim() == 3 && trace.size(0) == planes &&
-                  trace.size(1) >= 1 && trace.size(2) >= 1 && (trace.size(2) == 1 || trace.stride(2) == 1),
-              what, ": trace must be ", entry, " [", planes, ", T, B], contiguous within a row");
-  const int64_t T = trace.size(1), B = trace.size(2);
-  const int64_t pitch = T > 1 ? trace.stride(1) : B;
-  const int64_t plane = planes > 1 ? trace.stride(0) : T * pitch;
-  TORCH_CHECK(pitch >= B && plane >= T * pitch, what, ": trace rows must be >= B apart and its "
-              "planes >= T * pitch apart");
-  TORCH_CHECK(t_idx.dim() == 1 && t_idx.size(0) >= 1 && t_idx.device() == dev && t_idx.is_contiguous() &&
-                  (t_idx.scalar_type() == at::kLong || t_idx.scalar_type() == at::kInt),
-              what, ": t_idx must be a contiguous int64 or int32 [N] tensor on ", dev);
-  const int64_t N = t_idx.size(0);
-  want(e_idx, "e_idx", t_idx.scalar_type(), dev, {N});
-  std::vector<int64_t> shape{N};
-  shape.insert(shape.end(), frame.begin(), frame.end());
-  want(obs, "obs", obs.scalar_type(), dev, shape);
+  const StoredTrace s = want_stored_trace(what, trace, entry, dev, planes);
+  const int64_t N = want_pairs(what, t_idx, e_idx, dev);
+  want(obs, "obs", obs.scalar_type(), dev, {N, L, H, W});
   if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
   CampxGather g{};
   g.trace = trace.data_ptr();
   g.n_planes = planes;
-  g.T = T;
-  g.pitch = pitch;
-  g.plane = plane;
+  g.T = s.T;
+  g.pitch = s.pitch;
+  g.plane = s.plane;
   g.idx64 = t_idx.scalar_type() == at::kLong ? 1 : 0;
   g.obs_format = obs_format_of(obs);
   g.bad_count = opt_ptr<int32_t>(bad_count);
   g.bad_flag = flag_ptr(bad_flag, dev);
   g.streaming = streaming ? 1 : 0;
-  const int64_t idx_bytes = g.idx64 ? 8 : 4, elem = obs.element_size();
+  const int64_t row_bytes = L * H * W, idx_bytes = g.idx64 ? 8 : 4, elem = obs.element_size();
   const int64_t most = (((1ll << 32) - 65536 - 1) / row_bytes) & ~(int64_t)15;
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  void* stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  const DeviceGuard guard(dev);
+  void* stream = current_stream();
   for (int64_t n0 = 0; n0 < N; n0 += most) {
     g.N = N - n0 < most ? N - n0 : most;
     g.t_idx = static_cast<const char*>(t_idx.data_ptr()) + n0 * idx_bytes;
     g.e_idx = static_cast<const char*>(e_idx.data_ptr()) + n0 * idx_bytes;
     g.obs = static_cast<char*>(obs.data_ptr()) + n0 * row_bytes * elem;
-    check_ok(launch(&g, B, stream), what);
+    check_ok(launch(&g, s.B, stream), what);
   }
 }
 
@@ -917,13 +819,9 @@ void render_gather(const Tensor& spec_host, const Tensor& spec_dev, const Tensor
                    const Tensor& t_idx, const Tensor& e_idx, Tensor& obs, const OptTensor& bad_count,
                    const OptTensor& bad_flag, bool streaming) {
   const CampxSpec* hs = host_spec(spec_host);
-  TORCH_CHECK(spec_dev.device() == trace.device() && spec_dev.scalar_type() == at::kByte &&
-                  spec_dev.is_contiguous() && spec_dev.numel() == (int64_t)sizeof(CampxSpec),
-              "campx: spec_dev must be the CampxSpec blob as a uint8 tensor on ", trace.device());
-  const CampxSpec* ds = reinterpret_cast<const CampxSpec*>(spec_dev.data_ptr());
-  gather_rows("campx::render_gather", trace, at::kByte, hs->n_dyn,
-              (int64_t)hs->n_layers * hs->rows * hs->cols, t_idx, e_idx, obs, bad_count, bad_flag,
-              streaming, {hs->n_layers, hs->rows, hs->cols},
+  const CampxSpec* ds = dev_spec(spec_dev, trace.device());
+  gather_rows("campx::render_gather", trace, at::kByte, hs->n_dyn, hs->n_layers, hs->rows, hs->cols,
+              t_idx, e_idx, obs, bad_count, bad_flag, streaming,
               [&](const CampxGather* g, int64_t B, void* stream) {
                 return campx_render_gather_launch(hs, ds, g, B, stream);
               });
@@ -932,18 +830,11 @@ void render_gather(const Tensor& spec_host, const Tensor& spec_dev, const Tensor
 void wide_render_gather(const Tensor& spec_host, const Tensor& tables, const Tensor& trace,
                         const Tensor& t_idx, const Tensor& e_idx, Tensor& obs,
                         const OptTensor& bad_count, const OptTensor& bad_flag, bool streaming) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
-  TORCH_CHECK(tables.device() == trace.device() && tables.scalar_type() == at::kByte &&
-                  tables.is_contiguous() && tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", trace.device());
-  const int64_t K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  want_wide_tables(tables, hs, trace.device());
   const void* blob = tables.data_ptr();
-  gather_rows("campx::wide_render_gather", trace, at::kShort, K,
-              (int64_t)hs->n_layers * hs->rows * hs->cols, t_idx, e_idx, obs, bad_count, bad_flag,
-              streaming, {hs->n_layers, hs->rows, hs->cols},
+  gather_rows("campx::wide_render_gather", trace, at::kShort, wide_planes(hs), hs->n_layers, hs->rows,
+              hs->cols, t_idx, e_idx, obs, bad_count, bad_flag, streaming,
               [&](const CampxGather* g, int64_t B, void* stream) {
                 return campx_wide_render_gather_launch(hs, blob, g, B, stream);
               });
@@ -956,16 +847,11 @@ void wide_render_gather(const Tensor& spec_host, const Tensor& tables, const Ten
 void wide_render_states(const Tensor& spec_host, const Tensor& tables, const OptTensor& state_ids,
                         Tensor& obs, const OptTensor& scratch, const OptTensor& bad_count,
                         const OptTensor& bad_flag) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  const CampxWideSpec* hs = wide_spec(spec_host);
   TORCH_CHECK(tables.device().is_cuda(), "campx::wide_render_states: tables must be on a HIP device "
               "(no CPU implementation)");
   const c10::Device dev = tables.device();
-  TORCH_CHECK(tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want_wide_tables(tables, hs, dev);
   TORCH_CHECK(obs.dim() == 4 && obs.size(0) >= 1, "campx::wide_render_states: obs must be [N, L, H, W]");
   const int64_t N = obs.size(0);
   want(obs, "obs", obs.scalar_type(), dev, {N, hs->n_layers, hs->rows, hs->cols});
@@ -978,7 +864,7 @@ void wide_render_states(const Tensor& spec_host, const Tensor& tables, const Opt
   if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, dev, {1});
   const int64_t need = campx_wide_render_states_scratch_bytes(hs, N);
   TORCH_CHECK(need > 0, "campx::wide_render_states: bad spec or row count");
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(dev);
   Tensor trace;
   if (scratch.has_value()) {
     TORCH_CHECK(scratch->device() == dev && scratch->is_contiguous() && (int64_t)scratch->nbytes() >= need,
@@ -992,8 +878,7 @@ void wide_render_states(const Tensor& spec_host, const Tensor& tables, const Opt
                hs, tables.data_ptr(), state_ids.has_value() ? state_ids->data_ptr() : nullptr,
                state_ids.has_value() && state_ids->scalar_type() == at::kLong ? 1 : 0, N,
                obs.data_ptr(), format, trace.data_ptr(), (int64_t)trace.nbytes(),
-               opt_ptr<int32_t>(bad_count), flag_ptr(bad_flag, dev),
-               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+               opt_ptr<int32_t>(bad_count), flag_ptr(bad_flag, dev), current_stream()),
            "campx_wide_render_states_launch");
 }
 
@@ -1008,15 +893,10 @@ void wide_render_windows(const Tensor& spec_host, const Tensor& tables, const Te
                          int64_t r0, int64_t c0, int64_t pad_layer, const OptTensor& bad_count,
                          const OptTensor& bad_flag, bool streaming) {
   const char* what = "campx::wide_render_windows";
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  const CampxWideSpec* hs = wide_spec(spec_host);
   TORCH_CHECK(tables.device().is_cuda(), what, ": tables must be on a HIP device (no CPU implementation)");
   const c10::Device dev = tables.device();
-  TORCH_CHECK(tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want_wide_tables(tables, hs, dev);
   const int64_t V = hs->n_variants > 1 ? hs->n_variants : 1;
   want(layer_of_cell, "layer_of_cell", at::kByte, dev, {V, CAMPX_WIDE_MAX_CELLS});
   TORCH_CHECK(source >= CAMPX_WINDOWS_PAIRS && source <= CAMPX_WINDOWS_STATES, what, ": source must be 0, 1 or 2");
@@ -1028,28 +908,17 @@ void wide_render_windows(const Tensor& spec_host, const Tensor& tables, const Te
   int64_t B = 1;
   if (source != CAMPX_WINDOWS_STATES) {
     TORCH_CHECK(trace.has_value(), what, ": this source needs a trace");
-    const int64_t K = hs->n_dyn + ((hs->n_variants > 1 || hs->n_pieces > 0) ? 1 : 0);
-    TORCH_CHECK(trace->device() == dev && trace->scalar_type() == at::kShort && trace->dim() == 3 &&
-                    trace->size(0) == K && trace->size(1) >= 1 && trace->size(2) >= 1 &&
-                    (trace->size(2) == 1 || trace->stride(2) == 1),
-                what, ": trace must be int16 [", K, ", T, B] on ", dev, ", contiguous within a row");
-    const int64_t T = trace->size(1);
-    B = trace->size(2);
+    const StoredTrace s = want_stored_trace(what, *trace, at::kShort, dev, wide_planes(hs));
+    B = s.B;
     q.trace = trace->data_ptr();
-    q.n_planes = K;
-    q.T = T;
-    q.pitch = T > 1 ? trace->stride(1) : B;
-    q.plane = K > 1 ? trace->stride(0) : T * q.pitch;
-    TORCH_CHECK(q.pitch >= B && q.plane >= T * q.pitch, what, ": trace rows must be >= B apart and its "
-                "planes >= T * pitch apart");
+    q.n_planes = wide_planes(hs);
+    q.T = s.T;
+    q.pitch = s.pitch;
+    q.plane = s.plane;
   }
   if (source == CAMPX_WINDOWS_PAIRS) {
     TORCH_CHECK(t_idx.has_value() && e_idx.has_value(), what, ": sampled pairs need t_idx and e_idx");
-    TORCH_CHECK(t_idx->dim() == 1 && t_idx->size(0) >= 1 && t_idx->device() == dev && t_idx->is_contiguous() &&
-                    (t_idx->scalar_type() == at::kLong || t_idx->scalar_type() == at::kInt),
-                what, ": t_idx must be a contiguous int64 or int32 [N] tensor on ", dev);
-    q.N = t_idx->size(0);
-    want(*e_idx, "e_idx", t_idx->scalar_type(), dev, {q.N});
+    q.N = want_pairs(what, *t_idx, *e_idx, dev);
     q.t_idx = t_idx->data_ptr();
     q.e_idx = e_idx->data_ptr();
     q.idx64 = t_idx->scalar_type() == at::kLong ? 1 : 0;
@@ -1088,14 +957,14 @@ void wide_render_windows(const Tensor& spec_host, const Tensor& tables, const Te
   q.streaming = streaming ? 1 : 0;
   TORCH_CHECK(q.N <= ((1ll << 32) - 65536 - 1) / (L * h * w), what, ": ", q.N, " rows of ", L * h * w,
               " elements are past what one call addresses (2^32 - 65536 - 1): split the request");
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(dev);
   check_ok(campx_wide_render_windows_launch(hs, tables.data_ptr(), layer_of_cell.data_ptr(), &q, B,
-                                            c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+                                            current_stream()),
            "campx_wide_render_windows_launch");
 }
 
 // Discounted returns and GAE advantages of [T, B] streams (campx_returns_launch): every stream
-// contiguous within a row, rows any pitch >= B apart, each stream its own.
+// contiguous within a row, rows any pitch >= B apart, each stream its own (stream_rows()).
 void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTensor& discount,
              const OptTensor& values, const OptTensor& bootstrap, double lam, Tensor& returns_out,
              const OptTensor& advantages) {
@@ -1107,26 +976,15 @@ void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTe
   TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::returns: bad shape [", T, ", ", B, "]");
   TORCH_CHECK(values.has_value() == advantages.has_value(),
               "campx::returns: values and advantages come together");
-  auto rows = [&](const Tensor& t, const char* name, at::ScalarType dtype) -> int64_t {
-    TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
-    TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
-                t.scalar_type());
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
-                " must have shape [", T, ", ", B, "], it has ", t.sizes());
-    TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
-    TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
-                ", below its ", B, " columns");
-    return T == 1 ? B : t.stride(0);
-  };
   CampxReturns r{};
-  r.reward_pitch = rows(reward, "reward", at::kFloat);
-  r.done_pitch = rows(done, "done", at::kByte);
-  if (discount.has_value()) r.discount_pitch = rows(*discount, "discount", at::kFloat);
+  r.reward_pitch = stream_rows(reward, "reward", at::kFloat, dev, T, B);
+  r.done_pitch = stream_rows(done, "done", at::kByte, dev, T, B);
+  if (discount.has_value()) r.discount_pitch = stream_rows(*discount, "discount", at::kFloat, dev, T, B);
   if (values.has_value()) {
-    r.values_pitch = rows(*values, "values", at::kFloat);
-    r.advantages_pitch = rows(*advantages, "advantages", at::kFloat);
+    r.values_pitch = stream_rows(*values, "values", at::kFloat, dev, T, B);
+    r.advantages_pitch = stream_rows(*advantages, "advantages", at::kFloat, dev, T, B);
   }
-  r.returns_pitch = rows(returns_out, "returns", at::kFloat);
+  r.returns_pitch = stream_rows(returns_out, "returns", at::kFloat, dev, T, B);
   if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, dev, {B});
   r.reward = reinterpret_cast<const float*>(reward.data_ptr());
   r.done = reinterpret_cast<const uint8_t*>(done.data_ptr());
@@ -1137,24 +995,8 @@ void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTe
   r.advantages = opt_ptr<float>(advantages);
   r.gamma = (float)gamma;
   r.lam = (float)lam;
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_returns_launch(&r, B, (int32_t)T,
-                                c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
-           "campx_returns_launch");
-}
-
-// A [T, B] stream of the two ops below: contiguous within a row, rows any pitch >= B apart.
-int64_t stream_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
-                    int64_t T, int64_t B) {
-  TORCH_CHECK(t.device() == dev, "campx: ", name, " must be on ", dev, ", it is on ", t.device());
-  TORCH_CHECK(t.scalar_type() == dtype, "campx: ", name, " must be ", dtype, ", it is ",
-              t.scalar_type());
-  TORCH_CHECK(t.dim() == 2 && t.size(0) == T && t.size(1) == B, "campx: ", name,
-              " must have shape [", T, ", ", B, "], it has ", t.sizes());
-  TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
-  TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
-              ", below its ", B, " columns");
-  return T == 1 ? B : t.stride(0);
+  const DeviceGuard guard(dev);
+  check_ok(campx_returns_launch(&r, B, (int32_t)T, current_stream()), "campx_returns_launch");
 }
 
 // Per-(state, action) fixed-point sums of [T, B] streams (campx_state_sums_launch): `raw` int64
@@ -1199,10 +1041,8 @@ void state_sums(const Tensor& states, const OptTensor& actions, at::TensorList v
   s.acc = reinterpret_cast<int64_t*>(raw.data_ptr());
   s.skipped = reinterpret_cast<int64_t*>(skipped.data_ptr());
   s.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_state_sums_launch(&s, B, (int32_t)T,
-                                   c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
-           "campx_state_sums_launch");
+  const DeviceGuard guard(dev);
+  check_ok(campx_state_sums_launch(&s, B, (int32_t)T, current_stream()), "campx_state_sums_launch");
 }
 
 // out[t, e] = table[states[t, e] * n_actions + actions[t, e]] (campx_table_lookup_launch); `table`
@@ -1236,9 +1076,8 @@ void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& ac
   l.n_states = S;
   l.n_actions = (int32_t)A;
   l.bad_count = opt_ptr<int64_t>(bad_count);
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_table_lookup_launch(&l, B, (int32_t)T,
-                                     c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+  const DeviceGuard guard(dev);
+  check_ok(campx_table_lookup_launch(&l, B, (int32_t)T, current_stream()),
            "campx_table_lookup_launch");
 }
 
@@ -1250,17 +1089,12 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
                  const OptTensor& scratch, const OptTensor& q, const OptTensor& greedy,
                  Tensor& residual, const OptTensor& bad_rows, const OptTensor& bad_flag,
                  int64_t path) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  const CampxWideSpec* hs = wide_spec(spec_host);
   TORCH_CHECK(values_out.device().is_cuda(),
               "campx::wide_sweeps: values_out must be on a HIP device (no CPU implementation)");
   const c10::Device dev = values_out.device();
   const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want_wide_tables(tables, hs, dev);
   if (policy.has_value()) want(*policy, "policy", at::kFloat, dev, {S, A});
   if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
   want(values_in, "values_in", at::kFloat, dev, {S});
@@ -1274,15 +1108,14 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
               ", 1 <= sweeps <= 2^20");
   if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
   TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_sweeps: path must be 0, 1 or 2");
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(dev);
   check_ok(campx_wide_sweeps_launch(
                hs, tables.data_ptr(), opt_ptr<const float>(policy), opt_ptr<const float>(reward),
                (float)gamma, reinterpret_cast<const float*>(values_in.data_ptr()),
                reinterpret_cast<float*>(values_out.data_ptr()), opt_ptr<float>(scratch),
                opt_ptr<float>(q), opt_ptr<int8_t>(greedy),
                reinterpret_cast<float*>(residual.data_ptr()), opt_ptr<int32_t>(bad_rows),
-               flag_ptr(bad_flag, dev), (int32_t)residual.numel(), (int32_t)path,
-               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+               flag_ptr(bad_flag, dev), (int32_t)residual.numel(), (int32_t)path, current_stream()),
            "campx_wide_sweeps_launch");
 }
 
@@ -1294,17 +1127,12 @@ void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& pol
                 Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
                 const OptTensor& scratch, const OptTensor& bad_rows, const OptTensor& bad_flag,
                 int64_t path) {
-  TORCH_CHECK(spec_host.device().is_cpu() && spec_host.scalar_type() == at::kByte &&
-                  spec_host.is_contiguous() && spec_host.numel() == (int64_t)sizeof(CampxWideSpec),
-              "campx: spec_host must be the CampxWideSpec blob as a CPU uint8 tensor");
-  const CampxWideSpec* hs = reinterpret_cast<const CampxWideSpec*>(spec_host.data_ptr());
+  const CampxWideSpec* hs = wide_spec(spec_host);
   TORCH_CHECK(visits.device().is_cuda(),
               "campx::wide_visit: visits must be on a HIP device (no CPU implementation)");
   const c10::Device dev = visits.device();
   const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  TORCH_CHECK(tables.device() == dev && tables.scalar_type() == at::kByte && tables.is_contiguous() &&
-                  tables.numel() == campx_wide_tables_bytes(hs),
-              "campx: tables must be the campx_wide_tables_build() blob as a uint8 tensor on ", dev);
+  want_wide_tables(tables, hs, dev);
   want(policy, "policy", at::kFloat, dev, {S, A});
   if (start.has_value()) want(*start, "start", at::kLong, dev, {S});
   want(visits, "visits", at::kLong, dev, {S, A});
@@ -1319,7 +1147,7 @@ void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& pol
   if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, {S});
   if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
   TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_visit: path must be 0, 1 or 2");
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(dev);
   check_ok(campx_wide_visit_launch(
                hs, tables.data_ptr(), reinterpret_cast<const float*>(policy.data_ptr()),
                opt_ptr<const int64_t>(start), restart ? 1 : 0, (int32_t)T,
@@ -1327,26 +1155,25 @@ void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& pol
                reinterpret_cast<int64_t*>(finished.data_ptr()),
                reinterpret_cast<int64_t*>(final_mass.data_ptr()), opt_ptr<int64_t>(per_frame),
                reinterpret_cast<int32_t*>(counts.data_ptr()), opt_ptr<int64_t>(scratch),
-               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path,
-               c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path, current_stream()),
            "campx_wide_visit_launch");
 }
 
-void onehot_to_ids(const Tensor& onehot, Tensor& ids, Tensor& bad_count) {
+void onehot_to_ids(const Tensor& onehot, Tensor& ids_out, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
-  const int64_t n = ids.numel();
+  const int64_t n = ids_out.numel();
   TORCH_CHECK(onehot.scalar_type() == at::kFloat && onehot.is_contiguous() &&
                   onehot.numel() == n * CAMPX_N_ACTIONS,
               "campx::onehot_to_ids: onehot must be contiguous float32 [..., 5]");
-  TORCH_CHECK(ids.device() == dev && ids.scalar_type() == at::kChar && ids.is_contiguous(),
+  TORCH_CHECK(ids_out.device() == dev && ids_out.scalar_type() == at::kChar && ids_out.is_contiguous(),
               "campx::onehot_to_ids: ids must be contiguous int8 on ", dev);
   want(bad_count, "bad_count", at::kInt, dev, {1});
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+  const DeviceGuard guard(dev);
   check_ok(campx_onehot_to_ids_launch(reinterpret_cast<const float*>(onehot.data_ptr()),
-                                      reinterpret_cast<int8_t*>(ids.data_ptr()), n,
+                                      reinterpret_cast<int8_t*>(ids_out.data_ptr()), n,
                                       reinterpret_cast<int32_t*>(bad_count.data_ptr()),
-                                      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+                                      current_stream()),
            "campx_onehot_to_ids_launch");
 }
 
@@ -1356,72 +1183,18 @@ void check_actions(const Tensor& actions, Tensor& bad_count) {
   TORCH_CHECK(actions.scalar_type() == at::kChar && actions.is_contiguous(),
               "campx::check_actions: actions must be contiguous int8");
   want(bad_count, "bad_count", at::kInt, dev, {1});
-  const c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-  check_ok(campx_check_actions_launch(reinterpret_cast<const int8_t*>(actions.data_ptr()),
-                                      actions.numel(),
+  const DeviceGuard guard(dev);
+  check_ok(campx_check_actions_launch(ids(actions), actions.numel(),
                                       reinterpret_cast<int32_t*>(bad_count.data_ptr()),
-                                      c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream()),
+                                      current_stream()),
            "campx_check_actions_launch");
 }
 
-// Meta / fake-tensor implementations: the ops return nothing and write in place, so
-// there is nothing to infer.
-void reset_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const OptTensor&,
-                Tensor&, const OptTensor&) {}
-void rollout_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const OptTensor&,
-                  const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                  const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                  const OptTensor&, bool, const OptTensor&, const OptTensor&, const OptTensor&) {}
-void rollout_pipelined_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const OptTensor&,
-                            const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                            const OptTensor&, const OptTensor&, Tensor&, const OptTensor&, const OptTensor&,
-                            bool, bool) {}
-void step_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const OptTensor&,
-               const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-               const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&) {}
-void update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const OptTensor&,
-                 const Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                 const OptTensor&, Tensor&, const OptTensor&, const OptTensor&, bool) {}
-void render_meta(const Tensor&, const Tensor&, const Tensor&, Tensor&, const OptTensor&) {}
-void update_render_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&,
-                        const OptTensor&, const Tensor&, const OptTensor&, const OptTensor&,
-                        const OptTensor&, const OptTensor&, Tensor&, const OptTensor&,
-                        const OptTensor&, bool, const Tensor&, Tensor&) {}
-void shape_rollout_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&,
-                        const OptTensor&, const OptTensor&, Tensor&, const OptTensor&,
-                        const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                        const OptTensor&, bool, bool, const OptTensor&, const OptTensor&) {}
-void wide_rollout_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&,
-                       const OptTensor&, Tensor&, const OptTensor&, const OptTensor&,
-                       const OptTensor&, const OptTensor&, const OptTensor&, Tensor&,
-                       const OptTensor&, const OptTensor&, bool) {}
-void wide_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&, const Tensor&,
-                      const OptTensor&, const OptTensor&, const OptTensor&, const OptTensor&, Tensor&,
-                      const OptTensor&, const OptTensor&, bool) {}
-void wide_policy_update_meta(const Tensor&, const Tensor&, Tensor&, Tensor&, const OptTensor&,
-                             const Tensor&, int64_t, int64_t, const OptTensor&, const OptTensor&,
-                             const OptTensor&, const OptTensor&, Tensor&, Tensor&, const OptTensor&,
-                             const OptTensor&, const OptTensor&, bool) {}
-void render_gather_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor&,
-                        Tensor&, const OptTensor&, const OptTensor&, bool) {}
-void wide_render_states_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&,
-                             const OptTensor&, const OptTensor&) {}
-void wide_render_windows_meta(const Tensor&, const Tensor&, const Tensor&, int64_t, const OptTensor&,
-                              const OptTensor&, const OptTensor&, Tensor&, int64_t, int64_t, int64_t,
-                              int64_t, int64_t, int64_t, const OptTensor&, const OptTensor&, bool) {}
-void returns_meta(const Tensor&, const Tensor&, double, const OptTensor&, const OptTensor&,
-                  const OptTensor&, double, Tensor&, const OptTensor&) {}
-void state_sums_meta(const Tensor&, const OptTensor&, at::TensorList, int64_t, int64_t, int64_t, bool,
-                     int64_t, Tensor&, Tensor&, Tensor&) {}
-void table_lookup_meta(const Tensor&, const Tensor&, const OptTensor&, Tensor&, const OptTensor&) {}
-void wide_sweeps_meta(const Tensor&, const Tensor&, const OptTensor&, const OptTensor&, double,
-                      const Tensor&, Tensor&, const OptTensor&, const OptTensor&, const OptTensor&,
-                      Tensor&, const OptTensor&, const OptTensor&, int64_t) {}
-void wide_visit_meta(const Tensor&, const Tensor&, const Tensor&, const OptTensor&, bool, Tensor&,
-                     Tensor&, Tensor&, const OptTensor&, Tensor&, const OptTensor&, const OptTensor&,
-                     const OptTensor&, int64_t) {}
-void onehot_to_ids_meta(const Tensor&, Tensor&, Tensor&) {}
-void check_actions_meta(const Tensor&, Tensor&) {}
+// Meta / fake-tensor implementation of every op: the ops return nothing and write in place, so
+// there is nothing to infer - the arguments are dropped from the stack.
+void nothing_to_infer(const c10::OperatorHandle& op, torch::jit::Stack* stack) {
+  torch::jit::drop(*stack, op.schema().arguments().size());
+}
 
 // ADInplaceOrView: run the op, then mark every argument the schema declares written
 // (`Tensor(a!)`) as modified in place.
@@ -1444,6 +1217,13 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
   for (size_t i = 0; i < n_written; ++i)
     if (!written[i].is_inference()) written[i].unsafeGetTensorImpl()->bump_version();
 }
+
+// Every op, for the two boxed kernels (campx_amd/_hip.py OP_NAMES is the Python side's list).
+const char* const kOps[] = {
+    "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
+    "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "render_gather",
+    "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
+    "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids", "check_actions"};
 
 }  // namespace
 
@@ -1565,34 +1345,11 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
 }
 
 TORCH_LIBRARY_IMPL(campx, ADInplaceOrView, m) {
-  for (const char* name : {"reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render", "shape_rollout",
-                           "wide_rollout", "wide_update", "wide_policy_update", "render_gather", "wide_render_gather", "wide_render_states",
-                           "wide_render_windows", "returns", "state_sums", "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids",
-                           "check_actions"})
+  for (const char* name : kOps)
     m.impl(name, torch::CppFunction::makeFromBoxedFunction<&run_then_bump_versions>());
 }
 
 TORCH_LIBRARY_IMPL(campx, Meta, m) {
-  m.impl("reset", &reset_meta);
-  m.impl("step", &step_meta);
-  m.impl("rollout", &rollout_meta);
-  m.impl("update", &update_meta);
-  m.impl("render", &render_meta);
-  m.impl("rollout_pipelined", &rollout_pipelined_meta);
-  m.impl("update_render", &update_render_meta);
-  m.impl("shape_rollout", &shape_rollout_meta);
-  m.impl("wide_rollout", &wide_rollout_meta);
-  m.impl("wide_update", &wide_update_meta);
-  m.impl("wide_policy_update", &wide_policy_update_meta);
-  m.impl("render_gather", &render_gather_meta);
-  m.impl("wide_render_gather", &render_gather_meta);
-  m.impl("wide_render_states", &wide_render_states_meta);
-  m.impl("wide_render_windows", &wide_render_windows_meta);
-  m.impl("returns", &returns_meta);
-  m.impl("state_sums", &state_sums_meta);
-  m.impl("table_lookup", &table_lookup_meta);
-  m.impl("wide_sweeps", &wide_sweeps_meta);
-  m.impl("wide_visit", &wide_visit_meta);
-  m.impl("onehot_to_ids", &onehot_to_ids_meta);
-  m.impl("check_actions", &check_actions_meta);
+  for (const char* name : kOps)
+    m.impl(name, torch::CppFunction::makeFromBoxedFunction<&nothing_to_infer>());
 }
