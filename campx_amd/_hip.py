@@ -131,6 +131,9 @@ class CampxTableLookup(ctypes.Structure):
               ('reserved', ctypes.c_int32), ('bad_count', ctypes.c_void_p)]
 
 
+# second word of a state-table entry (csrc/wide_table.hip.h): next state | done << 24 | discount code << 25
+ENTRY_NEXT_MASK, ENTRY_DONE_SHIFT, ENTRY_DCODE_SHIFT, ENTRY_DCODE_MASK = 0xffffff, 24, 25, 15
+
 SUMS_MAX_VALUES = 4
 SUMS_LDS_BUDGET = 49152
 

@@ -23,35 +23,25 @@
 //     stream: a sweep boundary is a kernel boundary, there is no barrier across workgroups.
 // plan_sweeps() chooses; campx_wide_sweeps_plan() shows the choice to a test without a GPU.
 
-#include "campx_common.hip.h"
-
-#include <math.h>
+#include "wide_table.hip.h"
 
 namespace campx_impl {
 
-constexpr int kPlanLdsThreads = 1024;      // at most; a multiple of 64 that covers the states
 constexpr int kPlanThreads = 256;          // global path
 constexpr int64_t kPlanLdsHeader = 128;    // discount list, the two residual slots
 constexpr int32_t kPlanMaxSweeps = 1 << 20;
 
 struct SweepsPlan {
-  int32_t path;            // 1 LDS, 2 global
-  int32_t threads;         // of a workgroup
-  int64_t grid;            // workgroups of a sweep
-  int64_t lds_bytes;
+  TablePlan launch;
   int32_t off_v0, off_v1, off_w, off_c4;     // byte offsets into the dynamic LDS
 };
-
-inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 // The LDS a table of S states takes: header, entries [5][S] x 8 bytes, two value vectors, and for
 // a policy the weights [5][S] and the totals [S].  An override costs nothing: the staged entry
 // holds the reward the sweeps use, wherever it came from.
 inline int32_t plan_sweeps(int64_t S, int32_t policy, int32_t has_override, int64_t lds_max,
-                           int32_t path, SweepsPlan* p) {
-  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || (policy & ~1) || (has_override & ~1) || lds_max < 0 ||
-      path < 0 || path > 2)
-    return CAMPX_EINVAL;
+                           int32_t path, SweepsPlan* p, int64_t* plan_out) {
+  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || (policy & ~1) || (has_override & ~1)) return CAMPX_EINVAL;
   memset(p, 0, sizeof(*p));
   int64_t at = kPlanLdsHeader + up16(S * CAMPX_N_ACTIONS * (int64_t)sizeof(uint2));
   p->off_v0 = (int32_t)at;
@@ -64,21 +54,7 @@ inline int32_t plan_sweeps(int64_t S, int32_t policy, int32_t has_override, int6
     p->off_c4 = (int32_t)at;
     at += up16(S * 4);
   }
-  const bool fits = at <= lds_max;
-  if (path == 1 && !fits) return CAMPX_EINVAL;
-  if (path == 1 || (path == 0 && fits)) {
-    p->path = 1;
-    const int64_t t = (S + 63) / 64 * 64;
-    p->threads = (int32_t)(t > kPlanLdsThreads ? kPlanLdsThreads : t);
-    p->grid = 1;
-    p->lds_bytes = at;
-  } else {
-    p->path = 2;
-    p->threads = kPlanThreads;
-    p->grid = (S + kPlanThreads - 1) / kPlanThreads;
-    p->lds_bytes = 0;
-  }
-  return CAMPX_OK;
+  return plan_lds_or_launch(S, at, true, lds_max, path, kPlanThreads, &p->launch, plan_out);
 }
 
 struct SweepParams {
@@ -88,27 +64,10 @@ struct SweepParams {
   int32_t off_v0, off_v1, off_w, off_c4;
 };
 
-// policy_thresholds()'s total and its test of a row (k_policy.hip): the f32 sum in the sampler's
-// order, or 0 - which no good row has - for a row with a negative or NaN weight or a total that is
-// not a positive finite number.
-__device__ __forceinline__ float policy_total(const float (&w)[5]) {
-  const float c4 = (((w[0] + w[1]) + w[2]) + w[3]) + w[4];
-  const bool good = w[0] >= 0.0f && w[1] >= 0.0f && w[2] >= 0.0f && w[3] >= 0.0f && w[4] >= 0.0f &&
-                    c4 > 0.0f && c4 < INFINITY;
-  return good ? c4 : 0.0f;
-}
-
-// Where an entry leads.  (A next state outside the table cannot come out of
-// campx_wide_tables_build(); it reads state 0 rather than past the vector.)
-__device__ __forceinline__ uint32_t next_of(uint2 e, uint32_t S) {
-  const uint32_t next = e.y & 0xffffffu;
-  return next < S ? next : 0u;
-}
-
 // q of one entry whose reward word is already the reward to use, given v[next].
 __device__ __forceinline__ float backup(uint2 e, float gamma, const float* discounts, float vn) {
   const float r = __uint_as_float(e.x);
-  const uint32_t done = (e.y >> 24) & 1u, dcode = (e.y >> 25) & 15u;
+  const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
   const float c = gamma * __uint_as_float(discount_bits(discounts, dcode, done));
   return done ? r : r + c * vn;
 }
@@ -146,15 +105,8 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t m) {
   return m;
 }
 
-__device__ __forceinline__ void report_bad_rows(int32_t* bad_rows, int32_t* bad_flag, int bad) {
-  if (bad) {
-    if (bad_rows) atomicAdd(bad_rows, bad);
-    if (bad_flag) __hip_atomic_store(bad_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-
 template <bool kPolicy>
-__global__ __launch_bounds__(kPlanLdsThreads) void wide_sweeps_lds_kernel(
+__global__ __launch_bounds__(kTableLdsThreads) void wide_sweeps_lds_kernel(
     SweepParams sp, const uint2* __restrict__ g_entries, const float* __restrict__ g_policy,
     const float* __restrict__ g_reward, const float* v_in, float* v_out, float* __restrict__ q_out,
     int8_t* __restrict__ greedy_out, uint32_t* __restrict__ residual, int32_t* __restrict__ bad_rows,
@@ -182,7 +134,7 @@ __global__ __launch_bounds__(kPlanLdsThreads) void wide_sweeps_lds_kernel(
       for (int a = 0; a < 5; ++a) w[a] = g_policy[s * CAMPX_N_ACTIONS + a];
 #pragma unroll
       for (int a = 0; a < 5; ++a) wts[a * S + s] = w[a];
-      tot[s] = policy_total(w);
+      tot[s] = policy_row_total(w);
     }
   }
   if (tid < 16) discounts[tid] = sp.discounts[tid];
@@ -199,7 +151,7 @@ __global__ __launch_bounds__(kPlanLdsThreads) void wide_sweeps_lds_kernel(
 #pragma unroll
       for (int a = 0; a < 5; ++a) e[a] = ent[a * S + s];
 #pragma unroll
-      for (int a = 0; a < 5; ++a) vn[a] = vi[next_of(e[a], (uint32_t)S)];     // five reads in flight
+      for (int a = 0; a < 5; ++a) vn[a] = vi[entry_target(e[a].y, (uint32_t)S)];   // five in flight
 #pragma unroll
       for (int a = 0; a < 5; ++a) q[a] = backup(e[a], sp.gamma, discounts, vn[a]);
       if (kPolicy) {
@@ -233,7 +185,7 @@ __global__ __launch_bounds__(kPlanLdsThreads) void wide_sweeps_lds_kernel(
     vo = t;
   }
   for (int s = tid; s < S; s += nt) v_out[s] = vi[s];
-  report_bad_rows(bad_rows, bad_flag, bad);
+  report_bad(bad_rows, bad_flag, bad);
 }
 
 // What the global path starts with: the residual slots to zero (the sweeps raise them with
@@ -273,12 +225,12 @@ __global__ __launch_bounds__(kPlanThreads) void wide_sweep_kernel(
   if (kPolicy) {
 #pragma unroll
     for (int a = 0; a < 5; ++a) w[a] = policy[row + a];
-    c4 = policy_total(w);
+    c4 = policy_row_total(w);
   }
   const float before = v_src[live ? s : sp.S - 1];
   float q[5], vn[5];
 #pragma unroll
-  for (int a = 0; a < 5; ++a) vn[a] = v_src[next_of(e[a], (uint32_t)sp.S)];   // five gathers in flight
+  for (int a = 0; a < 5; ++a) vn[a] = v_src[entry_target(e[a].y, (uint32_t)sp.S)];   // five in flight
 #pragma unroll
   for (int a = 0; a < 5; ++a) {
     e[a].x = __float_as_uint(real_reward(__uint_as_float(e[a].x)));
@@ -306,16 +258,7 @@ __global__ __launch_bounds__(kPlanThreads) void wide_sweep_kernel(
     for (int i = 1; i < kPlanThreads / 64; ++i) m = partial[i] > m ? partial[i] : m;
     if (m) atomicMax(residual, m);
   }
-  if (last) report_bad_rows(bad_rows, bad_flag, (live && kPolicy && c4 == 0.0f) ? 1 : 0);
-}
-
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-// [a, a + S) and [b, b + S) share an element
-static bool overlap(const float* a, const float* b, int64_t S) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  const uintptr_t n = (uintptr_t)S * sizeof(float);
-  return x < y ? y - x < n : x - y < n;
+  if (last) report_bad(bad_rows, bad_flag, (live && kPolicy && c4 == 0.0f) ? 1 : 0);
 }
 
 }  // namespace campx_impl
@@ -328,13 +271,7 @@ int32_t campx_wide_sweeps_plan(int64_t n_states, int32_t policy, int32_t has_ove
                                int64_t wide_lds_max, int32_t path, int64_t* plan_out) {
   if (!plan_out) return CAMPX_EINVAL;
   SweepsPlan p;
-  const int32_t e = plan_sweeps(n_states, policy, has_override, wide_lds_max, path, &p);
-  if (e != CAMPX_OK) return e;
-  plan_out[0] = p.path;
-  plan_out[1] = p.lds_bytes;
-  plan_out[2] = p.threads;
-  plan_out[3] = p.grid;
-  return CAMPX_OK;
+  return plan_sweeps(n_states, policy, has_override, wide_lds_max, path, &p, plan_out);
 }
 
 int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev, const float* policy,
@@ -344,19 +281,21 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev,
                                  int32_t n_sweeps, int32_t path, void* stream) {
   if (!s || !tables_dev || !v_in || !v_out || !residual) return CAMPX_EINVAL;
   if (n_sweeps < 1 || n_sweeps > kPlanMaxSweeps || !(fabsf(gamma) < INFINITY)) return CAMPX_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(tables_dev) & 7) || !aligned4(policy) || !aligned4(reward_override) ||
-      !aligned4(v_in) || !aligned4(v_out) || !aligned4(scratch) || !aligned4(q) || !aligned4(residual) ||
-      !aligned4(bad_rows))
+  if (!aligned_to(tables_dev, 8) || !aligned_to(policy, 4) || !aligned_to(reward_override, 4) ||
+      !aligned_to(v_in, 4) || !aligned_to(v_out, 4) || !aligned_to(scratch, 4) || !aligned_to(q, 4) ||
+      !aligned_to(residual, 4) || !aligned_to(bad_rows, 4))
     return CAMPX_EINVAL;
   const int32_t v = wide_validate_plain(s);
   if (v != CAMPX_OK) return v;
   const int64_t S = s->n_states;
-  SweepsPlan plan;
+  SweepsPlan sweeps;
   const int32_t e = plan_sweeps(S, policy ? 1 : 0, reward_override ? 1 : 0, knob(K_WIDE_LDS_MAX), path,
-                                &plan);
+                                &sweeps, nullptr);
   if (e != CAMPX_OK) return e;
+  const TablePlan& plan = sweeps.launch;
+  const int64_t bytes = S * (int64_t)sizeof(float);
   // the values to start from and the values to leave are one vector or two apart
-  if (v_in != v_out && overlap(v_in, v_out, S)) return CAMPX_EINVAL;
+  if (v_in != v_out && ranges_overlap(v_in, v_out, bytes)) return CAMPX_EINVAL;
   SweepParams sp;
   memset(&sp, 0, sizeof(sp));
   sp.S = (int32_t)S;
@@ -364,10 +303,10 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev,
   sp.gamma = gamma;
   sp.discounts[0] = 1.0f;
   for (int i = 1; i < 16; ++i) sp.discounts[i] = s->discount_list[i];
-  sp.off_v0 = plan.off_v0;
-  sp.off_v1 = plan.off_v1;
-  sp.off_w = plan.off_w;
-  sp.off_c4 = plan.off_c4;
+  sp.off_v0 = sweeps.off_v0;
+  sp.off_v1 = sweeps.off_v1;
+  sp.off_w = sweeps.off_w;
+  sp.off_c4 = sweeps.off_c4;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const uint2* entries = reinterpret_cast<const uint2*>(tables_dev);
   uint32_t* res = reinterpret_cast<uint32_t*>(residual);
@@ -388,7 +327,8 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev,
   // Sweep k of n writes v_out when n - k is even and the scratch vector when it is odd, so that
   // the last one writes v_out; sweep 1 reads v_in - or, where it would write the vector it reads
   // (v_in == v_out, n odd), the copy of it that the first kernel leaves in the scratch vector.
-  if (!scratch || overlap(scratch, v_in, S) || overlap(scratch, v_out, S)) return CAMPX_EINVAL;
+  if (!scratch || ranges_overlap(scratch, v_in, bytes) || ranges_overlap(scratch, v_out, bytes))
+    return CAMPX_EINVAL;
   const bool copy = v_in == v_out && (n_sweeps & 1);
   {
     const int64_t most = (copy && S > n_sweeps) ? S : n_sweeps;

@@ -12,9 +12,7 @@
 // frame), then the entry of (state, action) as before.  The random words do not depend on the
 // state: both blocks of a chunk of eight frames are computed before its chain starts.
 
-#include "campx_common.hip.h"
-
-#include <math.h>
+#include "wide_table.hip.h"
 
 #include <type_traits>
 
@@ -49,24 +47,6 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
   out[1] = c1;
   out[2] = c2;
   out[3] = c3;
-}
-
-// A row's thresholds.  A bad row (a weight that is negative or NaN, a total that is not a
-// positive finite number) becomes {-1, -1, -1, -1, 0}: r = u * 0 = 0 passes all four tests -
-// action 4 - and c4 == 0, which no good row has, is what the frame counts as bad.
-__device__ __forceinline__ void policy_thresholds(const float* w, float (&c)[5]) {
-  const float w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-  c[0] = w0;
-  c[1] = c[0] + w1;
-  c[2] = c[1] + w2;
-  c[3] = c[2] + w3;
-  c[4] = c[3] + w4;
-  const bool good = w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f && w3 >= 0.0f && w4 >= 0.0f &&
-                    c[4] > 0.0f && c[4] < INFINITY;
-  if (!good) {
-    c[0] = c[1] = c[2] = c[3] = -1.0f;
-    c[4] = 0.0f;
-  }
 }
 
 // kLds: the state table AND the thresholds sit in LDS; else both are read through L1 / L2 (the
@@ -160,8 +140,8 @@ __global__ __launch_bounds__(kPolicyThreads) void wide_policy_update_kernel(
         if (kStates) states_out[at] = (int32_t)from;
         const uint32_t idx = from * CAMPX_N_ACTIONS + a;
         const uint2 e = entries[idx];
-        now = e.y & 0xffffffu;
-        const uint32_t done = (e.y >> 24) & 1u, dcode = (e.y >> 25) & 15u;
+        now = entry_next(e.y);
+        const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
         from = done ? 0u : now;                      // the chain: state -> thresholds -> entry -> state
         const u32x4 cs = cells[now];                 // where things show in the state reached
         trace[at] = (uint16_t)cs.x;
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(kPolicyThreads) void wide_policy_update_kernel(
   state[env] = (int32_t)now;
   st.done[env] = (uint8_t)over;
   if (st.ret) st.ret[env] = ret;
-  report_bad_actions(out, bad);
+  report_bad(out.bad_count, out.bad_flag, bad);      // (bad ROWS, on the rollout's counter)
 }
 
 }  // namespace campx_impl

@@ -24,7 +24,7 @@
 //
 // table_lookup_kernel: out[t, e] = table[state * A + action], the same walk without atomics.
 
-#include "campx_common.hip.h"
+#include "wide_table.hip.h"
 
 #include <type_traits>
 
@@ -280,8 +280,6 @@ __global__ __launch_bounds__(kSumsThreads) void table_lookup_kernel(
   add_counters(counters, n_bad, 0, bad_count, nullptr);
 }
 
-static bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -312,14 +310,15 @@ int32_t campx_state_sums_launch(const CampxStateSums* s, int64_t B, int32_t T, v
   if (e != CAMPX_OK) return e;
   const int K = s->n_values;
   if (!s->actions && s->n_actions != 1) return CAMPX_EINVAL;
-  if (!aligned(s->states, 4) || !aligned(s->acc, 8) || !aligned(s->skipped, 8) || !aligned(s->clamped, 8))
+  if (!aligned_to(s->states, 4) || !aligned_to(s->acc, 8) || !aligned_to(s->skipped, 8) ||
+      !aligned_to(s->clamped, 8))
     return CAMPX_EINVAL;
   // (a single frame never uses its pitch)
   const int64_t least = T > 1 ? B : 0, most = (1ll << 40) / T;
   auto pitch_ok = [&](int64_t pitch) { return pitch >= least && pitch <= most; };
   if (!pitch_ok(s->states_pitch) || (s->actions && !pitch_ok(s->actions_pitch))) return CAMPX_EINVAL;
   for (int k = 0; k < K; ++k)
-    if (!s->values[k] || !aligned(s->values[k], 4) || !pitch_ok(s->values_pitch[k])) return CAMPX_EINVAL;
+    if (!s->values[k] || !aligned_to(s->values[k], 4) || !pitch_ok(s->values_pitch[k])) return CAMPX_EINVAL;
   SumsParams sp;
   memset(&sp, 0, sizeof(sp));
   sp.T = T;
@@ -379,7 +378,8 @@ int32_t campx_table_lookup_launch(const CampxTableLookup* l, int64_t B, int32_t 
   if (!l || !l->table || !l->states || !l->out) return CAMPX_EINVAL;
   if (!sums_shape_ok(l->n_states, l->n_actions, B, T)) return CAMPX_EINVAL;
   if (!l->actions && l->n_actions != 1) return CAMPX_EINVAL;
-  if (!aligned(l->table, 4) || !aligned(l->states, 4) || !aligned(l->out, 4) || !aligned(l->bad_count, 8))
+  if (!aligned_to(l->table, 4) || !aligned_to(l->states, 4) || !aligned_to(l->out, 4) ||
+      !aligned_to(l->bad_count, 8))
     return CAMPX_EINVAL;
   const int64_t least = T > 1 ? B : 0, most = (1ll << 40) / T;
   auto pitch_ok = [&](int64_t pitch) { return pitch >= least && pitch <= most; };

@@ -23,15 +23,12 @@
 //     that the buffer is zero when it is the target of the frame after next.
 // plan_visit() chooses; campx_wide_visit_plan() shows the choice to a test without a GPU.
 
-#include "campx_common.hip.h"
-
-#include <math.h>
+#include "wide_table.hip.h"
 
 namespace campx_impl {
 
 typedef unsigned long long u64;
 
-constexpr int kVisitLdsThreads = 1024;     // at most; a multiple of 64 that covers the states
 constexpr int kVisitPerLane = 3;           // states a lane of the LDS workgroup owns, at most
 constexpr int kVisitThreads = 256;         // global path, and the counts
 constexpr int64_t kVisitLdsHeader = 64;    // the two slots of finished[t]
@@ -39,61 +36,26 @@ constexpr int32_t kVisitMaxFrames = 1 << 20;
 constexpr uint32_t kVisitWords = 1u << 24; // the sampler's values u
 
 struct VisitPlan {
-  int32_t path;            // 1 LDS, 2 global
-  int32_t threads;         // of a workgroup
-  int64_t grid;            // workgroups of a frame
-  int64_t lds_bytes;
+  TablePlan launch;
   int32_t off_n, off_d0, off_d1;     // byte offsets into the dynamic LDS
 };
-
-static inline int64_t visit_up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 // The LDS a table of S states takes: header, the entries' second words [5][S] x 4 bytes, N [4][S]
 // x 4 bytes and two mass vectors [S] x 8 bytes - 52 bytes per state.  A lane keeps the visits of
 // the states it owns in registers, kVisitPerLane of them at most.
-static inline int32_t plan_visit(int64_t S, int64_t lds_max, int32_t path, VisitPlan* p) {
-  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || lds_max < 0 || path < 0 || path > 2) return CAMPX_EINVAL;
+static inline int32_t plan_visit(int64_t S, int64_t lds_max, int32_t path, VisitPlan* p,
+                                 int64_t* plan_out) {
+  if (S < 1 || S > CAMPX_WIDE_MAX_STATES) return CAMPX_EINVAL;
   memset(p, 0, sizeof(*p));
-  int64_t at = kVisitLdsHeader + visit_up16(S * CAMPX_N_ACTIONS * 4);
+  int64_t at = kVisitLdsHeader + up16(S * CAMPX_N_ACTIONS * 4);
   p->off_n = (int32_t)at;
-  at += visit_up16(S * 4 * 4);
+  at += up16(S * 4 * 4);
   p->off_d0 = (int32_t)at;
-  at += visit_up16(S * 8);
+  at += up16(S * 8);
   p->off_d1 = (int32_t)at;
-  at += visit_up16(S * 8);
-  const bool fits = at <= lds_max && S <= (int64_t)kVisitLdsThreads * kVisitPerLane;
-  if (path == 1 && !fits) return CAMPX_EINVAL;
-  if (path == 1 || (path == 0 && fits)) {
-    p->path = 1;
-    const int64_t t = (S + 63) / 64 * 64;
-    p->threads = (int32_t)(t > kVisitLdsThreads ? kVisitLdsThreads : t);
-    p->grid = 1;
-    p->lds_bytes = at;
-  } else {
-    p->path = 2;
-    p->threads = kVisitThreads;
-    p->grid = (S + kVisitThreads - 1) / kVisitThreads;
-    p->lds_bytes = 0;
-    p->off_n = p->off_d0 = p->off_d1 = 0;
-  }
-  return CAMPX_OK;
-}
-
-// policy_thresholds() of k_policy.hip, restated: the sampler's thresholds of a row, a bad row's
-// {-1, -1, -1, -1, 0}.
-__device__ __forceinline__ void row_thresholds(const float* w, float (&c)[5]) {
-  const float w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
-  c[0] = w0;
-  c[1] = c[0] + w1;
-  c[2] = c[1] + w2;
-  c[3] = c[2] + w3;
-  c[4] = c[3] + w4;
-  const bool good = w0 >= 0.0f && w1 >= 0.0f && w2 >= 0.0f && w3 >= 0.0f && w4 >= 0.0f &&
-                    c[4] > 0.0f && c[4] < INFINITY;
-  if (!good) {
-    c[0] = c[1] = c[2] = c[3] = -1.0f;
-    c[4] = 0.0f;
-  }
+  at += up16(S * 8);
+  return plan_lds_or_launch(S, at, S <= (int64_t)kTableLdsThreads * kVisitPerLane, lds_max, path,
+                            kVisitThreads, &p->launch, plan_out);
 }
 
 // The smallest u in 0 .. 2^24 whose product reaches the threshold (2^24: none does): the
@@ -162,7 +124,7 @@ __global__ __launch_bounds__(kVisitThreads) void visit_counts_kernel(
   const int s = first;
   if (s >= S) return;
   float c[5];
-  row_thresholds(policy + (int64_t)s * CAMPX_N_ACTIONS, c);
+  policy_thresholds(policy + (int64_t)s * CAMPX_N_ACTIONS, c);
   uint32_t before = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -176,10 +138,7 @@ __global__ __launch_bounds__(kVisitThreads) void visit_counts_kernel(
     d_second[s] = 0;
     d_first[s] = m;
   }
-  if (c[4] == 0.0f) {
-    if (bad_rows) atomicAdd(bad_rows, 1);
-    if (bad_flag) __hip_atomic_store(bad_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  report_bad(bad_rows, bad_flag, c[4] == 0.0f);
 }
 
 struct VisitParams {
@@ -187,14 +146,7 @@ struct VisitParams {
   int32_t off_n, off_d0, off_d1;
 };
 
-// Where an entry leads.  (A next state outside the table cannot come out of
-// campx_wide_tables_build(); it adds to state 0 rather than past the vector.)
-__device__ __forceinline__ uint32_t target_of(uint32_t word, uint32_t S) {
-  const uint32_t next = word & 0xffffffu;
-  return next < S ? next : 0u;
-}
-
-__global__ __launch_bounds__(kVisitLdsThreads) void visit_lds_kernel(
+__global__ __launch_bounds__(kTableLdsThreads) void visit_lds_kernel(
     VisitParams vp, const uint2* __restrict__ g_entries, const int32_t* __restrict__ g_counts,
     const u64* start, u64* __restrict__ visits, u64* __restrict__ finished, u64* final_out,
     u64* __restrict__ per_frame) {
@@ -249,8 +201,8 @@ __global__ __launch_bounds__(kVisitLdsThreads) void visit_lds_kernel(
           for (int a = 0; a < 5; ++a) {
             acc[j][a] += x[a];
             if (x[a]) {
-              if ((e[a] >> 24) & 1u) over += x[a];
-              else lds_add(&nxt[target_of(e[a], (uint32_t)S)], x[a]);
+              if (entry_done(e[a])) over += x[a];
+              else lds_add(&nxt[entry_target(e[a], (uint32_t)S)], x[a]);
             }
           }
         }
@@ -312,8 +264,8 @@ __global__ __launch_bounds__(kVisitThreads) void visit_frame_kernel(
 #pragma unroll
       for (int a = 0; a < 5; ++a) {
         if (x[a]) {
-          if ((word[a] >> 24) & 1u) over += x[a];
-          else global_add(&dst[target_of(word[a], (uint32_t)S)], x[a]);
+          if (entry_done(word[a])) over += x[a];
+          else global_add(&dst[entry_target(word[a], (uint32_t)S)], x[a]);
         }
       }
     }
@@ -340,15 +292,6 @@ __global__ __launch_bounds__(kVisitThreads) void visit_last_row_kernel(
   if (s < S) row[s] = final_in[s];
 }
 
-static bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-// [a, a + S) and [b, b + S) share an element
-static bool overlap8(const void* a, const void* b, int64_t S) {
-  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-  const uintptr_t n = (uintptr_t)S * sizeof(int64_t);
-  return x < y ? y - x < n : x - y < n;
-}
-
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -359,13 +302,7 @@ int32_t campx_wide_visit_plan(int64_t n_states, int64_t wide_lds_max, int32_t pa
                               int64_t* plan_out) {
   if (!plan_out) return CAMPX_EINVAL;
   VisitPlan p;
-  const int32_t e = plan_visit(n_states, wide_lds_max, path, &p);
-  if (e != CAMPX_OK) return e;
-  plan_out[0] = p.path;
-  plan_out[1] = p.lds_bytes;
-  plan_out[2] = p.threads;
-  plan_out[3] = p.grid;
-  return CAMPX_OK;
+  return plan_visit(n_states, wide_lds_max, path, &p, plan_out);
 }
 
 int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, const float* policy,
@@ -384,13 +321,16 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
   const int32_t v = wide_validate_plain(s);
   if (v != CAMPX_OK) return v;
   const int64_t S = s->n_states;
-  VisitPlan plan;
-  const int32_t e = plan_visit(S, knob(K_WIDE_LDS_MAX), path, &plan);
+  VisitPlan visit;
+  const int32_t e = plan_visit(S, knob(K_WIDE_LDS_MAX), path, &visit, nullptr);
   if (e != CAMPX_OK) return e;
+  const TablePlan& plan = visit.launch;
+  const int64_t bytes = S * (int64_t)sizeof(int64_t);
   // the mass to start from and the mass to leave are one vector or two apart
-  if (start && start != final_mass && overlap8(start, final_mass, S)) return CAMPX_EINVAL;
+  if (start && start != final_mass && ranges_overlap(start, final_mass, bytes)) return CAMPX_EINVAL;
   if (plan.path == 2 &&
-      (!scratch || overlap8(scratch, final_mass, S) || (start && overlap8(scratch, start, S))))
+      (!scratch || ranges_overlap(scratch, final_mass, bytes) ||
+       (start && ranges_overlap(scratch, start, bytes))))
     return CAMPX_EINVAL;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const uint2* entries = reinterpret_cast<const uint2*>(tables_dev);
@@ -417,9 +357,9 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
     vp.S = (int32_t)S;
     vp.n_frames = n_frames;
     vp.restart = restart;
-    vp.off_n = plan.off_n;
-    vp.off_d0 = plan.off_d0;
-    vp.off_d1 = plan.off_d1;
+    vp.off_n = visit.off_n;
+    vp.off_d0 = visit.off_d0;
+    vp.off_d1 = visit.off_d1;
     CAMPX_ALLOW_LDS(visit_lds_kernel, (size_t)plan.lds_bytes);
     hipLaunchKernelGGL(visit_lds_kernel, dim3(1), dim3((unsigned)plan.threads),
                        (size_t)plan.lds_bytes, hs, vp, entries, counts, d_start, d_visits,

@@ -11,7 +11,7 @@
 // its time (20 us of 1 430 at 16x16, B = 65 536).  What bounds the tier is the render kernel's
 // write stream (7.2 TB/s).
 
-#include "campx_common.hip.h"
+#include "wide_table.hip.h"
 
 #include <type_traits>
 
@@ -27,13 +27,6 @@ struct WideParams {
   int64_t plane;               // entries from one thing's plane of the trace to the next's (the
                                // whole rollout's frames x row pitch, also when a launch runs a chunk of them)
 };
-
-// Table-blob entry of (state, action): x = reward; y = [0:23] the state after the frame,
-// [24] done, [25:28] discount code.  (The state the NEXT frame starts from is state 0 when
-// the frame ended the episode: the rebuild is one select on the chain.)
-__host__ __device__ __forceinline__ uint32_t wide_pack(uint32_t next, uint32_t done, uint32_t dcode) {
-  return next | (done << 24) | (dcode << 25);
-}
 
 // kLds: the state table (entries, per-state trace entries, perf bytes) sits in LDS; else it
 // is read through L1 / L2 (games with thousands of states).
@@ -107,8 +100,8 @@ __global__ __launch_bounds__(kWideThreads) void wide_update_kernel(
         bad += a[j] > 4u;
         const uint32_t idx = from * CAMPX_N_ACTIONS + (a[j] > 4u ? 4u : a[j]);
         const uint2 e = entries[idx];
-        now = e.y & 0xffffffu;
-        const uint32_t done = (e.y >> 24) & 1u, dcode = (e.y >> 25) & 15u;
+        now = entry_next(e.y);
+        const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
         from = done ? 0u : now;                      // the chain: state -> entry -> state
         const u32x4 c = cells[now];                  // where things show in the state reached
         trace[at] = (uint16_t)c.x;
@@ -246,8 +239,8 @@ __global__ __launch_bounds__(kWideThreads) void wide_step_kernel(
     bad = a > 4u;
     const uint32_t idx = (over ? 0u : now) * CAMPX_N_ACTIONS + (a > 4u ? 4u : a);
     const uint2 e = entries[idx];
-    now = e.y & 0xffffffu;
-    const uint32_t done = (e.y >> 24) & 1u, dcode = (e.y >> 25) & 15u;
+    now = entry_next(e.y);
+    const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
     const u32x4 c = cells[now];
     shown[wave][lane] = c;
     state[env] = (int32_t)now;
@@ -364,8 +357,8 @@ __global__ __launch_bounds__(kWideThreads) void wide_step_lds_kernel(
     bad = a > 4u;
     const uint32_t idx = (over ? 0u : now) * CAMPX_N_ACTIONS + (a > 4u ? 4u : a);
     const uint2 e = entries[idx];
-    now = e.y & 0xffffffu;
-    const uint32_t done = (e.y >> 24) & 1u, dcode = (e.y >> 25) & 15u;
+    now = entry_next(e.y);
+    const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
     mine = cells[now];
     state[env] = (int32_t)now;
     st.done[env] = (uint8_t)done;

@@ -1,0 +1,130 @@
+// wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_plan, k_visit,
+// k_sums) agree on, each said once: the table entry's format, the policy-row rule, the lazy error
+// report, and the host's choice between one LDS workgroup and one launch per step.
+#ifndef CAMPX_WIDE_TABLE_HIP_H_
+#define CAMPX_WIDE_TABLE_HIP_H_
+
+#include "campx_common.hip.h"
+
+#include <math.h>
+
+namespace campx_impl {
+
+// Table-blob entry of (state, action), 8 bytes: x = the reward's bits; y = [0:23] the state after
+// the frame, [24] done, [25:28] discount code.  (The state the NEXT frame starts from is state 0
+// when the frame ended the episode: the rebuild is one select on the chain.)  The accessors take
+// the y word; campx_amd/_hip.py names the same masks and shifts for table_arrays().
+__host__ __device__ __forceinline__ uint32_t wide_pack(uint32_t next, uint32_t done, uint32_t dcode) {
+  return next | (done << 24) | (dcode << 25);
+}
+__device__ __forceinline__ uint32_t entry_next(uint32_t y) { return y & 0xffffffu; }
+__device__ __forceinline__ uint32_t entry_done(uint32_t y) { return (y >> 24) & 1u; }
+__device__ __forceinline__ uint32_t entry_dcode(uint32_t y) { return (y >> 25) & 15u; }
+// Where an entry leads.  (A next state outside the table cannot come out of
+// campx_wide_tables_build(); it stands for state 0 rather than for an element past a vector.)
+__device__ __forceinline__ uint32_t entry_target(uint32_t y, uint32_t S) {
+  const uint32_t next = entry_next(y);
+  return next < S ? next : 0u;
+}
+
+// The test of a policy row, given its total c4 in the sampler's f32 order: no weight negative or
+// NaN, the total a positive finite number.  A macro, not a function: the two readers below must
+// compile to the code they had when each spelled the test out, and hipcc gives the && chain another
+// shape (no branch round the sum, other registers) once it comes through a call, inlined or not.
+#define CAMPX_POLICY_ROW_GOOD(w0, w1, w2, w3, w4, c4)                                            \
+  ((w0) >= 0.0f && (w1) >= 0.0f && (w2) >= 0.0f && (w3) >= 0.0f && (w4) >= 0.0f && (c4) > 0.0f && \
+   (c4) < INFINITY)
+
+// A policy row's thresholds, in the sampler's f32 order.  A bad row becomes {-1, -1, -1, -1, 0}:
+// r = u * 0 = 0 passes all four tests - action 4 - and c4 == 0, which no good row has, is what
+// counts as bad.
+__device__ __forceinline__ void policy_thresholds(const float* w, float (&c)[5]) {
+  const float w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+  c[0] = w0;
+  c[1] = c[0] + w1;
+  c[2] = c[1] + w2;
+  c[3] = c[2] + w3;
+  c[4] = c[3] + w4;
+  const bool good = CAMPX_POLICY_ROW_GOOD(w0, w1, w2, w3, w4, c[4]);
+  if (!good) {
+    c[0] = c[1] = c[2] = c[3] = -1.0f;
+    c[4] = 0.0f;
+  }
+}
+
+// c[4] of policy_thresholds() alone, for a reader that needs no threshold (k_plan.hip): the row's
+// total - the same sum in the same order - or 0 for a bad row.
+__device__ __forceinline__ float policy_row_total(const float (&w)[5]) {
+  const float c4 = (((w[0] + w[1]) + w[2]) + w[3]) + w[4];
+  const bool good = CAMPX_POLICY_ROW_GOOD(w[0], w[1], w[2], w[3], w[4], c4);
+  return good ? c4 : 0.0f;
+}
+
+// What a kernel found wrong in its input and went on from, for the host to read later: `n` more on
+// the device counter, and the pinned flag raised (either may be NULL).
+__device__ __forceinline__ void report_bad(int32_t* count, int32_t* flag, int n) {
+  if (n) {
+    if (count) atomicAdd(count, n);
+    if (flag) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// ---------------------------------------------------------------------------- host side
+
+inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
+
+inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
+// [a, a + bytes) and [b, b + bytes) share a byte
+inline bool ranges_overlap(const void* a, const void* b, int64_t bytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  const uintptr_t n = (uintptr_t)bytes;
+  return x < y ? y - x < n : x - y < n;
+}
+
+// Work that runs n steps over a table's S states, a lane per state, each step reading what the one
+// before it wrote: ONE workgroup that keeps everything in LDS and runs all steps, a barrier between
+// them (path 1) - or one launch per step (path 2).
+// threads of the LDS workgroup, at most; it has a multiple of 64 that covers the states
+constexpr int kTableLdsThreads = 1024;
+struct TablePlan {
+  int32_t path;            // 1 LDS, 2 global
+  int32_t threads;         // of a workgroup
+  int64_t grid;            // workgroups of a step
+  int64_t lds_bytes;
+};
+
+// S is within 1 .. CAMPX_WIDE_MAX_STATES (the caller's byte arithmetic needed that already).
+// `lds_bytes`: what the LDS workgroup would take; it is chosen (`path` 0) or allowed (`path` 1)
+// when that is within `lds_max` and `fits_too` holds.  `plan_out`: the four words the
+// campx_wide_*_plan() entry points show, or NULL.
+inline int32_t plan_lds_or_launch(int64_t S, int64_t lds_bytes, bool fits_too, int64_t lds_max,
+                                  int32_t path, int32_t global_threads, TablePlan* p,
+                                  int64_t* plan_out) {
+  if (lds_max < 0 || path < 0 || path > 2) return CAMPX_EINVAL;
+  const bool fits = lds_bytes <= lds_max && fits_too;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  if (path == 1 || (path == 0 && fits)) {
+    p->path = 1;
+    const int64_t t = (S + 63) / 64 * 64;
+    p->threads = (int32_t)(t > kTableLdsThreads ? kTableLdsThreads : t);
+    p->grid = 1;
+    p->lds_bytes = lds_bytes;
+  } else {
+    p->path = 2;
+    p->threads = global_threads;
+    p->grid = (S + global_threads - 1) / global_threads;
+    p->lds_bytes = 0;
+  }
+  if (plan_out) {
+    plan_out[0] = p->path;
+    plan_out[1] = p->lds_bytes;
+    plan_out[2] = p->threads;
+    plan_out[3] = p->grid;
+  }
+  return CAMPX_OK;
+}
+
+}  // namespace campx_impl
+
+#endif  // CAMPX_WIDE_TABLE_HIP_H_

@@ -421,68 +421,54 @@ class Engine(object):
       self._render()
     return self._board, reward, discount
 
+  def _batched(self, method):
+    """The tier behind a batched Engine, asked for on behalf of `method`."""
+    if self._fused is None:
+      raise RuntimeError('{}() needs a batched Engine (batch=B) that has '
+                         'been through its_showtime()'.format(method))
+    return self._fused
+
   def capture_play(self, n_frames, policy=None, record_obs=False):
     """Batched tiers only: `n_frames` consecutive `play()` calls captured once in a HIP graph - with
     `policy(observation, t) -> action ids [B]` the policy's forward pass and its sampling too, the
     loop of examples/reinforce.py:136-149 without the host in it.  Returns a
     `play_graph.PlayGraph`: `.replay([actions])`, then `.reward / .discount / .done / .actions`
     `[n_frames, B]`."""
-    if self._fused is None:
-      raise RuntimeError('capture_play() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.capture_play(n_frames, policy=policy, record_obs=record_obs)
+    return self._batched('capture_play').capture_play(n_frames, policy=policy, record_obs=record_obs)
 
   def rollout(self, actions, **kwargs):
     """Fused tier only: advance T frames with one kernel launch.
 
     `actions` is an integer tensor `[T, B]`.  See `fused.FusedGame.rollout`.
     """
-    if self._fused is None:
-      raise RuntimeError('rollout() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout(actions, **kwargs)
+    return self._batched('rollout').rollout(actions, **kwargs)
 
   def rollout_buffers(self, T, **kwargs):
     """Fused tiers only: the output buffers of a T-frame rollout, allocated once
     (`fused.FusedGame.rollout_buffers`)."""
-    if self._fused is None:
-      raise RuntimeError('rollout_buffers() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_buffers(T, **kwargs)
+    return self._batched('rollout_buffers').rollout_buffers(T, **kwargs)
 
   def rollout_trace(self, actions, reset_first=False, out=None):
     """Batched tiers only: T frames of update pass and nothing else - `rollout()`'s dict without
     'obs' / 'board'.  The trace is the stored trajectory; `render_frames()` materialises the
     transitions a minibatch samples.  See `fused.FusedGame.rollout_trace` (the shape tier raises
     NotImplementedError)."""
-    if self._fused is None:
-      raise RuntimeError('rollout_trace() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_trace(actions, reset_first=reset_first, out=out)
+    return self._batched('rollout_trace').rollout_trace(actions, reset_first=reset_first, out=out)
 
   def rollout_trace_buffers(self, T):
     """Batched tiers only: the dict of `rollout_trace(out=...)`, allocated once."""
-    if self._fused is None:
-      raise RuntimeError('rollout_trace_buffers() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_trace_buffers(T)
+    return self._batched('rollout_trace_buffers').rollout_trace_buffers(T)
 
   def rollout_policy(self, policy, T, **kwargs):
     """State-table tier only: T frames in one launch with every action sampled on the device from
     `policy`, float32 `[n_states, 5]` weights per state - `rollout_trace()`'s dict plus 'actions'
     and 'states'.  See `wide.WideGame.rollout_policy`; the other batched tiers raise
     NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('rollout_policy() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_policy(policy, T, **kwargs)
+    return self._batched('rollout_policy').rollout_policy(policy, T, **kwargs)
 
   def rollout_policy_buffers(self, T, want_states=True):
     """State-table tier only: the dict of `rollout_policy(out=...)`, allocated once."""
-    if self._fused is None:
-      raise RuntimeError('rollout_policy_buffers() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_policy_buffers(T, want_states=want_states)
+    return self._batched('rollout_policy_buffers').rollout_policy_buffers(T, want_states=want_states)
 
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
@@ -490,10 +476,7 @@ class Engine(object):
     environment in that state - what a network evaluated once per state is evaluated on.  See
     `wide.WideGame.render_states`; the other batched tiers raise NotImplementedError
     (`use_state_table()` before `its_showtime()` puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('render_states() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.render_states(state_ids, obs_dtype=obs_dtype, out=out)
+    return self._batched('render_states').render_states(state_ids, obs_dtype=obs_dtype, out=out)
 
   def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
     """State-table tier only: `[N, L, h, w]`, `render_frames()` of the pairs `(t_idx[i], e_idx[i])`
@@ -501,19 +484,15 @@ class Engine(object):
     without the full observations being written.  See `wide.WideGame.render_frame_windows`; the
     other batched tiers raise NotImplementedError (`use_state_table()` before `its_showtime()`
     puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('render_frame_windows() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.render_frame_windows(trace, t_idx, e_idx, window, obs_dtype=obs_dtype, out=out)
+    return self._batched('render_frame_windows').render_frame_windows(
+        trace, t_idx, e_idx, window, obs_dtype=obs_dtype, out=out)
 
   def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
     """State-table tier only: `[T, B, L, h, w]`, the windows of every frame of a trace.  See
     `wide.WideGame.render_trace_windows`; the other batched tiers raise NotImplementedError
     (`use_state_table()` before `its_showtime()` puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('render_trace_windows() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.render_trace_windows(trace, window, obs_dtype=obs_dtype, out=out)
+    return self._batched('render_trace_windows').render_trace_windows(
+        trace, window, obs_dtype=obs_dtype, out=out)
 
   def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: `[N, L, h, w]`, `render_states()` of the states `state_ids` (None:
@@ -521,37 +500,31 @@ class Engine(object):
     agent's surroundings is evaluated on, once per state.  See
     `wide.WideGame.render_state_windows`; the other batched tiers raise NotImplementedError
     (`use_state_table()` before `its_showtime()` puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('render_state_windows() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.render_state_windows(window, state_ids, obs_dtype=obs_dtype, out=out)
+    return self._batched('render_state_windows').render_state_windows(
+        window, state_ids, obs_dtype=obs_dtype, out=out)
+
+  def sweep_buffers(self, sweeps, want_q=True, greedy=True):
+    """State-table tier only: the dict of `evaluate_policy(out=...)` (`greedy=False`) or
+    `value_iteration(out=...)`, allocated once.  See `wide.WideGame.sweep_buffers`."""
+    return self._batched('sweep_buffers').sweep_buffers(sweeps, want_q=want_q, greedy=greedy)
 
   def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
     """State-table tier only: the exact value of `policy`, float32 `[n_states, 5]` weights per
     state, after `sweeps` Jacobi sweeps of the Bellman backup over the game's table - 'values',
     'q', 'residual', 'sweeps'.  See `wide.WideGame.evaluate_policy`; the other batched tiers raise
     NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('evaluate_policy() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.evaluate_policy(policy, gamma, sweeps, **kwargs)
+    return self._batched('evaluate_policy').evaluate_policy(policy, gamma, sweeps, **kwargs)
 
   def value_iteration(self, gamma, sweeps, **kwargs):
     """State-table tier only: `sweeps` sweeps of value iteration over the game's table - 'values',
     'q', 'greedy', 'residual', 'sweeps'.  See `wide.WideGame.value_iteration`; the other batched
     tiers raise NotImplementedError."""
-    if self._fused is None:
-      raise RuntimeError('value_iteration() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.value_iteration(gamma, sweeps, **kwargs)
+    return self._batched('value_iteration').value_iteration(gamma, sweeps, **kwargs)
 
   def table_arrays(self):
     """State-table tier only: the game's table as device tensors `[n_states, 5]` - 'next_state',
     'reward', 'done', 'discount', 'perf'.  See `wide.WideGame.table_arrays`."""
-    if self._fused is None:
-      raise RuntimeError('table_arrays() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.table_arrays()
+    return self._batched('table_arrays').table_arrays()
 
   def state_visitation(self, policy, frames, **kwargs):
     """State-table tier only: the exact visitation of `policy`, float32 `[n_states, 5]` weights per
@@ -559,37 +532,25 @@ class Engine(object):
     'final', 'per_frame', 'counts', 'probs', 'unit'.  See `wide.WideGame.state_visitation`; the
     other batched tiers raise NotImplementedError (`use_state_table()` before `its_showtime()`
     puts a game on this one)."""
-    if self._fused is None:
-      raise RuntimeError('state_visitation() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.state_visitation(policy, frames, **kwargs)
+    return self._batched('state_visitation').state_visitation(policy, frames, **kwargs)
 
   def visitation_buffers(self, frames, want_frames=False):
     """State-table tier only: the dict of `state_visitation(out=...)`.  See
     `wide.WideGame.visitation_buffers`."""
-    if self._fused is None:
-      raise RuntimeError('visitation_buffers() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.visitation_buffers(frames, want_frames)
+    return self._batched('visitation_buffers').visitation_buffers(frames, want_frames)
 
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
     `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See
     `fused.FusedGame.render_frames` (the shape tier raises NotImplementedError)."""
-    if self._fused is None:
-      raise RuntimeError('render_frames() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.render_frames(trace, t_idx, e_idx, obs_dtype=obs_dtype, out=out)
+    return self._batched('render_frames').render_frames(trace, t_idx, e_idx, obs_dtype=obs_dtype, out=out)
 
   def rollout_deferred(self, actions, out, reset_first=False, actions_ready=False):
     """Fused tiers only: T frames whose observations may arrive with the NEXT call - for action
     streams that do not wait for them.  Returns the previous call's buffers, complete; see
     `fused.FusedGame.rollout_deferred` (tiers without a shared launch run the rollout whole)."""
-    if self._fused is None:
-      raise RuntimeError('rollout_deferred() needs a batched Engine (batch=B) that has '
-                         'been through its_showtime()')
-    return self._fused.rollout_deferred(actions, out, reset_first=reset_first,
-                                        actions_ready=actions_ready)
+    return self._batched('rollout_deferred').rollout_deferred(
+        actions, out, reset_first=reset_first, actions_ready=actions_ready)
 
   def flush(self):
     """The buffers of the last `rollout_deferred()` call, complete (None if there is none)."""

@@ -210,85 +210,36 @@ class FusedGame(object):
 
   def _init_gather(self):
     """render_frames()'s bookkeeping of indices out of range: a device counter and a flag in
-    pinned host memory, as for bad actions."""
+    pinned host memory, as for bad actions - and the list of all such counters."""
     self._bad_idx = torch.zeros((1,), dtype=torch.int32, device=self.device)
     self._bad_idx_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._bad_idx_flag_view = self._bad_idx_flag.numpy()
-
-  def _take_bad_indices(self):
-    n = int(self._bad_idx.item())      # synchronises: we are about to raise anyway
-    self._bad_idx.zero_()
-    self._bad_idx_flag_view[0] = 0
-    return n
-
-  def _take_bad_policy_rows(self):
-    """Environment-frames of rollout_policy() that met a bad policy row (the state-table tier
-    counts them beside the bad action ids, under the same flag); 0 on the other tiers."""
-    return 0
-
-  def _take_bad_plan_rows(self):
-    """Bad rows of the policies given to evaluate_policy() (the state-table tier counts them under
-    the flag of the bad action ids); 0 on the other tiers."""
-    return 0
-
-  def _take_bad_visit_rows(self):
-    """Bad rows of the policies given to state_visitation() (the state-table tier counts them under
-    the flag of the bad action ids); 0 on the other tiers."""
-    return 0
-
-  def _take_bad_state_ids(self):
-    """Ids of render_states() outside the game's table (the state-table tier counts them under the
-    flag of render_frames()'s rows); 0 on the other tiers."""
-    return 0
-
-  def _take_bad_windows(self):
-    """(rows of render_frame_windows() outside the trace, state ids of render_state_windows()
-    outside the table): the state-table tier counts them under the flag of render_frames()'s rows;
-    (0, 0) on the other tiers."""
-    return 0, 0
+    # What the kernels count instead of stopping, in the order _raise_bad() words it: (device
+    # counter, view of the pinned flag it rides under, message taking the count and the id of the
+    # last action).  Action ids come first; the state-table tier adds its own (wide.WideGame).
+    self._lazy_errors = [
+        (self._bad, self._bad_flag_view,
+         '{} action ids are outside 0..{} (or came from rows that are not exactly one-hot)'),
+        (self._bad_idx, self._bad_idx_flag_view,
+         '{} rows of render_frames() named a frame or an environment outside the '
+         'trace (they were rendered from the nearest one inside)')]
 
   def _raise_bad(self, indices=False):
-    """One ValueError for everything the kernels counted: action ids outside 0..4, bad policy rows
-    met by rollout_policy() and - when their flag is up, or `indices` - rows of render_frames()
-    outside the trace.  Every counter is read before any is cleared, so none is lost to another's
-    error."""
-    n = int(self._bad.item())          # synchronises: we are about to raise anyway
-    rows = self._take_bad_indices() if indices or self._bad_idx_flag_view[0] else 0
-    policy_rows = self._take_bad_policy_rows()
-    state_ids = self._take_bad_state_ids()
-    plan_rows = self._take_bad_plan_rows()
-    visit_rows = self._take_bad_visit_rows()
-    window_rows, window_ids = self._take_bad_windows()
-    self._bad.zero_()
-    self._bad_flag_view[0] = 0
-    what = []
-    if n:
-      what.append('{} action ids are outside 0..{} (or came from rows that are not '
-                  'exactly one-hot)'.format(n, gamespec.N_ACTIONS - 1))
-    if policy_rows:
-      what.append('{} environment-frames of rollout_policy() met bad policy rows (a weight that is '
-                  'negative or NaN, or a sum that is not a positive finite number); they took '
-                  'action {}'.format(policy_rows, gamespec.N_ACTIONS - 1))
-    if rows:
-      what.append('{} rows of render_frames() named a frame or an environment outside the '
-                  'trace (they were rendered from the nearest one inside)'.format(rows))
-    if state_ids:
-      what.append('{} state ids of render_states() are outside the game\'s table (they were '
-                  'rendered as state 0)'.format(state_ids))
-    if plan_rows:
-      what.append('{} rows of the policy given to evaluate_policy() are bad (a weight that is '
-                  'negative or NaN, or a sum that is not a positive finite number); they were '
-                  'evaluated as taking action {}'.format(plan_rows, gamespec.N_ACTIONS - 1))
-    if visit_rows:
-      what.append('{} rows of the policy given to state_visitation() are bad (a weight that is '
-                  'negative or NaN, or a sum that is not a positive finite number); all their mass '
-                  'took action {}'.format(visit_rows, gamespec.N_ACTIONS - 1))
-    if window_rows:
-      what.append('{} rows of render_frame_windows() named a frame or an environment outside the '
-                  'trace (their windows were rendered from the nearest one inside)'.format(window_rows))
-    if window_ids:
-      what.append('{} state ids of render_state_windows() are outside the game\'s table (their '
-                  'windows were rendered as state 0\'s)'.format(window_ids))
+    """One ValueError for everything the kernels counted and went on from: `_lazy_errors`, in its
+    order.  The rows of render_frames() are read, and their flag cleared, when that flag is up or
+    `indices`; every other counter always.  Every counter is read before any is cleared, so none is
+    lost to another's error."""
+    errors = self._lazy_errors
+    counts = []
+    for counter, _, _ in errors:         # (the first read synchronises: we are about to raise anyway)
+      skip = counter is self._bad_idx and not (indices or self._bad_idx_flag_view[0])
+      counts.append(None if skip else int(counter.item()))
+    for (counter, flag, _), n in zip(errors, counts):
+      if n is not None:
+        counter.zero_()
+        if flag is self._bad_flag_view or counter is self._bad_idx:
+          flag[0] = 0
+    what = [text.format(n, gamespec.N_ACTIONS - 1) for (_, _, text), n in zip(errors, counts) if n]
     if what:
       raise ValueError('; '.join(what))
 
@@ -326,6 +277,13 @@ class FusedGame(object):
     if mode == 'sync':
       self._raise_bad()
     elif mode and (self._bad_flag_view[0] or self._bad_idx_flag_view[0]):
+      self._raise_bad()
+
+  def _after_index_launch(self):
+    """After a launch that counts under the flag of render_frames()'s rows: raise what is known."""
+    if self.validate_actions == 'sync':
+      self._raise_bad(indices=True)
+    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
       self._raise_bad()
 
   def _action_ids(self, actions, expect):
@@ -680,50 +638,6 @@ class FusedGame(object):
         'a policy can read: call Engine.use_state_table() before its_showtime() to run this game '
         'from its state table'.format(method))
 
-  def rollout_policy_buffers(self, T, want_states=True):
-    self._no_policy_rollouts('rollout_policy_buffers')
-
-  def rollout_policy(self, policy, T, seed=0, first_frame=None, reset_first=False, out=None,
-                     want_states=True):
-    """Closed-loop rollouts (`wide.WideGame.rollout_policy`): the state-table tier only."""
-    self._no_policy_rollouts('rollout_policy')
-
-  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
-    """Observations by state index (`wide.WideGame.render_states`): the state-table tier only."""
-    self._no_policy_rollouts('render_states')
-
-  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
-    """Observation windows (`wide.WideGame.render_frame_windows`): the state-table tier only."""
-    self._no_policy_rollouts('render_frame_windows')
-
-  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
-    """Observation windows (`wide.WideGame.render_trace_windows`): the state-table tier only."""
-    self._no_policy_rollouts('render_trace_windows')
-
-  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
-    """Observation windows (`wide.WideGame.render_state_windows`): the state-table tier only."""
-    self._no_policy_rollouts('render_state_windows')
-
-  def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
-    """Exact policy evaluation (`wide.WideGame.evaluate_policy`): the state-table tier only."""
-    self._no_policy_rollouts('evaluate_policy')
-
-  def value_iteration(self, gamma, sweeps, **kwargs):
-    """Value iteration (`wide.WideGame.value_iteration`): the state-table tier only."""
-    self._no_policy_rollouts('value_iteration')
-
-  def table_arrays(self):
-    """The game's table as tensors (`wide.WideGame.table_arrays`): the state-table tier only."""
-    self._no_policy_rollouts('table_arrays')
-
-  def state_visitation(self, policy, frames, **kwargs):
-    """Exact state visitation (`wide.WideGame.state_visitation`): the state-table tier only."""
-    self._no_policy_rollouts('state_visitation')
-
-  def visitation_buffers(self, frames, want_frames=False):
-    """The buffers of `state_visitation(out=...)`: the state-table tier only."""
-    self._no_policy_rollouts('visitation_buffers')
-
   def _gather_op(self, trace, t_idx, e_idx, out):
     _hip.ops.render_gather(self._spec_host, self._spec_dev, trace, t_idx, e_idx, out,
                            self._bad_idx, self._bad_idx_flag, GATHER_STREAMING)
@@ -775,10 +689,7 @@ class FusedGame(object):
     elif tuple(out.shape) != (N, L, H, W) or out.dtype not in _OBS_DTYPES or not out.is_contiguous():
       raise ValueError('out must be a contiguous int8 / float16 / bfloat16 [N, L, H, W] tensor')
     self._gather_op(trace, t_idx, e_idx, out)
-    if self.validate_actions == 'sync':
-      self._raise_bad(indices=True)
-    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
-      self._raise_bad()
+    self._after_index_launch()
     return out
 
   def rollout_deferred(self, actions, out, reset_first=False, actions_ready=False):
@@ -920,3 +831,7 @@ class FusedGame(object):
     self._deferred_rendered = False
     self.check_ok()
     return prev
+
+
+# (wide imports this module, and gives FusedGame its refusals of wide.STATE_TABLE_ONLY)
+from . import wide  # noqa: E402,F401

@@ -21,6 +21,7 @@ import torch
 
 from . import _hip
 from . import gamespec
+from . import wide
 from .rendering import Observation
 
 
@@ -185,40 +186,6 @@ class ShapeGame(object):
         'a policy can read (Engine.use_state_table() puts a game that can be tabulated there; the '
         'shape tier\'s games of translating multi-cell things cannot)'.format(method))
 
-  def rollout_policy_buffers(self, T, want_states=True):
-    self._no_policy_rollouts('rollout_policy_buffers')
-
-  def rollout_policy(self, policy, T, seed=0, first_frame=None, reset_first=False, out=None,
-                     want_states=True):
-    self._no_policy_rollouts('rollout_policy')
-
-  def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
-    self._no_policy_rollouts('render_states')
-
-  def render_frame_windows(self, trace, t_idx, e_idx, window, obs_dtype=torch.int8, out=None):
-    self._no_stored_trace('render_frame_windows')
-
-  def render_trace_windows(self, trace, window, obs_dtype=torch.int8, out=None):
-    self._no_stored_trace('render_trace_windows')
-
-  def render_state_windows(self, window, state_ids=None, obs_dtype=torch.int8, out=None):
-    self._no_policy_rollouts('render_state_windows')
-
-  def evaluate_policy(self, policy, gamma, sweeps, **kwargs):
-    self._no_policy_rollouts('evaluate_policy')
-
-  def value_iteration(self, gamma, sweeps, **kwargs):
-    self._no_policy_rollouts('value_iteration')
-
-  def table_arrays(self):
-    self._no_policy_rollouts('table_arrays')
-
-  def state_visitation(self, policy, frames, **kwargs):
-    self._no_policy_rollouts('state_visitation')
-
-  def visitation_buffers(self, frames, want_frames=False):
-    self._no_policy_rollouts('visitation_buffers')
-
   def rollout_trace_buffers(self, T):
     self._no_stored_trace('rollout_trace_buffers')
 
@@ -302,3 +269,8 @@ class ShapeGame(object):
     if validate:
       self._after_launch()
     return out
+
+
+# the windows of a stored trace are refused for the lack of one, the rest as the one-cell tier does
+wide.refuse_state_table_only(ShapeGame, {'render_frame_windows': '_no_stored_trace',
+                                         'render_trace_windows': '_no_stored_trace'})

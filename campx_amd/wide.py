@@ -26,6 +26,33 @@ from . import gamespec
 from . import tabulate
 
 
+# What this tier alone offers; the other batched tiers answer each of these with a
+# NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
+STATE_TABLE_ONLY = (
+    'rollout_policy_buffers', 'rollout_policy', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'value_iteration', 'visitation_buffers', 'state_visitation', 'render_states',
+    'render_frame_windows', 'render_trace_windows', 'render_state_windows')
+
+
+def refuse_state_table_only(tier, answers=None):
+  """Give the class of another batched tier a method for every name of STATE_TABLE_ONLY that raises
+  the tier's NotImplementedError with the name in it, whatever it is called with: through the tier's
+  `_no_policy_rollouts(name)`, or the method `answers` names for it."""
+  def refusal(name, answer):
+    def refuse(self, *args, **kwargs):
+      getattr(self, answer)(name)
+    refuse.__name__ = name
+    refuse.__qualname__ = '{}.{}'.format(tier.__name__, name)
+    refuse.__doc__ = '`wide.WideGame.{}`: the state-table tier only; raises NotImplementedError.'.format(name)
+    refuse.state_table_only = True
+    return refuse
+  for name in STATE_TABLE_ONLY:
+    setattr(tier, name, refusal(name, (answers or {}).get(name, '_no_policy_rollouts')))
+
+
+refuse_state_table_only(fused.FusedGame)       # (before WideGame overrides every one of them)
+
+
 class WideGame(fused.FusedGame):
 
   def __init__(self, engine, batch, device, traced):
@@ -116,6 +143,29 @@ class WideGame(fused.FusedGame):
     self._err_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
     self._err_flag_view = self._err_flag.numpy()
     self._init_gather()
+    # this tier's lazy errors, at their places in the order of the message (fused.FusedGame
+    # has the list): bad policy rows ride under the flag of the action ids, ids and rows of the
+    # state and window renders under that of render_frames()'s rows
+    bad_row = '(a weight that is negative or NaN, or a sum that is not a positive finite number)'
+    acts, idx = self._bad_flag_view, self._bad_idx_flag_view
+    self._lazy_errors.insert(1, (
+        self._bad_rows, acts,
+        '{} environment-frames of rollout_policy() met bad policy rows ' + bad_row + '; they took action {}'))
+    self._lazy_errors += [
+        (self._bad_state_ids, idx,
+         '{} state ids of render_states() are outside the game\'s table (they were rendered as state 0)'),
+        (self._bad_plan_rows, acts,
+         '{} rows of the policy given to evaluate_policy() are bad ' + bad_row +
+         '; they were evaluated as taking action {}'),
+        (self._bad_visit_rows, acts,
+         '{} rows of the policy given to state_visitation() are bad ' + bad_row +
+         '; all their mass took action {}'),
+        (self._bad_window_rows, idx,
+         '{} rows of render_frame_windows() named a frame or an environment outside the trace (their '
+         'windows were rendered from the nearest one inside)'),
+        (self._bad_window_ids, idx,
+         '{} state ids of render_state_windows() are outside the game\'s table (their windows were '
+         'rendered as state 0\'s)')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -183,11 +233,6 @@ class WideGame(fused.FusedGame):
     """States of the game's table: the rows of a `rollout_policy()` policy."""
     return int(self.spec.n_states)
 
-  def _take_bad_policy_rows(self):
-    n = int(self._bad_rows.item())
-    self._bad_rows.zero_()
-    return n
-
   def _check_policy(self, policy):
     S = self.n_states
     if (not torch.is_tensor(policy) or policy.dtype != torch.float32 or policy.dim() != 2
@@ -197,6 +242,45 @@ class WideGame(fused.FusedGame):
              if torch.is_tensor(policy) else type(policy).__name__)
       raise ValueError('policy must be a contiguous float32 [{}, {}] tensor (n_states x actions) '
                        'on {}, got {}'.format(S, gamespec.N_ACTIONS, self.device, got))
+
+  def _tensor_ok(self, t, dtype, shape):
+    return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape
+            and t.device == self.device and t.is_contiguous())
+
+  @staticmethod
+  def _check_count(name, n):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
+      raise ValueError('{0} must be an int, 1 <= {0} <= 2^20, got {1!r}'.format(name, n))
+
+  def _planned_path(self, path, plan_fn, *args):
+    """The path (1 LDS, 2 global) a planning call takes: `path` checked, then what the library's
+    plan function says for this table."""
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    plan = (ctypes.c_int64 * 4)()
+    if plan_fn(self.n_states, *(args + (_hip.config_get('wide_lds_max'), path, plan))) != 0:
+      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
+                       '(library setting wide_lds_max); use path=0 or path=2'.format(self.n_states))
+    return int(plan[0])
+
+  def _check_out(self, out, want, made_by):
+    """`out` holds every (key, dtype, shape) of `want`, as the dict `made_by` allocates does."""
+    if not isinstance(out, dict) or any(not self._tensor_ok(out.get(k), d, sh) for k, d, sh in want):
+      raise ValueError('out must be a dict from {} of this game: {}'.format(
+          made_by, ', '.join('{!r} {} {}'.format(k, d, list(sh)) for k, d, sh in want)))
+
+  def _check_state_ids(self, state_ids):
+    """(ids, N) of a `state_ids` argument: (None, n_states) for None - all states."""
+    if state_ids is None:
+      return None, self.n_states
+    ids = state_ids
+    if (not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1
+        or ids.numel() < 1 or ids.device != self.device):
+      got = ('{} {} on {}'.format(ids.dtype, list(ids.shape), ids.device)
+             if torch.is_tensor(ids) else type(ids).__name__)
+      raise ValueError('state_ids must be an int32 or int64 [N] tensor on {}, N >= 1 (or None for '
+                       'all {} states), got {}'.format(self.device, self.n_states, got))
+    return ids.contiguous(), int(ids.numel())
 
   def rollout_policy_buffers(self, T, want_states=True):
     """Allocate the dict of `rollout_policy(out=...)` once: `rollout_trace_buffers(T)` plus
@@ -274,11 +358,6 @@ class WideGame(fused.FusedGame):
 
   # ------------------------------------------------------------ planning on the table
 
-  def _take_bad_plan_rows(self):
-    n = int(self._bad_plan_rows.item())
-    self._bad_plan_rows.zero_()
-    return n
-
   def table_arrays(self):
     """The game's table - its complete, deterministic MDP - decoded from the blob the kernels
     walk, as device tensors `[n_states, 5]`, each entry as a rollout reports the frame that takes
@@ -288,8 +367,8 @@ class WideGame(fused.FusedGame):
     n = S * A
     entries = self._tables[:n * 8].view(torch.int32).view(S, A, 2)
     word = entries[..., 1]
-    done = (word >> 24) & 1
-    code = ((word >> 25) & 15).long()
+    done = (word >> _hip.ENTRY_DONE_SHIFT) & 1
+    code = ((word >> _hip.ENTRY_DCODE_SHIFT) & _hip.ENTRY_DCODE_MASK).long()
     listed = torch.tensor([float(x) for x in self.spec.discount_list], dtype=torch.float32,
                           device=self.device)
     plain = torch.where(done != 0, torch.zeros((), device=self.device),
@@ -299,7 +378,7 @@ class WideGame(fused.FusedGame):
       perf = self._tables[perf_off:perf_off + n].view(torch.int8).view(S, A).clone()
     else:
       perf = torch.zeros((S, A), dtype=torch.int8, device=self.device)
-    return {'next_state': (word & 0xffffff).contiguous(),
+    return {'next_state': (word & _hip.ENTRY_NEXT_MASK).contiguous(),
             'reward': entries[..., 0].contiguous().view(torch.float32),
             'done': done.to(torch.uint8),
             'discount': torch.where(code != 0, listed[code], plain),
@@ -323,20 +402,14 @@ class WideGame(fused.FusedGame):
   def _sweeps(self, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path):
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
     greedy = policy is None
-
-    def tensor_ok(t, dtype, shape):
-      return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape
-              and t.device == dev and t.is_contiguous())
-
     if (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
         or abs(gamma) > torch.finfo(torch.float32).max):
       raise ValueError('gamma must be a finite number (as a float32), got {!r}'.format(gamma))
-    if isinstance(sweeps, bool) or not isinstance(sweeps, int) or not 1 <= sweeps <= 1 << 20:
-      raise ValueError('sweeps must be an int, 1 <= sweeps <= 2^20, got {!r}'.format(sweeps))
-    if values is not None and not tensor_ok(values, torch.float32, (S,)):
+    self._check_count('sweeps', sweeps)
+    if values is not None and not self._tensor_ok(values, torch.float32, (S,)):
       raise ValueError('values must be a contiguous float32 [{}] tensor (n_states) on {}, or '
                        'None for zeros'.format(S, dev))
-    if reward is not None and not tensor_ok(reward, torch.float32, (S, A)):
+    if reward is not None and not self._tensor_ok(reward, torch.float32, (S, A)):
       raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
                        '{}, or None for the table\'s own'.format(S, A, dev))
     if tol is not None and (isinstance(tol, bool) or not isinstance(tol, (int, float))
@@ -344,15 +417,10 @@ class WideGame(fused.FusedGame):
       raise ValueError('tol must be a finite number >= 0 or None, got {!r}'.format(tol))
     if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
       raise ValueError('check_every must be an int >= 1, got {!r}'.format(check_every))
-    if path not in (0, 1, 2):
-      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
-    plan = (ctypes.c_int64 * 4)()
-    if _hip.lib.campx_wide_sweeps_plan(S, 0 if greedy else 1, 0 if reward is None else 1,
-                                       _hip.config_get('wide_lds_max'), path, plan) != 0:
-      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
-                       '(library setting wide_lds_max); use path=0 or path=2'.format(S))
+    planned = self._planned_path(path, _hip.lib.campx_wide_sweeps_plan, 0 if greedy else 1,
+                                 0 if reward is None else 1)
     want = [('values', torch.float32, (S,)), ('residual', torch.float32, (sweeps,))]
-    if plan[0] == 2:
+    if planned == 2:
       want.append(('scratch', torch.float32, (S,)))
     if want_q:
       want.append(('q', torch.float32, (S, A)))
@@ -361,10 +429,8 @@ class WideGame(fused.FusedGame):
     if out is None:
       out = self.sweep_buffers(sweeps, want_q, greedy)
     else:
-      if not isinstance(out, dict) or any(not tensor_ok(out.get(k), d, sh) for k, d, sh in want):
-        raise ValueError('out must be a dict from sweep_buffers({}, want_q={}, greedy={}) of this '
-                         'game: {}'.format(sweeps, bool(want_q), greedy,
-                                           ', '.join('{!r} {} {}'.format(k, d, list(sh)) for k, d, sh in want)))
+      self._check_out(out, want, 'sweep_buffers({}, want_q={}, greedy={})'.format(
+          sweeps, bool(want_q), greedy))
       if values is not None and out.get('scratch') is not None and \
           values.data_ptr() == out['scratch'].data_ptr():
         raise ValueError('values must not be out[\'scratch\']')
@@ -460,11 +526,6 @@ class WideGame(fused.FusedGame):
 
   VISIT_UNIT = 1 << 38             # one environment, in the int64 units of state_visitation()
 
-  def _take_bad_visit_rows(self):
-    n = int(self._bad_visit_rows.item())
-    self._bad_visit_rows.zero_()
-    return n
-
   def visitation_buffers(self, frames, want_frames=False):
     """Allocate the dict of `state_visitation(out=...)` once: 'visits' int64 [S, 5], 'finished'
     int64 [frames], 'final' int64 [S], 'counts' int32 [S, 5], 'scratch' int64 [S] (the second mass
@@ -534,19 +595,8 @@ class WideGame(fused.FusedGame):
     self._check_policy(policy)
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
     unit = self.VISIT_UNIT
-
-    def tensor_ok(t, dtype, shape):
-      return (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == shape
-              and t.device == dev and t.is_contiguous())
-
-    if isinstance(frames, bool) or not isinstance(frames, int) or not 1 <= frames <= 1 << 20:
-      raise ValueError('frames must be an int, 1 <= frames <= 2^20, got {!r}'.format(frames))
-    if path not in (0, 1, 2):
-      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
-    plan = (ctypes.c_int64 * 4)()
-    if _hip.lib.campx_wide_visit_plan(S, _hip.config_get('wide_lds_max'), path, plan) != 0:
-      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
-                       '(library setting wide_lds_max); use path=0 or path=2'.format(S))
+    self._check_count('frames', frames)
+    planned = self._planned_path(path, _hip.lib.campx_wide_visit_plan)
     if start is not None:
       if (not torch.is_tensor(start) or tuple(start.shape) != (S,) or start.device != dev
           or not (start.dtype == torch.int64 or start.is_floating_point())):
@@ -569,17 +619,15 @@ class WideGame(fused.FusedGame):
           raise ValueError('a float start sums to more than 1 by more than its largest entry')
     want = [('visits', torch.int64, (S, A)), ('finished', torch.int64, (frames,)),
             ('final', torch.int64, (S,)), ('counts', torch.int32, (S, A))]
-    if plan[0] == 2:
+    if planned == 2:
       want.append(('scratch', torch.int64, (S,)))
     if want_frames:
       want.append(('per_frame', torch.int64, (frames + 1, S)))
     if out is None:
       out = self.visitation_buffers(frames, want_frames)
     else:
-      if not isinstance(out, dict) or any(not tensor_ok(out.get(k), d, sh) for k, d, sh in want):
-        raise ValueError('out must be a dict from visitation_buffers({}, want_frames={}) of this '
-                         'game: {}'.format(frames, bool(want_frames),
-                                           ', '.join('{!r} {} {}'.format(k, d, list(sh)) for k, d, sh in want)))
+      self._check_out(out, want, 'visitation_buffers({}, want_frames={})'.format(
+          frames, bool(want_frames)))
       if start is not None and out.get('scratch') is not None and \
           start.data_ptr() == out['scratch'].data_ptr():
         raise ValueError('start must not be out[\'scratch\']')
@@ -598,11 +646,6 @@ class WideGame(fused.FusedGame):
     return res
 
   # ------------------------------------------------------------ observations by state
-
-  def _take_bad_state_ids(self):
-    n = int(self._bad_state_ids.item())
-    self._bad_state_ids.zero_()
-    return n
 
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """The observations of states of the game's table, `[N, L, H, W]`: what a network that is
@@ -625,18 +668,7 @@ class WideGame(fused.FusedGame):
           with the game).
     """
     L, H, W = self.n_layers, self.rows, self.cols
-    if state_ids is None:
-      ids, N = None, self.n_states
-    else:
-      ids = state_ids
-      if (not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1
-          or ids.numel() < 1 or ids.device != self.device):
-        got = ('{} {} on {}'.format(ids.dtype, list(ids.shape), ids.device)
-               if torch.is_tensor(ids) else type(ids).__name__)
-        raise ValueError('state_ids must be an int32 or int64 [N] tensor on {}, N >= 1 (or None for '
-                         'all {} states), got {}'.format(self.device, self.n_states, got))
-      ids = ids.contiguous()
-      N = int(ids.numel())
+    ids, N = self._check_state_ids(state_ids)
     scratch = None
     if out is None:
       if obs_dtype not in fused._OBS_DTYPES:
@@ -654,19 +686,10 @@ class WideGame(fused.FusedGame):
       scratch = self._states_scratch[-1]
     _hip.ops.wide_render_states(self._spec_host, self._tables, ids, out, scratch,
                                 self._bad_state_ids, self._bad_idx_flag)
-    if self.validate_actions == 'sync':
-      self._raise_bad(indices=True)
-    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
-      self._raise_bad()
+    self._after_index_launch()
     return out
 
   # ------------------------------------------------------------ observation windows
-
-  def _take_bad_windows(self):
-    rows, ids = int(self._bad_window_rows.item()), int(self._bad_window_ids.item())
-    self._bad_window_rows.zero_()
-    self._bad_window_ids.zero_()
-    return rows, ids
 
   def _window_table(self):
     """uint8 [variants, 1024] on the device: the scenery's layer per cell of each variant, from
@@ -713,10 +736,7 @@ class WideGame(fused.FusedGame):
         window.height, window.width, where.thing, where.r0, where.c0, where.pad_layer,
         self._bad_window_ids if source == _hip.WINDOWS_STATES else self._bad_window_rows,
         self._bad_idx_flag, fused.GATHER_STREAMING)
-    if self.validate_actions == 'sync':
-      self._raise_bad(indices=True)
-    elif self.validate_actions and (self._bad_idx_flag_view[0] or self._bad_flag_view[0]):
-      self._raise_bad()
+    self._after_index_launch()
     return out
 
   def _check_window_trace(self, trace):
@@ -784,18 +804,7 @@ class WideGame(fused.FusedGame):
       out: a contiguous `[N, L, h, w]` tensor of such a dtype to write into (no allocation, no
           synchronisation: capturable in a HIP graph).
     """
-    if state_ids is None:
-      ids, N = None, self.n_states
-    else:
-      ids = state_ids
-      if (not torch.is_tensor(ids) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1
-          or ids.numel() < 1 or ids.device != self.device):
-        got = ('{} {} on {}'.format(ids.dtype, list(ids.shape), ids.device)
-               if torch.is_tensor(ids) else type(ids).__name__)
-        raise ValueError('state_ids must be an int32 or int64 [N] tensor on {}, N >= 1 (or None for '
-                         'all {} states), got {}'.format(self.device, self.n_states, got))
-      ids = ids.contiguous()
-      N = int(ids.numel())
+    ids, N = self._check_state_ids(state_ids)
     return self._windows('render_state_windows', _hip.WINDOWS_STATES, window, None, ids, None,
                          (N,), obs_dtype, out)
 

@@ -39,7 +39,7 @@ def run(iterations=60, frames=64, gamma=0.9, lr=4.0, device='cuda', log=None):
   theta = torch.zeros((S, 5), dtype=torch.float64, device=device)
   weight = gamma ** torch.arange(frames, dtype=torch.float64, device=device)
   visit_out = game.visitation_buffers(frames, want_frames=True)
-  sweep_out = game.fused.sweep_buffers(frames, greedy=False)
+  sweep_out = game.sweep_buffers(frames, greedy=False)
   history = []
   for it in range(iterations + 1):
     pi = torch.softmax(theta, dim=1)
