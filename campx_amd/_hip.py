@@ -32,6 +32,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_tables_build', 'campx_wide_reset_launch', 'campx_wide_rollout_launch',
            'campx_wide_rules_size', 'campx_wide_enumerate_launch',
            'campx_wide_update_launch', 'campx_wide_policy_update_launch',
+           'campx_wide_policy_population_launch', 'campx_wide_population_plan',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
@@ -222,6 +223,11 @@ def _load():
   lib.campx_wide_policy_update_launch.restype = i32
   lib.campx_wide_policy_update_launch.argtypes = [wide_p, vp, CampxState, vp, ctypes.c_uint64, i64,
                                                   CampxOutputs, vp, vp, i64, i32, i32, vp]
+  lib.campx_wide_policy_population_launch.restype = i32
+  lib.campx_wide_policy_population_launch.argtypes = [wide_p, vp, CampxState, vp, ctypes.c_uint64, i64,
+                                                      CampxOutputs, vp, vp, i64, i32, i32, i64, i32, vp]
+  lib.campx_wide_population_plan.restype = i32
+  lib.campx_wide_population_plan.argtypes = [i64, i32, i64, i64, i64, i32, ctypes.POINTER(i64)]
   lib.campx_render_gather_launch.restype = i32
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
@@ -303,7 +309,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'wide_policy_update', 'render_gather', 'wide_render_gather', 'wide_render_states',
+            'wide_update', 'wide_policy_update', 'wide_policy_population', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
 
 

@@ -16,6 +16,7 @@
 //   campx::wide_update              the wide tier's update pass alone (trace-only rollouts)
 //   campx::wide_policy_update       the same with every frame's action sampled on the device from a
 //                                   policy over the game's states (closed-loop rollouts)
+//   campx::wide_policy_population   wide_policy_update for P policies, each over its block of environments
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -777,6 +778,46 @@ void wide_policy_update(const Tensor& spec_host, const Tensor& tables, Tensor& s
            "campx_wide_policy_update_launch");
 }
 
+// Wide tier, closed loop for a population (campx_wide_policy_population_launch): campx::wide_policy_update
+// with `policy` float32 [P, n_states, 5], environment e sampling member e / (B / P); `states_out`
+// holds the flat row member * n_states + state.  `path`: 0 chosen by arithmetic, 1 LDS, 2 global.
+void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                            const OptTensor& ret, const Tensor& policy, int64_t seed,
+                            int64_t first_frame, const OptTensor& reward, const OptTensor& discount,
+                            const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
+                            Tensor& actions_out, const OptTensor& states_out,
+                            const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                            int64_t path) {
+  const char* what = "campx::wide_policy_population";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  TORCH_CHECK(policy.dim() == 3 && policy.size(0) >= 1, what,
+              ": policy must be float32 [P, n_states, 5] with P >= 1");
+  const int64_t P = policy.size(0);
+  want(policy, "policy", at::kFloat, g.dev, {P, (int64_t)g.hs->n_states, (int64_t)CAMPX_N_ACTIONS});
+  TORCH_CHECK(g.B % P == 0, what, ": the ", g.B, " environments do not split into ", P,
+              " equal blocks");
+  TORCH_CHECK(P * (int64_t)g.hs->n_states < (1ll << 31), what, ": P * n_states must be below 2^31");
+  TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  TORCH_CHECK(trace.dim() == 3, what, ": trace must be int16 [K, T, B]");
+  const int64_t T = trace.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff, what, ": bad frame count");
+  int64_t pitch = 0;
+  want_trace(trace, at::kShort, g.dev, g.K, T, g.B, pitch);
+  want_rows(actions_out, "actions_out", at::kChar, g.dev, T, g.B, pitch);
+  if (states_out.has_value()) want_rows(*states_out, "states_out", at::kInt, g.dev, T, g.B, pitch);
+  CampxOutputs out{};
+  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
+  out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_policy_population_launch(
+               g.hs, g.tables, g.state, reinterpret_cast<const float*>(policy.data_ptr()),
+               (uint64_t)seed, first_frame, out, reinterpret_cast<int8_t*>(actions_out.data_ptr()),
+               opt_ptr<int32_t>(states_out), g.B, (int32_t)T, reset_first ? 1 : 0, P, (int32_t)path,
+               current_stream()),
+           "campx_wide_policy_population_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1221,7 +1262,8 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 // Every op, for the two boxed kernels (campx_amd/_hip.py OP_NAMES is the Python side's list).
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
-    "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "render_gather",
+    "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
+    "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
     "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids", "check_actions"};
 
@@ -1283,6 +1325,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(i!) actions_out, Tensor(j!)? states_out, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, "
       "bool reset_first) -> ()");
   m.def(
+      "wide_policy_population(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor policy, int seed, int first_frame, Tensor(d!)? reward, "
+      "Tensor(e!)? discount, Tensor(f!)? step_done, Tensor(g!)? perf, Tensor(h!) trace, "
+      "Tensor(i!) actions_out, Tensor(j!)? states_out, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, "
+      "bool reset_first, int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1331,6 +1379,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_rollout", &wide_rollout);
   m.impl("wide_update", &wide_update);
   m.impl("wide_policy_update", &wide_policy_update);
+  m.impl("wide_policy_population", &wide_policy_population);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

@@ -11,6 +11,9 @@
 // THRESHOLDS (the sums are taken once per state when the table is staged in LDS, not once per
 // frame), then the entry of (state, action) as before.  The random words do not depend on the
 // state: both blocks of a chunk of eight frames are computed before its chain starts.
+//
+// k_population.hip holds this kernel's twin for a population of policies - the same frame loop with
+// two per-lane constants added.  A change to the sampling or to the chunk logic here is made there too.
 
 #include "wide_table.hip.h"
 
@@ -29,25 +32,6 @@ struct PolicyParams {
   int64_t plane;               // entries from one plane of the trace to the next (T x row pitch)
   int64_t first_frame;         // absolute number of the launch's frame 0
 };
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t* out) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0;
-  out[1] = c1;
-  out[2] = c2;
-  out[3] = c3;
-}
 
 // kLds: the state table AND the thresholds sit in LDS; else both are read through L1 / L2 (the
 // thresholds are then summed from the weights at every frame).  kStates: the row each frame

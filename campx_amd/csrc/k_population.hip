@@ -1,0 +1,334 @@
+// k_population.hip - closed-loop rollouts of a POPULATION of policies in one launch: the walk of
+// k_policy.hip (a lane per environment, every frame's action sampled on the chain) with the B
+// environments split into P equal contiguous blocks, block m sampling policies[m]: environment e
+// reads row policies[e / n][state], n = B / P.  Same sampling rule, same Philox counter (absolute
+// environment, absolute frame >> 2): with P = 1 the launch writes what k_policy.hip's writes.
+//
+// A lane works its member out once, before the frame loop; the frame loop then differs from the
+// sibling's in two per-lane constants only - where the member's thresholds start, and what is
+// added to the state that goes to `states_out` (the flat row m * S + state).  On the LDS path a
+// workgroup stages, beside the table, the thresholds of just the members its 256 environments
+// belong to (m_lo .. m_hi, rows [m - m_lo][state][5] - a contiguous piece of the policy tensor),
+// so the dependent chain stays state -> thresholds -> entry -> state with nothing read from global
+// memory inside the loop.
+
+#include "wide_table.hip.h"
+
+#include <type_traits>
+
+namespace campx_impl {
+
+constexpr int kPopThreads = 256;
+constexpr int kPopChunk = 8;        // frames per chunk: two Philox blocks
+
+struct PopulationParams {
+  int32_t n_states, n_planes;
+  int32_t has_dcodes;          // some entry of the table carries a discount code
+  uint32_t key0, key1;         // seed & 0xffffffff, seed >> 32
+  uint32_t envs_per_member;    // n = B / P
+  float discounts[16];
+  int64_t plane;               // entries from one plane of the trace to the next (T x row pitch)
+  int64_t first_frame;         // absolute number of the launch's frame 0
+};
+
+// What a launch takes: campx_wide_population_plan()'s four words.
+struct PopulationPlan {
+  int32_t path;                // 1 table and thresholds in LDS, 2 through L1 / L2
+  int64_t lds_bytes;
+  int32_t threads;
+  int64_t members_per_block;   // distinct members among one workgroup's environments, at most
+};
+
+// The largest number of members any workgroup of kPopThreads consecutive environments touches,
+// exactly.  A workgroup that starts r environments into a member and holds L of them touches
+// (r + L - 1) / n + 1.  n >= 256: at most two, and two exactly when a member boundary lies inside a
+// workgroup - the first one, at n, does unless n is a multiple of 256 (then none does).  n < 256:
+// r = 256 b mod n repeats after at most n workgroups, so the first 256 and the last, which may be
+// short, are all there is to look at.
+inline int64_t members_per_block(int64_t B, int64_t P) {
+  const int64_t n = B / P;
+  if (n >= kPopThreads) return (P > 1 && n % kPopThreads != 0) ? 2 : 1;
+  const int64_t blocks = (B + kPopThreads - 1) / kPopThreads;
+  int64_t most = 1;
+  auto look = [&](int64_t b) {
+    const int64_t a = b * kPopThreads, last = (a + kPopThreads < B ? a + kPopThreads : B) - 1;
+    const int64_t count = last / n - a / n + 1;
+    if (count > most) most = count;
+  };
+  for (int64_t b = 0; b < blocks && b < kPopThreads; ++b) look(b);
+  look(blocks - 1);
+  return most;
+}
+
+inline int32_t plan_population(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
+                               int32_t path, PopulationPlan* p, int64_t* plan_out) {
+  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || (has_perf & ~1) || B < 1 || B > 0xffffffffll || P < 1 ||
+      B % P != 0 || P * S >= (1ll << 31) || lds_max < 0 || path < 0 || path > 2)
+    return CAMPX_EINVAL;
+  const int64_t n_entries = S * CAMPX_N_ACTIONS;
+  p->members_per_block = members_per_block(B, P);
+  // the sibling's table bytes - entries, the states' cells, the hidden performance - and the
+  // thresholds of the staged members, five floats per state each
+  const int64_t want = up16(n_entries * (int64_t)sizeof(uint2)) + S * (int64_t)sizeof(u32x4) +
+                       (has_perf ? up16(n_entries) : 0) +
+                       p->members_per_block * n_entries * (int64_t)sizeof(float);
+  const bool fits = want <= lds_max;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
+  p->lds_bytes = p->path == 1 ? want : 0;
+  p->threads = kPopThreads;
+  if (plan_out) {
+    plan_out[0] = p->path;
+    plan_out[1] = p->lds_bytes;
+    plan_out[2] = p->threads;
+    plan_out[3] = p->members_per_block;
+  }
+  return CAMPX_OK;
+}
+
+// kLds: the state table AND the thresholds of the workgroup's members sit in LDS; else both are
+// read through L1 / L2 (the thresholds are then summed from the weights at every frame).
+// kStates: the flat row each frame sampled from is written out.
+template <bool kLds, bool kPerf, bool kStates>
+__global__ __launch_bounds__(kPopThreads) void wide_policy_population_kernel(
+    PopulationParams pp, const uint2* __restrict__ g_entries, const u32x4* __restrict__ g_cells,
+    const int8_t* __restrict__ g_perf, const float* __restrict__ g_policy,
+    int32_t* __restrict__ state, CampxState st, CampxOutputs out,
+    int8_t* __restrict__ actions_out, int32_t* __restrict__ states_out, int64_t B, int32_t T,
+    int32_t reset_first) {
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_tables[];
+  __shared__ float discounts[16];
+  const int S = pp.n_states, n_entries = S * CAMPX_N_ACTIONS, K = pp.n_planes;
+  const int64_t env = (int64_t)blockIdx.x * kPopThreads + threadIdx.x;
+  // The lane's member: one division per lane.  (A lane past the batch staged with the others and
+  // leaves below; it is given the last environment's member so that nothing it forms is out of range.)
+  const uint32_t n = pp.envs_per_member;
+  const uint32_t m = (uint32_t)(env < B ? env : B - 1) / n;
+  const uint2* entries = g_entries;
+  const u32x4* cells = g_cells;
+  const int8_t* perf_tab = g_perf;
+  // the thresholds (LDS) or the weights (global) of the lane's member, row 0
+  const float* rows = g_policy + (int64_t)m * n_entries;
+  if (kLds) {
+    uint2* l_entries = lds_tables;
+    u32x4* l_cells = reinterpret_cast<u32x4*>(l_entries + n_entries + (n_entries & 1));   // 16-byte aligned
+    int8_t* l_perf = reinterpret_cast<int8_t*>(l_cells + S);
+    float* l_thr = reinterpret_cast<float*>(l_perf + (kPerf ? (n_entries + 15) & ~15 : 0));
+    // the members of this workgroup's environments: uniform, one division each
+    const int64_t env_lo = (int64_t)blockIdx.x * kPopThreads;
+    const int64_t env_hi = (env_lo + kPopThreads < B ? env_lo + kPopThreads : B) - 1;
+    const uint32_t m_lo = (uint32_t)env_lo / n, m_hi = (uint32_t)env_hi / n;
+    const int staged = (int)(m_hi - m_lo + 1) * S;           // rows; the host sized the LDS for them
+    const float* g_rows = g_policy + (int64_t)m_lo * n_entries;
+    for (int i = threadIdx.x; i < n_entries; i += kPopThreads) l_entries[i] = g_entries[i];
+    for (int i = threadIdx.x; i < S; i += kPopThreads) l_cells[i] = g_cells[i];
+    if (kPerf)
+      for (int i = threadIdx.x; i < n_entries; i += kPopThreads) l_perf[i] = g_perf[i];
+    for (int i = threadIdx.x; i < staged; i += kPopThreads) {
+      float c[5];
+      policy_thresholds(g_rows + (int64_t)i * CAMPX_N_ACTIONS, c);
+#pragma unroll
+      for (int k = 0; k < 5; ++k) l_thr[i * CAMPX_N_ACTIONS + k] = c[k];
+    }
+    entries = l_entries;
+    cells = l_cells;
+    perf_tab = l_perf;
+    rows = l_thr + (m - m_lo) * (uint32_t)n_entries;
+  }
+  if (threadIdx.x < 16) discounts[threadIdx.x] = pp.discounts[threadIdx.x];
+  __syncthreads();
+
+  if (env >= B) return;
+  const int32_t row0 = (int32_t)(m * (uint32_t)S);     // flat row of the member's state 0: P * S < 2^31
+  uint32_t now = 0;
+  int over = 0;
+  float ret = 0.0f;
+  if (!reset_first) {
+    now = (uint32_t)state[env];
+    now = now < (uint32_t)S ? now : 0u;      // (a state index from outside: start over)
+    over = st.done[env];
+    if (st.ret) ret = st.ret[env];
+  }
+  uint32_t from = over ? 0u : now;
+  uint16_t* trace = reinterpret_cast<uint16_t*>(out.trace);
+  const int64_t pitch = row_pitch(out, B), plane = pp.plane;
+  int bad = 0;
+  // Chunks start on a multiple of four ABSOLUTE frames, as in wide_policy_update_kernel: frame j
+  // of a chunk takes word j & 3 of block j >> 2 whatever first_frame is.
+  const int lead = (int)(pp.first_frame & 3);
+  const uint64_t group0 = (uint64_t)(pp.first_frame - lead) >> 2;
+  int64_t at = env - (int64_t)lead * pitch;        // element (frame, env) of the [T, pitch] streams
+  // One chunk of frames.  `plain_tag`: 0 = the general chunk (any frame may lie outside the launch,
+  // any stream may be missing, discount codes); k = 1 .. 8 = a whole chunk of a game with k planes,
+  // no test inside.
+  auto chunk = [&](auto plain_tag, int t0) {
+    constexpr int kThings = decltype(plain_tag)::value;
+    constexpr bool kPlain = kThings > 0;
+    uint32_t x[kPopChunk];
+    const uint64_t g = group0 + (uint64_t)((t0 + lead) >> 2);
+    philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 0u, pp.key0, pp.key1, x);
+    philox4x32_10((uint32_t)env, (uint32_t)(g + 1), (uint32_t)((g + 1) >> 32), 0u, pp.key0, pp.key1,
+                  x + 4);
+#pragma unroll
+    for (int j = 0; j < kPopChunk; ++j) {
+      if (kPlain || (t0 + j >= 0 && t0 + j < T)) {
+        float c[5];
+        if (kLds) {
+#pragma unroll
+          for (int k = 0; k < 5; ++k) c[k] = rows[from * CAMPX_N_ACTIONS + k];
+        } else {
+          policy_thresholds(rows + from * CAMPX_N_ACTIONS, c);
+        }
+        const float u = (float)(x[j] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
+        const float r = u * c[4];
+        const uint32_t a = (uint32_t)(r >= c[0]) + (uint32_t)(r >= c[1]) + (uint32_t)(r >= c[2]) +
+                           (uint32_t)(r >= c[3]);
+        bad += c[4] == 0.0f;
+        actions_out[at] = (int8_t)a;
+        if (kStates) states_out[at] = row0 + (int32_t)from;
+        const uint32_t idx = from * CAMPX_N_ACTIONS + a;
+        const uint2 e = entries[idx];
+        now = entry_next(e.y);
+        const uint32_t done = entry_done(e.y), dcode = entry_dcode(e.y);
+        from = done ? 0u : now;                      // the chain: state -> thresholds -> entry -> state
+        const u32x4 cs = cells[now];                 // where things show in the state reached
+        trace[at] = (uint16_t)cs.x;
+        if (kPlain) {
+          const uint32_t w[4] = {cs.x, cs.y, cs.z, cs.w};
+#pragma unroll
+          for (int d = 1; d < kThings; ++d)
+            trace[at + d * plane] = (uint16_t)(w[d >> 1] >> (16 * (d & 1)));
+        }
+        if (!kPlain && K > 1) {
+          uint16_t* tk = trace + at + plane;
+          tk[0] = (uint16_t)(cs.x >> 16);
+          if (K > 2) tk[plane] = (uint16_t)cs.y;
+          if (K > 3) tk[2 * plane] = (uint16_t)(cs.y >> 16);
+          if (K > 4) tk[3 * plane] = (uint16_t)cs.z;
+          if (K > 5) tk[4 * plane] = (uint16_t)(cs.z >> 16);
+          if (K > 6) tk[5 * plane] = (uint16_t)cs.w;
+          if (K > 7) tk[6 * plane] = (uint16_t)(cs.w >> 16);
+        }
+        if (kPlain) {
+          out.reward[at] = __uint_as_float(e.x);
+          out.discount[at] = done ? 0.0f : 1.0f;
+          out.done[at] = (uint8_t)done;
+        } else {
+          if (out.reward) out.reward[at] = __uint_as_float(e.x);
+          if (out.discount) out.discount[at] = __uint_as_float(discount_bits(discounts, dcode, done));
+          if (out.done) out.done[at] = (uint8_t)done;
+        }
+        if (kPerf && out.perf) out.perf[at] = perf_tab[idx];
+        ret = (over ? 0.0f : ret) + real_reward(__uint_as_float(e.x));
+        over = (int)done;
+      }
+      at += pitch;
+    }
+  };
+  const bool plain = !pp.has_dcodes && out.reward && out.discount && out.done &&
+                     (!kPerf || out.perf);
+  for (int t0 = -lead; t0 < T; t0 += kPopChunk) {
+    if (plain && t0 >= 0 && t0 + kPopChunk <= T) {
+      switch (K) {      // (one uniform branch per chunk of eight frames)
+        case 1: chunk(std::integral_constant<int, 1>{}, t0); break;
+        case 2: chunk(std::integral_constant<int, 2>{}, t0); break;
+        case 3: chunk(std::integral_constant<int, 3>{}, t0); break;
+        case 4: chunk(std::integral_constant<int, 4>{}, t0); break;
+        case 5: chunk(std::integral_constant<int, 5>{}, t0); break;
+        case 6: chunk(std::integral_constant<int, 6>{}, t0); break;
+        case 7: chunk(std::integral_constant<int, 7>{}, t0); break;
+        default: chunk(std::integral_constant<int, 8>{}, t0); break;
+      }
+    } else {
+      chunk(std::integral_constant<int, 0>{}, t0);
+    }
+  }
+  state[env] = (int32_t)now;
+  st.done[env] = (uint8_t)over;
+  if (st.ret) st.ret[env] = ret;
+  report_bad(out.bad_count, out.bad_flag, bad);      // (bad ROWS, on the rollout's counter)
+}
+
+}  // namespace campx_impl
+
+using namespace campx_impl;
+
+extern "C" {
+
+int32_t campx_wide_population_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t n_members,
+                                   int64_t wide_lds_max, int32_t path, int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  PopulationPlan plan;
+  return plan_population(n_states, has_perf, B, n_members, wide_lds_max, path, &plan, plan_out);
+}
+
+int32_t campx_wide_policy_population_launch(const CampxWideSpec* s, const void* tables_dev,
+                                            CampxState st, const float* policy, uint64_t seed,
+                                            int64_t first_frame, CampxOutputs out,
+                                            int8_t* actions_out, int32_t* states_out, int64_t B,
+                                            int32_t T, int32_t reset_first, int64_t n_members,
+                                            int32_t path, void* stream) {
+  if (!s || !tables_dev || !st.pos || !st.done || !policy || !out.trace || !actions_out || B <= 0 ||
+      T <= 0)
+    return CAMPX_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(out.trace) & 1) || (reinterpret_cast<uintptr_t>(st.pos) & 3) ||
+      (reinterpret_cast<uintptr_t>(policy) & 3) || (reinterpret_cast<uintptr_t>(states_out) & 3))
+    return CAMPX_EINVAL;
+  if (out.scalar_pitch && out.scalar_pitch < B) return CAMPX_EINVAL;
+  // (the environment is one 32-bit word of the Philox counter; frames count up to 2^63 - 1)
+  if (B > 0xffffffffll || first_frame < 0 || first_frame > INT64_MAX - T) return CAMPX_EINVAL;
+  if (n_members < 1 || B % n_members != 0) return CAMPX_EINVAL;
+  const int32_t v = wide_validate_plain(s);
+  if (v != CAMPX_OK) return v;
+  if (out.perf && !s->has_perf) return CAMPX_EINVAL;
+  PopulationPlan plan;
+  const int32_t planned = plan_population(s->n_states, out.perf ? 1 : 0, B, n_members,
+                                          knob(K_WIDE_LDS_MAX), path, &plan, nullptr);
+  if (planned != CAMPX_OK) return planned;
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  const WideLayout w = wide_layout(*s);
+  PopulationParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.n_states = s->n_states;
+  pp.n_planes = w.n_planes;
+  pp.discounts[0] = 1.0f;
+  for (int i = 1; i < 16; ++i) pp.discounts[i] = s->discount_list[i];
+  pp.has_dcodes = s->any_dcode;
+  pp.key0 = (uint32_t)seed;
+  pp.key1 = (uint32_t)(seed >> 32);
+  pp.envs_per_member = (uint32_t)(B / n_members);
+  pp.plane = (int64_t)T * row_pitch(out, B);
+  pp.first_frame = first_frame;
+  const char* blob = static_cast<const char*>(tables_dev);
+  const uint2* entries = reinterpret_cast<const uint2*>(blob);
+  const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
+  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
+  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
+  const bool in_lds = plan.path == 1;
+  const size_t lds = (size_t)plan.lds_bytes;
+  const dim3 grid((unsigned)((B + kPopThreads - 1) / kPopThreads));
+  out.obs = nullptr;
+  out.board = nullptr;
+#define CAMPX_POPULATION_LAUNCH(LDS, PERF, STATES)                                                 \
+  do {                                                                                             \
+    CAMPX_ALLOW_LDS((wide_policy_population_kernel<LDS, PERF, STATES>), lds);                      \
+    hipLaunchKernelGGL((wide_policy_population_kernel<LDS, PERF, STATES>), grid,                   \
+                       dim3(kPopThreads), lds, hs, pp, entries, cells, perf, policy, state, st,    \
+                       out, actions_out, states_out, B, T, reset_first);                           \
+  } while (0)
+#define CAMPX_POPULATION_LAUNCH2(LDS, PERF)                        \
+  do {                                                             \
+    if (states_out) CAMPX_POPULATION_LAUNCH(LDS, PERF, true);      \
+    else CAMPX_POPULATION_LAUNCH(LDS, PERF, false);                \
+  } while (0)
+  if (in_lds && out.perf) CAMPX_POPULATION_LAUNCH2(true, true);
+  else if (in_lds) CAMPX_POPULATION_LAUNCH2(true, false);
+  else if (out.perf) CAMPX_POPULATION_LAUNCH2(false, true);
+  else CAMPX_POPULATION_LAUNCH2(false, false);
+#undef CAMPX_POPULATION_LAUNCH2
+#undef CAMPX_POPULATION_LAUNCH
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+}
+
+}  // extern "C"

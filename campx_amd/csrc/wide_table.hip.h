@@ -1,6 +1,7 @@
-// wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_plan, k_visit,
-// k_sums) agree on, each said once: the table entry's format, the policy-row rule, the lazy error
-// report, and the host's choice between one LDS workgroup and one launch per step.
+// wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_population,
+// k_plan, k_visit, k_sums) agree on, each said once: the table entry's format, the policy-row rule,
+// the sampler's Philox block, the lazy error report, and the host's choice between one LDS
+// workgroup and one launch per step.
 #ifndef CAMPX_WIDE_TABLE_HIP_H_
 #define CAMPX_WIDE_TABLE_HIP_H_
 
@@ -58,6 +59,27 @@ __device__ __forceinline__ float policy_row_total(const float (&w)[5]) {
   const float c4 = (((w[0] + w[1]) + w[2]) + w[3]) + w[4];
   const bool good = CAMPX_POLICY_ROW_GOOD(w[0], w[1], w[2], w[3], w[4], c4);
   return good ? c4 : 0.0f;
+}
+
+// One Philox4x32-10 block: the sampler of the closed-loop rollouts (k_policy.hip and
+// k_population.hip; include/campx_hip.h has the rule).
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0;
+  out[1] = c1;
+  out[2] = c2;
+  out[3] = c3;
 }
 
 // What a kernel found wrong in its input and went on from, for the host to read later: `n` more on

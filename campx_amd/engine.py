@@ -470,6 +470,19 @@ class Engine(object):
     """State-table tier only: the dict of `rollout_policy(out=...)`, allocated once."""
     return self._batched('rollout_policy_buffers').rollout_policy_buffers(T, want_states=want_states)
 
+  def rollout_population(self, policies, T, **kwargs):
+    """State-table tier only: `rollout_policy()` for P policies in one launch, `policies` float32
+    `[P, n_states, 5]`, block m of the B environments sampling policy m; 'states' holds the flat
+    row `member * n_states + state`.  See `wide.WideGame.rollout_population`; the other batched
+    tiers raise NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on
+    this one)."""
+    return self._batched('rollout_population').rollout_population(policies, T, **kwargs)
+
+  def rollout_population_buffers(self, T, want_states=True):
+    """State-table tier only: the dict of `rollout_population(out=...)`, allocated once."""
+    return self._batched('rollout_population_buffers').rollout_population_buffers(
+        T, want_states=want_states)
+
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
     game's table (None: all of them), bit for bit what `play()` / `rollout()` show for an

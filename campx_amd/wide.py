@@ -29,7 +29,8 @@ from . import tabulate
 # What this tier alone offers; the other batched tiers answer each of these with a
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
-    'rollout_policy_buffers', 'rollout_policy', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
+    'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'visitation_buffers', 'state_visitation', 'render_states',
     'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
@@ -118,7 +119,9 @@ class WideGame(fused.FusedGame):
     self._onehot_bad = torch.zeros((1,), dtype=torch.int32, device=dev)
     # environment-frames of rollout_policy() that met a bad policy row (raised with the bad ids)
     self._bad_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
-    self._policy_frame = 0            # absolute frame the next rollout_policy() continues at
+    # the same of rollout_population(), counted apart so that the error says where they came from
+    self._bad_member_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._policy_frame = 0            # absolute frame the next rollout_policy() / rollout_population() continues at
     # bad rows of the policies given to evaluate_policy() (raised under the same flag)
     self._bad_plan_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     # bad rows of the policies given to state_visitation() (raised under the same flag)
@@ -151,6 +154,10 @@ class WideGame(fused.FusedGame):
     self._lazy_errors.insert(1, (
         self._bad_rows, acts,
         '{} environment-frames of rollout_policy() met bad policy rows ' + bad_row + '; they took action {}'))
+    self._lazy_errors.insert(2, (
+        self._bad_member_rows, acts,
+        '{} environment-frames of rollout_population() met bad policy rows ' + bad_row +
+        '; they took action {}'))
     self._lazy_errors += [
         (self._bad_state_ids, idx,
          '{} state ids of render_states() are outside the game\'s table (they were rendered as state 0)'),
@@ -252,15 +259,22 @@ class WideGame(fused.FusedGame):
     if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
       raise ValueError('{0} must be an int, 1 <= {0} <= 2^20, got {1!r}'.format(name, n))
 
-  def _planned_path(self, path, plan_fn, *args):
+  def _planned_path(self, path, plan_fn, *args, what=None):
     """The path (1 LDS, 2 global) a planning call takes: `path` checked, then what the library's
-    plan function says for this table."""
+    plan function says for this table.  `what`: what path 1 would have to hold, for the message
+    that it does not fit (default: the table)."""
     if path not in (0, 1, 2):
       raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
     plan = (ctypes.c_int64 * 4)()
-    if plan_fn(self.n_states, *(args + (_hip.config_get('wide_lds_max'), path, plan))) != 0:
-      raise ValueError('path=1: a table of {} states does not fit the LDS of one workgroup '
-                       '(library setting wide_lds_max); use path=0 or path=2'.format(self.n_states))
+    lds_max = _hip.config_get('wide_lds_max')
+    code = plan_fn(self.n_states, *(args + (lds_max, path, plan)))
+    if code != 0 and path != 1:      # (only a forced path 1 can be refused for a checked call)
+      raise ValueError('path={}: the library refused the plan (code {}; library setting '
+                       'wide_lds_max = {})'.format(path, code, lds_max))
+    if code != 0:
+      raise ValueError('path=1: {} does not fit the LDS of one workgroup (library setting '
+                       'wide_lds_max); use path=0 or path=2'.format(
+                           what or 'a table of {} states'.format(self.n_states)))
     return int(plan[0])
 
   def _check_out(self, out, want, made_by):
@@ -349,6 +363,104 @@ class WideGame(fused.FusedGame):
         out['done'], out['perf'], out['trace'], out['actions'],
         out.get('states') if want_states else None, self._bad_rows if validate else None,
         self._bad_flag if validate else None, bool(reset_first))
+    self._policy_frame = first + T
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if validate:
+      self._after_launch()
+    return out
+
+  # ------------------------------------------------------------ closed-loop rollouts of a population
+
+  def _check_population(self, policies):
+    """P of a `policies` argument, checked as `_check_policy()` checks a policy."""
+    S, A, B = self.n_states, gamespec.N_ACTIONS, self.batch
+    if (not torch.is_tensor(policies) or policies.dtype != torch.float32 or policies.dim() != 3
+        or tuple(policies.shape[1:]) != (S, A) or policies.shape[0] < 1
+        or policies.device != self.device or not policies.is_contiguous()):
+      got = ('{} {} on {}'.format(policies.dtype, list(policies.shape), policies.device)
+             if torch.is_tensor(policies) else type(policies).__name__)
+      raise ValueError('policies must be a contiguous float32 [P, {}, {}] tensor (members x n_states x '
+                       'actions) on {}, got {}'.format(S, A, self.device, got))
+    P = int(policies.shape[0])
+    if P > B or B % P != 0:
+      raise ValueError('policies: the {} environments do not split into P = {} equal blocks (P must '
+                       'divide the batch)'.format(B, P))
+    if P * S >= 1 << 31:
+      raise ValueError('policies: P * n_states = {} x {} must be below 2^31 (the flat rows of '
+                       '\'states\' are int32)'.format(P, S))
+    return P
+
+  def rollout_population_buffers(self, T, want_states=True):
+    """Allocate the dict of `rollout_population(out=...)` once: `rollout_policy_buffers()`'s, stream
+    for stream."""
+    return self.rollout_policy_buffers(T, want_states)
+
+  def rollout_population(self, policies, T, seed=0, first_frame=None, reset_first=False, out=None,
+                         want_states=True, path=0):
+    """`rollout_policy()` for a POPULATION of P policies in one launch: block m of the environments
+    samples policy m.
+
+    `policies` is a contiguous float32 `[P, n_states, 5]` tensor on the game's device, P a divisor
+    of the batch B, `P * n_states < 2^31`; a tensor that requires grad is used through `.detach()`.
+    With `n = B // P`, environment e belongs to member `e // n`: members own equal, contiguous
+    blocks of environments, so every `[T, B]` stream of the result is `[T, P, n]` by
+    `unflatten(1, (P, n))` and `game.ret.view(P, n).mean(1)` is each member's mean episode return.
+
+    Sampling is `rollout_policy()`'s rule, word for word - key `seed`, counter (absolute environment
+    e, absolute frame >> 2), thresholds in f32 in action order, a bad row takes action 4 and is
+    counted -; the row read for environment e in state s is `policies[e // n, s]` (s = 0 after a
+    'done').  `first_frame=None` continues the per-game frame counter `rollout_policy()` advances:
+    the two calls can be mixed and continued.
+
+    Returns `rollout_policy()`'s dict - same keys, shapes, dtypes and row padding - in which
+    'states' holds the FLAT row `(e // n) * n_states + s`: the row of
+    `policies.view(P * n_states, 5)` the action was sampled from.  The learner's calls then serve
+    all members in one launch each: `returns.table_lookup(policies.view(-1, 5), out['states'],
+    out['actions'])`, `returns.sum_by_state(out['states'], out['actions'], ...,
+    n_states=P * n_states)`, `V.view(-1)[out['states'].long()]` for a critic `[P, n_states]`.  The
+    game's own state is `out['states'] % n_states` (for `render_states()`).  With P = 1 the call is
+    `rollout_policy()` byte for byte.
+
+    `out`: a dict from `rollout_population_buffers(T, want_states)`, overwritten; the call then
+    allocates nothing and is capturable in a HIP graph.  `path`: 0 - a workgroup keeps the table
+    and the thresholds of the members its 256 environments belong to in LDS whenever they fit
+    (library setting wide_lds_max), else table and weights are read through L1 / L2; 1 / 2 force
+    either (1 raises ValueError for what does not fit).  Both give the same bytes.
+
+    Argument errors raise ValueError before anything is launched.  Bad rows raise lazily, as
+    `rollout_policy()`'s do, in a message that names this call.
+    """
+    P = self._check_population(policies)
+    T = int(T)
+    if T < 1:
+      raise ValueError('a rollout needs at least one frame: T >= 1')
+    first = self._policy_frame if first_frame is None else int(first_frame)
+    if first < 0 or first + T >= 1 << 63:
+      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
+    seed = int(seed) & ((1 << 64) - 1)
+    self._planned_path(
+        path, _hip.lib.campx_wide_population_plan, 1 if self.has_perf else 0, self.batch, P,
+        what='a table of {} states with the thresholds of the members of one workgroup ({} environments '
+             'per member)'.format(self.n_states, self.batch // P))
+    if out is None:
+      out = self.rollout_population_buffers(T, want_states)
+    else:
+      rows = ([out.get('actions')] + ([out.get('states')] if want_states else [])
+              if isinstance(out, dict) else [None])
+      trace = out.get('trace') if isinstance(out, dict) else None
+      if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.shape[1] != T
+          or any(not torch.is_tensor(r) or tuple(r.shape) != (T, self.batch)
+                 or (T > 1 and r.stride(0) != trace.stride(1)) for r in rows)):
+        raise ValueError('out must be a dict from rollout_population_buffers({}, want_states={}) of '
+                         'this game ({} environments)'.format(T, bool(want_states), self.batch))
+    validate = self.validate_actions
+    _hip.ops.wide_policy_population(
+        self._spec_host, self._tables, self.state, self.done, self.ret, policies.detach(),
+        seed - (1 << 64) if seed >= 1 << 63 else seed, first, out['reward'], out['discount'],
+        out['done'], out['perf'], out['trace'], out['actions'],
+        out.get('states') if want_states else None, self._bad_member_rows if validate else None,
+        self._bad_flag if validate else None, bool(reset_first), path)
     self._policy_frame = first + T
     self.frame = T if reset_first else self.frame + T
     self.check_ok()

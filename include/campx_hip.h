@@ -762,6 +762,46 @@ int32_t campx_wide_policy_update_launch(const CampxWideSpec* spec_host, const vo
                                         int32_t* states_out, int64_t B, int32_t T,
                                         int32_t reset_first, void* stream);
 /*
+ * ---- Closed-loop rollouts of a population of policies -----------------------------------------
+ * campx_wide_policy_update_launch() for `n_members` policies at once (csrc/k_population.hip):
+ * `policy` is DEVICE float32 [n_members][n_states][5], B is a multiple of n_members, and with
+ * n = B / n_members environment e belongs to member e / n - members own equal, contiguous blocks
+ * of environments.  The sampling rule is the one above, word for word: the key is `seed`, the
+ * counter (absolute environment e, absolute frame >> 2), and the row read for environment e in
+ * state s is policy[e / n][s] (s = 0 after a done).  Everything written is what
+ * campx_wide_policy_update_launch() writes, except `states_out`, which holds the FLAT row
+ * (e / n) * n_states + s: the row of `policy` seen as [n_members * n_states][5] the action was
+ * sampled from, so that campx_table_lookup_launch() and campx_state_sums_launch() (with n_states =
+ * n_members * n_states) serve all members in one launch each.  With n_members = 1 the call writes
+ * what campx_wide_policy_update_launch() writes, byte for byte.
+ *
+ * A lane per environment, 256 to a workgroup.  Two paths, `path`: 1 = a workgroup stages the table
+ * in LDS and, beside it, the thresholds of only the members its 256 environments belong to; 2 =
+ * table and weights are read through L1 / L2.  0 = path 1 whenever its LDS bytes - the table's
+ * (entries, the states' cells, the hidden performance when out.perf is given) plus
+ * members_per_block * n_states * 20 - are within the library setting wide_lds_max.  Neither path
+ * changes a bit of any result.
+ *
+ * campx_wide_population_plan() is the choice as host-only arithmetic (nothing is launched):
+ * plan_out[4] = the path taken (1 / 2); dynamic LDS bytes (0 on path 2); threads of a workgroup;
+ * members_per_block, the largest number of distinct members the environments of any one workgroup
+ * belong to (1 when n is a multiple of 256; 256 when n = 1 and B >= 256).  CAMPX_EINVAL: n_states
+ * outside 1 .. CAMPX_WIDE_MAX_STATES, a has_perf that is not 0 / 1, B outside 1 .. 2^32 - 1,
+ * n_members < 1, B % n_members != 0, n_members * n_states >= 2^31, wide_lds_max < 0, a `path`
+ * outside 0 .. 2, path 1 for what does not fit, plan_out NULL.
+ * campx_wide_policy_population_launch() returns CAMPX_EINVAL, before anything is launched, for
+ * the same and for everything campx_wide_policy_update_launch() refuses.  Asynchronous on
+ * `stream`, no synchronisation, no allocation, no library state.
+ */
+int32_t campx_wide_population_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t n_members,
+                                   int64_t wide_lds_max, int32_t path, int64_t* plan_out);
+int32_t campx_wide_policy_population_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                            CampxState state, const float* policy, uint64_t seed,
+                                            int64_t first_frame, CampxOutputs out,
+                                            int8_t* actions_out, int32_t* states_out, int64_t B,
+                                            int32_t T, int32_t reset_first, int64_t n_members,
+                                            int32_t path, void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
