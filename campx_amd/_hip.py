@@ -33,6 +33,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_rules_size', 'campx_wide_enumerate_launch',
            'campx_wide_update_launch', 'campx_wide_policy_update_launch',
            'campx_wide_policy_population_launch', 'campx_wide_population_plan',
+           'campx_wide_learn_plan', 'campx_wide_learn_launch',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
@@ -132,6 +133,19 @@ class CampxTableLookup(ctypes.Structure):
               ('reserved', ctypes.c_int32), ('bad_count', ctypes.c_void_p)]
 
 
+class CampxLearner(ctypes.Structure):
+  """include/campx_hip.h: one campx_wide_learn_launch() call."""
+  _fields_ = [('q', ctypes.c_void_p), ('alpha', ctypes.c_void_p), ('gamma', ctypes.c_void_p),
+              ('epsilon', ctypes.c_void_p), ('reward_sum', ctypes.c_void_p),
+              ('perf_sum', ctypes.c_void_p), ('episodes', ctypes.c_void_p),
+              ('bad_count', ctypes.c_void_p), ('bad_flag', ctypes.c_void_p),
+              ('seed', ctypes.c_uint64), ('first_frame', ctypes.c_int64),
+              ('window', ctypes.c_int32), ('rule', ctypes.c_int32), ('path', ctypes.c_int32),
+              ('reset_first', ctypes.c_int32)]
+
+
+LEARN_RULES = {'q': 0, 'expected_sarsa': 1}
+
 # second word of a state-table entry (csrc/wide_table.hip.h): next state | done << 24 | discount code << 25
 ENTRY_NEXT_MASK, ENTRY_DONE_SHIFT, ENTRY_DCODE_SHIFT, ENTRY_DCODE_MASK = 0xffffff, 24, 25, 15
 
@@ -228,6 +242,10 @@ def _load():
                                                       CampxOutputs, vp, vp, i64, i32, i32, i64, i32, vp]
   lib.campx_wide_population_plan.restype = i32
   lib.campx_wide_population_plan.argtypes = [i64, i32, i64, i64, i64, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_learn_plan.restype = i32
+  lib.campx_wide_learn_plan.argtypes = [i64, i32, i64, i64, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_learn_launch.restype = i32
+  lib.campx_wide_learn_launch.argtypes = [wide_p, vp, CampxState, ctypes.POINTER(CampxLearner), i64, i32, vp]
   lib.campx_render_gather_launch.restype = i32
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
@@ -309,7 +327,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'wide_policy_update', 'wide_policy_population', 'render_gather', 'wide_render_gather', 'wide_render_states',
+            'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
 
 

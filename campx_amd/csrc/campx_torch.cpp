@@ -17,6 +17,7 @@
 //   campx::wide_policy_update       the same with every frame's action sampled on the device from a
 //                                   policy over the game's states (closed-loop rollouts)
 //   campx::wide_policy_population   wide_policy_update for P policies, each over its block of environments
+//   campx::wide_learn               online tabular learners: a Q-table per environment, T frames per launch
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -818,6 +819,56 @@ void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tenso
            "campx_wide_policy_population_launch");
 }
 
+// Wide tier, online tabular learners (campx_wide_learn_launch): environment e learns on its own
+// table `q[e]` float32 [B, n_states, 5] for `frames` frames; `alpha`, `gamma`, `epsilon` float32 [B];
+// the window sums are [ceil(frames / window), B].  `rule`: 0 Q-learning, 1 expected SARSA.
+void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                const OptTensor& ret, Tensor& q, const Tensor& alpha, const Tensor& gamma,
+                const Tensor& epsilon, int64_t rule, int64_t seed, int64_t first_frame, int64_t frames,
+                int64_t window, Tensor& reward_sum, const OptTensor& perf_sum, Tensor& episodes,
+                const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                int64_t path) {
+  const char* what = "campx::wide_learn";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  const int64_t S = g.hs->n_states, A = CAMPX_N_ACTIONS;
+  TORCH_CHECK(g.B * S * A < (1ll << 31), what, ": B * n_states * 5 must be below 2^31");
+  want(q, "q", at::kFloat, g.dev, {g.B, S, A});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": q must be 16-byte aligned");
+  want(alpha, "alpha", at::kFloat, g.dev, {g.B});
+  want(gamma, "gamma", at::kFloat, g.dev, {g.B});
+  want(epsilon, "epsilon", at::kFloat, g.dev, {g.B});
+  TORCH_CHECK(rule == CAMPX_LEARN_Q || rule == CAMPX_LEARN_EXPECTED_SARSA, what,
+              ": rule must be 0 (Q-learning) or 1 (expected SARSA)");
+  TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
+  TORCH_CHECK(frames >= 1 && frames <= 0x7fffffff, what, ": bad frame count");
+  TORCH_CHECK(window >= 1 && window <= 0x7fffffff, what, ": window must be 1 .. 2^31 - 1");
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  const int64_t W = (frames + window - 1) / window;
+  want(reward_sum, "reward_sum", at::kFloat, g.dev, {W, g.B});
+  if (perf_sum.has_value()) want(*perf_sum, "perf_sum", at::kInt, g.dev, {W, g.B});
+  want(episodes, "episodes", at::kInt, g.dev, {W, g.B});
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
+  CampxLearner l{};
+  l.q = reinterpret_cast<float*>(q.data_ptr());
+  l.alpha = reinterpret_cast<const float*>(alpha.data_ptr());
+  l.gamma = reinterpret_cast<const float*>(gamma.data_ptr());
+  l.epsilon = reinterpret_cast<const float*>(epsilon.data_ptr());
+  l.reward_sum = reinterpret_cast<float*>(reward_sum.data_ptr());
+  l.perf_sum = opt_ptr<int32_t>(perf_sum);
+  l.episodes = reinterpret_cast<int32_t*>(episodes.data_ptr());
+  l.bad_count = opt_ptr<int32_t>(bad_count);
+  l.bad_flag = flag_ptr(bad_flag, g.dev);
+  l.seed = (uint64_t)seed;
+  l.first_frame = first_frame;
+  l.window = (int32_t)window;
+  l.rule = (int32_t)rule;
+  l.path = (int32_t)path;
+  l.reset_first = reset_first ? 1 : 0;
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_learn_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
+           "campx_wide_learn_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1263,7 +1314,7 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
-    "render_gather",
+    "wide_learn", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
     "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids", "check_actions"};
 
@@ -1331,6 +1382,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(i!) actions_out, Tensor(j!)? states_out, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, "
       "bool reset_first, int path=0) -> ()");
   m.def(
+      "wide_learn(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) q, Tensor alpha, Tensor gamma, Tensor epsilon, int rule, int seed, "
+      "int first_frame, int frames, int window, Tensor(e!) reward_sum, Tensor(f!)? perf_sum, "
+      "Tensor(g!) episodes, Tensor(h!)? bad_count, Tensor(i!)? bad_flag, bool reset_first, "
+      "int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1380,6 +1437,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_update", &wide_update);
   m.impl("wide_policy_update", &wide_policy_update);
   m.impl("wide_policy_population", &wide_policy_population);
+  m.impl("wide_learn", &wide_learn);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

@@ -483,6 +483,20 @@ class Engine(object):
     return self._batched('rollout_population_buffers').rollout_population_buffers(
         T, want_states=want_states)
 
+  def learn_tabular(self, T, q=None, *args, **kwargs):
+    """State-table tier only: T frames of online tabular learning - Q-learning (`rule='q'`) or
+    expected SARSA - for B independent learners in one launch, environment e learning on its own
+    table `q[e]` float32 `[B, n_states, 5]`, updated in place; `alpha`, `gamma` and `epsilon` are
+    numbers or float32 `[B]` tensors.  Returns 'q' and the per-window sums 'reward_sum',
+    'perf_sum' and 'episodes', `[W, B]`.  See `wide.WideGame.learn_tabular`; the other batched
+    tiers raise NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on
+    this one)."""
+    return self._batched('learn_tabular').learn_tabular(T, q, *args, **kwargs)
+
+  def learner_buffers(self, T, window=None):
+    """State-table tier only: the dict of `learn_tabular(out=...)`, allocated once."""
+    return self._batched('learner_buffers').learner_buffers(T, window=window)
+
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
     game's table (None: all of them), bit for bit what `play()` / `rollout()` show for an

@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'visitation_buffers', 'state_visitation', 'render_states',
     'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
@@ -134,6 +134,10 @@ class WideGame(fused.FusedGame):
     # the same two of the window calls, counted apart so that the error says where they came from
     self._bad_window_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_window_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
+    # learners of learn_tabular() with bad hyper-parameters, once per launch (raised under the
+    # flag of the action ids), and the [3, B] tensor its Python-float hyper-parameters are filled into
+    self._bad_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._learn_floats = None
     self._layer_of_cell = None        # the window kernel's scenery table
     self._window_table()
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
@@ -172,7 +176,11 @@ class WideGame(fused.FusedGame):
          'windows were rendered from the nearest one inside)'),
         (self._bad_window_ids, idx,
          '{} state ids of render_state_windows() are outside the game\'s table (their windows were '
-         'rendered as state 0\'s)')]
+         'rendered as state 0\'s)'),
+        (self._bad_learners, acts,
+         '{} learners of learn_tabular() have bad hyper-parameters (alpha, gamma or epsilon not '
+         'finite, or epsilon outside [0, 1]); they took action {} at every frame and their tables were '
+         'left untouched')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -467,6 +475,151 @@ class WideGame(fused.FusedGame):
     if validate:
       self._after_launch()
     return out
+
+  # ------------------------------------------------------------ online tabular learners
+
+  def _windows_of(self, T, window):
+    """(T, window, W) of a learner call: `window=None` is one window of T frames."""
+    T = int(T)
+    if T < 1 or T >= 1 << 31:
+      raise ValueError('a run needs at least one frame: 1 <= T < 2^31')
+    if window is None:
+      window = T
+    if isinstance(window, bool) or not isinstance(window, int) or not 1 <= window < 1 << 31:
+      raise ValueError('window must be None or an int, 1 <= window < 2^31, got {!r}'.format(window))
+    return T, window, (T + window - 1) // window
+
+  def learner_buffers(self, T, window=None):
+    """Allocate the dict of `learn_tabular(out=...)` once: 'reward_sum' float32 [W, B], 'episodes'
+    int32 [W, B] and - a game with hidden performance - 'perf_sum' int32 [W, B], with
+    W = ceil(T / window) (`window=None`: one window of T frames)."""
+    T, window, W = self._windows_of(T, window)
+    B, dev = self.batch, self.device
+    out = {'reward_sum': torch.zeros((W, B), dtype=torch.float32, device=dev),
+           'episodes': torch.zeros((W, B), dtype=torch.int32, device=dev)}
+    if self.has_perf:
+      out['perf_sum'] = torch.zeros((W, B), dtype=torch.int32, device=dev)
+    return out
+
+  def _hyper_parameter(self, name, value, row):
+    """float32 [B] on the device of `alpha`, `gamma` or `epsilon`: a tensor as given, a Python
+    number checked here and filled into row `row` of a tensor the game keeps (no allocation after
+    the first call)."""
+    B = self.batch
+    if torch.is_tensor(value):
+      if not self._tensor_ok(value, torch.float32, (B,)):
+        raise ValueError('{} must be a number or a contiguous float32 [{}] tensor (one per learner) '
+                         'on {}, got {} {} on {}'.format(name, B, self.device, value.dtype,
+                                                         list(value.shape), value.device))
+      return value.detach()
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+      raise ValueError('{} must be a number or a float32 [{}] tensor, got {}'.format(
+          name, B, type(value).__name__))
+    if (not math.isfinite(value) or abs(value) > torch.finfo(torch.float32).max
+        or (name == 'epsilon' and not 0.0 <= value <= 1.0)):
+      raise ValueError('{} must be a finite number (as a float32){}, got {!r}'.format(
+          name, ' in [0, 1]' if name == 'epsilon' else '', value))
+    if self._learn_floats is None:
+      self._learn_floats = torch.zeros((3, B), dtype=torch.float32, device=self.device)
+    return self._learn_floats[row].fill_(float(value))
+
+  def learn_tabular(self, T, q=None, alpha=0.1, gamma=0.99, epsilon=0.1, rule='q', seed=0,
+                    first_frame=None, reset_first=False, window=None, out=None, path=0):
+    """T frames of ONLINE tabular learning for B independent learners in ONE launch: environment e
+    is learner e, with its own Q-table `q[e]`.  Every frame it acts epsilon-greedily on its table,
+    and `q[e, s, a]` is updated at once - the next frame's action is chosen from the updated table
+    (csrc/k_learn.hip, `campx::wide_learn`).  Nothing is shared between learners, so there are no
+    atomics and the run is reproducible bit for bit (include/campx_hip.h has the rule in full;
+    tests/learner_reference.py restates it in numpy).
+
+    Args:
+      q: contiguous float32 `[B, n_states, 5]` on the game's device (16-byte aligned,
+          `B * n_states * 5 < 2^31`), updated IN PLACE; None: zeros.  `q[m]` compares with
+          `value_iteration()`'s 'q'; `softmax(q, 2)` or a one-hot of `q.argmax(2)` is what
+          `rollout_population()` takes.
+      alpha, gamma, epsilon: the step size, the discount factor and the exploration rate, each a
+          Python number or a float32 `[B]` tensor - a tensor is what makes a sweep.  A learner
+          whose alpha, gamma or epsilon is not finite, or whose epsilon is outside [0, 1], is BAD:
+          it takes action 4 at every frame, its table is left untouched, and it raises ValueError -
+          counted once per call - lazily, as bad actions do: from `check_actions()` or a later
+          call, under `validate_actions='sync'` from this one.  Python numbers are checked at once.
+      rule: 'q' - Q-learning, the bootstrap is `max_a q[e, n, a]` - or 'expected_sarsa': the
+          bootstrap is the expectation of `q[e, n, .]` under the learner's own epsilon-greedy
+          policy, `(1 - epsilon) * max + epsilon * mean`.  In both, the target is
+          `r + (gamma * D) * bootstrap` (r alone on a frame that ends the episode; a reward of None
+          counts as 0; D is the frame's discount as in `evaluate_policy()`), and
+          `q[e, s, a] += alpha * (target - q[e, s, a])`.  Expected SARSA is the on-policy form
+          that needs nothing carried between frames; SARSA proper needs the NEXT frame's committed
+          action, across launches too, and is not offered.  Several environments feeding ONE
+          learner would need atomics and would not repeat bit for bit: out of scope as well.
+      seed, first_frame: exploration is counter-based - learner e at absolute frame f draws from
+          the Philox4x32-10 block of key `seed`, counter (e, f >> 1, 1) - a stream unrelated to
+          `rollout_policy()`'s for the same seed.  `first_frame=None` continues the per-game frame
+          counter that `rollout_policy()` advances, so that two calls of T1 and T2 frames learn
+          what one call of T1 + T2 does; an explicit `first_frame` sets it to `first_frame + T`.
+      reset_first: every learner starts a new episode (its table stays).
+      window: frames per window of the learning curves; None: one window of T frames.  Windows
+          count from this call's frame 0; the last one may be short.
+      out: a dict from `learner_buffers(T, window)`, overwritten.  With `q` and `out` (and
+          tensors, or the same numbers as before, for the hyper-parameters) the call allocates
+          nothing and is capturable in a HIP graph.
+      path: 0 - a workgroup keeps the table and its 256 learners' Q-tables in LDS whenever they
+          fit (library setting wide_lds_max: up to 28 states), else each learner reads and writes
+          its rows of `q` through L1 / L2; 1 / 2 force either (1 raises ValueError for what does
+          not fit).  Both give the same bits.
+
+    Returns a dict: 'q'; 'reward_sum' float32 `[W, B]`, the real reward per window, summed in
+    frame order; 'perf_sum' int32 `[W, B]`, the hidden performance per window (games that have
+    one); 'episodes' int32 `[W, B]`, the episodes that ended in the window; W = ceil(T / window).
+    No `[T, B]` stream is written.  `state`, `done`, `ret` and `frame` carry over exactly as
+    `rollout_policy()` leaves them.  Argument errors raise ValueError before anything is launched.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    T, window, W = self._windows_of(T, window)
+    if rule not in _hip.LEARN_RULES:
+      raise ValueError('rule must be \'q\' or \'expected_sarsa\', got {!r}'.format(rule))
+    if B * S * A >= 1 << 31:
+      raise ValueError('learn_tabular(): B * n_states * 5 = {} x {} x 5 must be below 2^31; use a '
+                       'smaller batch'.format(B, S))
+    first = self._policy_frame if first_frame is None else int(first_frame)
+    if first < 0 or first + T >= 1 << 63:
+      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
+    seed = int(seed) & ((1 << 64) - 1)
+    if q is not None and (not self._tensor_ok(q, torch.float32, (B, S, A)) or q.data_ptr() % 16):
+      got = ('{} {} on {}'.format(q.dtype, list(q.shape), q.device) if torch.is_tensor(q)
+             else type(q).__name__)
+      raise ValueError('q must be a contiguous, 16-byte aligned float32 [{}, {}, {}] tensor (learners '
+                       'x n_states x actions) on {}, or None for zeros; got {}'.format(B, S, A, dev, got))
+    self._planned_path(path, _hip.lib.campx_wide_learn_plan, 1 if self.has_perf else 0, B,
+                       what='a table of {} states with the Q-tables of a workgroup\'s 256 '
+                            'learners'.format(S))
+    want = [('reward_sum', torch.float32, (W, B)), ('episodes', torch.int32, (W, B))]
+    if self.has_perf:
+      want.append(('perf_sum', torch.int32, (W, B)))
+    if out is None:
+      out = self.learner_buffers(T, window)
+    else:
+      self._check_out(out, want, 'learner_buffers({}, window={})'.format(T, window))
+    hyper = [self._hyper_parameter(name, value, row) for row, (name, value) in
+             enumerate((('alpha', alpha), ('gamma', gamma), ('epsilon', epsilon)))]
+    if q is None:
+      q = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
+    validate = self.validate_actions
+    _hip.ops.wide_learn(
+        self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), hyper[0],
+        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed - (1 << 64) if seed >= 1 << 63 else seed,
+        first, T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
+        out['episodes'], self._bad_learners if validate else None,
+        self._bad_flag if validate else None, bool(reset_first), path)
+    self._policy_frame = first + T
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if validate:
+      self._after_launch()
+    res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes']}
+    if self.has_perf:
+      res['perf_sum'] = out['perf_sum']
+    return res
 
   # ------------------------------------------------------------ planning on the table
 

@@ -802,6 +802,93 @@ int32_t campx_wide_policy_population_launch(const CampxWideSpec* spec_host, cons
                                             int32_t T, int32_t reset_first, int64_t n_members,
                                             int32_t path, void* stream);
 /*
+ * ---- Online tabular learners: one Q-table per environment, a whole run per launch -------------
+ * Q-learning and expected SARSA update q[s][a] after every single frame and choose the next
+ * frame's action from the updated table: no batch of the calls above expresses that.  Here
+ * environment e IS learner e: it owns `q[e]` (DEVICE float32 [B][n_states][5], 16-byte aligned,
+ * B * n_states * 5 < 2^31, updated in place), acts epsilon-greedily on it and learns from every
+ * frame, T frames in one launch (csrc/k_learn.hip).  Nothing is shared between learners: no
+ * atomics, and the run is reproducible bit for bit.  No trace and no per-frame stream is written.
+ * No reference counterpart.
+ *
+ * The rule.  f32 throughout, every operation rounded on its own (no fused multiply-add), so that a
+ * float32 restatement is bit-exact (tests/learner_reference.py is one, in numpy).  For learner e
+ * with alpha[e], gamma[e], epsilon[e] (DEVICE float32 [B] each) at absolute frame
+ * f = first_frame + t:
+ *   1. One Philox4x32-10 block per learner and PAIR of frames: key (seed & 0xffffffff, seed >> 32),
+ *      counter (e, g & 0xffffffff, g >> 32, 1) with g = f >> 1, constants as above; x0 is output
+ *      word 2 * (f & 1) and x1 word 2 * (f & 1) + 1.  (The fourth counter word is 1 where the
+ *      closed-loop rollouts have 0: the same seed gives unrelated streams.)
+ *   2. s = state 0 if the learner's episode is over (or `reset_first`), else its state.
+ *   3. u = float(x0 >> 8) * 2^-24; the learner explores iff u < epsilon[e], and then takes the
+ *      action ((x1 >> 8) * 5) >> 24, an integer in 0 .. 4; otherwise the greedy action of
+ *      q[e][s]: best = q0; for a = 1 .. 4: if (q[a] > best) best = q[a] - the lowest index wins a
+ *      tie, NaN never wins.
+ *   4. Entry (s, a) of the table: n, r (NaN - "None" - counted as 0, here, in `ret` and in
+ *      reward_sum), d and D exactly as in the rule of campx_wide_sweeps_launch() below.
+ *   5. The bootstrap b, from q[e][n] as it stands BEFORE this frame's update (which matters when
+ *      n == s).  CAMPX_LEARN_Q: the greedy maximum `best` of that row.
+ *      CAMPX_LEARN_EXPECTED_SARSA: m = ((((q0 + q1) + q2) + q3) + q4) * 0.2f, then
+ *      b = (keep * best) + (epsilon[e] * m) with keep = 1.0f - epsilon[e].
+ *   6. target = d ? r : r + (gamma[e] * D) * b.
+ *   7. delta = target - q[e][s][a];  q[e][s][a] = q[e][s][a] + alpha[e] * delta.
+ *   8. Per window of `window` frames, counted from the launch's frame 0 (the last may be short),
+ *      row w of three DEVICE [W][B] arrays, W = ceil(T / window): reward_sum float32 - r added in
+ *      frame order, from 0 -, perf_sum int32 - the entries' hidden performance; NULL when not
+ *      wanted, must be NULL for a game without - and episodes int32 - frames with d set.
+ * state / done / ret are read and left as campx_wide_policy_update_launch() reads and leaves them.
+ * A learner whose alpha, gamma or epsilon is not finite, or whose epsilon is outside [0, 1], is
+ * BAD: it takes action 4 at every frame, its table is left untouched (its sums are still written),
+ * and it is counted ONCE per launch into *bad_count (DEVICE int32, added to, may be NULL);
+ * *bad_flag (device or mapped pinned int32, may be NULL) is set to 1.
+ *
+ * A lane per learner, 256 to a workgroup.  Two paths, `path`: 1 = a workgroup stages the entries,
+ * the perf bytes (when perf_sum is given) and its 256 learners' tables in LDS, the tables
+ * lane-innermost, (s * 5 + a) * 256 + lane; 2 = each lane reads and writes its own 20-byte rows
+ * of q through L1 / L2, the entries (and perf bytes) staying in LDS when they alone fit.
+ * The LDS bytes:   table = up16(n_states * 40) + (has_perf ? up16(n_states * 5) : 0)
+ *                  path 1: table + 256 * n_states * 20          path 2: table if it fits, else 0
+ * 0 = path 1 whenever its bytes are within the library setting wide_lds_max.  Neither path
+ * changes a bit of any result.
+ *
+ * campx_wide_learn_plan() is the choice as host-only arithmetic (nothing is launched):
+ * plan_out[4] = the path taken (1 / 2); dynamic LDS bytes; threads of a workgroup; 1 when the
+ * entries are staged in LDS, else 0.  CAMPX_EINVAL: n_states outside 1 .. CAMPX_WIDE_MAX_STATES,
+ * a has_perf that is not 0 / 1, B outside 1 .. 2^32 - 1, B * n_states * 5 >= 2^31,
+ * wide_lds_max < 0, a `path` outside 0 .. 2, path 1 for what does not fit, plan_out NULL.
+ * campx_wide_learn_launch() returns CAMPX_EINVAL, before anything touches a device, for the same
+ * and for: NULL where it is not allowed, a q that is not 16-byte aligned, other pointers that are
+ * not 4-byte aligned, T <= 0, window < 1, first_frame < 0 or first_frame + T past 2^63 - 1, a
+ * `rule` that is neither, perf_sum for a game without hidden performance.  Asynchronous on
+ * `stream`, no synchronisation, no allocation, no library state.
+ */
+#define CAMPX_LEARN_Q 0
+#define CAMPX_LEARN_EXPECTED_SARSA 1
+
+typedef struct CampxLearner {
+  float* q;               /* DEVICE [B][n_states][5], 16-byte aligned; updated in place */
+  const float* alpha;     /* DEVICE [B] each */
+  const float* gamma;
+  const float* epsilon;
+  float* reward_sum;      /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;      /* DEVICE [W][B], or NULL */
+  int32_t* episodes;      /* DEVICE [W][B] */
+  int32_t* bad_count;     /* optional device int32: += bad learners */
+  int32_t* bad_flag;      /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;    /* absolute number of the launch's frame 0 */
+  int32_t window;         /* frames per window, >= 1 (may exceed T) */
+  int32_t rule;           /* CAMPX_LEARN_Q / CAMPX_LEARN_EXPECTED_SARSA */
+  int32_t path;           /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+} CampxLearner;
+
+int32_t campx_wide_learn_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                              int32_t path, int64_t* plan_out);
+int32_t campx_wide_learn_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                CampxState state, const CampxLearner* learner, int64_t B, int32_t T,
+                                void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
