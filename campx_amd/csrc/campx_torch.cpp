@@ -749,55 +749,23 @@ void wide_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, T
            "campx_wide_update_launch");
 }
 
-// Wide tier, closed loop (campx_wide_policy_update_launch): campx::wide_update with the action
-// stream replaced by `policy` float32 [n_states, 5]; the actions taken and - optionally - the rows
-// they were sampled from come back as streams of the call's row pitch.  T is the trace's.
-void wide_policy_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
-                        const OptTensor& ret, const Tensor& policy, int64_t seed, int64_t first_frame,
-                        const OptTensor& reward, const OptTensor& discount,
-                        const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
-                        Tensor& actions_out, const OptTensor& states_out, const OptTensor& bad_count,
-                        const OptTensor& bad_flag, bool reset_first) {
-  const WideGame g = unpack_wide("campx::wide_policy_update", spec_host, tables, state, done, ret);
-  want(policy, "policy", at::kFloat, g.dev, {(int64_t)g.hs->n_states, (int64_t)CAMPX_N_ACTIONS});
-  TORCH_CHECK(first_frame >= 0, "campx::wide_policy_update: first_frame must be >= 0");
-  TORCH_CHECK(trace.dim() == 3, "campx::wide_policy_update: trace must be int16 [K, T, B]");
-  const int64_t T = trace.size(1);
-  TORCH_CHECK(T >= 1 && T <= 0x7fffffff, "campx::wide_policy_update: bad frame count");
-  int64_t pitch = 0;
-  want_trace(trace, at::kShort, g.dev, g.K, T, g.B, pitch);
-  want_rows(actions_out, "actions_out", at::kChar, g.dev, T, g.B, pitch);
-  if (states_out.has_value()) want_rows(*states_out, "states_out", at::kInt, g.dev, T, g.B, pitch);
-  CampxOutputs out{};
-  want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
-  out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
-  const DeviceGuard guard(g.dev);
-  check_ok(campx_wide_policy_update_launch(
-               g.hs, g.tables, g.state, reinterpret_cast<const float*>(policy.data_ptr()),
-               (uint64_t)seed, first_frame, out, reinterpret_cast<int8_t*>(actions_out.data_ptr()),
-               opt_ptr<int32_t>(states_out), g.B, (int32_t)T, reset_first ? 1 : 0, current_stream()),
-           "campx_wide_policy_update_launch");
-}
-
-// Wide tier, closed loop for a population (campx_wide_policy_population_launch): campx::wide_policy_update
-// with `policy` float32 [P, n_states, 5], environment e sampling member e / (B / P); `states_out`
-// holds the flat row member * n_states + state.  `path`: 0 chosen by arithmetic, 1 LDS, 2 global.
-void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
-                            const OptTensor& ret, const Tensor& policy, int64_t seed,
-                            int64_t first_frame, const OptTensor& reward, const OptTensor& discount,
-                            const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
-                            Tensor& actions_out, const OptTensor& states_out,
-                            const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
-                            int64_t path) {
-  const char* what = "campx::wide_policy_population";
+// Wide tier, closed loop: what campx::wide_policy_update (`rank` 2: `policy` float32 [n_states, 5],
+// P = 1) and campx::wide_policy_population (`rank` 3: [P, n_states, 5]) share.  T is the trace's.
+void closed_loop(const char* what, int rank, int64_t P, int64_t path, const Tensor& spec_host,
+                 const Tensor& tables, Tensor& state, Tensor& done, const OptTensor& ret,
+                 const Tensor& policy, int64_t seed, int64_t first_frame, const OptTensor& reward,
+                 const OptTensor& discount, const OptTensor& step_done, const OptTensor& perf,
+                 Tensor& trace, Tensor& actions_out, const OptTensor& states_out,
+                 const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first) {
   const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
-  TORCH_CHECK(policy.dim() == 3 && policy.size(0) >= 1, what,
+  const int64_t S = g.hs->n_states, A = CAMPX_N_ACTIONS;
+  const bool members = rank == 3;
+  TORCH_CHECK(!members || (policy.dim() == 3 && P >= 1), what,
               ": policy must be float32 [P, n_states, 5] with P >= 1");
-  const int64_t P = policy.size(0);
-  want(policy, "policy", at::kFloat, g.dev, {P, (int64_t)g.hs->n_states, (int64_t)CAMPX_N_ACTIONS});
-  TORCH_CHECK(g.B % P == 0, what, ": the ", g.B, " environments do not split into ", P,
-              " equal blocks");
-  TORCH_CHECK(P * (int64_t)g.hs->n_states < (1ll << 31), what, ": P * n_states must be below 2^31");
+  if (members) want(policy, "policy", at::kFloat, g.dev, {P, S, A});
+  else want(policy, "policy", at::kFloat, g.dev, {S, A});
+  TORCH_CHECK(g.B % P == 0, what, ": the ", g.B, " environments do not split into ", P, " equal blocks");
+  TORCH_CHECK(P * S < (1ll << 31), what, ": P * n_states must be below 2^31");
   TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
   TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
   TORCH_CHECK(trace.dim() == 3, what, ": trace must be int16 [K, T, B]");
@@ -811,12 +779,43 @@ void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tenso
   want_streams(out, g.dev, T, g.B, pitch, true, reward, discount, step_done, perf, bad_count, bad_flag);
   out.trace = reinterpret_cast<uint8_t*>(trace.data_ptr());
   const DeviceGuard guard(g.dev);
-  check_ok(campx_wide_policy_population_launch(
-               g.hs, g.tables, g.state, reinterpret_cast<const float*>(policy.data_ptr()),
-               (uint64_t)seed, first_frame, out, reinterpret_cast<int8_t*>(actions_out.data_ptr()),
-               opt_ptr<int32_t>(states_out), g.B, (int32_t)T, reset_first ? 1 : 0, P, (int32_t)path,
-               current_stream()),
-           "campx_wide_policy_population_launch");
+  const float* weights = reinterpret_cast<const float*>(policy.data_ptr());
+  int8_t* actions = reinterpret_cast<int8_t*>(actions_out.data_ptr());
+  int32_t* rows = opt_ptr<int32_t>(states_out);
+  check_ok(members ? campx_wide_policy_population_launch(
+                         g.hs, g.tables, g.state, weights, (uint64_t)seed, first_frame, out, actions,
+                         rows, g.B, (int32_t)T, reset_first ? 1 : 0, P, (int32_t)path, current_stream())
+                   : campx_wide_policy_update_launch(
+                         g.hs, g.tables, g.state, weights, (uint64_t)seed, first_frame, out, actions,
+                         rows, g.B, (int32_t)T, reset_first ? 1 : 0, current_stream()),
+           members ? "campx_wide_policy_population_launch" : "campx_wide_policy_update_launch");
+}
+
+// campx::wide_update with the action stream replaced by `policy` float32 [n_states, 5]; the actions taken
+// and - optionally - the rows they were sampled from come back as streams of the call's row pitch.
+void wide_policy_update(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                        const OptTensor& ret, const Tensor& policy, int64_t seed, int64_t first_frame,
+                        const OptTensor& reward, const OptTensor& discount,
+                        const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
+                        Tensor& actions_out, const OptTensor& states_out, const OptTensor& bad_count,
+                        const OptTensor& bad_flag, bool reset_first) {
+  closed_loop("campx::wide_policy_update", 2, 1, 0, spec_host, tables, state, done, ret, policy, seed,
+              first_frame, reward, discount, step_done, perf, trace, actions_out, states_out, bad_count,
+              bad_flag, reset_first);
+}
+
+// The same for `policy` float32 [P, n_states, 5], environment e sampling member e / (B / P); `states_out`
+// holds the flat row member * n_states + state.  `path`: 0 chosen by arithmetic, 1 LDS, 2 global.
+void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                            const OptTensor& ret, const Tensor& policy, int64_t seed,
+                            int64_t first_frame, const OptTensor& reward, const OptTensor& discount,
+                            const OptTensor& step_done, const OptTensor& perf, Tensor& trace,
+                            Tensor& actions_out, const OptTensor& states_out,
+                            const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                            int64_t path) {
+  closed_loop("campx::wide_policy_population", 3, policy.dim() == 3 ? policy.size(0) : 0, path,
+              spec_host, tables, state, done, ret, policy, seed, first_frame, reward, discount,
+              step_done, perf, trace, actions_out, states_out, bad_count, bad_flag, reset_first);
 }
 
 // Wide tier, online tabular learners (campx_wide_learn_launch): environment e learns on its own

@@ -1,4 +1,4 @@
-// wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_population,
+// wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_learn,
 // k_plan, k_visit, k_sums) agree on, each said once: the table entry's format, the policy-row rule,
 // the sampler's Philox block, the lazy error report, and the host's choice between one LDS
 // workgroup and one launch per step.
@@ -61,8 +61,8 @@ __device__ __forceinline__ float policy_row_total(const float (&w)[5]) {
   return good ? c4 : 0.0f;
 }
 
-// One Philox4x32-10 block: the sampler of the closed-loop rollouts (k_policy.hip and
-// k_population.hip; include/campx_hip.h has the rule).
+// One Philox4x32-10 block: the sampler of the closed-loop rollouts (k_policy.hip;
+// include/campx_hip.h has the rule).
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                               uint32_t k0, uint32_t k1, uint32_t* out) {
 #pragma unroll

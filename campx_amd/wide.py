@@ -347,6 +347,15 @@ class WideGame(fused.FusedGame):
     `out`: a dict from `rollout_policy_buffers(T, want_states)`, overwritten.
     """
     self._check_policy(policy)
+    return self._closed_loop(_hip.ops.wide_policy_update, (), self._bad_rows,
+                             'rollout_policy_buffers', policy, T, seed, first_frame, reset_first,
+                             out, want_states)
+
+  def _closed_loop(self, op, op_tail, bad_rows, made_by, policy, T, seed, first_frame, reset_first,
+                   out, want_states):
+    """What `rollout_policy()` and `rollout_population()` do once their policy is checked: T and
+    the frame counter, `out` (a dict from `made_by`), the launch of `op` - whose last arguments are
+    `op_tail` - with bad rows counted into `bad_rows`, and the tail."""
     T = int(T)
     if T < 1:
       raise ValueError('a rollout needs at least one frame: T >= 1')
@@ -357,20 +366,20 @@ class WideGame(fused.FusedGame):
     if out is None:
       out = self.rollout_policy_buffers(T, want_states)
     else:
-      rows = [out.get('actions')] + ([out.get('states')] if want_states else [])
-      trace = out.get('trace')
+      rows = ([out.get('actions')] + ([out.get('states')] if want_states else [])
+              if isinstance(out, dict) else [None])
+      trace = out.get('trace') if isinstance(out, dict) else None
       if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.shape[1] != T
           or any(not torch.is_tensor(r) or tuple(r.shape) != (T, self.batch)
                  or (T > 1 and r.stride(0) != trace.stride(1)) for r in rows)):
-        raise ValueError('out must be a dict from rollout_policy_buffers({}, want_states={}) of '
-                         'this game ({} environments)'.format(T, bool(want_states), self.batch))
+        raise ValueError('out must be a dict from {}({}, want_states={}) of '
+                         'this game ({} environments)'.format(made_by, T, bool(want_states), self.batch))
     validate = self.validate_actions
-    _hip.ops.wide_policy_update(
-        self._spec_host, self._tables, self.state, self.done, self.ret, policy.detach(),
-        seed - (1 << 64) if seed >= 1 << 63 else seed, first, out['reward'], out['discount'],
-        out['done'], out['perf'], out['trace'], out['actions'],
-        out.get('states') if want_states else None, self._bad_rows if validate else None,
-        self._bad_flag if validate else None, bool(reset_first))
+    op(self._spec_host, self._tables, self.state, self.done, self.ret, policy.detach(),
+       seed - (1 << 64) if seed >= 1 << 63 else seed, first, out['reward'], out['discount'],
+       out['done'], out['perf'], out['trace'], out['actions'],
+       out.get('states') if want_states else None, bad_rows if validate else None,
+       self._bad_flag if validate else None, bool(reset_first), *op_tail)
     self._policy_frame = first + T
     self.frame = T if reset_first else self.frame + T
     self.check_ok()
@@ -440,41 +449,13 @@ class WideGame(fused.FusedGame):
     `rollout_policy()`'s do, in a message that names this call.
     """
     P = self._check_population(policies)
-    T = int(T)
-    if T < 1:
-      raise ValueError('a rollout needs at least one frame: T >= 1')
-    first = self._policy_frame if first_frame is None else int(first_frame)
-    if first < 0 or first + T >= 1 << 63:
-      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
-    seed = int(seed) & ((1 << 64) - 1)
     self._planned_path(
         path, _hip.lib.campx_wide_population_plan, 1 if self.has_perf else 0, self.batch, P,
         what='a table of {} states with the thresholds of the members of one workgroup ({} environments '
              'per member)'.format(self.n_states, self.batch // P))
-    if out is None:
-      out = self.rollout_population_buffers(T, want_states)
-    else:
-      rows = ([out.get('actions')] + ([out.get('states')] if want_states else [])
-              if isinstance(out, dict) else [None])
-      trace = out.get('trace') if isinstance(out, dict) else None
-      if (not torch.is_tensor(trace) or trace.dim() != 3 or trace.shape[1] != T
-          or any(not torch.is_tensor(r) or tuple(r.shape) != (T, self.batch)
-                 or (T > 1 and r.stride(0) != trace.stride(1)) for r in rows)):
-        raise ValueError('out must be a dict from rollout_population_buffers({}, want_states={}) of '
-                         'this game ({} environments)'.format(T, bool(want_states), self.batch))
-    validate = self.validate_actions
-    _hip.ops.wide_policy_population(
-        self._spec_host, self._tables, self.state, self.done, self.ret, policies.detach(),
-        seed - (1 << 64) if seed >= 1 << 63 else seed, first, out['reward'], out['discount'],
-        out['done'], out['perf'], out['trace'], out['actions'],
-        out.get('states') if want_states else None, self._bad_member_rows if validate else None,
-        self._bad_flag if validate else None, bool(reset_first), path)
-    self._policy_frame = first + T
-    self.frame = T if reset_first else self.frame + T
-    self.check_ok()
-    if validate:
-      self._after_launch()
-    return out
+    return self._closed_loop(_hip.ops.wide_policy_population, (path,), self._bad_member_rows,
+                             'rollout_population_buffers', policies, T, seed, first_frame,
+                             reset_first, out, want_states)
 
   # ------------------------------------------------------------ online tabular learners
 

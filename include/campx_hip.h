@@ -763,17 +763,18 @@ int32_t campx_wide_policy_update_launch(const CampxWideSpec* spec_host, const vo
                                         int32_t reset_first, void* stream);
 /*
  * ---- Closed-loop rollouts of a population of policies -----------------------------------------
- * campx_wide_policy_update_launch() for `n_members` policies at once (csrc/k_population.hip):
- * `policy` is DEVICE float32 [n_members][n_states][5], B is a multiple of n_members, and with
- * n = B / n_members environment e belongs to member e / n - members own equal, contiguous blocks
- * of environments.  The sampling rule is the one above, word for word: the key is `seed`, the
- * counter (absolute environment e, absolute frame >> 2), and the row read for environment e in
- * state s is policy[e / n][s] (s = 0 after a done).  Everything written is what
+ * campx_wide_policy_update_launch() for `n_members` policies at once - the same kernel source,
+ * the same launch; the sampling rule, what is written, what is refused and the stream contract are
+ * the ones above.  The member rule: `policy` is DEVICE float32 [n_members][n_states][5], B is a
+ * multiple of n_members, and with n = B / n_members environment e belongs to member e / n -
+ * members own equal, contiguous blocks of environments; the counter stays (absolute environment e,
+ * absolute frame >> 2), and the row read for environment e in state s is policy[e / n][s] (s = 0
+ * after a done).  Everything written is what
  * campx_wide_policy_update_launch() writes, except `states_out`, which holds the FLAT row
  * (e / n) * n_states + s: the row of `policy` seen as [n_members * n_states][5] the action was
  * sampled from, so that campx_table_lookup_launch() and campx_state_sums_launch() (with n_states =
- * n_members * n_states) serve all members in one launch each.  With n_members = 1 the call writes
- * what campx_wide_policy_update_launch() writes, byte for byte.
+ * n_members * n_states) serve all members in one launch each.  With n_members = 1 the call IS
+ * campx_wide_policy_update_launch(): the same machine code, chosen by the same arithmetic.
  *
  * A lane per environment, 256 to a workgroup.  Two paths, `path`: 1 = a workgroup stages the table
  * in LDS and, beside it, the thresholds of only the members its 256 environments belong to; 2 =
@@ -790,8 +791,7 @@ int32_t campx_wide_policy_update_launch(const CampxWideSpec* spec_host, const vo
  * n_members < 1, B % n_members != 0, n_members * n_states >= 2^31, wide_lds_max < 0, a `path`
  * outside 0 .. 2, path 1 for what does not fit, plan_out NULL.
  * campx_wide_policy_population_launch() returns CAMPX_EINVAL, before anything is launched, for
- * the same and for everything campx_wide_policy_update_launch() refuses.  Asynchronous on
- * `stream`, no synchronisation, no allocation, no library state.
+ * the same and for everything campx_wide_policy_update_launch() refuses.
  */
 int32_t campx_wide_population_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t n_members,
                                    int64_t wide_lds_max, int32_t path, int64_t* plan_out);

@@ -1,5 +1,5 @@
 """Closed-loop rollouts of a population on the GPU: `WideGame.rollout_population()`
-(csrc/k_population.hip, `campx::wide_policy_population`) against tests/population_reference.py -
+(csrc/k_policy.hip, `campx::wide_policy_population`) against tests/population_reference.py -
 a host walk of the game's state table under P policies, byte for byte - and against
 `rollout_policy()`, member by member.
 
@@ -163,6 +163,32 @@ def test_population_rollouts_against_the_existing_kernel(name, B, P):
     for got, want in zip(end, _snapshot(fb)):
       assert _same(got.cpu().numpy(), want.cpu().numpy()), T
     start, first = end, first + T
+  fa.check_actions()
+  fb.check_actions()
+
+
+@pytest.mark.parametrize('path', [0, 2])
+@pytest.mark.parametrize('name', ['boat_race', 'maze'])
+def test_one_member_is_the_solo_call_at_a_real_shape(name, path):
+  """P = 1 runs the instances without members through the population's entry point: B = 257 (a
+  second workgroup of one lane), T = 11 from frame 3 (three skipped frames in front, a ragged last
+  chunk).  Every stream, the trace, 'states', state, done and ret are `rollout_policy()`'s, byte
+  for byte, on both paths; the plan stages one member."""
+  B, T, first = 257, 11, 3
+  a, b = _game(name, B), _game(name, B)
+  fa, fb = a.fused, b.fused
+  policy = torch.from_numpy(_policies(name, 1, fa.n_states)).cuda()
+  code, plan = _plan(fa, 1, path)
+  assert code == 0 and plan[0] == (path or 1) and plan[2:] == [256, 1]
+  # a start that is not the reset: the same 5 frames on both games
+  a.rollout_policy(policy[0], 5, seed=7, reset_first=True)
+  b.rollout_policy(policy[0], 5, seed=7, reset_first=True)
+  got = a.rollout_population(policy, T, seed=SEED, first_frame=first, path=path)
+  want = b.rollout_policy(policy[0], T, seed=SEED, first_frame=first)
+  _equal_dicts(got, want)
+  for x, y in zip(_snapshot(fa), _snapshot(fb)):
+    assert _same(x.cpu().numpy(), y.cpu().numpy())
+  assert fa._policy_frame == fb._policy_frame == first + T
   fa.check_actions()
   fb.check_actions()
 
