@@ -270,6 +270,21 @@ def reward_f32(reward):
   return np.float32(reward)
 
 
+def board_bytes(obs):
+  """The rendered board of an observation as uint8 character codes, row by row."""
+  return obs.board.detach().to(torch.int64).numpy().astype(np.uint8).tobytes()
+
+
+def start_probe(engine):
+  """A deep copy of the set-up `engine` on the generic tier, its Plot one that notices reads of
+  the frame number (`probe_plot_class`), put through `its_showtime()`: (probe, first observation)."""
+  probe = clone_engine(engine)
+  probe._batch, probe._device, probe._fused = None, None, None
+  probe._the_plot.__class__ = probe_plot_class(type(probe._the_plot))
+  obs, _, _ = probe.its_showtime()
+  return probe, obs
+
+
 class _Edge(object):
   __slots__ = ('next', 'reward', 'discount', 'over', 'board')
 
@@ -853,10 +868,7 @@ def _trace_once(engine, actions, max_plays, with_frame):
   if len(actions) != N_ACTIONS:
     raise ValueError('exactly {} actions are needed'.format(N_ACTIONS))
 
-  probe = clone_engine(engine)
-  probe._batch, probe._device, probe._fused = None, None, None
-  probe._the_plot.__class__ = probe_plot_class(type(probe._the_plot))
-  obs, _, _ = probe.its_showtime()
+  probe, obs = start_probe(engine)
   if probe.game_over:
     _fail('the episode is over after its_showtime()')
   # (reads of the frame number during the priming frame are not held against the game: every
@@ -878,7 +890,7 @@ def _trace_once(engine, actions, max_plays, with_frame):
   hiddens = [hidden0]        # per state: `hidden_image()`
   engines = [probe]          # an engine standing in that state, or None (only seen ended)
   second = {}                # state -> an engine that arrived there over another history
-  boards = [obs.board.detach().to(torch.int64).numpy().astype(np.uint8).tobytes()]
+  boards = [board_bytes(obs)]
   edges = {}
   queue = collections.deque([0])
   plays = [0]
@@ -917,8 +929,8 @@ def _trace_once(engine, actions, max_plays, with_frame):
     things, backdrop, z = _image(eng)
     over = bool(eng.game_over)
     discount = float(np.float32(discount))
-    board = obs.board.detach().to(torch.int64).numpy().astype(np.uint8).tobytes()
-    return (things, z, hidden_image(eng, with_frame), backdrop), reward_f32(reward), discount, over, board
+    return ((things, z, hidden_image(eng, with_frame), backdrop), reward_f32(reward), discount, over,
+            board_bytes(obs))
 
   while queue:
     s = queue.popleft()
@@ -969,10 +981,11 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
   """From the walked state graph to a `TracedGame`: `images[s]` (per-thing byte images, things in
   ascending character order), `orders[s]` (z-order string), `hiddens[s]` (`hidden_image()`),
   `boards[s]` (the rendered board's bytes) of every reached state, state 0 the one after
-  `its_showtime()` (`things0`, `backdrop0`, `z0`), and `edges[(s, a)]` = `_Edge`.  Shared by the
-  one-frame-per-play walker above and the many-states-per-call one (tabulate_batched.py)."""
+  `its_showtime()` (`things0`, `backdrop0`, `z0`), and `edges[(s, a)]` = `_Edge`.  The
+  one-frame-per-play walker's own: who moves, pieces / mask / variants, the modes, the cell of
+  every thing in every state and the board checks, a state at a time.  The tables themselves are
+  `_fill_tables`' business, which the many-states-per-call walker (tabulate_batched.py) calls too."""
   HW = H * W
-  plays = [n_plays]
   # ---- who moves
   order = sorted(probe.things.keys())                     # the order of _image()'s parts
   varying = [i for i in range(len(order))
@@ -1114,29 +1127,11 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
       mode_index[key] = len(modes)
       modes.append(key)
   state_mode = [mode_index[key] for key in mode_keys]
-  n_tracked = len(movers) + (1 if len(modes) > 1 else 0)
-  if not 1 <= len(movers) <= gamespec.WIDE_MAX_DYN and not pieces_as_mask:
-    _fail('needs between 1 and {} moving things, found {} ({})'.format(
-        gamespec.WIDE_MAX_DYN, len(movers), ''.join(movers) or 'nothing moves'))
+  if not pieces_as_mask:
+    _check_mover_count(movers)
   K = len(movers)
-  # Two table forms come out of a tabulation.  The STATE table - one row per reachable
-  # state, (state, action) -> state - always exists.  The DENSE table the one-cell tier's
-  # kernels index by the things' cells, (cell, ..., cell, action), only when it fits them:
-  dense_reason = None
-  if HW > gamespec.MAX_CELLS:
-    dense_reason = 'the board has more than {} cells'.format(gamespec.MAX_CELLS)
-  elif n_tracked > gamespec.MAX_DYN:
-    dense_reason = ('{} moving things{} are more than {} tracked values'.format(
-        K, ' plus the z-order in force' if len(modes) > 1 else '', gamespec.MAX_DYN))
-  elif len(modes) > HW:
-    dense_reason = ('{} different modes (z-orders x hidden values: {}) are reached, more than '
-                    'rows*cols'.format(len(modes), ', '.join(free_paths) or 'none'))
-  elif HW ** n_tracked * N_ACTIONS > DENSE_MAX_ENTRIES:
-    dense_reason = 'a table over {} cells ^ {} things has more than {} entries'.format(
-        HW, n_tracked, DENSE_MAX_ENTRIES)
-  if (any(in_backdrop) or len(variants) > 1 or pieces_as_mask) and dense_reason is None:
-    dense_reason = ('the scenery changes (a Backdrop that repaints itself, drapes of several cells that come '
-                    'and go): pieces the state names a mask of, or pictures it names the variant of')
+  dense_reason = _dense_reason(HW, K, len(modes), free_paths,
+                               any(in_backdrop) or len(variants) > 1 or pieces_as_mask)
 
   def where_is(s, k):
     """('at', cell) or ('absent', key): the one cell moving thing k occupies in state s, or - an
@@ -1185,21 +1180,7 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
     kind, what = places[k][s]
     return what if kind == 'at' else absent_alias[k][what]
 
-  game = TracedGame()
-  game.rows, game.cols, game.chars = H, W, chars
-  game.z_order = list(z0)
-  game.mode_orders = [list(key[0]) for key in modes]
-  game.hidden_paths = free_paths
-  game.frame_in_state = bool(with_frame)
-  game.backdrop = np.frombuffer(backdrop0, np.int64).astype(np.uint8).reshape(H, W)
-  game.movers = movers
-  game.piece_cell = piece_cell
-  game.in_backdrop = in_backdrop
-  game.variants = [np.frombuffer(b, np.int64).astype(np.uint8).reshape(H, W) for b in variants]
-  game.variant_masks = variant_masks
-  game.pieces_as_mask = pieces_as_mask
-  game.absent_cells = absent_cells
-  game.statics = []
+  statics = []
   for ch in schedule:
     if ch in movers[:n_thing_movers] or ch in folded:
       continue
@@ -1212,9 +1193,13 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
       mask = np.frombuffer(things0[order.index(ch)], np.uint8).reshape(H, W).copy()
       if mask.max() > 1:
         _fail('the curtain of {!r} holds values other than 0 and 1'.format(ch))
-    game.statics.append((ch, mask))
-  if len(game.statics) > gamespec.MAX_STATIC:
-    _fail('more than {} static things'.format(gamespec.MAX_STATIC))
+    statics.append((ch, mask))
+  game = _new_game(
+      H, W, chars, z0, backdrop0, movers, absent_cells, statics,
+      mode_orders=[list(key[0]) for key in modes], hidden_paths=free_paths, frame_in_state=bool(with_frame),
+      piece_cell=piece_cell, in_backdrop=in_backdrop, pieces_as_mask=pieces_as_mask,
+      variants=[np.frombuffer(b, np.int64).astype(np.uint8).reshape(H, W) for b in variants],
+      variant_masks=variant_masks)
 
   state_cells = [tuple(cell_of(s, k) for k in range(K)) +
                  ((state_mode[s],) if len(modes) > 1 else ())
@@ -1222,13 +1207,6 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
   if len(set(zip(state_cells, state_variant))) != len(state_cells):
     _fail('two reachable states have every moving thing on the same cells and the same mode '
           '(a thing that is "absent" in more ways than its free cells can name)')
-  game.init_cells = state_cells[0]
-  board0 = np.frombuffer(boards[0], np.uint8)
-  game.init_visible = [int(places[k][0][0] == 'at' and board0[state_cells[0][k]] == ord(ch))
-                       for k, ch in enumerate(movers)]
-  if places[0][0][0] != 'at' and dense_reason is None:
-    dense_reason = ('the first moving thing ({!r}) is not on the board after its_showtime()'
-                    .format(movers[0]))
 
   # ---- the render kernels lay ONE scenery row under the movers: no order may change it
   for m in range(1, len(modes)):
@@ -1245,94 +1223,181 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
       _fail('a rendered board is not "backdrop, then every thing in z-order" of the moving '
             'things\' cells')
 
-  # ---- hidden performance (examples/boat_race.py:117-151): classes of the watched mover
-  perf_of = None
+  # ---- the graph as arrays.  `edges` holds (s, 0..4) for every state in the order the walk's
+  # queue expanded them; a state the walk only ever saw ended has no edges.
+  S = len(images)
+  nxt = np.full((S, N_ACTIONS), -1, np.int64)
+  reward = np.full((S, N_ACTIONS), np.nan, np.float32)
+  over = np.zeros((S, N_ACTIONS), bool)
+  disc = np.ones((S, N_ACTIONS), np.float32)
+  queue_pos = np.full(S, S, np.int64)
+  for (s, a), e in edges.items():
+    nxt[s, a], reward[s, a], over[s, a], disc[s, a] = e.next, e.reward, e.over, e.discount
+  for at, s in enumerate(dict.fromkeys(s for s, _ in edges)):
+    queue_pos[s] = at
+  present = np.array([[kind == 'at' for kind, _ in seen] for seen in places], bool).T
+  return _fill_tables(game, engine, np.array(state_cells, np.int64).reshape(S, game.n_tracked), present,
+                      np.stack([np.frombuffer(b, np.uint8) for b in boards]),
+                      np.array(state_mode, np.int32), np.array(state_variant, np.uint16),
+                      nxt, reward, over, disc, queue_pos, dense_reason, n_plays)
+
+
+def _check_mover_count(movers):
+  if not 1 <= len(movers) <= gamespec.WIDE_MAX_DYN:
+    _fail('needs between 1 and {} moving things, found {} ({})'.format(
+        gamespec.WIDE_MAX_DYN, len(movers), ''.join(movers) or 'nothing moves'))
+
+
+def _dense_reason(HW, K, n_modes=1, free_paths=(), scenery_changes=False):
+  """Two table forms come out of a tabulation.  The STATE table - one row per reachable state,
+  (state, action) -> state - always exists.  The DENSE table the one-cell tier's kernels index by
+  the things' cells, (cell, ..., cell, action), only when it fits them: None, or why it does not."""
+  n_tracked = K + (1 if n_modes > 1 else 0)
+  if HW > gamespec.MAX_CELLS:
+    return 'the board has more than {} cells'.format(gamespec.MAX_CELLS)
+  if n_tracked > gamespec.MAX_DYN:
+    return '{} moving things{} are more than {} tracked values'.format(
+        K, ' plus the z-order in force' if n_modes > 1 else '', gamespec.MAX_DYN)
+  if n_modes > HW:
+    return ('{} different modes (z-orders x hidden values: {}) are reached, more than '
+            'rows*cols'.format(n_modes, ', '.join(free_paths) or 'none'))
+  if HW ** n_tracked * N_ACTIONS > DENSE_MAX_ENTRIES:
+    return 'a table over {} cells ^ {} things has more than {} entries'.format(
+        HW, n_tracked, DENSE_MAX_ENTRIES)
+  if scenery_changes:
+    return ('the scenery changes (a Backdrop that repaints itself, drapes of several cells that come '
+            'and go): pieces the state names a mask of, or pictures it names the variant of')
+  return None
+
+
+def _new_game(H, W, chars, z0, backdrop0, movers, absent_cells, statics, mode_orders=None,
+              hidden_paths=(), frame_in_state=False, piece_cell=None, in_backdrop=None,
+              pieces_as_mask=False, variants=None, variant_masks=None):
+  """A `TracedGame` with everything set that is not a table.  The defaults are the game of one
+  mode whose scenery never changes: one z-order, no hidden values, no pieces, one picture."""
+  game = TracedGame()
+  game.rows, game.cols, game.chars = H, W, chars
+  game.z_order = list(z0)
+  game.mode_orders = mode_orders or [list(z0)]
+  game.hidden_paths = list(hidden_paths)
+  game.frame_in_state = frame_in_state
+  game.backdrop = np.frombuffer(backdrop0, np.int64).astype(np.uint8).reshape(H, W)
+  game.movers = movers
+  game.piece_cell = piece_cell or [None] * len(movers)
+  game.in_backdrop = in_backdrop or [False] * len(movers)
+  game.variants = variants or [game.backdrop]
+  game.variant_masks = variant_masks or [{}]
+  game.pieces_as_mask = pieces_as_mask
+  game.absent_cells = absent_cells
+  game.statics = statics
+  if len(statics) > gamespec.MAX_STATIC:
+    _fail('more than {} static things'.format(gamespec.MAX_STATIC))
+  return game
+
+
+def _fill_tables(game, engine, state_cells, present, boards, state_mode, state_variant, nxt, reward,
+                 over, disc, queue_pos, dense_reason, n_plays):
+  """From a walked state graph, as arrays, to the tables of `game` (a `_new_game`) - for both
+  walkers, without a Python loop over states or edges.  Per state: `state_cells` int64 [S, Kt] (the
+  movers' cells - the alias of `absent_cells` for one that is nowhere - and, Kt = K + 1, the mode),
+  `present` bool [S, K], `boards` uint8 [S, HW], `state_mode` int32 [S], `state_variant` uint16
+  [S].  Per (state, action): `nxt` [S, 5] (-1: that edge was never played - a state the walk never
+  went on from), `reward` f32 (NaN = None), `over`, `disc` f32.  `queue_pos` [S]: the place of a
+  state in the order the walk expanded them, which with the action is the order edges are
+  discovered in.  Fills `init_cells`, `init_visible`, `dense_reason` (`dense_reason` so far, or
+  that the first mover starts absent), the state table `st_*`, `discount_list`, and - when
+  `dense_reason` stays None - the dense table; returns `game`."""
+  movers = game.movers
+  HW, K = game.rows * game.cols, len(movers)
+  S, Kt = state_cells.shape
+  rows = np.arange(S)
+  reached = nxt >= 0
+  nxt = np.where(reached, nxt, rows[:, None])               # never played: stay where you are
+  cells = state_cells[:, :K]
+  shows = present & (boards[rows[:, None], cells] == np.array([ord(ch) for ch in movers]))
+  game.init_cells = tuple(int(c) for c in state_cells[0])
+  game.init_visible = [int(v) for v in shows[0]]
+  if not present[0, 0] and dense_reason is None:
+    dense_reason = ('the first moving thing ({!r}) is not on the board after its_showtime()'
+                    .format(movers[0]))
+  game.dense_reason = dense_reason
+
+  # ---- hidden performance (examples/boat_race.py:117-151): classes of the cells the watched
+  # movers stand on - a level (the penalty), or a step round a cycle of classes
+  perf = np.zeros((S, N_ACTIONS), np.int64)
+  who = None
   if engine.hidden_penalty is not None:
-    who, masks, unit = engine.hidden_penalty
+    (who, masks, unit), what = engine.hidden_penalty, 'hidden penalty'
+  elif engine.hidden_performance is not None:
+    (agent, masks), what = engine.hidden_performance, 'hidden performance'
+    who = [agent]
+  if who is not None:
     for ch in who:
       if ch not in movers:
-        _fail('hidden penalty watches {!r}, which never moves'.format(ch))
+        _fail('{} watches {!r}, which never moves'.format(what, ch))
       if movers.count(ch) > 1:
-        _fail('hidden penalty watches {!r}, a drape of several cells'.format(ch))
-      if absent_cells[movers.index(ch)]:
-        _fail('hidden penalty watches {!r}, which leaves the board'.format(ch))
-    cls = np.zeros(HW, np.int32)
-    for k, m in enumerate(masks):
-      cls[np.flatnonzero(m.detach().cpu().numpy().reshape(-1))] = k + 1
-    watched = [movers.index(ch) for ch in who]
-
-    def perf_of(src, dst):
-      return int(unit) * sum(int(cls[dst[k]]) for k in watched)
-  elif engine.hidden_performance is not None:
-    agent, masks = engine.hidden_performance
-    if agent not in movers:
-      _fail('hidden performance watches {!r}, which never moves'.format(agent))
-    if movers.count(agent) > 1:
-      _fail('hidden performance watches {!r}, a drape of several cells'.format(agent))
-    if absent_cells[movers.index(agent)]:
-      _fail('hidden performance watches {!r}, which leaves the board'.format(agent))
-    cls = np.zeros(HW, np.int32)
-    for k, m in enumerate(masks):
-      cls[np.flatnonzero(m.detach().cpu().numpy().reshape(-1))] = k + 1
-    n_cls, who = len(masks), movers.index(agent)
-
-    def perf_of(src, dst):
-      a, b = int(cls[src[who]]), int(cls[dst[who]])
-      if a == 0 or b == 0:
-        return 0
-      fwd = 1 if a == n_cls else a + 1
-      back = n_cls if a == 1 else a - 1
-      return int(b == fwd) - int(b == back)
+        _fail('{} watches {!r}, a drape of several cells'.format(what, ch))
+      if game.absent_cells[movers.index(ch)]:
+        _fail('{} watches {!r}, which leaves the board'.format(what, ch))
+    cls = np.zeros(HW, np.int64)
+    for j, m in enumerate(masks):
+      cls[m.detach().cpu().numpy().reshape(-1) != 0] = j + 1
+    if engine.hidden_penalty is not None:
+      perf = int(unit) * sum(cls[cells[nxt, movers.index(ch)]] for ch in who)
+    else:
+      n_cls, k = len(masks), movers.index(agent)
+      a, b = cls[cells[:, k]][:, None], cls[cells[nxt, k]]
+      fwd = np.where(a == n_cls, 1, a + 1)
+      back = np.where(a == 1, n_cls, a - 1)
+      perf = np.where((a == 0) | (b == 0), 0, (b == fwd).astype(np.int64) - (b == back).astype(np.int64))
+    perf = np.where(reached, perf, 0)
+    ss, aa = np.nonzero((perf < -128) | (perf > 127))
+    if len(ss):
+      # (not through `Engine.set_hidden_penalty`, which keeps |unit * classes| within 112.)  The
+      # first such edge in discovery order, in the words numpy has for an int8 it cannot hold
+      i = np.lexsort((aa, queue_pos[ss]))[0]
+      raise OverflowError('Python integer {} out of bounds for int8'.format(perf[ss[i], aa[i]]))
 
   # ---- the state table: one row per reachable state
-  S = len(images)
-  codes = [ord(ch) for ch in movers]
-  game.dense_reason = dense_reason
-  game.st_cells = np.array([cells[:K] for cells in state_cells], np.uint16).reshape(S, K)
-  game.st_present = np.array([[places[k][s][0] == 'at' for k in range(K)] for s in range(S)],
-                             bool).reshape(S, K)
-  game.st_board = np.stack([np.frombuffer(b, np.uint8) for b in boards])
-  game.st_shows = np.zeros((S, K), np.uint8)
-  for k in range(K):
-    game.st_shows[:, k] = (game.st_present[:, k] &
-                           (game.st_board[np.arange(S), game.st_cells[:, k]] == codes[k]))
-  game.st_mode = np.array(state_mode, np.int32)
-  game.st_variant = np.array(state_variant, np.uint16)
-  game.st_next = np.tile(np.arange(S, dtype=np.int32)[:, None], (1, N_ACTIONS))
-  game.st_reward = np.full((S, N_ACTIONS), np.nan, np.float32)
-  game.st_done = np.zeros((S, N_ACTIONS), np.uint8)
-  game.st_discount = np.ones((S, N_ACTIONS), np.float32)
+  game.st_cells = cells.astype(np.uint16).reshape(S, K)
+  game.st_present = present.reshape(S, K).copy()
+  game.st_board = boards
+  game.st_shows = shows.astype(np.uint8)
+  game.st_mode = np.asarray(state_mode, np.int32)
+  game.st_variant = np.asarray(state_variant, np.uint16)
+  game.st_next = nxt.astype(np.int32)
+  game.st_reached = reached
+  game.st_reward = np.where(reached, reward, np.float32(np.nan)).astype(np.float32)
+  over = over.astype(bool) & reached
+  game.st_done = over.astype(np.uint8)
+  game.st_discount = np.where(reached, disc, np.float32(1.0)).astype(np.float32)
   game.st_dcode = np.zeros((S, N_ACTIONS), np.uint8)
-  game.st_perf = np.zeros((S, N_ACTIONS), np.int8)
-  game.st_reached = np.zeros((S, N_ACTIONS), bool)
+  game.st_perf = perf.astype(np.int8)
   game.discount_list = [1.0]          # code -> value; code 0 stands for the default
-  for (s, a), e in edges.items():
-    game.st_next[s, a] = e.next
-    game.st_reward[s, a] = e.reward
-    game.st_done[s, a] = int(e.over)
-    game.st_discount[s, a] = e.discount
-    if e.discount != (0.0 if e.over else 1.0):
-      if e.discount not in game.discount_list[1:]:
-        if len(game.discount_list) == 16:
-          _fail('more than 15 distinct discounts besides the default')
-        game.discount_list.append(e.discount)
-      game.st_dcode[s, a] = 1 + game.discount_list[1:].index(e.discount)
-    game.st_perf[s, a] = perf_of(state_cells[s], state_cells[e.next]) if perf_of else 0
-    game.st_reached[s, a] = True
-  game.any_reward = bool((~np.isnan(game.st_reward[game.st_reached])).any())
-  game.has_perf = perf_of is not None
+  special = reached & (game.st_discount != np.where(over, np.float32(0.0), np.float32(1.0)))
+  ss, aa = np.nonzero(special)
+  if len(ss):
+    # codes in the order the edges were discovered: states as they left the queue, actions 0..4
+    found = game.st_discount[ss, aa][np.lexsort((aa, queue_pos[ss]))]
+    values, first = np.unique(found, return_index=True)
+    for d in values[np.argsort(first)]:
+      if len(game.discount_list) == 16:
+        _fail('more than 15 distinct discounts besides the default')
+      game.st_dcode[special & (game.st_discount == d)] = len(game.discount_list)
+      game.discount_list.append(float(d))
+  game.any_reward = bool((~np.isnan(game.st_reward[reached])).any())
+  game.has_perf = who is not None
   game.perf_spec = engine.hidden_performance
   game.penalty_spec = engine.hidden_penalty
-  game.n_states, game.n_plays = S, plays[0]
+  game.n_states, game.n_plays = S, n_plays
 
   # ---- the dense table (one-cell tier), when the game fits it
   game.n = None
   if dense_reason is None:
-    Kt = n_tracked
     n = HW ** Kt * N_ACTIONS
     game.n = n
     game.next_cells = np.zeros((Kt, n), np.uint16)
-    game.visible = np.zeros((Kt, n), np.uint8)
+    game.visible = np.zeros((Kt, n), np.uint8)          # (the mode is never visible)
     game.reward = np.full((n,), np.nan, np.float32)
     game.done = np.zeros((n,), np.uint8)
     game.discount = np.ones((n,), np.float32)
@@ -1344,19 +1409,19 @@ def _finish(engine, probe, H, W, chars, with_frame, things0, backdrop0, z0, imag
     for k in range(Kt - 1, -1, -1):
       game.next_cells[k] = idx % HW
       idx = idx // HW
-    for (s, a), e in edges.items():
-      i = game.index_of(state_cells[s], a)
-      dst = state_cells[e.next]
-      for k in range(K):
-        game.next_cells[k, i] = dst[k]
-        game.visible[k, i] = game.st_shows[e.next, k]
-      if Kt > K:
-        game.next_cells[K, i] = dst[K]            # the mode: never visible
-      game.reward[i] = game.st_reward[s, a]
-      game.done[i] = game.st_done[s, a]
-      game.discount[i] = game.st_discount[s, a]
-      game.dcode[i] = game.st_dcode[s, a]
-      game.perf[i] = game.st_perf[s, a]
+    base = np.zeros(S, np.int64)
+    for k in range(Kt):
+      base = base * HW + state_cells[:, k]
+    for a in range(N_ACTIONS):
+      src = np.flatnonzero(reached[:, a])
+      i, t = base[src] * N_ACTIONS + a, nxt[src, a]
+      game.next_cells[:, i] = state_cells[t].T
+      game.visible[:K, i] = game.st_shows[t].T
+      game.reward[i] = game.st_reward[src, a]
+      game.done[i] = game.st_done[src, a]
+      game.discount[i] = game.st_discount[src, a]
+      game.dcode[i] = game.st_dcode[src, a]
+      game.perf[i] = game.st_perf[src, a]
       game.reached[i] = True
   return game
 

@@ -14,8 +14,9 @@ ONCE per action for the whole frontier - `Engine._update_and_render()` / `_apply
 themselves (campx/engine.py:168-293), on a deep copy of the user's engine whose drape curtains
 and rendered layers are `Lanes`.  Next states are keyed exactly (the cell of every one-cell
 drape; anything else is not this tier's game), deduplicated with sort / searchsorted, and numbered
-in the order the one-frame-per-play walker discovers them, so both walkers hand `tabulate._finish`
-the same graph and produce the same `TracedGame`.
+in the order the one-frame-per-play walker discovers them, so both walkers hand
+`tabulate._fill_tables` the same graph - this one as the arrays it walked on (`_finish_arrays`),
+the other from its per-state images (`tabulate._finish`) - and produce the same `TracedGame`.
 
 What this tier takes - checked, `CannotBatch` otherwise, and `tabulate.trace()` then falls back
 to the one-frame-per-play walk, which takes anything and says what is wrong with the rest:
@@ -392,14 +393,11 @@ def _trace_on_lanes(engine, actions, max_plays, device):
 
 
 def _trace(engine, actions, device, H, W, HW, chars):
-  probe = tabulate.clone_engine(engine)
-  probe._batch, probe._device, probe._fused = None, None, None
-  probe._the_plot.__class__ = tabulate.probe_plot_class(type(probe._the_plot))
-  obs, _, _ = probe.its_showtime()
+  probe, obs = tabulate.start_probe(engine)
   if probe.game_over:
     raise CannotBatch('the episode is over after its_showtime()')
-  things0, backdrop0, z0 = tabulate._image(probe)
-  hidden0 = tabulate.hidden_image(probe, False)
+  _, backdrop0, z0 = tabulate._image(probe)
+  tabulate.hidden_image(probe, False)                     # (refuses a game it cannot image)
   front = _Frontier(probe, actions, device)
   drapes = front.drapes                                   # ascending characters = _image()'s order
   start = {ch: (front.sprite_mask(ch, 1) if ch in front.sprites
@@ -429,23 +427,19 @@ def _trace(engine, actions, device, H, W, HW, chars):
   cells, nxt, reward, over, disc, queue_pos, boards, n_frames = graph
   game = _finish_arrays(engine, probe, chars, sorted(moving), start, cells.cpu().numpy(),
                         nxt.cpu().numpy(), reward.cpu().numpy(), over.cpu().numpy(), disc.cpu().numpy(),
-                        queue_pos.cpu().numpy(), boards.cpu().numpy(), n_frames, obs, things0,
-                        backdrop0, z0, actions)
+                        queue_pos.cpu().numpy(), boards.cpu().numpy(), n_frames, obs, backdrop0, z0, actions)
   game.batched_frames = n_frames
   return game
 
 
-def _fail(msg):
-  raise tabulate.TabulationError('cannot tabulate this game for the HIP tier: ' + msg)
-
-
 def _finish_arrays(engine, probe, chars, movers_sorted, start, cells, nxt, reward, over, disc,
-                   queue_pos, boards, n_frames, obs0, things0, backdrop0, z0, actions):
-  """`tabulate._finish` for the many-states-per-call walk, on arrays: the same `TracedGame`,
-  field for field (tests/test_tabulate_batched.py compares the two walkers' results), without a
-  Python loop over states - one z-order, no hidden values, drapes only, which is what this tier
-  takes.  cells [S, K] (HW: the mover's curtain is empty) in `movers_sorted` order; nxt [S, 5]
-  (-1: the state was never walked on from); boards uint8 [S, HW]."""
+                   queue_pos, boards, n_frames, obs0, backdrop0, z0, actions):
+  """From the walk's arrays to the `TracedGame`: what `tabulate._finish` does a state at a time
+  for the other walker, without a Python loop over states - one z-order, no hidden values, one-cell
+  drapes only, which is what this tier takes - and then the same `tabulate._fill_tables`.  cells
+  [S, K] (HW: the mover's curtain is empty) in `movers_sorted` order; nxt [S, 5] (-1: the state was
+  never walked on from); boards uint8 [S, HW].  `CannotBatch` - the other walker's game after all -
+  for a first board or a start the lanes do not describe, and from `_cross_check`'s replayed sample."""
   H, W = probe.rows, probe.cols
   HW = H * W
   S = cells.shape[0]
@@ -455,25 +449,14 @@ def _finish_arrays(engine, probe, chars, movers_sorted, start, cells, nxt, rewar
     schedule.extend(ent.character for ent in members)
   movers = [ch for ch in schedule if ch in movers_sorted]
   K = len(movers)
-  if not 1 <= K <= gamespec.WIDE_MAX_DYN:
-    _fail('needs between 1 and {} moving things, found {} ({})'.format(
-        gamespec.WIDE_MAX_DYN, K, ''.join(movers) or 'nothing moves'))
+  tabulate._check_mover_count(movers)
   cells = cells[:, [movers_sorted.index(ch) for ch in movers]]          # schedule order
-  if boards[0].tobytes() != obs0.board.detach().to(torch.int64).numpy().astype(np.uint8).tobytes():
+  if boards[0].tobytes() != tabulate.board_bytes(obs0):
     raise CannotBatch('the lanes renderer disagrees with the generic tier on the first board')
   start_np = {ch: start[ch][0].cpu().numpy().astype(np.uint8) for ch in drapes}
   for k, ch in enumerate(movers):
     if start_np[ch].sum() > 1:
       raise CannotBatch('moving drape {!r} covers more than one cell at the start'.format(ch))
-
-  dense_reason = None
-  if HW > gamespec.MAX_CELLS:
-    dense_reason = 'the board has more than {} cells'.format(gamespec.MAX_CELLS)
-  elif K > gamespec.MAX_DYN:
-    dense_reason = '{} moving things are more than {} tracked values'.format(K, gamespec.MAX_DYN)
-  elif HW ** K * N_ACTIONS > tabulate.DENSE_MAX_ENTRIES:
-    dense_reason = 'a table over {} cells ^ {} things has more than {} entries'.format(
-        HW, K, tabulate.DENSE_MAX_ENTRIES)
 
   # a mover that is nowhere (an empty curtain) stands on a cell index it never occupies
   present = cells < HW
@@ -484,36 +467,17 @@ def _finish_arrays(engine, probe, chars, movers_sorted, start, cells, nxt, rewar
       used = np.unique(cells[present[:, k], k])
       free = np.setdiff1d(np.arange(HW), used)
       if len(free) < 1:
-        _fail('{!r} has 1 different states in which it is not on the board; there is room '
-              'for 0'.format(ch))
+        tabulate._fail('{!r} has 1 different states in which it is not on the board; there is room '
+                       'for 0'.format(ch))
       st_cells[gone, k] = free[0]
       absent_cells.append({int(free[0])})
     else:
       absent_cells.append(set())
 
-  game = tabulate.TracedGame()
-  game.rows, game.cols, game.chars = H, W, chars
-  game.z_order = list(z0)
-  game.mode_orders = [list(z0)]
-  game.hidden_paths = []
-  game.frame_in_state = False
-  game.backdrop = np.frombuffer(backdrop0, np.int64).astype(np.uint8).reshape(H, W)
-  game.movers = movers
-  game.piece_cell = [None] * K          # (drapes of several cells go to the one-frame-per-play walker)
-  game.in_backdrop = [False] * K
-  game.variants = [game.backdrop]       # (a Backdrop with an update() of its own goes to the other walker too)
-  game.variant_masks = [{}]
-  game.pieces_as_mask = False
-  game.absent_cells = absent_cells
-  game.statics = [(ch, start_np[ch].copy()) for ch in schedule if ch not in movers]
-  if len(game.statics) > gamespec.MAX_STATIC:
-    _fail('more than {} static things'.format(gamespec.MAX_STATIC))
-  game.init_cells = tuple(int(c) for c in st_cells[0])
-  game.init_visible = [int(present[0, k] and boards[0, st_cells[0, k]] == ord(ch))
-                       for k, ch in enumerate(movers)]
-  if not present[0, 0] and dense_reason is None:
-    dense_reason = ('the first moving thing ({!r}) is not on the board after its_showtime()'
-                    .format(movers[0]))
+  # (no pieces, one picture: drapes of several cells and a Backdrop with an update() of its own
+  # go to the one-frame-per-play walker)
+  game = tabulate._new_game(H, W, chars, z0, backdrop0, movers, absent_cells,
+                            [(ch, start_np[ch].copy()) for ch in schedule if ch not in movers])
 
   # ---- every reached board is "backdrop + things in z-order" of the cells alone
   model = np.broadcast_to(game.backdrop.reshape(-1), (S, HW)).copy()
@@ -527,112 +491,11 @@ def _finish_arrays(engine, probe, chars, movers_sorted, start, cells, nxt, rewar
     else:
       model[:, static[ch].reshape(-1) != 0] = ord(ch)
   if not np.array_equal(model, boards):
-    _fail('a rendered board is not "backdrop, then every thing in z-order" of the moving '
-          'things\' cells')
+    tabulate._fail('a rendered board is not "backdrop, then every thing in z-order" of the moving '
+                   'things\' cells')
 
-  # ---- hidden performance (examples/boat_race.py:117-151): classes of the watched mover
-  walked = nxt[:, 0] >= 0
-  nxt_safe = np.where(nxt >= 0, nxt, np.arange(S)[:, None])
-  perf = np.zeros((S, N_ACTIONS), np.int64)
-  has_perf = False
-  if engine.hidden_penalty is not None or engine.hidden_performance is not None:
-    has_perf = True
-    if engine.hidden_penalty is not None:
-      who, masks, unit = engine.hidden_penalty
-      what = 'hidden penalty'
-    else:
-      agent, masks = engine.hidden_performance
-      who, what = [agent], 'hidden performance'
-    for ch in who:
-      if ch not in movers:
-        _fail('{} watches {!r}, which never moves'.format(what, ch))
-      if absent_cells[movers.index(ch)]:
-        _fail('{} watches {!r}, which leaves the board'.format(what, ch))
-    cls = np.zeros(HW + 1, np.int64)
-    for j, m in enumerate(masks):
-      cls[:HW][m.detach().cpu().numpy().reshape(-1) != 0] = j + 1
-    if engine.hidden_penalty is not None:
-      for ch in who:
-        perf += int(unit) * cls[st_cells[nxt_safe, movers.index(ch)]]
-    else:
-      n_cls, k = len(masks), movers.index(who[0])
-      a = cls[st_cells[:, k]][:, None]
-      b = cls[st_cells[nxt_safe, k]]
-      fwd = np.where(a == n_cls, 1, a + 1)
-      back = np.where(a == 1, n_cls, a - 1)
-      perf = np.where((a == 0) | (b == 0), 0, (b == fwd).astype(np.int64) - (b == back).astype(np.int64))
-
-  # ---- the state table
-  codes = np.array([ord(ch) for ch in movers])
-  game.dense_reason = dense_reason
-  game.st_cells = st_cells.astype(np.uint16).reshape(S, K)
-  game.st_present = present.reshape(S, K).copy()
-  game.st_board = boards
-  game.st_shows = (present & (boards[rows[:, None], st_cells] == codes[None, :])).astype(np.uint8)
-  game.st_mode = np.zeros(S, np.int32)
-  game.st_variant = np.zeros(S, np.uint16)
-  game.st_next = nxt_safe.astype(np.int32)
-  game.st_reached = np.broadcast_to(walked[:, None], (S, N_ACTIONS)).copy()
-  game.st_reward = np.where(game.st_reached, reward, np.float32(np.nan)).astype(np.float32)
-  over = over.astype(bool) & game.st_reached                 # [S, 5]: per state since the frames may split
-  game.st_done = over.astype(np.uint8)
-  disc = disc.astype(np.float32)
-  game.st_discount = np.where(game.st_reached, disc, np.float32(1.0)).astype(np.float32)
-  game.st_dcode = np.zeros((S, N_ACTIONS), np.uint8)
-  game.discount_list = [1.0]
-  special = game.st_reached & (game.st_discount != np.where(over, np.float32(0.0), np.float32(1.0)))
-  if special.any():
-    # codes in the order the one-frame walker meets them: states as they leave its queue, actions 0..4
-    ss, aa = np.nonzero(special)
-    for i in np.lexsort((aa, queue_pos[ss])):
-      d = float(game.st_discount[ss[i], aa[i]])
-      if d not in game.discount_list[1:]:
-        if len(game.discount_list) == 16:
-          _fail('more than 15 distinct discounts besides the default')
-        game.discount_list.append(d)
-    for code, d in enumerate(game.discount_list[1:], 1):
-      game.st_dcode[special & (game.st_discount == np.float32(d))] = code
-  game.st_perf = np.where(game.st_reached, perf, 0).astype(np.int8)
-  game.any_reward = bool((~np.isnan(game.st_reward[game.st_reached])).any())
-  game.has_perf = has_perf
-  game.perf_spec = engine.hidden_performance
-  game.penalty_spec = engine.hidden_penalty
-  game.n_states, game.n_plays = S, n_frames
-
-  # ---- the dense table (one-cell tier), when the game fits it
-  game.n = None
-  if dense_reason is None:
-    n = HW ** K * N_ACTIONS
-    game.n = n
-    game.next_cells = np.zeros((K, n), np.uint16)
-    game.visible = np.zeros((K, n), np.uint8)
-    game.reward = np.full((n,), np.nan, np.float32)
-    game.done = np.zeros((n,), np.uint8)
-    game.discount = np.ones((n,), np.float32)
-    game.dcode = np.zeros((n,), np.uint8)
-    game.perf = np.zeros((n,), np.int8)
-    game.reached = np.zeros((n,), bool)
-    idx = np.arange(n) // N_ACTIONS
-    for k in range(K - 1, -1, -1):
-      game.next_cells[k] = idx % HW
-      idx = idx // HW
-    base = np.zeros(S, np.int64)
-    for k in range(K):
-      base = base * HW + st_cells[:, k]
-    src = np.flatnonzero(walked)
-    for a in range(N_ACTIONS):
-      i = base[src] * N_ACTIONS + a
-      t = nxt_safe[src, a]
-      for k in range(K):
-        game.next_cells[k, i] = st_cells[t, k]
-        game.visible[k, i] = game.st_shows[t, k]
-      game.reward[i] = game.st_reward[src, a]
-      game.done[i] = game.st_done[src, a]
-      game.discount[i] = game.st_discount[src, a]
-      game.dcode[i] = game.st_dcode[src, a]
-      game.perf[i] = game.st_perf[src, a]
-      game.reached[i] = True
-
+  tabulate._fill_tables(game, engine, st_cells, present, boards, np.zeros(S, np.int32), np.zeros(S, np.uint16),
+                        nxt, reward, over, disc, queue_pos, tabulate._dense_reason(HW, K), n_frames)
   _cross_check(probe, actions, drapes, movers, start_np, cells, present, nxt, reward, over, disc, boards)
   return game
 
@@ -836,7 +699,7 @@ def _cross_check(probe, actions, drapes, movers, start_np, cells, present, nxt, 
     obs, got_reward, discount = eng.play(copy.deepcopy(actions[a]))
     t = int(nxt[s, a])
     ok = (bool(eng.game_over) == bool(over[s, a]) and float(np.float32(discount)) == float(disc[s, a]) and
-          obs.board.detach().to(torch.int64).numpy().astype(np.uint8).tobytes() == boards[t].tobytes() and
+          tabulate.board_bytes(obs) == boards[t].tobytes() and
           np.array([tabulate.reward_f32(got_reward)]).view(np.uint32)[0] ==
           np.array([np.float32(reward[s, a])]).view(np.uint32)[0])
     for ch in drapes:
