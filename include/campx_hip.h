@@ -747,7 +747,9 @@ int32_t campx_wide_update_launch(const CampxWideSpec* spec_host, const void* tab
  * An action of weight exactly 0 is never taken; a one-hot row is a deterministic policy.  A row
  * with a negative or NaN weight, or whose c4 is not a positive finite number, is BAD: the
  * environment-frame that meets it takes action 4 and is counted into out.bad_count / out.bad_flag,
- * as an action id outside 0..4 is.
+ * as an action id outside 0..4 is.  A subnormal weight is a good weight - nothing is flushed: a row
+ * of subnormal weights has a subnormal c4, and r = u * c4 is compared as the subnormal it is -
+ * and -0.0 is not negative; finite weights whose c4 overflows to infinity make a bad row.
  *
  * Writes what campx_wide_update_launch() writes (state, trace with every plane, the per-frame
  * scalars, same row pitch), plus `actions_out` DEVICE int8 [T][pitch] - the actions taken - and,
@@ -823,7 +825,8 @@ int32_t campx_wide_policy_population_launch(const CampxWideSpec* spec_host, cons
  *   3. u = float(x0 >> 8) * 2^-24; the learner explores iff u < epsilon[e], and then takes the
  *      action ((x1 >> 8) * 5) >> 24, an integer in 0 .. 4; otherwise the greedy action of
  *      q[e][s]: best = q0; for a = 1 .. 4: if (q[a] > best) best = q[a] - the lowest index wins a
- *      tie, NaN never wins.
+ *      tie (among several +inf too), a NaN at a = 1 .. 4 never wins, and a NaN q0 is never
+ *      displaced (no comparison with it holds): the action is then 0 and `best` that NaN.
  *   4. Entry (s, a) of the table: n, r (NaN - "None" - counted as 0, here, in `ret` and in
  *      reward_sum), d and D exactly as in the rule of campx_wide_sweeps_launch() below.
  *   5. The bootstrap b, from q[e][n] as it stands BEFORE this frame's update (which matters when
@@ -832,6 +835,9 @@ int32_t campx_wide_policy_population_launch(const CampxWideSpec* spec_host, cons
  *      b = (keep * best) + (epsilon[e] * m) with keep = 1.0f - epsilon[e].
  *   6. target = d ? r : r + (gamma[e] * D) * b.
  *   7. delta = target - q[e][s][a];  q[e][s][a] = q[e][s][a] + alpha[e] * delta.
+ *      q may hold any float32: subnormals are kept, zeros keep their sign, an infinity or a NaN
+ *      in q propagates through 5 - 7, `0 * inf` and `inf - inf` are NaN and are written as such
+ *      (the payload and sign of a generated NaN are unspecified).
  *   8. Per window of `window` frames, counted from the launch's frame 0 (the last may be short),
  *      row w of three DEVICE [W][B] arrays, W = ceil(T / window): reward_sum float32 - r added in
  *      frame order, from 0 -, perf_sum int32 - the entries' hidden performance; NULL when not
@@ -1007,7 +1013,10 @@ int32_t campx_wide_render_windows_plan(int64_t N, int32_t Rw, int32_t obs_format
  *     v_next = t == T-1 ? bootstrap[e] : values[t+1]
  *     delta  = (done[t] ? r : r + c * v_next) - values[t]
  *     A[t]   = done[t] ? delta : delta + (c * lam) * A_next        (A_next = 0 past the last frame)
- * G goes to `returns`, A to `advantages`.
+ * G goes to `returns`, A to `advantages`.  This holds over all of float32: subnormals are kept
+ * (nothing is flushed) and zeros keep their sign.  Only a NaN REWARD counts as 0: a NaN in `values`
+ * or `bootstrap` propagates, as does an infinity; `0 * inf` is NaN and is written as such, up to
+ * the next frame whose `done` is set.  The payload and sign of a generated NaN are unspecified.
  *
  * Every stream is DEVICE memory, rows contiguous, frame t's row `*_pitch` elements after frame
  * t-1's (>= B; the padded rows of the rollout buffers are fine, each stream may have its own).
@@ -1156,7 +1165,12 @@ int32_t campx_table_lookup_launch(const CampxTableLookup* lookup, int64_t B, int
  * *bad_rows (DEVICE int32, added to, may be NULL) once per call, and *bad_flag (device or mapped
  * pinned int32, may be NULL) is set to 1.
  * Greedy reduction (`policy` NULL): v'[s] = max over a of q[s][a], found as  best = q0; for a = 1
- * .. 4: if (q[a] > best) best = q[a]  - so the greedy action is the lowest a attaining it.
+ * .. 4: if (q[a] > best) best = q[a]  - so the greedy action is the lowest a attaining it (among
+ * several +inf too); a NaN at a = 1 .. 4 never wins, a NaN q0 is never displaced.
+ * All of this holds over all of float32: subnormals are kept (nothing is flushed, the division by
+ * a subnormal c4 included), zeros keep their sign, a NaN or an infinity in `v_in` propagates,
+ * `0 * inf` and `inf - inf` are NaN and are written as such; the payload and sign of a generated
+ * NaN are unspecified.
  *
  * Sweeps are Jacobi.  With v_0 = `v_in`, for k = 1 .. n_sweeps:
  *     q_k = the backup of v_{k-1}        v_k = the reduction of q_k

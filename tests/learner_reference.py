@@ -69,8 +69,9 @@ class Learners(object):
   def learn(self, T, alpha=0.1, gamma=0.99, epsilon=0.1, rule='q', seed=0, first_frame=None,
             reset_first=False, window=None, record=False):
     """-> dict(reward_sum float32 [W, B], perf_sum int32 [W, B], episodes int32 [W, B], bad: the bad
-    learners, explored [T, B] bool, and - `record` - states, actions [T, B]); `q`, `state`, `over`,
-    `ret` and `frame` carry over."""
+    learners, explored [T, B] bool, and - `record` - states, actions [T, B] and the float32 [T, B]
+    intermediates delta and step = alpha * delta); `q`, `state`, `over`, `ret` and `frame` carry
+    over."""
     assert rule in RULES
     g, B, q = self.game, self.B, self.q
     window = T if window is None else int(window)
@@ -85,6 +86,7 @@ class Learners(object):
                explored=np.zeros((T, B), bool))
     if record:
       out['states'], out['actions'] = np.zeros((T, B), np.int32), np.zeros((T, B), np.int8)
+      out['delta'], out['step'] = np.zeros((T, B), F), np.zeros((T, B), F)
     if reset_first:
       self.over[:] = True
     with np.errstate(all='ignore'):
@@ -117,7 +119,8 @@ class Learners(object):
         target = np.where(done, r, (r + (c * b).astype(F)).astype(F)).astype(F)
         old = q[lanes, s, a]
         delta = (target - old).astype(F)
-        fresh = (old + (alpha * delta).astype(F)).astype(F)
+        step = (alpha * delta).astype(F)
+        fresh = (old + step).astype(F)
         q[lanes, s, a] = np.where(bad, old, fresh)
         out['reward_sum'][w] = (out['reward_sum'][w] + r).astype(F)
         out['perf_sum'][w] += g.st_perf[s, a].astype(np.int32)
@@ -125,6 +128,7 @@ class Learners(object):
         out['explored'][t] = explore & ~bad
         if record:
           out['states'][t], out['actions'][t] = s, a
+          out['delta'][t], out['step'][t] = delta, step
         self.ret = (np.where(self.over, F(0), self.ret).astype(F) + r).astype(F)
         self.state = n
         self.over = done

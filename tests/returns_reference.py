@@ -44,7 +44,7 @@ def inputs(T, B, seed=0):
   0.25 behind T <= 100 factors of 0.99 * 0.5): rewards from {-1, -0.25, 0, 0.5, 1, 3} with 5 %
   NaN, discounts from {1, 0.5, 0}, values and bootstrap uniform in [-2, 2], done with probability
   0.1 - and, where the batch has room, columns forced all-done, never-done, done only at t = 0 and
-  done only at t = T - 1."""
+  done only at t = T - 1.  (Subnormals, signed zeros, overflow and NaN: tests/float_edges.py.)"""
   rng = np.random.RandomState(1000 * T + B + seed)
   reward = rng.choice(np.array([-1, -0.25, 0, 0.5, 1, 3], dtype=F), size=(T, B))
   reward[rng.random_sample((T, B)) < 0.05] = np.nan

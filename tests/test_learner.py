@@ -4,6 +4,8 @@ under the rule of include/campx_hip.h - bit for bit: q, the three window tensors
 
 The games are test_policy_rollout.py's: boat_race (8 states, hidden performance: q in LDS), maze
 (159 states: q through L1 / L2, the entries in LDS), pickups (470 states, episodes that end).
+Hyper-parameters and tables are ordinary numbers; tests/test_float_edges.py runs the learners on
+subnormals, signed zeros, infinities and NaN.
 """
 
 import ctypes

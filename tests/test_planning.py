@@ -8,7 +8,8 @@ tests/test_wide_table_fuzz.py.  Sizes: one state, the kernels' thread counts eit
 256, 257; 1 023, 1 025: one state per thread of the LDS workgroup, and two), the plan's largest
 table in LDS and the next, for either reduction.  Every case runs both forced paths where the
 table fits LDS, so the two kernels are also checked against each other.  Inputs are finite and
-away from subnormals (weights >= 2^-20 or exactly 0).
+away from subnormals (weights >= 2^-20 or exactly 0); tests/test_float_edges.py holds the same
+kernels to the rule at subnormals, signed zeros, overflow and NaN.
 """
 
 import ctypes

@@ -17,6 +17,9 @@ The games:
   * variants    tests/random_pickups.py definition 12 (test_render_states.py's), a tide that turns
                 the whole floor: the scenery comes in VARIANTS, and which one shows is the trace's
                 second plane (two planes, no discount codes: the K = 2 plain chunks, in LDS).
+
+The weights here are ordinary numbers; tests/test_float_edges.py samples rows of subnormal, -0.0
+and FLT_MAX weights.
 """
 
 import re

@@ -4,7 +4,8 @@ bits.  Shapes: every T of {1, 7, 8, 9, 100} - both sides of the kernel's 8-frame
 many chunks - at B = 257, and every B of {1, 63, 64, 65, 257, 4 099} - both sides of a wave, more
 than one 256-lane block, sixteen blocks and a tail - at T = 9.  Inputs dense and as padded views
 (the streams of `rollout_trace_buffers()`, every other tensor with a pitch of its own); every
-combination of discount / values / bootstrap present or None; lam 1.0, 0.95 and 0.0."""
+combination of discount / values / bootstrap present or None; lam 1.0, 0.95 and 0.0.  The inputs
+are ordinary numbers; tests/test_float_edges.py has the subnormals, signed zeros, overflow and NaN."""
 
 import functools
 import itertools

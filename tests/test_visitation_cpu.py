@@ -17,7 +17,7 @@ import wide_table_reference as ref
 F = np.float32
 UNIT = 1 << 38
 WORDS = 1 << 24
-SUB = 2.0 ** -140                 # a float32 subnormal
+SUB = 2.0 ** -140                 # a float32 subnormal (on the GPU: tests/test_float_edges.py)
 
 ROWS = {
     'random': [0.731, 1.914, 0.502, 1.333, 0.871],
