@@ -465,6 +465,11 @@ inline TupleParams make_tuple_params(const CampxSpec& s) {
 // campx_api.hip
 extern thread_local int32_t g_last_hip_error;
 int32_t hip_failed(hipError_t e);
+// What a launcher returns once its kernel is launched: CAMPX_OK, or the launch's error.
+inline int32_t launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+}
 // The library's settings (campx_api.hip holds the table: name, default, range, what each selects;
 // campx_config_set / _get / _string in include/campx_hip.h).  Read at every use - a plain load.
 enum Knob : int {
@@ -611,17 +616,8 @@ struct GatherPlan {
 GatherPlan gather_plan(int64_t N, int64_t R, int fmt, uint64_t dst_addr);
 int32_t gather_check(const CampxGather* g, int64_t B, int64_t R, int64_t n_planes, int entry_bytes);
 int32_t launch_gather_from(const RenderSource& src, const CampxGather& g, int64_t B, hipStream_t stream);
-// k_wide.hip
+// k_wide.hip (the state-table blob and its view: wide_table.hip.h)
 RenderSource wide_render_source(const CampxWideSpec& s, const void* tables_dev);
-// where the parts of the state-table blob are (campx_wide_tables_build() lays it out)
-struct WideLayout {
-  int64_t n_entries, cells_off, perf_off, rot_obs_off, rot_board_off, pieces_off, total;
-  int pitch_obs, pitch_board;
-  int n_variants;          // sets of rotations (1: the scenery never changes)
-  int n_planes;            // planes of the trace: the things, plus the variant's when there are several,
-                           // or the mask of the pieces that show
-};
-WideLayout wide_layout(const CampxWideSpec& s);
 int32_t wide_validate_plain(const CampxWideSpec* s);
 
 }  // namespace campx_impl

@@ -271,6 +271,17 @@ __global__ __launch_bounds__(kLearnThreads) void wide_learn_kernel(
   }
 }
 
+// The twelve instances, at [where q and the table are][kPerf][kSarsa]: 0 both read through the
+// caches, 1 the table in LDS, 2 q and the table in LDS.  (q in LDS without the table does not exist.)
+using LearnKernel = decltype(&wide_learn_kernel<false, false, false, false>);
+static const LearnKernel kLearnKernels[3][2][2] = {
+    {{wide_learn_kernel<false, false, false, false>, wide_learn_kernel<false, false, false, true>},
+     {wide_learn_kernel<false, false, true, false>, wide_learn_kernel<false, false, true, true>}},
+    {{wide_learn_kernel<false, true, false, false>, wide_learn_kernel<false, true, false, true>},
+     {wide_learn_kernel<false, true, true, false>, wide_learn_kernel<false, true, true, true>}},
+    {{wide_learn_kernel<true, true, false, false>, wide_learn_kernel<true, true, false, true>},
+     {wide_learn_kernel<true, true, true, false>, wide_learn_kernel<true, true, true, true>}}};
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -306,49 +317,25 @@ int32_t campx_wide_learn_launch(const CampxWideSpec* s, const void* tables_dev, 
   const int32_t planned = plan_learn(s->n_states, l->perf_sum ? 1 : 0, B, knob(K_WIDE_LDS_MAX),
                                      l->path, &plan, nullptr);
   if (planned != CAMPX_OK) return planned;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const WideLayout w = wide_layout(*s);
+  const WideTables t = wide_tables(*s, tables_dev);
   LearnParams pp;
   memset(&pp, 0, sizeof(pp));
   pp.n_states = s->n_states;
   pp.window = l->window;
-  pp.discounts[0] = 1.0f;
-  for (int i = 1; i < 16; ++i) pp.discounts[i] = s->discount_list[i];
+  wide_discounts(*s, pp.discounts);
   pp.key0 = (uint32_t)l->seed;
   pp.key1 = (uint32_t)(l->seed >> 32);
   pp.first_frame = l->first_frame;
-  const char* blob = static_cast<const char*>(tables_dev);
-  const uint2* entries = reinterpret_cast<const uint2*>(blob);
-  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
-  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
   const size_t lds = (size_t)plan.lds_bytes;
-  const dim3 grid((unsigned)((B + kLearnThreads - 1) / kLearnThreads));
-#define CAMPX_LEARN_LAUNCH(QLDS, TLDS, PERF, SARSA)                                               \
-  do {                                                                                            \
-    CAMPX_ALLOW_LDS((wide_learn_kernel<QLDS, TLDS, PERF, SARSA>), lds);                           \
-    hipLaunchKernelGGL((wide_learn_kernel<QLDS, TLDS, PERF, SARSA>), grid, dim3(kLearnThreads),   \
-                       lds, hs, pp, entries, perf, l->q, l->alpha, l->gamma, l->epsilon, state,   \
-                       st, l->reward_sum, l->perf_sum, l->episodes, l->bad_count, l->bad_flag, B, \
-                       T, l->reset_first);                                                        \
-  } while (0)
-#define CAMPX_LEARN_LAUNCH2(QLDS, TLDS, PERF)                                        \
-  do {                                                                               \
-    if (l->rule == CAMPX_LEARN_EXPECTED_SARSA) CAMPX_LEARN_LAUNCH(QLDS, TLDS, PERF, true); \
-    else CAMPX_LEARN_LAUNCH(QLDS, TLDS, PERF, false);                                \
-  } while (0)
-#define CAMPX_LEARN_LAUNCH3(QLDS, TLDS)                      \
-  do {                                                       \
-    if (l->perf_sum) CAMPX_LEARN_LAUNCH2(QLDS, TLDS, true);  \
-    else CAMPX_LEARN_LAUNCH2(QLDS, TLDS, false);             \
-  } while (0)
-  if (plan.path == 1) CAMPX_LEARN_LAUNCH3(true, true);
-  else if (plan.table_in_lds) CAMPX_LEARN_LAUNCH3(false, true);
-  else CAMPX_LEARN_LAUNCH3(false, false);
-#undef CAMPX_LEARN_LAUNCH3
-#undef CAMPX_LEARN_LAUNCH2
-#undef CAMPX_LEARN_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  const LearnKernel kernel = kLearnKernels[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)]
+                                          [l->perf_sum != nullptr][l->rule == CAMPX_LEARN_EXPECTED_SARSA];
+  CAMPX_ALLOW_LDS(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kLearnThreads - 1) / kLearnThreads)),
+                     dim3(kLearnThreads), lds, static_cast<hipStream_t>(stream), pp, t.entries, t.perf,
+                     l->q, l->alpha, l->gamma, l->epsilon, reinterpret_cast<int32_t*>(st.pos), st,
+                     l->reward_sum, l->perf_sum, l->episodes, l->bad_count, l->bad_flag, B, T,
+                     l->reset_first);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -301,28 +301,20 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev,
   sp.S = (int32_t)S;
   sp.n_sweeps = n_sweeps;
   sp.gamma = gamma;
-  sp.discounts[0] = 1.0f;
-  for (int i = 1; i < 16; ++i) sp.discounts[i] = s->discount_list[i];
+  wide_discounts(*s, sp.discounts);
   sp.off_v0 = sweeps.off_v0;
   sp.off_v1 = sweeps.off_v1;
   sp.off_w = sweeps.off_w;
   sp.off_c4 = sweeps.off_c4;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const uint2* entries = reinterpret_cast<const uint2*>(tables_dev);
+  const uint2* entries = wide_tables(*s, tables_dev).entries;
   uint32_t* res = reinterpret_cast<uint32_t*>(residual);
   if (plan.path == 1) {
-#define CAMPX_SWEEPS_LDS(POLICY)                                                                   \
-  do {                                                                                             \
-    CAMPX_ALLOW_LDS((wide_sweeps_lds_kernel<POLICY>), (size_t)plan.lds_bytes);                     \
-    hipLaunchKernelGGL((wide_sweeps_lds_kernel<POLICY>), dim3(1), dim3((unsigned)plan.threads),    \
-                       (size_t)plan.lds_bytes, hs, sp, entries, policy, reward_override, v_in,     \
-                       v_out, q, greedy, res, bad_rows, bad_flag);                                 \
-  } while (0)
-    if (policy) CAMPX_SWEEPS_LDS(true);
-    else CAMPX_SWEEPS_LDS(false);
-#undef CAMPX_SWEEPS_LDS
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? CAMPX_OK : hip_failed(le);
+    const auto kernel = policy ? wide_sweeps_lds_kernel<true> : wide_sweeps_lds_kernel<false>;
+    CAMPX_ALLOW_LDS(kernel, (size_t)plan.lds_bytes);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3((unsigned)plan.threads), (size_t)plan.lds_bytes, hs, sp,
+                       entries, policy, reward_override, v_in, v_out, q, greedy, res, bad_rows, bad_flag);
+    return launch_status();
   }
   // Sweep k of n writes v_out when n - k is even and the scratch vector when it is odd, so that
   // the last one writes v_out; sweep 1 reads v_in - or, where it would write the vector it reads
@@ -336,23 +328,18 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* s, const void* tables_dev,
     hipLaunchKernelGGL(sweeps_prepare_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)),
                        dim3(kPlanThreads), 0, hs, res, n_sweeps, v_in, copy ? scratch : nullptr,
                        (int32_t)S);
-    const hipError_t pe = hipGetLastError();
-    if (pe != hipSuccess) return hip_failed(pe);
+    const int32_t launched = launch_status();
+    if (launched != CAMPX_OK) return launched;
   }
   const float* src = copy ? scratch : v_in;
+  const auto sweep = policy ? wide_sweep_kernel<true> : wide_sweep_kernel<false>;
   for (int32_t k = 1; k <= n_sweeps; ++k) {
     float* dst = ((n_sweeps - k) & 1) ? scratch : v_out;
     const int32_t last = k == n_sweeps;
-    if (policy)
-      hipLaunchKernelGGL((wide_sweep_kernel<true>), dim3((unsigned)plan.grid), dim3(kPlanThreads), 0, hs,
-                         sp, entries, policy, reward_override, src, dst, q, greedy, res + (k - 1),
-                         bad_rows, bad_flag, last);
-    else
-      hipLaunchKernelGGL((wide_sweep_kernel<false>), dim3((unsigned)plan.grid), dim3(kPlanThreads), 0, hs,
-                         sp, entries, policy, reward_override, src, dst, q, greedy, res + (k - 1),
-                         bad_rows, bad_flag, last);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return hip_failed(le);
+    hipLaunchKernelGGL(sweep, dim3((unsigned)plan.grid), dim3(kPlanThreads), 0, hs, sp, entries, policy,
+                       reward_override, src, dst, q, greedy, res + (k - 1), bad_rows, bad_flag, last);
+    const int32_t launched = launch_status();
+    if (launched != CAMPX_OK) return launched;
     src = dst;
   }
   return CAMPX_OK;

@@ -299,23 +299,18 @@ static int32_t policy_launch(const CampxWideSpec* s, const void* tables_dev, Cam
   const int32_t planned = plan_population(s->n_states, out.perf ? 1 : 0, B, n_members,
                                           knob(K_WIDE_LDS_MAX), path, &plan, nullptr);
   if (planned != CAMPX_OK) return planned;
-  const WideLayout w = wide_layout(*s);
+  const WideTables t = wide_tables(*s, tables_dev);
   PolicyParams pp;
   memset(&pp, 0, sizeof(pp));
   pp.n_states = s->n_states;
-  pp.n_planes = w.n_planes;
-  pp.discounts[0] = 1.0f;
-  for (int i = 1; i < 16; ++i) pp.discounts[i] = s->discount_list[i];
+  pp.n_planes = t.lay.n_planes;
+  wide_discounts(*s, pp.discounts);
   pp.has_dcodes = s->any_dcode;
   pp.key0 = (uint32_t)seed;
   pp.key1 = (uint32_t)(seed >> 32);
   pp.envs_per_member = (uint32_t)(B / n_members);
   pp.plane = (int64_t)T * row_pitch(out, B);
   pp.first_frame = first_frame;
-  const char* blob = static_cast<const char*>(tables_dev);
-  const uint2* entries = reinterpret_cast<const uint2*>(blob);
-  const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
-  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
   out.obs = nullptr;
   out.board = nullptr;
   const PolicyKernel kernel =
@@ -323,10 +318,9 @@ static int32_t policy_launch(const CampxWideSpec* s, const void* tables_dev, Cam
   CAMPX_ALLOW_LDS(kernel, (size_t)plan.lds_bytes);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kPolicyThreads - 1) / kPolicyThreads)),
                      dim3(kPolicyThreads), (size_t)plan.lds_bytes, static_cast<hipStream_t>(stream), pp,
-                     entries, cells, perf, policy, reinterpret_cast<int32_t*>(st.pos), st, out,
+                     t.entries, t.cells, t.perf, policy, reinterpret_cast<int32_t*>(st.pos), st, out,
                      actions_out, states_out, B, T, reset_first);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  return launch_status();
 }
 
 }  // namespace campx_impl

@@ -8,7 +8,7 @@
 // kernel (k_render.hip, through wide_render_source) renders it with T = 1 and B := N.  Nothing
 // about the render is restated here.
 
-#include "campx_common.hip.h"
+#include "wide_table.hip.h"
 
 namespace campx_impl {
 
@@ -76,22 +76,17 @@ int32_t campx_wide_render_states_launch(const CampxWideSpec* s, const void* tabl
   if (obs_format < CAMPX_OBS_INT8 || obs_format > CAMPX_OBS_BF16) return CAMPX_EINVAL;
   const int32_t v = wide_validate_plain(s);
   if (v != CAMPX_OK) return v;
-  const WideLayout w = wide_layout(*s);
+  const WideTables t = wide_tables(*s, tables_dev);
   const int64_t P = state_rows_pitch(N);
-  if (scratch_bytes < (int64_t)w.n_planes * P * (int64_t)sizeof(uint16_t)) return CAMPX_EINVAL;
+  if (scratch_bytes < (int64_t)t.lay.n_planes * P * (int64_t)sizeof(uint16_t)) return CAMPX_EINVAL;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const u32x4* cells =
-      reinterpret_cast<const u32x4*>(static_cast<const char*>(tables_dev) + w.cells_off);
   uint16_t* trace = static_cast<uint16_t*>(scratch);
   const dim3 grid((unsigned)((N + kStateRowsThreads - 1) / kStateRowsThreads));
-  if (ids64)
-    hipLaunchKernelGGL(wide_state_rows_kernel<true>, grid, dim3(kStateRowsThreads), 0, hs, cells,
-                       state_ids, s->n_states, w.n_planes, trace, P, N, bad_count, bad_flag);
-  else
-    hipLaunchKernelGGL(wide_state_rows_kernel<false>, grid, dim3(kStateRowsThreads), 0, hs, cells,
-                       state_ids, s->n_states, w.n_planes, trace, P, N, bad_count, bad_flag);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_failed(e);
+  hipLaunchKernelGGL(ids64 ? wide_state_rows_kernel<true> : wide_state_rows_kernel<false>, grid,
+                     dim3(kStateRowsThreads), 0, hs, t.cells, state_ids, s->n_states, t.lay.n_planes, trace,
+                     P, N, bad_count, bad_flag);
+  const int32_t launched = launch_status();
+  if (launched != CAMPX_OK) return launched;
   // One render launch addresses rows x row bytes < 2^32 - 65536: more rows go as several launches
   // of a multiple of 16 rows each (every part's output then starts on a 16-byte boundary); the
   // planes of the trace stay P entries apart whatever part is rendered.

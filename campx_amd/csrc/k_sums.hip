@@ -280,6 +280,24 @@ __global__ __launch_bounds__(kSumsThreads) void table_lookup_kernel(
   add_counters(counters, n_bad, 0, bad_count, nullptr);
 }
 
+// The instances, at [K][kActions][kLds] and [kActions][kLds].
+using SumsKernel = decltype(&state_sums_kernel<0, false, false>);
+static const SumsKernel kSumsKernels[CAMPX_SUMS_MAX_VALUES + 1][2][2] = {
+    {{state_sums_kernel<0, false, false>, state_sums_kernel<0, false, true>},
+     {state_sums_kernel<0, true, false>, state_sums_kernel<0, true, true>}},
+    {{state_sums_kernel<1, false, false>, state_sums_kernel<1, false, true>},
+     {state_sums_kernel<1, true, false>, state_sums_kernel<1, true, true>}},
+    {{state_sums_kernel<2, false, false>, state_sums_kernel<2, false, true>},
+     {state_sums_kernel<2, true, false>, state_sums_kernel<2, true, true>}},
+    {{state_sums_kernel<3, false, false>, state_sums_kernel<3, false, true>},
+     {state_sums_kernel<3, true, false>, state_sums_kernel<3, true, true>}},
+    {{state_sums_kernel<4, false, false>, state_sums_kernel<4, false, true>},
+     {state_sums_kernel<4, true, false>, state_sums_kernel<4, true, true>}}};
+using LookupKernel = decltype(&table_lookup_kernel<false, false>);
+static const LookupKernel kLookupKernels[2][2] = {
+    {table_lookup_kernel<false, false>, table_lookup_kernel<false, true>},
+    {table_lookup_kernel<true, false>, table_lookup_kernel<true, true>}};
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -348,30 +366,12 @@ int32_t campx_state_sums_launch(const CampxStateSums* s, int64_t B, int32_t T, v
     const int64_t blocks = (n + 4 * kSumsThreads - 1) / (4 * kSumsThreads);
     hipLaunchKernelGGL(sums_zero_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)),
                        dim3(kSumsThreads), 0, hs, acc, n, skipped, clamped);
-    const hipError_t ze = hipGetLastError();
-    if (ze != hipSuccess) return hip_failed(ze);
+    const int32_t launched = launch_status();
+    if (launched != CAMPX_OK) return launched;
   }
-#define CAMPX_SUMS(KV, ACTIONS, LDS)                                                              \
-  hipLaunchKernelGGL((state_sums_kernel<KV, ACTIONS, LDS>), grid, dim3(kSumsThreads),             \
-                     (size_t)plan.lds_bytes, hs, sp, s->states, s->actions, acc, skipped, clamped)
-#define CAMPX_SUMS_K(KV)                                         \
-  do {                                                           \
-    if (s->actions && plan.path == 1) CAMPX_SUMS(KV, true, true); \
-    else if (s->actions) CAMPX_SUMS(KV, true, false);            \
-    else if (plan.path == 1) CAMPX_SUMS(KV, false, true);        \
-    else CAMPX_SUMS(KV, false, false);                           \
-  } while (0)
-  switch (K) {
-    case 0: CAMPX_SUMS_K(0); break;
-    case 1: CAMPX_SUMS_K(1); break;
-    case 2: CAMPX_SUMS_K(2); break;
-    case 3: CAMPX_SUMS_K(3); break;
-    default: CAMPX_SUMS_K(4); break;
-  }
-#undef CAMPX_SUMS_K
-#undef CAMPX_SUMS
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? CAMPX_OK : hip_failed(le);
+  hipLaunchKernelGGL(kSumsKernels[K][s->actions != nullptr][plan.path == 1], grid, dim3(kSumsThreads),
+                     (size_t)plan.lds_bytes, hs, sp, s->states, s->actions, acc, skipped, clamped);
+  return launch_status();
 }
 
 int32_t campx_table_lookup_launch(const CampxTableLookup* l, int64_t B, int32_t T, void* stream) {
@@ -403,17 +403,9 @@ int32_t campx_table_lookup_launch(const CampxTableLookup* l, int64_t B, int32_t 
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)grid_b, (unsigned)grid_t);
   u64* bad = reinterpret_cast<u64*>(l->bad_count);
-#define CAMPX_LOOKUP(ACTIONS, LDS)                                                            \
-  hipLaunchKernelGGL((table_lookup_kernel<ACTIONS, LDS>), grid, dim3(kSumsThreads),           \
-                     (size_t)(LDS ? entries * 4 : 0), hs, lp, l->table, l->states, l->actions, \
-                     l->out, bad)
-  if (l->actions && lds) CAMPX_LOOKUP(true, true);
-  else if (l->actions) CAMPX_LOOKUP(true, false);
-  else if (lds) CAMPX_LOOKUP(false, true);
-  else CAMPX_LOOKUP(false, false);
-#undef CAMPX_LOOKUP
-  const hipError_t le = hipGetLastError();
-  return le == hipSuccess ? CAMPX_OK : hip_failed(le);
+  hipLaunchKernelGGL(kLookupKernels[l->actions != nullptr][lds], grid, dim3(kSumsThreads),
+                     (size_t)(lds ? entries * 4 : 0), hs, lp, l->table, l->states, l->actions, l->out, bad);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -333,7 +333,7 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
        (start && ranges_overlap(scratch, start, bytes))))
     return CAMPX_EINVAL;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const uint2* entries = reinterpret_cast<const uint2*>(tables_dev);
+  const uint2* entries = wide_tables(*s, tables_dev).entries;
   const u64* d_start = reinterpret_cast<const u64*>(start);
   u64* d_visits = reinterpret_cast<u64*>(visits);
   u64* d_finished = reinterpret_cast<u64*>(finished);
@@ -349,8 +349,8 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
   hipLaunchKernelGGL(visit_counts_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S, policy,
                      counts, d_start, global ? src : nullptr, global ? dst : nullptr, d_finished,
                      n_frames, bad_rows, bad_flag);
-  const hipError_t pe = hipGetLastError();
-  if (pe != hipSuccess) return hip_failed(pe);
+  const int32_t launched = launch_status();
+  if (launched != CAMPX_OK) return launched;
   if (!global) {
     VisitParams vp;
     memset(&vp, 0, sizeof(vp));
@@ -364,15 +364,14 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
     hipLaunchKernelGGL(visit_lds_kernel, dim3(1), dim3((unsigned)plan.threads),
                        (size_t)plan.lds_bytes, hs, vp, entries, counts, d_start, d_visits,
                        d_finished, d_final, d_rows);
-    const hipError_t le = hipGetLastError();
-    return le == hipSuccess ? CAMPX_OK : hip_failed(le);
+    return launch_status();
   }
   for (int32_t k = 1; k <= n_frames; ++k) {
     hipLaunchKernelGGL(visit_frame_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S, restart,
                        (int32_t)(k == 1), entries, counts, src, dst, d_visits, d_finished + (k - 1),
                        d_rows ? d_rows + (int64_t)(k - 1) * S : nullptr);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return hip_failed(le);
+    const int32_t launched = launch_status();
+    if (launched != CAMPX_OK) return launched;
     u64* swap = src;
     src = dst;
     dst = swap;
@@ -380,8 +379,8 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* s, const void* tables_dev, 
   if (d_rows) {
     hipLaunchKernelGGL(visit_last_row_kernel, per_state, dim3(kVisitThreads), 0, hs, (int32_t)S,
                        d_final, d_rows + (int64_t)n_frames * S);
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return hip_failed(le);
+    const int32_t launched = launch_status();
+    if (launched != CAMPX_OK) return launched;
   }
   return CAMPX_OK;
 }

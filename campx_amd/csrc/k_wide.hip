@@ -487,10 +487,24 @@ __global__ void wide_reset_kernel(const u32x4* __restrict__ cells, int32_t K, in
   if (K > 7) trace[7 * P + env] = (uint16_t)(c.w >> 16);
 }
 
-// ---- the table blob: [entries uint2 x 5S, padded to 16][cells 8 x uint16 x S][perf int8 x 5S, padded to 16]
-// [rot_obs][rot_board][pieces: 16 words for the layered rows, 16 for the flat board]
-// (struct WideLayout: campx_common.hip.h - k_policy.hip reads the same blob)
+// ---- the table blob (struct WideLayout and the launchers' view of a blob, struct WideTables:
+// wide_table.hip.h - every launcher of the tier reads the same blob)
 static int wide_variants(const CampxWideSpec& s) { return s.n_variants > 1 ? s.n_variants : 1; }
+
+// the scenery's front-most layer per cell in one of its variants
+static const uint8_t* wide_top_layer(const CampxWideSpec& s, int variant) {
+  return s.n_variants > 1 ? s.variant_top_layer + (int64_t)variant * s.rows * s.cols : s.static_top_layer;
+}
+
+// A piece's two words: for the layered rows (byte it sets) | (byte of the scenery it clears) << 16,
+// for the flat board cell | character << 16.
+static void wide_piece_words(const CampxWideSpec& s, int p, uint32_t* obs, uint32_t* board) {
+  const uint32_t HW = (uint32_t)(s.rows * s.cols), cell = s.piece_cell[p];
+  const uint32_t sets = (uint32_t)s.piece_layer[p] * HW + cell;          // < 16 * 1024
+  const uint32_t clears = (uint32_t)s.static_top_layer[cell] * HW + cell;
+  *obs = sets | (clears << 16);
+  *board = cell | ((uint32_t)s.layer_char[s.piece_layer[p]] << 16);
+}
 
 WideLayout wide_layout(const CampxWideSpec& s) {
   WideLayout w;
@@ -510,7 +524,7 @@ WideLayout wide_layout(const CampxWideSpec& s) {
 }
 
 RenderSource wide_render_source(const CampxWideSpec& s, const void* tables_dev) {
-  const WideLayout w = wide_layout(s);
+  const WideTables t = wide_tables(s, tables_dev);
   RenderSource src;
   memset(&src, 0, sizeof(src));
   src.rows = s.rows;
@@ -519,19 +533,16 @@ RenderSource wide_render_source(const CampxWideSpec& s, const void* tables_dev) 
   src.n_dyn = s.n_dyn;
   for (int d = 0; d < s.n_dyn; ++d) src.dyn_layer[d] = s.dyn_layer[d];
   memcpy(src.layer_char, s.layer_char, sizeof(src.layer_char));
-  const char* blob = static_cast<const char*>(tables_dev);
-  src.rot_obs = reinterpret_cast<const int8_t*>(blob + w.rot_obs_off);
-  src.rot_board = reinterpret_cast<const int8_t*>(blob + w.rot_board_off);
+  src.rot_obs = t.rot_obs;
+  src.rot_board = t.rot_board;
   src.top_layer = nullptr;
   src.wide = true;
-  src.n_variants = w.n_variants;
-  src.rot_obs_stride = 16ll * w.pitch_obs;
-  src.rot_board_stride = 16ll * w.pitch_board;
+  src.n_variants = t.lay.n_variants;
+  src.rot_obs_stride = 16ll * t.lay.pitch_obs;
+  src.rot_board_stride = 16ll * t.lay.pitch_board;
   src.n_pieces = s.n_pieces;
-  if (s.n_pieces > 0) {
-    src.pieces_obs = reinterpret_cast<const uint32_t*>(blob + w.pieces_off);
-    src.pieces_board = src.pieces_obs + CAMPX_WIDE_MAX_PIECES;
-  }
+  src.pieces_obs = t.pieces_obs;
+  src.pieces_board = t.pieces_board;
   return src;
 }
 
@@ -589,29 +600,114 @@ int32_t wide_check(const CampxWideSpec* s, const void* tables, const CampxState&
   return CAMPX_OK;
 }
 
+// The observations of frames [t0, t0 + n) of a rollout from its trace; `out` is the whole rollout's.
 // `plane`: distance between two things' planes of the trace, in entries.
-int32_t wide_renders(const CampxWideSpec& s, const void* tables_dev, const uint16_t* trace,
-                     CampxOutputs out, int64_t B, int32_t T, int64_t plane, hipStream_t stream) {
+int32_t wide_renders(const CampxWideSpec& s, const void* tables_dev, const CampxOutputs& out, int64_t B,
+                     int64_t t0, int32_t n, int64_t plane, hipStream_t stream) {
   const RenderSource src = wide_render_source(s, tables_dev);
   const int64_t pitch = row_pitch(out, B);
   const int64_t elem = out.obs_format == CAMPX_OBS_INT8 ? 1 : 2;
-  if (wide_last_only(out)) {
-    trace += (int64_t)(T - 1) * pitch;
-    T = 1;
+  if (wide_last_only(out)) {          // (strides 0: the frame lands in slot 0 wherever it is in the trace)
+    t0 += n - 1;
+    n = 1;
   }
+  const uint16_t* trace = reinterpret_cast<const uint16_t*>(out.trace);
   // (a render launch has one grid row per frame: at most 65 535 of them)
-  for (int64_t t0 = 0; t0 < T; t0 += 65520) {
-    const int32_t n = (int32_t)(T - t0 < 65520 ? T - t0 : 65520);
+  for (const int64_t end = t0 + n; t0 < end; t0 += 65520) {
+    const int32_t frames = (int32_t)(end - t0 < 65520 ? end - t0 : 65520);
     int32_t rc = launch_render_from(src, trace + t0 * pitch, out.obs + t0 * out.obs_t_stride * elem,
-                                    B, n, plane, pitch, false, out.obs_format, stream);
+                                    B, frames, plane, pitch, false, out.obs_format, stream);
     if (rc != CAMPX_OK) return rc;
     if (out.board) {
-      rc = launch_render_from(src, trace + t0 * pitch, out.board + t0 * out.board_t_stride, B, n,
+      rc = launch_render_from(src, trace + t0 * pitch, out.board + t0 * out.board_t_stride, B, frames,
                               plane, pitch, true, 0, stream);
       if (rc != CAMPX_OK) return rc;
     }
   }
   return CAMPX_OK;
+}
+
+// ---- the launch set-up of the three kernels above, each said once
+
+// [kLds][kPerf]
+using WideUpdateKernel = decltype(&wide_update_kernel<false, false>);
+static const WideUpdateKernel kWideUpdateKernels[2][2] = {
+    {wide_update_kernel<false, false>, wide_update_kernel<false, true>},
+    {wide_update_kernel<true, false>, wide_update_kernel<true, true>}};
+
+// The update pass of `n` frames.  `plane`: entries from one thing's plane of the trace to the
+// next's - the WHOLE rollout's frames x row pitch, also when these frames are a chunk of them.
+static int32_t wide_update(const CampxWideSpec& s, const WideTables& t, CampxState st,
+                           const int8_t* actions, const CampxOutputs& out, int64_t B, int32_t n,
+                           int64_t plane, int32_t reset_first, hipStream_t stream) {
+  WideParams wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.n_states = s.n_states;
+  wp.n_dyn = t.lay.n_planes;       // (planes the update pass writes: the variant's / the pieces' is one of them)
+  wide_discounts(s, wp.discounts);
+  wp.has_dcodes = s.any_dcode;
+  wp.plane = plane;
+  // The table goes to LDS when it fits: the entries and the cells as they lie in the blob (up to
+  // where its perf bytes start), then the perf bytes.  (Setting wide_lds_max = bytes: tests run small
+  // games through the global-memory path that games with thousands of states take.)
+  const size_t want = (size_t)(t.perf - reinterpret_cast<const int8_t*>(t.entries)) +
+                      (out.perf ? (size_t)t.lay.n_entries : 0);
+  const bool in_lds = want <= (size_t)knob(K_WIDE_LDS_MAX);
+  const size_t lds = in_lds ? want : 0;
+  const WideUpdateKernel kernel = kWideUpdateKernels[in_lds][out.perf != nullptr];
+  CAMPX_ALLOW_LDS(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kWideThreads - 1) / kWideThreads)), dim3(kWideThreads),
+                     lds, stream, wp, t.entries, t.cells, t.perf, reinterpret_cast<int32_t*>(st.pos), st,
+                     actions, out, B, n, reset_first);
+  return launch_status();
+}
+
+// [kBoard][kPerf][kFmt]: CampxOutputs.obs_format is the index
+static_assert(CAMPX_OBS_INT8 == 0 && CAMPX_OBS_F16 == 1 && CAMPX_OBS_BF16 == 2, "kFmt is obs_format");
+using WideStepKernel = decltype(&wide_step_kernel<false, false, 0>);
+static const WideStepKernel kWideStepKernels[2][2][3] = {
+    {{wide_step_kernel<false, false, 0>, wide_step_kernel<false, false, 1>, wide_step_kernel<false, false, 2>},
+     {wide_step_kernel<false, true, 0>, wide_step_kernel<false, true, 1>, wide_step_kernel<false, true, 2>}},
+    {{wide_step_kernel<true, false, 0>, wide_step_kernel<true, false, 1>, wide_step_kernel<true, false, 2>},
+     {wide_step_kernel<true, true, 0>, wide_step_kernel<true, true, 1>, wide_step_kernel<true, true, 2>}}};
+using WideStepLdsKernel = decltype(&wide_step_lds_kernel<false, false, 0>);
+static const WideStepLdsKernel kWideStepLdsKernels[2][2][3] = {
+    {{wide_step_lds_kernel<false, false, 0>, wide_step_lds_kernel<false, false, 1>,
+      wide_step_lds_kernel<false, false, 2>},
+     {wide_step_lds_kernel<false, true, 0>, wide_step_lds_kernel<false, true, 1>,
+      wide_step_lds_kernel<false, true, 2>}},
+    {{wide_step_lds_kernel<true, false, 0>, wide_step_lds_kernel<true, false, 1>,
+      wide_step_lds_kernel<true, false, 2>},
+     {wide_step_lds_kernel<true, true, 0>, wide_step_lds_kernel<true, true, 1>,
+      wide_step_lds_kernel<true, true, 2>}}};
+
+// What both one-kernel forms of Engine.play() are told; `n_env`: environments per wave.
+static WideStepParams wide_step_params(const CampxWideSpec& s, const WideLayout& w, int n_env) {
+  const int HW = s.rows * s.cols, R = HW * s.n_layers;
+  WideStepParams sp;
+  memset(&sp, 0, sizeof(sp));
+  sp.n_states = s.n_states;
+  sp.n_dyn = s.n_dyn;
+  sp.cells = HW;
+  sp.R = R;
+  sp.n_env = n_env;
+  sp.inv_r = (uint32_t)(((1ull << 32) + R - 1) / R);
+  sp.n_variants = w.n_variants;
+  sp.n_planes = w.n_planes;
+  sp.rot_obs_stride = 16ll * w.pitch_obs;
+  sp.rot_board_stride = 16ll * w.pitch_board;
+  for (int d = 0; d < s.n_dyn; ++d) {
+    sp.dyn_off[d] = s.dyn_layer[d] * HW;
+    sp.dyn_char[d] = s.layer_char[s.dyn_layer[d]];
+  }
+  wide_discounts(s, sp.discounts);
+  return sp;
+}
+
+// workgroups of a one-kernel play(): a wave per `n_env` environments
+static dim3 wide_step_grid(int64_t B, int n_env) {
+  const int64_t n_waves = (B + n_env - 1) / n_env;
+  return dim3((unsigned)((n_waves + kWideThreads / kWave - 1) / (kWideThreads / kWave)));
 }
 
 
@@ -778,18 +874,11 @@ int32_t launch_wide_enumerate(const CampxWideRules& r, const uint16_t* cells_in,
   memcpy(ep.rules, r.rules, sizeof(ep.rules));
   const int64_t threads = N * CAMPX_N_ACTIONS;
   const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-#define CAMPX_ENUM(KK)                                                                          \
-  hipLaunchKernelGGL((wide_enumerate_kernel<KK>), grid, block, 0, stream, ep, r.top_layer,      \
-                     r.top_z, r.cover, r.cell_class, cells_in, N, next_cells, reward, done, shows, perf)
-  switch (r.n_dyn) {
-    case 1: CAMPX_ENUM(1); break;
-    case 2: CAMPX_ENUM(2); break;
-    case 3: CAMPX_ENUM(3); break;
-    default: CAMPX_ENUM(4); break;
-  }
-#undef CAMPX_ENUM
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  static const decltype(&wide_enumerate_kernel<1>) kernels[CAMPX_MAX_DYN] = {      // [n_dyn - 1]
+      wide_enumerate_kernel<1>, wide_enumerate_kernel<2>, wide_enumerate_kernel<3>, wide_enumerate_kernel<4>};
+  hipLaunchKernelGGL(kernels[r.n_dyn - 1], grid, block, 0, stream, ep, r.top_layer, r.top_z, r.cover,
+                     r.cell_class, cells_in, N, next_cells, reward, done, shows, perf);
+  return launch_status();
 }
 
 }  // namespace campx_impl
@@ -862,7 +951,7 @@ int32_t campx_wide_tables_build(const CampxWideSpec* s, void* tables_dev, void* 
     uint32_t e[CAMPX_WIDE_MAX_DYN] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     // (what a thing covers is the scenery of the STATE's variant)
     const int variant = V > 1 ? s->state_variant[st] : 0;
-    const uint8_t* top = V > 1 ? s->variant_top_layer + (int64_t)variant * HW : s->static_top_layer;
+    const uint8_t* top = wide_top_layer(*s, variant);
     for (int d = 0; d < K; ++d) {
       const uint32_t c = s->state_cells[(int64_t)st * K + d];
       const uint32_t cell = c & 0x3ffu;
@@ -883,7 +972,7 @@ int32_t campx_wide_tables_build(const CampxWideSpec* s, void* tables_dev, void* 
   }
   int8_t* brow = row + R;
   for (int variant = 0; variant < V; ++variant) {
-    const uint8_t* top = V > 1 ? s->variant_top_layer + (int64_t)variant * HW : s->static_top_layer;
+    const uint8_t* top = wide_top_layer(*s, variant);
     memset(row, 0, (size_t)R + HW);
     for (int i = 0; i < HW; ++i) {
       row[(int)top[i] * HW + i] = 1;
@@ -900,13 +989,7 @@ int32_t campx_wide_tables_build(const CampxWideSpec* s, void* tables_dev, void* 
   if (s->n_pieces > 0) {
     uint32_t* pieces_obs = reinterpret_cast<uint32_t*>(blob + w.pieces_off);
     uint32_t* pieces_board = pieces_obs + CAMPX_WIDE_MAX_PIECES;
-    for (int p = 0; p < s->n_pieces; ++p) {
-      const uint32_t cell = s->piece_cell[p];
-      const uint32_t sets = (uint32_t)s->piece_layer[p] * (uint32_t)HW + cell;          // < 16 * 1024
-      const uint32_t clears = (uint32_t)s->static_top_layer[cell] * (uint32_t)HW + cell;
-      pieces_obs[p] = sets | (clears << 16);
-      pieces_board[p] = cell | ((uint32_t)s->layer_char[s->piece_layer[p]] << 16);
-    }
+    for (int p = 0; p < s->n_pieces; ++p) wide_piece_words(*s, p, &pieces_obs[p], &pieces_board[p]);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemcpyAsync(tables_dev, blob, (size_t)w.total, hipMemcpyHostToDevice, st);
@@ -917,22 +1000,21 @@ int32_t campx_wide_tables_build(const CampxWideSpec* s, void* tables_dev, void* 
 
 int32_t campx_wide_reset_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
                                 CampxOutputs out, int64_t B, void* stream) {
-  int32_t rc = wide_check(s, tables_dev, st, out, B, 0);
+  const int32_t rc = wide_check(s, tables_dev, st, out, B, 0);
   if (rc != CAMPX_OK) return rc;
   if (out.obs_format != CAMPX_OBS_INT8) return CAMPX_EINVAL;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const WideLayout w = wide_layout(*s);
-  const u32x4* cells = reinterpret_cast<const u32x4*>(static_cast<const char*>(tables_dev) + w.cells_off);
-  uint16_t* trace = reinterpret_cast<uint16_t*>(out.trace);
+  const WideTables t = wide_tables(*s, tables_dev);
   const int64_t P = row_pitch(out, B);
-  hipLaunchKernelGGL(wide_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, hs, cells,
-                     w.n_planes, reinterpret_cast<int32_t*>(st.pos), st, trace, P, B);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_failed(e);
+  hipLaunchKernelGGL(wide_reset_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, hs, t.cells,
+                     t.lay.n_planes, reinterpret_cast<int32_t*>(st.pos), st,
+                     reinterpret_cast<uint16_t*>(out.trace), P, B);
+  const int32_t launched = launch_status();
+  if (launched != CAMPX_OK) return launched;
   CampxOutputs one = out;     // one frame, written to slot 0 of each buffer
   one.obs_t_stride = 0;
   one.board_t_stride = 0;
-  return wide_renders(*s, tables_dev, trace, one, B, 1, P, hs);
+  return wide_renders(*s, tables_dev, one, B, 0, 1, P, hs);
 }
 
 int32_t campx_wide_rollout_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
@@ -943,166 +1025,60 @@ int32_t campx_wide_rollout_launch(const CampxWideSpec* s, const void* tables_dev
   if (T == 0) return CAMPX_OK;
   if (!actions) return CAMPX_EINVAL;
   hipStream_t hs = static_cast<hipStream_t>(stream);
-  const WideLayout w = wide_layout(*s);
-  {
-    // Engine.play(): one launch when the rows are whole 16-byte chunks (see wide_step_kernel)
-    const int HW = s->rows * s->cols, R = HW * s->n_layers;
-    if (T == 1 && !reset_first && (R & 15) == 0 && s->n_pieces == 0 && knob(K_WIDE_STEP) &&
-        (!out.board || (HW & 15) == 0) &&
-        (int64_t)kStepEnvMax * R < (1ll << 24)) {
-      WideStepParams sp;
-      memset(&sp, 0, sizeof(sp));
-      sp.n_states = s->n_states;
-      sp.n_dyn = s->n_dyn;
-      sp.cells = HW;
-      sp.R = R;
-      // environments per wave: a span of about 2 KiB, whole KiB when the row allows
-      int n_env = 1;
-      if (R < 2048) {
-        n_env = 2048 / R;
-        for (int c = 1; c <= kStepEnvMax; ++c)
-          if (((int64_t)c * R) % 1024 == 0) {
-            n_env = c;
-            break;
-          }
-        n_env = n_env > kStepEnvMax ? kStepEnvMax : (n_env < 1 ? 1 : n_env);
-      }
-      sp.n_env = n_env;
-      sp.inv_r = (uint32_t)(((1ull << 32) + R - 1) / R);
-      sp.n_variants = w.n_variants;
-      sp.n_planes = w.n_planes;
-      sp.rot_obs_stride = 16ll * w.pitch_obs;
-      sp.rot_board_stride = 16ll * w.pitch_board;
-      for (int d = 0; d < s->n_dyn; ++d) {
-        sp.dyn_off[d] = s->dyn_layer[d] * HW;
-        sp.dyn_char[d] = s->layer_char[s->dyn_layer[d]];
-      }
-      sp.discounts[0] = 1.0f;
-      for (int i = 1; i < 16; ++i) sp.discounts[i] = s->discount_list[i];
-      const char* blob = static_cast<const char*>(tables_dev);
-      const uint2* entries = reinterpret_cast<const uint2*>(blob);
-      const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
-      const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
-      const int8_t* rot_obs = reinterpret_cast<const int8_t*>(blob + w.rot_obs_off);
-      const int8_t* rot_board = reinterpret_cast<const int8_t*>(blob + w.rot_board_off);
-      const int64_t n_waves = (B + n_env - 1) / n_env;
-      const dim3 grid((unsigned)((n_waves + kWideThreads / kWave - 1) / (kWideThreads / kWave)));
-      int32_t* state = reinterpret_cast<int32_t*>(st.pos);
-#define CAMPX_WIDE_STEP2(BOARD, PERF, FMT)                                                       \
-  hipLaunchKernelGGL((wide_step_kernel<BOARD, PERF, FMT>), grid, dim3(kWideThreads), 0, hs, sp,  \
-                     entries, cells, perf, rot_obs, rot_board, state, st, actions, out, B)
-#define CAMPX_WIDE_STEP(BOARD, PERF)                                      \
-  do {                                                                    \
-    if (out.obs_format == CAMPX_OBS_F16) CAMPX_WIDE_STEP2(BOARD, PERF, 1);      \
-    else if (out.obs_format == CAMPX_OBS_BF16) CAMPX_WIDE_STEP2(BOARD, PERF, 2); \
-    else CAMPX_WIDE_STEP2(BOARD, PERF, 0);                                \
-  } while (0)
-      if (out.board && out.perf) CAMPX_WIDE_STEP(true, true);
-      else if (out.board) CAMPX_WIDE_STEP(true, false);
-      else if (out.perf) CAMPX_WIDE_STEP(false, true);
-      else CAMPX_WIDE_STEP(false, false);
-#undef CAMPX_WIDE_STEP
-#undef CAMPX_WIDE_STEP2
-      const hipError_t e = hipGetLastError();
-      return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  const WideTables t = wide_tables(*s, tables_dev);
+  const int HW = s->rows * s->cols, R = HW * s->n_layers;
+  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
+  const bool play = T == 1 && !reset_first && knob(K_WIDE_STEP);     // Engine.play()
+  // One launch when the rows are whole 16-byte chunks (see wide_step_kernel)
+  if (play && (R & 15) == 0 && s->n_pieces == 0 && (!out.board || (HW & 15) == 0) &&
+      (int64_t)kStepEnvMax * R < (1ll << 24)) {
+    // environments per wave: a span of about 2 KiB, whole KiB when the row allows
+    int n_env = 1;
+    if (R < 2048) {
+      n_env = 2048 / R;
+      for (int c = 1; c <= kStepEnvMax; ++c)
+        if (((int64_t)c * R) % 1024 == 0) {
+          n_env = c;
+          break;
+        }
+      n_env = n_env > kStepEnvMax ? kStepEnvMax : (n_env < 1 ? 1 : n_env);
     }
-    // ... and the rest - rows that are not whole chunks, a scenery of pieces - when a wave's span can
-    // start on a 16-byte boundary and fits its LDS window (wide_step_lds_kernel), for frames up to
-    // 24 MB: us per play(), one kernel / the pair (tools/bench_wide_play.py, round 6): the coin
-    // field (300-byte rows, three pieces) B = 1 000 6.6 / 12.9, 4 096 6.7 / 13.0, 16 384 7.3 / 13.1,
-    // 65 536 (19.7 MB) 12.1 / 13.3, 131 072 (39 MB) 20.4 / 15.8, 262 144 36.3 / 22.7; seven coins on
-    // 4x9 B = 65 536 7.5 / 13.0, 262 144 (47 MB) 18.4 / 20.4
-    if (T == 1 && !reset_first && knob(K_WIDE_STEP) && B * R <= (24ll << 20) &&
-        (!out.board || (reinterpret_cast<uintptr_t>(out.board) & 15) == 0)) {
-      // environments per aligned span: of the layered rows and - when the flat board is asked for - of
-      // the board's (rows * cols divides R)
-      const int unit = out.board ? HW : R;
-      int step = 1;
-      while (step < 16 && (unit * step) % 16 != 0) step <<= 1;
-      int n_env = (kStepLdsSpan / R) / step * step;                // as many as the window holds
-      n_env = n_env < step ? step : (n_env > kStepEnvMax ? kStepEnvMax : n_env);
-      if ((int64_t)n_env * R <= kStepLdsSpan) {
-        WideStepParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.n_states = s->n_states;
-        sp.n_dyn = s->n_dyn;
-        sp.cells = HW;
-        sp.R = R;
-        sp.n_env = n_env;
-        sp.inv_r = (uint32_t)(((1ull << 32) + R - 1) / R);
-        sp.n_variants = w.n_variants;
-        sp.n_planes = w.n_planes;
-        sp.rot_obs_stride = 16ll * w.pitch_obs;
-        sp.rot_board_stride = 16ll * w.pitch_board;
-        for (int d = 0; d < s->n_dyn; ++d) {
-          sp.dyn_off[d] = s->dyn_layer[d] * HW;
-          sp.dyn_char[d] = s->layer_char[s->dyn_layer[d]];
-        }
-        sp.discounts[0] = 1.0f;
-        for (int i = 1; i < 16; ++i) sp.discounts[i] = s->discount_list[i];
-        WideStepLdsParams lp;
-        memset(&lp, 0, sizeof(lp));
-        lp.n_pieces = s->n_pieces;
-        lp.n_planes = w.n_planes;
-        lp.pitch_obs = w.pitch_obs;
-        lp.pitch_board = w.pitch_board;
-        for (int p = 0; p < s->n_pieces; ++p) {
-          const uint32_t cell = s->piece_cell[p];
-          lp.piece_obs[p] = ((uint32_t)s->piece_layer[p] * (uint32_t)HW + cell) |
-                            (((uint32_t)s->static_top_layer[cell] * (uint32_t)HW + cell) << 16);
-          lp.piece_board[p] = cell | ((uint32_t)s->layer_char[s->piece_layer[p]] << 16);
-        }
-        const char* blob = static_cast<const char*>(tables_dev);
-        const uint2* entries = reinterpret_cast<const uint2*>(blob);
-        const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
-        const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
-        const int8_t* rot_obs = reinterpret_cast<const int8_t*>(blob + w.rot_obs_off);
-        const int8_t* rot_board = reinterpret_cast<const int8_t*>(blob + w.rot_board_off);
-        const int64_t n_waves = (B + n_env - 1) / n_env;
-        const dim3 grid((unsigned)((n_waves + kWideThreads / kWave - 1) / (kWideThreads / kWave)));
-        int32_t* state = reinterpret_cast<int32_t*>(st.pos);
-#define CAMPX_WIDE_STEP2(BOARD, PERF, FMT)                                                           \
-  hipLaunchKernelGGL((wide_step_lds_kernel<BOARD, PERF, FMT>), grid, dim3(kWideThreads), 0, hs, sp,  \
-                     lp, entries, cells, perf, rot_obs, rot_board, state, st, actions, out, B)
-#define CAMPX_WIDE_STEP(BOARD, PERF)                                      \
-  do {                                                                    \
-    if (out.obs_format == CAMPX_OBS_F16) CAMPX_WIDE_STEP2(BOARD, PERF, 1);      \
-    else if (out.obs_format == CAMPX_OBS_BF16) CAMPX_WIDE_STEP2(BOARD, PERF, 2); \
-    else CAMPX_WIDE_STEP2(BOARD, PERF, 0);                                \
-  } while (0)
-        if (out.board && out.perf) CAMPX_WIDE_STEP(true, true);
-        else if (out.board) CAMPX_WIDE_STEP(true, false);
-        else if (out.perf) CAMPX_WIDE_STEP(false, true);
-        else CAMPX_WIDE_STEP(false, false);
-#undef CAMPX_WIDE_STEP
-#undef CAMPX_WIDE_STEP2
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? CAMPX_OK : hip_failed(e);
-      }
+    WideStepParams sp = wide_step_params(*s, t.lay, n_env);
+    hipLaunchKernelGGL(kWideStepKernels[out.board != nullptr][out.perf != nullptr][out.obs_format],
+                       wide_step_grid(B, n_env), dim3(kWideThreads), 0, hs, sp, t.entries, t.cells, t.perf,
+                       t.rot_obs, t.rot_board, state, st, actions, out, B);
+    return launch_status();
+  }
+  // ... and the rest - rows that are not whole chunks, a scenery of pieces - when a wave's span can
+  // start on a 16-byte boundary and fits its LDS window (wide_step_lds_kernel), for frames up to
+  // 24 MB: us per play(), one kernel / the pair (tools/bench_wide_play.py, round 6): the coin
+  // field (300-byte rows, three pieces) B = 1 000 6.6 / 12.9, 4 096 6.7 / 13.0, 16 384 7.3 / 13.1,
+  // 65 536 (19.7 MB) 12.1 / 13.3, 131 072 (39 MB) 20.4 / 15.8, 262 144 36.3 / 22.7; seven coins on
+  // 4x9 B = 65 536 7.5 / 13.0, 262 144 (47 MB) 18.4 / 20.4
+  if (play && B * R <= (24ll << 20) && (!out.board || aligned_to(out.board, 16))) {
+    // environments per aligned span: of the layered rows and - when the flat board is asked for - of
+    // the board's (rows * cols divides R)
+    const int unit = out.board ? HW : R;
+    int step = 1;
+    while (step < 16 && (unit * step) % 16 != 0) step <<= 1;
+    int n_env = (kStepLdsSpan / R) / step * step;                // as many as the window holds
+    n_env = n_env < step ? step : (n_env > kStepEnvMax ? kStepEnvMax : n_env);
+    if ((int64_t)n_env * R <= kStepLdsSpan) {
+      WideStepParams sp = wide_step_params(*s, t.lay, n_env);
+      WideStepLdsParams lp;
+      memset(&lp, 0, sizeof(lp));
+      lp.n_pieces = s->n_pieces;
+      lp.n_planes = t.lay.n_planes;
+      lp.pitch_obs = t.lay.pitch_obs;
+      lp.pitch_board = t.lay.pitch_board;
+      for (int p = 0; p < s->n_pieces; ++p) wide_piece_words(*s, p, &lp.piece_obs[p], &lp.piece_board[p]);
+      hipLaunchKernelGGL(kWideStepLdsKernels[out.board != nullptr][out.perf != nullptr][out.obs_format],
+                         wide_step_grid(B, n_env), dim3(kWideThreads), 0, hs, sp, lp, t.entries, t.cells,
+                         t.perf, t.rot_obs, t.rot_board, state, st, actions, out, B);
+      return launch_status();
     }
   }
-  WideParams wp;
-  memset(&wp, 0, sizeof(wp));
-  wp.n_states = s->n_states;
-  wp.n_dyn = w.n_planes;           // (planes the update pass writes: the variant's / the pieces' is one of them)
-  wp.discounts[0] = 1.0f;
-  for (int i = 1; i < 16; ++i) wp.discounts[i] = s->discount_list[i];
-  wp.has_dcodes = s->any_dcode;
-  const int64_t pitch = row_pitch(out, B);
-  wp.plane = (int64_t)T * pitch;
-  const char* blob = static_cast<const char*>(tables_dev);
-  const uint2* entries = reinterpret_cast<const uint2*>(blob);
-  const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
-  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
-  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
-  const size_t want = (size_t)(w.cells_off) + (size_t)s->n_states * sizeof(u32x4) +
-                      (out.perf ? (size_t)w.n_entries : 0);
-  // (setting wide_lds_max = bytes: tests run small games through the global-memory path that
-  // games with thousands of states take)
-  const size_t lds_max = (size_t)knob(K_WIDE_LDS_MAX);
-  const bool in_lds = want <= lds_max;
-  const size_t lds = in_lds ? want : 0;
-  const dim3 grid((unsigned)((B + kWideThreads - 1) / kWideThreads));
+  // Else the update pass and the renders.
   // The render kernel runs at the write ceiling only while the trace it reads stays cached
   // (launch_split() in campx_api.hip has the one-cell tier's numbers).  Here an entry is two
   // bytes and a game has up to nine planes.  The coin field of examples/coins_batched.py, B = 262 144,
@@ -1116,40 +1092,22 @@ int32_t campx_wide_rollout_launch(const CampxWideSpec* s, const void* tables_dev
   // T = 1 000 0.797 / 0.847 / 0.821, maze 16x16 at B = 524 288 0.774 / 0.884 / 0.876; at B = 262 144
   // 0.871 / 0.860 / 0.842).  So: a launch whose trace is more than 4 x trace_chunk_mb (64 MB) runs
   // as chunks of frames of at most 2 x trace_chunk_mb (32 MB), update pass and render alternating.
-  const int64_t per_frame = pitch * (int64_t)sizeof(uint16_t) * w.n_planes;
+  const int64_t pitch = row_pitch(out, B), plane = (int64_t)T * pitch;
+  const int64_t per_frame = pitch * (int64_t)sizeof(uint16_t) * t.lay.n_planes;
   int64_t chunk = (2 * (knob(K_TRACE_CHUNK_MB) << 20)) / per_frame;
   chunk = chunk < 16 ? 16 : chunk & ~(int64_t)15;
   const bool whole = per_frame * T <= 4 * (knob(K_TRACE_CHUNK_MB) << 20) || T <= chunk || wide_last_only(out);
-  const int64_t elem = out.obs_format == CAMPX_OBS_INT8 ? 1 : 2;
-  const uint16_t* trace0 = reinterpret_cast<const uint16_t*>(out.trace);
   for (int64_t t0 = 0; t0 < T; t0 += whole ? T : chunk) {
     const int32_t n = whole ? T : (int32_t)(T - t0 < chunk ? T - t0 : chunk);
-    CampxOutputs part = out;
-    if (!whole) {
-      part.obs = out.obs + t0 * out.obs_t_stride * elem;
-      if (out.board) part.board = out.board + t0 * out.board_t_stride;
-      if (out.reward) part.reward = out.reward + t0 * pitch;
-      if (out.discount) part.discount = out.discount + t0 * pitch;
-      if (out.done) part.done = out.done + t0 * pitch;
-      if (out.perf) part.perf = out.perf + t0 * pitch;
-      part.trace = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(trace0 + t0 * pitch));
-    }
-    const int8_t* acts = actions + t0 * B;
-    const int32_t first = t0 == 0 ? reset_first : 0;
-#define CAMPX_WIDE_LAUNCH(LDS, PERF)                                                              \
-  do {                                                                                            \
-    CAMPX_ALLOW_LDS((wide_update_kernel<LDS, PERF>), lds);                                        \
-    hipLaunchKernelGGL((wide_update_kernel<LDS, PERF>), grid, dim3(kWideThreads), lds, hs, wp,    \
-                       entries, cells, perf, state, st, acts, part, B, n, first);                 \
-  } while (0)
-    if (in_lds && out.perf) CAMPX_WIDE_LAUNCH(true, true);
-    else if (in_lds) CAMPX_WIDE_LAUNCH(true, false);
-    else if (out.perf) CAMPX_WIDE_LAUNCH(false, true);
-    else CAMPX_WIDE_LAUNCH(false, false);
-#undef CAMPX_WIDE_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_failed(e);
-    const int32_t rc = wide_renders(*s, tables_dev, trace0 + t0 * pitch, part, B, n, wp.plane, hs);
+    CampxOutputs part = out;      // the update pass's streams from frame t0 on (it writes no frame)
+    if (out.reward) part.reward = out.reward + t0 * pitch;
+    if (out.discount) part.discount = out.discount + t0 * pitch;
+    if (out.done) part.done = out.done + t0 * pitch;
+    if (out.perf) part.perf = out.perf + t0 * pitch;
+    part.trace = out.trace + t0 * pitch * (int64_t)sizeof(uint16_t);
+    rc = wide_update(*s, t, st, actions + t0 * B, part, B, n, plane, t0 == 0 ? reset_first : 0, hs);
+    if (rc != CAMPX_OK) return rc;
+    rc = wide_renders(*s, tables_dev, out, B, t0, n, plane, hs);
     if (rc != CAMPX_OK) return rc;
   }
   return CAMPX_OK;
@@ -1168,41 +1126,10 @@ int32_t campx_wide_update_launch(const CampxWideSpec* s, const void* tables_dev,
   const int32_t v = wide_validate_plain(s);
   if (v != CAMPX_OK) return v;
   if (out.perf && !s->has_perf) return CAMPX_EINVAL;
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const WideLayout w = wide_layout(*s);
-  WideParams wp;
-  memset(&wp, 0, sizeof(wp));
-  wp.n_states = s->n_states;
-  wp.n_dyn = w.n_planes;
-  wp.discounts[0] = 1.0f;
-  for (int i = 1; i < 16; ++i) wp.discounts[i] = s->discount_list[i];
-  wp.has_dcodes = s->any_dcode;
-  wp.plane = (int64_t)T * row_pitch(out, B);
-  const char* blob = static_cast<const char*>(tables_dev);
-  const uint2* entries = reinterpret_cast<const uint2*>(blob);
-  const u32x4* cells = reinterpret_cast<const u32x4*>(blob + w.cells_off);
-  const int8_t* perf = reinterpret_cast<const int8_t*>(blob + w.perf_off);
-  int32_t* state = reinterpret_cast<int32_t*>(st.pos);
-  const size_t want = (size_t)(w.cells_off) + (size_t)s->n_states * sizeof(u32x4) +
-                      (out.perf ? (size_t)w.n_entries : 0);
-  const bool in_lds = want <= (size_t)knob(K_WIDE_LDS_MAX);
-  const size_t lds = in_lds ? want : 0;
-  const dim3 grid((unsigned)((B + kWideThreads - 1) / kWideThreads));
   out.obs = nullptr;
   out.board = nullptr;
-#define CAMPX_WIDE_LAUNCH(LDS, PERF)                                                              \
-  do {                                                                                            \
-    CAMPX_ALLOW_LDS((wide_update_kernel<LDS, PERF>), lds);                                        \
-    hipLaunchKernelGGL((wide_update_kernel<LDS, PERF>), grid, dim3(kWideThreads), lds, hs, wp,    \
-                       entries, cells, perf, state, st, actions, out, B, T, reset_first);         \
-  } while (0)
-  if (in_lds && out.perf) CAMPX_WIDE_LAUNCH(true, true);
-  else if (in_lds) CAMPX_WIDE_LAUNCH(true, false);
-  else if (out.perf) CAMPX_WIDE_LAUNCH(false, true);
-  else CAMPX_WIDE_LAUNCH(false, false);
-#undef CAMPX_WIDE_LAUNCH
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  return wide_update(*s, wide_tables(*s, tables_dev), st, actions, out, B, T,
+                     (int64_t)T * row_pitch(out, B), reset_first, static_cast<hipStream_t>(stream));
 }
 
 int32_t campx_wide_render_gather_launch(const CampxWideSpec* s, const void* tables_dev,

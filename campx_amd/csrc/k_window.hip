@@ -1,7 +1,7 @@
 // k_window.hip - window_kernel: observation WINDOWS of a state-table game - h x w cells round a
 // tracked thing (egocentric) or at a fixed place of the board - rendered straight from trace
 // entries, without the full [L, H, W] observation ever being written.
-#include "campx_common.hip.h"
+#include "wide_table.hip.h"
 
 namespace campx_impl {
 
@@ -330,6 +330,23 @@ __global__ __launch_bounds__(kWindowWaves * kWave) void window_kernel(WindowPara
   }
 }
 
+// The twenty-seven instances, at [kScen][kSrc][kFmt]: the request's `source` and `obs_format` are
+// the indices.
+static_assert(CAMPX_WINDOWS_PAIRS == 0 && CAMPX_WINDOWS_TRACE == 1 && CAMPX_WINDOWS_STATES == 2 &&
+                  CAMPX_OBS_INT8 == 0 && CAMPX_OBS_F16 == 1 && CAMPX_OBS_BF16 == 2,
+              "kSrc is CampxWindows.source, kFmt is obs_format");
+using WindowKernel = decltype(&window_kernel<0, 0, 0>);
+static const WindowKernel kWindowKernels[3][3][3] = {
+    {{window_kernel<0, 0, 0>, window_kernel<1, 0, 0>, window_kernel<2, 0, 0>},
+     {window_kernel<0, 1, 0>, window_kernel<1, 1, 0>, window_kernel<2, 1, 0>},
+     {window_kernel<0, 2, 0>, window_kernel<1, 2, 0>, window_kernel<2, 2, 0>}},
+    {{window_kernel<0, 0, 1>, window_kernel<1, 0, 1>, window_kernel<2, 0, 1>},
+     {window_kernel<0, 1, 1>, window_kernel<1, 1, 1>, window_kernel<2, 1, 1>},
+     {window_kernel<0, 2, 1>, window_kernel<1, 2, 1>, window_kernel<2, 2, 1>}},
+    {{window_kernel<0, 0, 2>, window_kernel<1, 0, 2>, window_kernel<2, 0, 2>},
+     {window_kernel<0, 1, 2>, window_kernel<1, 1, 2>, window_kernel<2, 1, 2>},
+     {window_kernel<0, 2, 2>, window_kernel<1, 2, 2>, window_kernel<2, 2, 2>}}};
+
 // What campx_wide_render_windows_launch() asks of a request; before anything touches a device.
 static int32_t windows_check(const CampxWideSpec* s, const void* tables, const void* loc,
                              const CampxWindows* q, int64_t B) {
@@ -387,7 +404,8 @@ int32_t campx_wide_render_windows_launch(const CampxWideSpec* s, const void* tab
                                          void* stream) {
   const int32_t rc = windows_check(s, tables_dev, layer_of_cell, q, B);
   if (rc != CAMPX_OK) return rc;
-  const WideLayout lay = wide_layout(*s);
+  const WideTables t = wide_tables(*s, tables_dev);
+  const WideLayout& lay = t.lay;
   const int HW = s->rows * s->cols;
   const int64_t Rw = (int64_t)s->n_layers * q->h * q->w;
   const GatherPlan plan = gather_plan(q->N, Rw, q->obs_format, reinterpret_cast<uintptr_t>(q->obs));
@@ -431,36 +449,17 @@ int32_t campx_wide_render_windows_launch(const CampxWideSpec* s, const void* tab
   }
   wp.loc = static_cast<const uint8_t*>(layer_of_cell);
   wp.trace = static_cast<const uint16_t*>(q->trace);
-  wp.cells = reinterpret_cast<const u32x4*>(static_cast<const char*>(tables_dev) + lay.cells_off);
+  wp.cells = t.cells;
   wp.t_idx = q->source == CAMPX_WINDOWS_STATES ? q->state_ids : q->t_idx;
   wp.e_idx = q->e_idx;
   wp.bad_count = q->bad_count;
   wp.bad_flag = q->bad_flag;
   const dim3 grid(plan.grid), block(kWindowWaves * kWave);
   int8_t* dst = static_cast<int8_t*>(q->obs);
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-#define CAMPX_WINDOW3(FMT, SRC, SCEN) \
-  hipLaunchKernelGGL((window_kernel<FMT, SRC, SCEN>), grid, block, 0, hs, wp, dst)
-#define CAMPX_WINDOW2(SRC, SCEN)                                              \
-  do {                                                                        \
-    if (q->obs_format == CAMPX_OBS_F16) CAMPX_WINDOW3(1, SRC, SCEN);          \
-    else if (q->obs_format == CAMPX_OBS_BF16) CAMPX_WINDOW3(2, SRC, SCEN);    \
-    else CAMPX_WINDOW3(0, SRC, SCEN);                                         \
-  } while (0)
-#define CAMPX_WINDOW(SCEN)                                                            \
-  do {                                                                                \
-    if (q->source == CAMPX_WINDOWS_PAIRS) CAMPX_WINDOW2(CAMPX_WINDOWS_PAIRS, SCEN);   \
-    else if (q->source == CAMPX_WINDOWS_TRACE) CAMPX_WINDOW2(CAMPX_WINDOWS_TRACE, SCEN); \
-    else CAMPX_WINDOW2(CAMPX_WINDOWS_STATES, SCEN);                                   \
-  } while (0)
-  if (lay.n_variants > 1) CAMPX_WINDOW(1);
-  else if (s->n_pieces > 0) CAMPX_WINDOW(2);
-  else CAMPX_WINDOW(0);
-#undef CAMPX_WINDOW
-#undef CAMPX_WINDOW2
-#undef CAMPX_WINDOW3
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? CAMPX_OK : hip_failed(e);
+  const int scen = lay.n_variants > 1 ? 1 : (s->n_pieces > 0 ? 2 : 0);
+  hipLaunchKernelGGL(kWindowKernels[scen][q->source][q->obs_format], grid, block, 0,
+                     static_cast<hipStream_t>(stream), wp, dst);
+  return launch_status();
 }
 
 int32_t campx_wide_render_windows_plan(int64_t N, int32_t Rw, int32_t obs_format, uint64_t dst_addr,

@@ -1,7 +1,8 @@
 // wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_learn,
-// k_plan, k_visit, k_sums) agree on, each said once: the table entry's format, the policy-row rule,
-// the sampler's Philox block, the lazy error report, and the host's choice between one LDS
-// workgroup and one launch per step.
+// k_plan, k_visit, k_sums, k_states, k_window) and their launchers agree on, each said once: the
+// table entry's format, the policy-row rule, the sampler's Philox block, the lazy error report -
+// and, host side, the table blob's layout and the view a launcher takes of it, the discount list,
+// and the choice between one LDS workgroup and one launch per step.
 #ifndef CAMPX_WIDE_TABLE_HIP_H_
 #define CAMPX_WIDE_TABLE_HIP_H_
 
@@ -102,6 +103,49 @@ inline bool ranges_overlap(const void* a, const void* b, int64_t bytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   const uintptr_t n = (uintptr_t)bytes;
   return x < y ? y - x < n : x - y < n;
+}
+
+// Where the parts of the state-table blob are: [entries uint2 x 5S, padded to 16][cells 8 x uint16
+// x S][perf int8 x 5S, padded to 16][rot_obs][rot_board][pieces: 16 words for the layered rows, 16
+// for the flat board].  wide_layout() (k_wide.hip) is the one place that computes the offsets;
+// campx_wide_tables_build() fills a blob by them and wide_tables() below reads one.
+struct WideLayout {
+  int64_t n_entries, cells_off, perf_off, rot_obs_off, rot_board_off, pieces_off, total;
+  int pitch_obs, pitch_board;
+  int n_variants;          // sets of rotations (1: the scenery never changes)
+  int n_planes;            // planes of the trace: the things, plus the variant's when there are several,
+                           // or the mask of the pieces that show
+};
+WideLayout wide_layout(const CampxWideSpec& s);
+
+// A blob on the device as its launchers read it: the layout and a typed pointer to each part.
+struct WideTables {
+  WideLayout lay;
+  const uint2* entries;
+  const u32x4* cells;
+  const int8_t* perf;
+  const int8_t *rot_obs, *rot_board;            // variant v's rotations start v * 16 * pitch bytes on
+  const uint32_t *pieces_obs, *pieces_board;    // NULL for a scenery without pieces
+};
+inline WideTables wide_tables(const CampxWideSpec& s, const void* tables_dev) {
+  WideTables t;
+  t.lay = wide_layout(s);
+  const char* blob = static_cast<const char*>(tables_dev);
+  t.entries = reinterpret_cast<const uint2*>(blob);
+  t.cells = reinterpret_cast<const u32x4*>(blob + t.lay.cells_off);
+  t.perf = reinterpret_cast<const int8_t*>(blob + t.lay.perf_off);
+  t.rot_obs = reinterpret_cast<const int8_t*>(blob + t.lay.rot_obs_off);
+  t.rot_board = reinterpret_cast<const int8_t*>(blob + t.lay.rot_board_off);
+  t.pieces_obs = s.n_pieces > 0 ? reinterpret_cast<const uint32_t*>(blob + t.lay.pieces_off) : nullptr;
+  t.pieces_board = s.n_pieces > 0 ? t.pieces_obs + CAMPX_WIDE_MAX_PIECES : nullptr;
+  return t;
+}
+
+// The discount a kernel reports for each code of an entry: code 0 has none of its own (slot 0
+// is 1), codes 1 .. 15 are the game's list.
+inline void wide_discounts(const CampxWideSpec& s, float (&discounts)[16]) {
+  discounts[0] = 1.0f;
+  for (int i = 1; i < 16; ++i) discounts[i] = s.discount_list[i];
 }
 
 // Work that runs n steps over a table's S states, a lane per state, each step reading what the one

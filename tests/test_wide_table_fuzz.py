@@ -573,6 +573,47 @@ def test_every_launch_of_the_tier_against_the_model(c, monkeypatch):
     f.check_actions()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('lds0', [False, True], ids=['lds', 'lds0'])
+def test_rollout_trace_streams_are_rollouts(lds0):
+  """`rollout()` and `rollout_trace()` launch the update pass through one function: the same actions
+  from the same start leave the same 'trace', 'reward', 'discount', 'done' and 'perf' - bit for bit,
+  against each other and against the model - on a table with discount codes and hidden performance,
+  with the table in LDS and read through the caches."""
+  import contextlib
+  import torch
+  from campx_amd import _hip
+  c = Case(seed=4100, rows=3, cols=7, L=3, K=2, S=37, V=1, P=0, dcodes=True, perf=True, reward=True,
+           B=17, padded=False, lds0=lds0, sixteen=False)
+  T = 3
+  with (_hip.config(wide_lds_max=0) if lds0 else contextlib.nullcontext()):
+    g, f = _game(c)
+    f.showtime()
+    walker = ref.Walker(g, c.B)
+    lead = _actions(c, 30, 5)                    # (a start that is not state 0 everywhere)
+    f.rollout_trace(torch.from_numpy(lead).cuda())
+    walker.rollout(lead)
+    assert len(set(walker.state.tolist())) > 1
+    a = _actions(c, 31, T)
+    ids = torch.from_numpy(a).cuda()
+    start = (f.state.clone(), f.done.clone(), f.ret.clone())
+    full = f.rollout(ids)
+    after = (f.state.clone(), f.done.clone(), f.ret.clone())
+    for x, y in zip((f.state, f.done, f.ret), start):
+      x.copy_(y)
+    only = f.rollout_trace(ids)
+    want = walker.rollout(a)
+    want['trace'] = ref.trace(g, want['states'].reshape(-1)).reshape(f._n_planes, T, c.B)
+    assert len(set(want['discount'].reshape(-1).tolist()) - {0.0, 1.0}) >= 2 and want['perf'].any()
+    for k in ('trace', 'reward', 'discount', 'done', 'perf'):
+      _eq(only[k], _bits(full[k]), ('rollout_trace against rollout', k))
+      _eq(full[k], want[k], ('rollout', k))
+      _eq(only[k], want[k], ('rollout_trace', k))
+    for x, y in zip((f.state, f.done, f.ret), after):
+      _eq(x, _bits(y), 'state after')
+    _state(f, walker, 'rollout_trace')
+
+
 DIRECT = [i for i, c in enumerate(CASES) if (c.K in (3, 5, 8) or c.S == 1) and c.B <= 257][:12]
 
 

@@ -2,7 +2,7 @@
 """Engine.play() per frame on the wide tier (16x16 / 32x32 maze; the coin field of
 examples/coins_batched.py, rows of 300 bytes and three pieces in a mask): us per call, validation off.
 
-    python tools/bench_wide_play.py
+    python tools/bench_wide_play.py [--batch B]
 """
 import os
 import sys
@@ -17,8 +17,12 @@ from campx_amd.games import maze  # noqa: E402
 def main():
   sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'examples'))
   import coins_batched
-  for rows, B in ((16, 65536), (16, 4096), (32, 16384), (32, 1024), (0, 65536), (0, 16384), (0, 4096), (0, 1000),
-                  (-1, 32768), (-1, 4096)):
+  cases = ((16, 65536), (16, 4096), (32, 16384), (32, 1024), (0, 65536), (0, 16384), (0, 4096), (0, 1000),
+           (-1, 32768), (-1, 4096))
+  if len(sys.argv) == 3 and sys.argv[1] == '--batch':
+    # the host's share of a call: one game per one-kernel form (wide_step_kernel, wide_step_lds_kernel)
+    cases = ((16, int(sys.argv[2])), (0, int(sys.argv[2])))
+  for rows, B in cases:
     if rows == -1:       # ... with its switch: a floor that turns, 13 variants of the scenery, rows of 420 bytes
       game = coins_batched.make_game(batch=B, device='cuda')
     elif rows == 0:
