@@ -25,6 +25,7 @@
 //   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
 //   campx::table_lookup             table[states, actions] of a rollout's streams
 //   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
+//   campx::wide_population_sweeps   the policy-evaluation sweeps for a population of policies
 //   campx::wide_visit               exact state visitation of a policy over the state table
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
@@ -1210,6 +1211,48 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
            "campx_wide_sweeps_launch");
 }
 
+// The policy-evaluation sweeps for a population (campx_wide_population_sweeps_launch): `policies`
+// float32 [P, n_states, 5], `residual` float32 [sweeps, P], `gammas` float32 [P] or None for the
+// scalar `gamma`.  `values_in` may be `values_out`.
+void wide_population_sweeps(const Tensor& spec_host, const Tensor& tables, const Tensor& policies,
+                            const OptTensor& reward, double gamma, const OptTensor& gammas,
+                            const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
+                            const OptTensor& q, Tensor& residual, const OptTensor& bad_rows,
+                            const OptTensor& bad_flag, int64_t path) {
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  TORCH_CHECK(values_out.device().is_cuda(),
+              "campx::wide_population_sweeps: values_out must be on a HIP device (no CPU "
+              "implementation)");
+  const c10::Device dev = values_out.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  want_wide_tables(tables, hs, dev);
+  TORCH_CHECK(policies.dim() == 3 && policies.size(0) >= 1,
+              "campx::wide_population_sweeps: policies must be float32 [P, n_states, 5], P >= 1");
+  const int64_t P = policies.size(0);
+  want(policies, "policies", at::kFloat, dev, {P, S, A});
+  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
+  if (gammas.has_value()) want(*gammas, "gammas", at::kFloat, dev, {P});
+  want(values_in, "values_in", at::kFloat, dev, {P, S});
+  want(values_out, "values_out", at::kFloat, dev, {P, S});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, {P, S});
+  if (q.has_value()) want(*q, "q", at::kFloat, dev, {P, S, A});
+  TORCH_CHECK(residual.dim() == 2 && residual.size(0) >= 1 && residual.size(0) <= (1 << 20),
+              "campx::wide_population_sweeps: residual must be float32 [sweeps, P], 1 <= sweeps <= 2^20");
+  want(residual, "residual", at::kFloat, dev, {residual.size(0), P});
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_population_sweeps: path must be 0, 1 or 2");
+  const DeviceGuard guard(dev);
+  check_ok(campx_wide_population_sweeps_launch(
+               hs, tables.data_ptr(), reinterpret_cast<const float*>(policies.data_ptr()), P,
+               opt_ptr<const float>(reward), (float)gamma, opt_ptr<const float>(gammas),
+               reinterpret_cast<const float*>(values_in.data_ptr()),
+               reinterpret_cast<float*>(values_out.data_ptr()), opt_ptr<float>(scratch),
+               opt_ptr<float>(q), reinterpret_cast<float*>(residual.data_ptr()),
+               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)residual.size(0),
+               (int32_t)path, current_stream()),
+           "campx_wide_population_sweeps_launch");
+}
+
 // Exact state visitation of a policy over the state table (campx_wide_visit_launch): as many
 // frames as `finished` has elements, from `start` (int64 [n_states] units of 2^-38; None: one
 // environment in state 0), which may be `final_mass`.
@@ -1315,7 +1358,8 @@ const char* const kOps[] = {
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
     "wide_learn", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
-    "table_lookup", "wide_sweeps", "wide_visit", "onehot_to_ids", "check_actions"};
+    "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "onehot_to_ids",
+    "check_actions"};
 
 }  // namespace
 
@@ -1415,6 +1459,11 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(d!)? greedy, Tensor(e!) residual, Tensor(f!)? bad_rows, Tensor(g!)? bad_flag, "
       "int path) -> ()");
   m.def(
+      "wide_population_sweeps(Tensor spec_host, Tensor tables, Tensor policies, Tensor? reward, "
+      "float gamma, Tensor? gammas, Tensor values_in, Tensor(a!) values_out, Tensor(b!)? scratch, "
+      "Tensor(c!)? q, Tensor(d!) residual, Tensor(e!)? bad_rows, Tensor(f!)? bad_flag, "
+      "int path) -> ()");
+  m.def(
       "wide_visit(Tensor spec_host, Tensor tables, Tensor policy, Tensor? start, bool restart, "
       "Tensor(a!) visits, Tensor(b!) finished, Tensor(c!) final_mass, Tensor(d!)? per_frame, "
       "Tensor(e!) counts, Tensor(f!)? scratch, Tensor(g!)? bad_rows, Tensor(h!)? bad_flag, "
@@ -1445,6 +1494,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("state_sums", &state_sums);
   m.impl("table_lookup", &table_lookup);
   m.impl("wide_sweeps", &wide_sweeps);
+  m.impl("wide_population_sweeps", &wide_population_sweeps);
   m.impl("wide_visit", &wide_visit);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);

@@ -542,6 +542,19 @@ class Engine(object):
     NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
     return self._batched('evaluate_policy').evaluate_policy(policy, gamma, sweeps, **kwargs)
 
+  def population_sweep_buffers(self, P, sweeps, want_q=False):
+    """State-table tier only: the dict of `evaluate_population(out=...)`, allocated once.  See
+    `wide.WideGame.population_sweep_buffers`."""
+    return self._batched('population_sweep_buffers').population_sweep_buffers(P, sweeps, want_q=want_q)
+
+  def evaluate_population(self, policies, gamma, sweeps, **kwargs):
+    """State-table tier only: `evaluate_policy()` for P policies in one launch, `policies` float32
+    `[P, n_states, 5]`, `gamma` a number or a float32 `[P]` tensor; member m of 'values'
+    `[P, n_states]`, 'residual' `[sweeps, P]` and 'q' is bit for bit what `evaluate_policy()` gives
+    for `policies[m]` alone.  See `wide.WideGame.evaluate_population`; the other batched tiers raise
+    NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    return self._batched('evaluate_population').evaluate_population(policies, gamma, sweeps, **kwargs)
+
   def value_iteration(self, gamma, sweeps, **kwargs):
     """State-table tier only: `sweeps` sweeps of value iteration over the game's table - 'values',
     'q', 'greedy', 'residual', 'sweeps'.  See `wide.WideGame.value_iteration`; the other batched

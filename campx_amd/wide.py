@@ -31,8 +31,8 @@ from . import tabulate
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
     'learner_buffers', 'learn_tabular', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
-    'value_iteration', 'visitation_buffers', 'state_visitation', 'render_states',
-    'render_frame_windows', 'render_trace_windows', 'render_state_windows')
+    'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'visitation_buffers',
+    'state_visitation', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
 
 def refuse_state_table_only(tier, answers=None):
@@ -124,6 +124,9 @@ class WideGame(fused.FusedGame):
     self._policy_frame = 0            # absolute frame the next rollout_policy() / rollout_population() continues at
     # bad rows of the policies given to evaluate_policy() (raised under the same flag)
     self._bad_plan_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    # the same of evaluate_population(), summed over the members
+    self._bad_population_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._n_cus = None                # compute units of the device, asked when a plan first needs them
     # bad rows of the policies given to state_visitation() (raised under the same flag)
     self._bad_visit_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     # ids of render_states() outside the table (raised with the rows of render_frames(), under
@@ -167,6 +170,9 @@ class WideGame(fused.FusedGame):
          '{} state ids of render_states() are outside the game\'s table (they were rendered as state 0)'),
         (self._bad_plan_rows, acts,
          '{} rows of the policy given to evaluate_policy() are bad ' + bad_row +
+         '; they were evaluated as taking action {}'),
+        (self._bad_population_rows, acts,
+         '{} rows of the policies given to evaluate_population() are bad ' + bad_row +
          '; they were evaluated as taking action {}'),
         (self._bad_visit_rows, acts,
          '{} rows of the policy given to state_visitation() are bad ' + bad_row +
@@ -267,15 +273,16 @@ class WideGame(fused.FusedGame):
     if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
       raise ValueError('{0} must be an int, 1 <= {0} <= 2^20, got {1!r}'.format(name, n))
 
-  def _planned_path(self, path, plan_fn, *args, what=None):
+  def _planned_path(self, path, plan_fn, *args, what=None, n_cus=None, words=4):
     """The path (1 LDS, 2 global) a planning call takes: `path` checked, then what the library's
     plan function says for this table.  `what`: what path 1 would have to hold, for the message
-    that it does not fit (default: the table)."""
+    that it does not fit (default: the table).  `n_cus`: for a plan that asks for the device's
+    compute units after wide_lds_max; `words`: of the plan it writes."""
     if path not in (0, 1, 2):
       raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
-    plan = (ctypes.c_int64 * 4)()
+    plan = (ctypes.c_int64 * words)()
     lds_max = _hip.config_get('wide_lds_max')
-    code = plan_fn(self.n_states, *(args + (lds_max, path, plan)))
+    code = plan_fn(self.n_states, *(args + (lds_max,) + (() if n_cus is None else (n_cus,)) + (path, plan)))
     if code != 0 and path != 1:      # (only a forced path 1 can be refused for a checked call)
       raise ValueError('path={}: the library refused the plan (code {}; library setting '
                        'wide_lds_max = {})'.format(path, code, lds_max))
@@ -389,8 +396,9 @@ class WideGame(fused.FusedGame):
 
   # ------------------------------------------------------------ closed-loop rollouts of a population
 
-  def _check_population(self, policies):
-    """P of a `policies` argument, checked as `_check_policy()` checks a policy."""
+  def _check_population(self, policies, split=True):
+    """P of a `policies` argument, checked as `_check_policy()` checks a policy; `split`: the
+    members also share out the environments (a rollout's do, an evaluation's need not)."""
     S, A, B = self.n_states, gamespec.N_ACTIONS, self.batch
     if (not torch.is_tensor(policies) or policies.dtype != torch.float32 or policies.dim() != 3
         or tuple(policies.shape[1:]) != (S, A) or policies.shape[0] < 1
@@ -400,6 +408,8 @@ class WideGame(fused.FusedGame):
       raise ValueError('policies must be a contiguous float32 [P, {}, {}] tensor (members x n_states x '
                        'actions) on {}, got {}'.format(S, A, self.device, got))
     P = int(policies.shape[0])
+    if not split:
+      return P
     if P > B or B % P != 0:
       raise ValueError('policies: the {} environments do not split into P = {} equal blocks (P must '
                        'divide the batch)'.format(B, P))
@@ -767,6 +777,128 @@ class WideGame(fused.FusedGame):
     and `evaluate_policy()` take."""
     return self._sweeps(None, gamma, sweeps, values, reward, want_q, tol,
                         check_every, out, path)
+
+  # ------------------------------------------------------------ planning for a population
+
+  POPULATION_MAX_ELEMENTS = (1 << 31) - 1      # P * n_states * 5 of evaluate_population()
+
+  def _check_members(self, P):
+    S, A = self.n_states, gamespec.N_ACTIONS
+    if isinstance(P, bool) or not isinstance(P, int) or P < 1:
+      raise ValueError('P must be an int >= 1, got {!r}'.format(P))
+    if P * S * A > self.POPULATION_MAX_ELEMENTS:
+      raise ValueError('evaluate_population(): P * n_states * 5 = {} x {} x 5 must be at most '
+                       '2^31 - 1; evaluate the population in parts'.format(P, S))
+
+  def population_sweep_buffers(self, P, sweeps, want_q=False):
+    """Allocate the dict of `evaluate_population(out=...)` once: 'values' float32 [P, S], 'residual'
+    float32 [sweeps, P], 'scratch' float32 [P, S] (the second value array of the
+    one-launch-per-sweep path), 'gamma' float32 [P] (for the caller to fill and pass as `gamma`; a
+    number needs none) and with `want_q` 'q' float32 [P, S, 5]."""
+    S, dev = self.n_states, self.device
+    self._check_members(P)
+    self._check_count('sweeps', sweeps)
+    out = {'values': torch.zeros((P, S), dtype=torch.float32, device=dev),
+           'residual': torch.zeros((sweeps, P), dtype=torch.float32, device=dev),
+           'scratch': torch.zeros((P, S), dtype=torch.float32, device=dev),
+           'gamma': torch.zeros((P,), dtype=torch.float32, device=dev)}
+    if want_q:
+      out['q'] = torch.zeros((P, S, gamespec.N_ACTIONS), dtype=torch.float32, device=dev)
+    return out
+
+  def evaluate_population(self, policies, gamma, sweeps, values=None, reward=None, want_q=False,
+                          out=None, path=0):
+    """`evaluate_policy()` for a POPULATION of P policies in one launch: member m of every result
+    is, bit for bit, `evaluate_policy(policies[m], gamma[m], sweeps, ...)` - the exact score that
+    population-based training, an evolution strategy, a sweep over gammas or a set of seeds selects
+    on, without a launch per member (csrc/k_plan.hip, `campx::wide_population_sweeps`).  The rule is
+    `evaluate_policy()`'s and is stated there; no result depends on P, on the order of the members
+    or on the path.
+
+    Args:
+      policies: what `rollout_population()` takes, checked by the same helper - contiguous float32
+          `[P, n_states, 5]` on the game's device - except that P need not divide the batch;
+          `P * n_states * 5 <= 2^31 - 1`.  Bad rows are evaluated as taking action 4 and raise
+          ValueError with their count, summed over the members, lazily as `evaluate_policy()`'s do,
+          in a message that names this call.
+      gamma: a finite number for every member, or a contiguous float32 `[P]` tensor on the game's
+          device, one factor per member.  A tensor is NEVER read on the host: a NaN or an infinity
+          in it is not refused, it propagates through `gamma * D` as the f32 rule says (the
+          member's values come out NaN wherever the product is used).
+      sweeps: how many sweeps to run, 1 .. 2^20.  There is no `tol`: stopping per member would
+          need a host read; 'residual' is there for the caller to read where it matters.
+      values: float32 `[P, n_states]` to start from, or None for zeros.  n sweeps and then m more
+          from the returned 'values' equal n + m sweeps, bit for bit.
+      reward: float32 `[n_states, 5]` used instead of the table's rewards by ALL members.
+      want_q: also return 'q'.
+      out: a dict from `population_sweep_buffers(P, sweeps, want_q)`, overwritten; the call then
+          allocates nothing and is capturable in a HIP graph ('scratch' is needed on path 2 only,
+          'gamma' never).
+      path: 0 - a workgroup keeps the table and several members' vectors in LDS and runs all
+          sweeps in the one launch whenever one member fits there (library setting wide_lds_max),
+          else one launch per sweep for all members; 1 / 2 force either (1 raises ValueError for a
+          table that does not fit).  Both give the same bits.
+
+    Returns a dict: 'values' float32 `[P, n_states]` - `[:, 0]` is each member's value of the state
+    an episode starts from -; 'residual' float32 `[sweeps, P]`; 'sweeps'; with `want_q` 'q' float32
+    `[P, n_states, 5]`.  Argument errors raise ValueError before anything is launched.
+    """
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    P = self._check_population(policies, split=False)
+    self._check_members(P)
+    gammas = None
+    if torch.is_tensor(gamma):
+      if not self._tensor_ok(gamma, torch.float32, (P,)):
+        raise ValueError('gamma must be a finite number or a contiguous float32 [{}] tensor (one per '
+                         'member) on {}, got {} {} on {}'.format(P, dev, gamma.dtype, list(gamma.shape),
+                                                                 gamma.device))
+      gammas, gamma = gamma.detach(), 0.0
+    elif (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
+          or abs(gamma) > torch.finfo(torch.float32).max):
+      raise ValueError('gamma must be a finite number (as a float32) or a float32 [{}] tensor, got '
+                       '{!r}'.format(P, gamma))
+    self._check_count('sweeps', sweeps)
+    if values is not None and not self._tensor_ok(values, torch.float32, (P, S)):
+      raise ValueError('values must be a contiguous float32 [{}, {}] tensor (members x n_states) on '
+                       '{}, or None for zeros'.format(P, S, dev))
+    if reward is not None and not self._tensor_ok(reward, torch.float32, (S, A)):
+      raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
+                       '{}, or None for the table\'s own'.format(S, A, dev))
+    if self._n_cus is None:
+      self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+    planned = self._planned_path(path, _hip.lib.campx_wide_population_sweeps_plan, P,
+                                 0 if reward is None else 1, n_cus=self._n_cus, words=5)
+    want = [('values', torch.float32, (P, S)), ('residual', torch.float32, (sweeps, P))]
+    if planned == 2:
+      want.append(('scratch', torch.float32, (P, S)))
+    if want_q:
+      want.append(('q', torch.float32, (P, S, A)))
+    if out is None:
+      out = self.population_sweep_buffers(P, sweeps, want_q)
+    else:
+      self._check_out(out, want, 'population_sweep_buffers({}, {}, want_q={})'.format(
+          P, sweeps, bool(want_q)))
+      if values is not None and out.get('scratch') is not None and \
+          values.data_ptr() == out['scratch'].data_ptr():
+        raise ValueError('values must not be out[\'scratch\']')
+    v_out = out['values']
+    if values is None:
+      v_out.zero_()
+      v_in = v_out
+    else:
+      v_in = values.detach()
+    validate = self.validate_actions
+    _hip.ops.wide_population_sweeps(
+        self._spec_host, self._tables, policies.detach(), None if reward is None else reward.detach(),
+        float(gamma), gammas, v_in, v_out, out.get('scratch'), out['q'] if want_q else None,
+        out['residual'], self._bad_population_rows if validate else None,
+        self._bad_flag if validate else None, path)
+    if validate:
+      self._after_launch()
+    res = {'values': v_out, 'residual': out['residual'], 'sweeps': sweeps}
+    if want_q:
+      res['q'] = out['q']
+    return res
 
   # ------------------------------------------------------------ exact visitation on the table
 

@@ -1210,6 +1210,53 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* spec_host, const void* tab
                                  int8_t* greedy, float* residual, int32_t* bad_rows,
                                  int32_t* bad_flag, int32_t n_sweeps, int32_t path, void* stream);
 /*
+ * ---- The same for a population of policies, in one launch --------------------------------------
+ * Member m of campx_wide_population_sweeps_launch() IS campx_wide_sweeps_launch() of the policy
+ * `policies[m]` with the factor gamma[m]: the rule above, policy reduction, word for word, and so
+ * the same bits - whatever `members` is, whichever workgroup or lane takes the member, however
+ * members are packed, on either path.
+ *   policies          DEVICE float32 [members][n_states][5]; members * n_states * 5 <= 2^31 - 1
+ *   gammas            DEVICE float32 [members], or NULL: the scalar `gamma`, which must then be
+ *                     finite, holds for every member.  `gammas` is never read on the host: a NaN
+ *                     or an infinity in it propagates through c = gamma * D as the rule says
+ *   reward_override   DEVICE float32 [n_states][5] shared by all members, or NULL
+ *   v_in, v_out       DEVICE float32 [members][n_states]; they may be the same array
+ *   scratch           DEVICE float32 [members][n_states], needed on path 2 only
+ *   q                 DEVICE float32 [members][n_states][5] = each member's q_n, or NULL
+ *   residual          DEVICE float32 [n_sweeps][members]: residual[k-1][m] is member m's for sweep k
+ *   bad_rows          bad rows summed over the members, once per call (as above)
+ * Path 1: a workgroup stages the entries in LDS once and takes G consecutive members - their value
+ * vectors, weights, totals and gammas in LDS too - through all n_sweeps in the ONE launch, one
+ * workgroup barrier per sweep; ceil(members / G) workgroups.  Path 2: one launch per sweep, a lane
+ * per (member, state), a workgroup per 256 states of one member, all members' blocks along grid.x,
+ * between `v_out` and `scratch` after one small kernel that zeroes `residual`.  0 = path 1
+ * whenever ONE member fits the library setting wide_lds_max.  Either grid stops at 2^20
+ * workgroups, each then taking several groups in turn.
+ *
+ * campx_wide_population_sweeps_plan() is the choice as host-only arithmetic: plan_out[5] = the
+ * path; dynamic LDS bytes; threads of a workgroup; workgroups launched; G (1 on path 2).  G is the
+ * least of: what fits wide_lds_max; floor(256 / n_states) or 1, about four waves of (member,
+ * state) pairs to a workgroup; ceil(members / n_cus), so that a small population still spreads
+ * over the chip's `n_cus` compute units.  CAMPX_EINVAL: plan_out NULL, n_states outside 1 ..
+ * CAMPX_WIDE_MAX_STATES, members < 1, members * n_states * 5 above 2^31 - 1, a flag that is not
+ * 0 / 1, n_cus < 1, wide_lds_max < 0, a `path` outside 0..2, path 1 where one member does not fit.
+ * The launch returns CAMPX_EINVAL for the same and for: NULL where it is not allowed, pointers
+ * that are not 4-byte aligned, n_sweeps outside 1 .. 2^20, `gammas` NULL with a `gamma` that is
+ * not finite, `v_in` and `v_out` that overlap without being equal, on path 2 a `scratch` that is
+ * NULL or overlaps either.  Asynchronous on `stream`, no synchronisation, no allocation, no
+ * library state.
+ */
+int32_t campx_wide_population_sweeps_plan(int64_t n_states, int64_t members, int32_t has_override,
+                                          int64_t wide_lds_max, int64_t n_cus, int32_t path,
+                                          int64_t* plan_out);
+int32_t campx_wide_population_sweeps_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                            const float* policies, int64_t members,
+                                            const float* reward_override, float gamma,
+                                            const float* gammas, const float* v_in, float* v_out,
+                                            float* scratch, float* q, float* residual,
+                                            int32_t* bad_rows, int32_t* bad_flag, int32_t n_sweeps,
+                                            int32_t path, void* stream);
+/*
  * ---- Exact state visitation of a policy on the state table ------------------------------------
  * The forward half of the same MDP: given the weights campx_wide_policy_update_launch() samples
  * from, how much probability sits in each state at each frame and how often each (state, action)
