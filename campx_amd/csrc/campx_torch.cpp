@@ -1173,6 +1173,68 @@ void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& ac
            "campx_table_lookup_launch");
 }
 
+// Both sweeps ops.  `what` names the op in its messages; `members`: `policy` is a population's
+// [P, n_states, 5] and every per-member shape has that leading P.
+void sweeps(const char* what, bool members, const Tensor& spec_host, const Tensor& tables,
+            const OptTensor& policy, const OptTensor& reward, double gamma, const OptTensor& gammas,
+            const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
+            const OptTensor& q, const OptTensor& greedy, Tensor& residual,
+            const OptTensor& bad_rows, const OptTensor& bad_flag, int64_t path) {
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  TORCH_CHECK(values_out.device().is_cuda(), what,
+              ": values_out must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = values_out.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  want_wide_tables(tables, hs, dev);
+  TORCH_CHECK(!members || (policy->dim() == 3 && policy->size(0) >= 1), what,
+              ": policies must be float32 [P, n_states, 5], P >= 1");
+  const int64_t P = members ? policy->size(0) : 1;
+  const auto each = [&](std::initializer_list<int64_t> shape) {      // ... of every member
+    std::vector<int64_t> all(members ? 1 : 0, P);
+    all.insert(all.end(), shape);
+    return all;
+  };
+  if (policy.has_value()) want(*policy, members ? "policies" : "policy", at::kFloat, dev, each({S, A}));
+  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
+  if (gammas.has_value()) want(*gammas, "gammas", at::kFloat, dev, {P});
+  want(values_in, "values_in", at::kFloat, dev, each({S}));
+  want(values_out, "values_out", at::kFloat, dev, each({S}));
+  if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, each({S}));
+  if (q.has_value()) want(*q, "q", at::kFloat, dev, each({S, A}));
+  if (greedy.has_value()) want(*greedy, "greedy", at::kChar, dev, {S});
+  if (members) {
+    TORCH_CHECK(residual.dim() == 2 && residual.size(0) >= 1 && residual.size(0) <= (1 << 20), what,
+                ": residual must be float32 [sweeps, P], 1 <= sweeps <= 2^20");
+    want(residual, "residual", at::kFloat, dev, {residual.size(0), P});
+  } else {
+    TORCH_CHECK(residual.device() == dev && residual.scalar_type() == at::kFloat && residual.dim() == 1 &&
+                    residual.is_contiguous() && residual.numel() >= 1 && residual.numel() <= (1 << 20),
+                what, ": residual must be a contiguous float32 [sweeps] tensor on ", dev,
+                ", 1 <= sweeps <= 2^20");
+  }
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  const DeviceGuard guard(dev);
+  const float* v_in = reinterpret_cast<const float*>(values_in.data_ptr());
+  float* v_out = reinterpret_cast<float*>(values_out.data_ptr());
+  float* res = reinterpret_cast<float*>(residual.data_ptr());
+  const int32_t n_sweeps = (int32_t)residual.size(0);
+  if (members)
+    check_ok(campx_wide_population_sweeps_launch(
+                 hs, tables.data_ptr(), opt_ptr<const float>(policy), P, opt_ptr<const float>(reward),
+                 (float)gamma, opt_ptr<const float>(gammas), v_in, v_out, opt_ptr<float>(scratch),
+                 opt_ptr<float>(q), res, opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), n_sweeps,
+                 (int32_t)path, current_stream()),
+             "campx_wide_population_sweeps_launch");
+  else
+    check_ok(campx_wide_sweeps_launch(
+                 hs, tables.data_ptr(), opt_ptr<const float>(policy), opt_ptr<const float>(reward),
+                 (float)gamma, v_in, v_out, opt_ptr<float>(scratch), opt_ptr<float>(q),
+                 opt_ptr<int8_t>(greedy), res, opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev),
+                 n_sweeps, (int32_t)path, current_stream()),
+             "campx_wide_sweeps_launch");
+}
+
 // Sweeps of the Bellman backup over the state table (campx_wide_sweeps_launch): `policy` float32
 // [n_states, 5] for the value of a policy, None for value iteration; as many sweeps as `residual`
 // has elements.  `values_in` may be `values_out`.
@@ -1181,34 +1243,8 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
                  const OptTensor& scratch, const OptTensor& q, const OptTensor& greedy,
                  Tensor& residual, const OptTensor& bad_rows, const OptTensor& bad_flag,
                  int64_t path) {
-  const CampxWideSpec* hs = wide_spec(spec_host);
-  TORCH_CHECK(values_out.device().is_cuda(),
-              "campx::wide_sweeps: values_out must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = values_out.device();
-  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  want_wide_tables(tables, hs, dev);
-  if (policy.has_value()) want(*policy, "policy", at::kFloat, dev, {S, A});
-  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
-  want(values_in, "values_in", at::kFloat, dev, {S});
-  want(values_out, "values_out", at::kFloat, dev, {S});
-  if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, {S});
-  if (q.has_value()) want(*q, "q", at::kFloat, dev, {S, A});
-  if (greedy.has_value()) want(*greedy, "greedy", at::kChar, dev, {S});
-  TORCH_CHECK(residual.device() == dev && residual.scalar_type() == at::kFloat && residual.dim() == 1 &&
-                  residual.is_contiguous() && residual.numel() >= 1 && residual.numel() <= (1 << 20),
-              "campx::wide_sweeps: residual must be a contiguous float32 [sweeps] tensor on ", dev,
-              ", 1 <= sweeps <= 2^20");
-  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
-  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_sweeps: path must be 0, 1 or 2");
-  const DeviceGuard guard(dev);
-  check_ok(campx_wide_sweeps_launch(
-               hs, tables.data_ptr(), opt_ptr<const float>(policy), opt_ptr<const float>(reward),
-               (float)gamma, reinterpret_cast<const float*>(values_in.data_ptr()),
-               reinterpret_cast<float*>(values_out.data_ptr()), opt_ptr<float>(scratch),
-               opt_ptr<float>(q), opt_ptr<int8_t>(greedy),
-               reinterpret_cast<float*>(residual.data_ptr()), opt_ptr<int32_t>(bad_rows),
-               flag_ptr(bad_flag, dev), (int32_t)residual.numel(), (int32_t)path, current_stream()),
-           "campx_wide_sweeps_launch");
+  sweeps("campx::wide_sweeps", false, spec_host, tables, policy, reward, gamma, std::nullopt, values_in,
+         values_out, scratch, q, greedy, residual, bad_rows, bad_flag, path);
 }
 
 // The policy-evaluation sweeps for a population (campx_wide_population_sweeps_launch): `policies`
@@ -1219,38 +1255,8 @@ void wide_population_sweeps(const Tensor& spec_host, const Tensor& tables, const
                             const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
                             const OptTensor& q, Tensor& residual, const OptTensor& bad_rows,
                             const OptTensor& bad_flag, int64_t path) {
-  const CampxWideSpec* hs = wide_spec(spec_host);
-  TORCH_CHECK(values_out.device().is_cuda(),
-              "campx::wide_population_sweeps: values_out must be on a HIP device (no CPU "
-              "implementation)");
-  const c10::Device dev = values_out.device();
-  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  want_wide_tables(tables, hs, dev);
-  TORCH_CHECK(policies.dim() == 3 && policies.size(0) >= 1,
-              "campx::wide_population_sweeps: policies must be float32 [P, n_states, 5], P >= 1");
-  const int64_t P = policies.size(0);
-  want(policies, "policies", at::kFloat, dev, {P, S, A});
-  if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
-  if (gammas.has_value()) want(*gammas, "gammas", at::kFloat, dev, {P});
-  want(values_in, "values_in", at::kFloat, dev, {P, S});
-  want(values_out, "values_out", at::kFloat, dev, {P, S});
-  if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, {P, S});
-  if (q.has_value()) want(*q, "q", at::kFloat, dev, {P, S, A});
-  TORCH_CHECK(residual.dim() == 2 && residual.size(0) >= 1 && residual.size(0) <= (1 << 20),
-              "campx::wide_population_sweeps: residual must be float32 [sweeps, P], 1 <= sweeps <= 2^20");
-  want(residual, "residual", at::kFloat, dev, {residual.size(0), P});
-  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
-  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_population_sweeps: path must be 0, 1 or 2");
-  const DeviceGuard guard(dev);
-  check_ok(campx_wide_population_sweeps_launch(
-               hs, tables.data_ptr(), reinterpret_cast<const float*>(policies.data_ptr()), P,
-               opt_ptr<const float>(reward), (float)gamma, opt_ptr<const float>(gammas),
-               reinterpret_cast<const float*>(values_in.data_ptr()),
-               reinterpret_cast<float*>(values_out.data_ptr()), opt_ptr<float>(scratch),
-               opt_ptr<float>(q), reinterpret_cast<float*>(residual.data_ptr()),
-               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)residual.size(0),
-               (int32_t)path, current_stream()),
-           "campx_wide_population_sweeps_launch");
+  sweeps("campx::wide_population_sweeps", true, spec_host, tables, policies, reward, gamma, gammas,
+         values_in, values_out, scratch, q, std::nullopt, residual, bad_rows, bad_flag, path);
 }
 
 // Exact state visitation of a policy over the state table (campx_wide_visit_launch): as many

@@ -640,31 +640,47 @@ class WideGame(fused.FusedGame):
             'discount': torch.where(code != 0, listed[code], plain),
             'perf': perf}
 
+  def _sweep_buffers(self, lead, sweeps, want_q):
+    """What both dicts of buffers share; `lead`: the leading dimensions of a member's, () or (P,)."""
+    S, dev = self.n_states, self.device
+    out = {'values': torch.zeros(lead + (S,), dtype=torch.float32, device=dev),
+           'residual': torch.zeros((int(sweeps),) + lead, dtype=torch.float32, device=dev),
+           'scratch': torch.zeros(lead + (S,), dtype=torch.float32, device=dev)}
+    if want_q:
+      out['q'] = torch.zeros(lead + (S, gamespec.N_ACTIONS), dtype=torch.float32, device=dev)
+    return out
+
   def sweep_buffers(self, sweeps, want_q=True, greedy=True):
     """Allocate the dict of `evaluate_policy(out=...)` (`greedy=False`) or
     `value_iteration(out=...)` once: 'values' float32 [S], 'residual' float32 [sweeps], 'scratch'
     float32 [S] (the second value vector of the one-launch-per-sweep path), with `want_q` 'q'
     float32 [S, 5] and with `greedy` 'greedy' int8 [S]."""
-    S, dev = self.n_states, self.device
-    out = {'values': torch.zeros((S,), dtype=torch.float32, device=dev),
-           'residual': torch.zeros((int(sweeps),), dtype=torch.float32, device=dev),
-           'scratch': torch.zeros((S,), dtype=torch.float32, device=dev)}
-    if want_q:
-      out['q'] = torch.zeros((S, gamespec.N_ACTIONS), dtype=torch.float32, device=dev)
+    out = self._sweep_buffers((), sweeps, want_q)
     if greedy:
-      out['greedy'] = torch.zeros((S,), dtype=torch.int8, device=dev)
+      out['greedy'] = torch.zeros((self.n_states,), dtype=torch.int8, device=self.device)
     return out
 
-  def _sweeps(self, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path):
+  def _sweeps(self, P, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path):
+    """The body of `evaluate_policy()`, of `value_iteration()` (`policy` None) and - `P` not None,
+    every per-member shape with that leading P - of `evaluate_population()`, their policy checked."""
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
-    greedy = policy is None
-    if (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
-        or abs(gamma) > torch.finfo(torch.float32).max):
-      raise ValueError('gamma must be a finite number (as a float32), got {!r}'.format(gamma))
+    greedy, members = policy is None, P is not None
+    lead = (P,) if members else ()
+    gammas = None
+    if members and torch.is_tensor(gamma):
+      if not self._tensor_ok(gamma, torch.float32, (P,)):
+        raise ValueError('gamma must be a finite number or a contiguous float32 [{}] tensor (one per '
+                         'member) on {}, got {} {} on {}'.format(P, dev, gamma.dtype, list(gamma.shape),
+                                                                 gamma.device))
+      gammas, gamma = gamma.detach(), 0.0
+    elif (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
+          or abs(gamma) > torch.finfo(torch.float32).max):
+      raise ValueError('gamma must be a finite number (as a float32){}, got {!r}'.format(
+          ' or a float32 [{}] tensor'.format(P) if members else '', gamma))
     self._check_count('sweeps', sweeps)
-    if values is not None and not self._tensor_ok(values, torch.float32, (S,)):
-      raise ValueError('values must be a contiguous float32 [{}] tensor (n_states) on {}, or '
-                       'None for zeros'.format(S, dev))
+    if values is not None and not self._tensor_ok(values, torch.float32, lead + (S,)):
+      raise ValueError('values must be a contiguous float32 {} tensor ({}n_states) on {}, or '
+                       'None for zeros'.format(list(lead + (S,)), 'members x ' if members else '', dev))
     if reward is not None and not self._tensor_ok(reward, torch.float32, (S, A)):
       raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
                        '{}, or None for the table\'s own'.format(S, A, dev))
@@ -673,20 +689,29 @@ class WideGame(fused.FusedGame):
       raise ValueError('tol must be a finite number >= 0 or None, got {!r}'.format(tol))
     if isinstance(check_every, bool) or not isinstance(check_every, int) or check_every < 1:
       raise ValueError('check_every must be an int >= 1, got {!r}'.format(check_every))
-    planned = self._planned_path(path, _hip.lib.campx_wide_sweeps_plan, 0 if greedy else 1,
-                                 0 if reward is None else 1)
-    want = [('values', torch.float32, (S,)), ('residual', torch.float32, (sweeps,))]
+    override = 0 if reward is None else 1
+    if members:
+      if self._n_cus is None:
+        self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+      planned = self._planned_path(path, _hip.lib.campx_wide_population_sweeps_plan, P, override,
+                                   n_cus=self._n_cus, words=5)
+    else:
+      planned = self._planned_path(path, _hip.lib.campx_wide_sweeps_plan, 0 if greedy else 1, override)
+    want = [('values', torch.float32, lead + (S,)), ('residual', torch.float32, (sweeps,) + lead)]
     if planned == 2:
-      want.append(('scratch', torch.float32, (S,)))
+      want.append(('scratch', torch.float32, lead + (S,)))
     if want_q:
-      want.append(('q', torch.float32, (S, A)))
+      want.append(('q', torch.float32, lead + (S, A)))
     if greedy:
       want.append(('greedy', torch.int8, (S,)))
     if out is None:
-      out = self.sweep_buffers(sweeps, want_q, greedy)
+      out = (self.population_sweep_buffers(P, sweeps, want_q) if members
+             else self.sweep_buffers(sweeps, want_q, greedy))
     else:
-      self._check_out(out, want, 'sweep_buffers({}, want_q={}, greedy={})'.format(
-          sweeps, bool(want_q), greedy))
+      self._check_out(out, want,
+                      'population_sweep_buffers({}, {}, want_q={})'.format(P, sweeps, bool(want_q))
+                      if members else
+                      'sweep_buffers({}, want_q={}, greedy={})'.format(sweeps, bool(want_q), greedy))
       if values is not None and out.get('scratch') is not None and \
           values.data_ptr() == out['scratch'].data_ptr():
         raise ValueError('values must not be out[\'scratch\']')
@@ -700,22 +725,27 @@ class WideGame(fused.FusedGame):
       v_in = values.detach()
     residual = out['residual']
     validate = self.validate_actions
+    bad_rows = self._bad_population_rows if members else self._bad_plan_rows
     ran = 0
     while ran < sweeps:
       n = sweeps - ran if tol is None else min(check_every, sweeps - ran)
       count = validate and ran == 0 and not greedy        # bad rows: once per call
-      _hip.ops.wide_sweeps(self._spec_host, self._tables, policy, reward, float(gamma), v_in, v_out,
-                           out.get('scratch'), out['q'] if want_q else None,
-                           out['greedy'] if greedy else None, residual[ran:ran + n],
-                           self._bad_plan_rows if count else None,
-                           self._bad_flag if count else None, path)
+      head = (self._spec_host, self._tables, policy, reward, float(gamma))
+      tail = (residual[ran:ran + n], bad_rows if count else None, self._bad_flag if count else None,
+              path)
+      q = out['q'] if want_q else None
+      if members:
+        _hip.ops.wide_population_sweeps(*head, gammas, v_in, v_out, out.get('scratch'), q, *tail)
+      else:
+        _hip.ops.wide_sweeps(*head, v_in, v_out, out.get('scratch'), q,
+                             out['greedy'] if greedy else None, *tail)
       ran += n
       v_in = v_out
       if tol is not None and bool((residual[ran - n:ran] <= tol).any()):     # (synchronises)
         break
     if validate:
       self._after_launch()
-    res = {'values': v_out, 'residual': residual[:ran], 'sweeps': ran}
+    res = {'values': v_out, 'residual': residual if ran == sweeps else residual[:ran], 'sweeps': ran}
     if want_q:
       res['q'] = out['q']
     if greedy:
@@ -764,7 +794,7 @@ class WideGame(fused.FusedGame):
     'sweeps' int, the sweeps run.  Argument errors raise ValueError before anything is launched.
     """
     self._check_policy(policy)
-    return self._sweeps(policy.detach(), gamma, sweeps, values, reward, want_q,
+    return self._sweeps(None, policy.detach(), gamma, sweeps, values, reward, want_q,
                         tol, check_every, out, path)
 
   def value_iteration(self, gamma, sweeps, values=None, reward=None, want_q=True, tol=None,
@@ -775,7 +805,7 @@ class WideGame(fused.FusedGame):
     lowest action that attains the maximum of the returned q.  A one-hot policy built from it -
     `torch.nn.functional.one_hot(res['greedy'].long(), 5).float()` - is what `rollout_policy()`
     and `evaluate_policy()` take."""
-    return self._sweeps(None, gamma, sweeps, values, reward, want_q, tol,
+    return self._sweeps(None, None, gamma, sweeps, values, reward, want_q, tol,
                         check_every, out, path)
 
   # ------------------------------------------------------------ planning for a population
@@ -795,15 +825,10 @@ class WideGame(fused.FusedGame):
     float32 [sweeps, P], 'scratch' float32 [P, S] (the second value array of the
     one-launch-per-sweep path), 'gamma' float32 [P] (for the caller to fill and pass as `gamma`; a
     number needs none) and with `want_q` 'q' float32 [P, S, 5]."""
-    S, dev = self.n_states, self.device
     self._check_members(P)
     self._check_count('sweeps', sweeps)
-    out = {'values': torch.zeros((P, S), dtype=torch.float32, device=dev),
-           'residual': torch.zeros((sweeps, P), dtype=torch.float32, device=dev),
-           'scratch': torch.zeros((P, S), dtype=torch.float32, device=dev),
-           'gamma': torch.zeros((P,), dtype=torch.float32, device=dev)}
-    if want_q:
-      out['q'] = torch.zeros((P, S, gamespec.N_ACTIONS), dtype=torch.float32, device=dev)
+    out = self._sweep_buffers((P,), sweeps, want_q)
+    out['gamma'] = torch.zeros((P,), dtype=torch.float32, device=self.device)
     return out
 
   def evaluate_population(self, policies, gamma, sweeps, values=None, reward=None, want_q=False,
@@ -843,62 +868,9 @@ class WideGame(fused.FusedGame):
     an episode starts from -; 'residual' float32 `[sweeps, P]`; 'sweeps'; with `want_q` 'q' float32
     `[P, n_states, 5]`.  Argument errors raise ValueError before anything is launched.
     """
-    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
     P = self._check_population(policies, split=False)
     self._check_members(P)
-    gammas = None
-    if torch.is_tensor(gamma):
-      if not self._tensor_ok(gamma, torch.float32, (P,)):
-        raise ValueError('gamma must be a finite number or a contiguous float32 [{}] tensor (one per '
-                         'member) on {}, got {} {} on {}'.format(P, dev, gamma.dtype, list(gamma.shape),
-                                                                 gamma.device))
-      gammas, gamma = gamma.detach(), 0.0
-    elif (isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma)
-          or abs(gamma) > torch.finfo(torch.float32).max):
-      raise ValueError('gamma must be a finite number (as a float32) or a float32 [{}] tensor, got '
-                       '{!r}'.format(P, gamma))
-    self._check_count('sweeps', sweeps)
-    if values is not None and not self._tensor_ok(values, torch.float32, (P, S)):
-      raise ValueError('values must be a contiguous float32 [{}, {}] tensor (members x n_states) on '
-                       '{}, or None for zeros'.format(P, S, dev))
-    if reward is not None and not self._tensor_ok(reward, torch.float32, (S, A)):
-      raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
-                       '{}, or None for the table\'s own'.format(S, A, dev))
-    if self._n_cus is None:
-      self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-    planned = self._planned_path(path, _hip.lib.campx_wide_population_sweeps_plan, P,
-                                 0 if reward is None else 1, n_cus=self._n_cus, words=5)
-    want = [('values', torch.float32, (P, S)), ('residual', torch.float32, (sweeps, P))]
-    if planned == 2:
-      want.append(('scratch', torch.float32, (P, S)))
-    if want_q:
-      want.append(('q', torch.float32, (P, S, A)))
-    if out is None:
-      out = self.population_sweep_buffers(P, sweeps, want_q)
-    else:
-      self._check_out(out, want, 'population_sweep_buffers({}, {}, want_q={})'.format(
-          P, sweeps, bool(want_q)))
-      if values is not None and out.get('scratch') is not None and \
-          values.data_ptr() == out['scratch'].data_ptr():
-        raise ValueError('values must not be out[\'scratch\']')
-    v_out = out['values']
-    if values is None:
-      v_out.zero_()
-      v_in = v_out
-    else:
-      v_in = values.detach()
-    validate = self.validate_actions
-    _hip.ops.wide_population_sweeps(
-        self._spec_host, self._tables, policies.detach(), None if reward is None else reward.detach(),
-        float(gamma), gammas, v_in, v_out, out.get('scratch'), out['q'] if want_q else None,
-        out['residual'], self._bad_population_rows if validate else None,
-        self._bad_flag if validate else None, path)
-    if validate:
-      self._after_launch()
-    res = {'values': v_out, 'residual': out['residual'], 'sweeps': sweeps}
-    if want_q:
-      res['q'] = out['q']
-    return res
+    return self._sweeps(P, policies.detach(), gamma, sweeps, values, reward, want_q, None, 32, out, path)
 
   # ------------------------------------------------------------ exact visitation on the table
 

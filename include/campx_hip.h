@@ -1214,7 +1214,9 @@ int32_t campx_wide_sweeps_launch(const CampxWideSpec* spec_host, const void* tab
  * Member m of campx_wide_population_sweeps_launch() IS campx_wide_sweeps_launch() of the policy
  * `policies[m]` with the factor gamma[m]: the rule above, policy reduction, word for word, and so
  * the same bits - whatever `members` is, whichever workgroup or lane takes the member, however
- * members are packed, on either path.
+ * members are packed, on either path.  Both launches are one launch inside: members = 1 with
+ * `gammas` NULL runs campx_wide_sweeps_launch()'s own kernels (planned as a population of one);
+ * members = 1 with a `gammas` runs the population's.
  *   policies          DEVICE float32 [members][n_states][5]; members * n_states * 5 <= 2^31 - 1
  *   gammas            DEVICE float32 [members], or NULL: the scalar `gamma`, which must then be
  *                     finite, holds for every member.  `gammas` is never read on the host: a NaN

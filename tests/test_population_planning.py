@@ -226,19 +226,118 @@ def test_more_workgroups_than_a_grid_holds():
   _eq(packed['residual'][:, sample], want['residual'], 'residual')
 
 
+ONE_MEMBER = ((37, 7), (257, 7), (1025, 2), (1025, 3))   # less than a wave; a second workgroup of one
+                                                         # live lane on path 2; two states to a thread
+
+
+def _one_member(S, seed=4):
+  g = _table(S, dcodes=True)
+  w, _ = _policy(S, 'zeros', seed)
+  rng = np.random.RandomState(S)
+  over = rng.uniform(-1, 1, size=(S, 5)).astype(np.float32)
+  start = rng.uniform(-2, 2, size=S).astype(np.float32)
+  return g, _game(g), w, over, start
+
+
+def _eq_member(res, alone, what):
+  n, S = alone['residual'].shape[0], alone['values'].shape[0]
+  assert tuple(res['values'].shape) == (1, S) and tuple(res['residual'].shape) == (n, 1)
+  _eq(res['values'][0], alone['values'], (what, 'values'))
+  _eq(res['q'][0], alone['q'], (what, 'q'))
+  _eq(res['residual'][:, 0], alone['residual'], (what, 'residual'))
+
+
 def test_one_member_is_evaluate_policy():
-  for S, n in ((37, 7), (1025, 2)):
-    g = _table(S, dcodes=True)
-    f = _game(g)
-    w, _ = _policy(S, 'zeros', 4)
+  """P = 1 without a gamma of its own runs evaluate_policy()'s kernels: every path of either call
+  against every path of the other and against the reference - from zeros with the table's rewards,
+  from given values with a reward override, and with `values is out['values']` (an odd count: on
+  path 2 the start is copied into the scratch array first)."""
+  for S, n in ONE_MEMBER:
+    g, f, w, over, start = _one_member(S)
     policy = torch.from_numpy(w).cuda()
     alone = f.evaluate_policy(policy, 0.99, n)
     for path in (1, 2):
       res = f.evaluate_population(policy[None], 0.99, n, want_q=True, path=path)
-      assert tuple(res['values'].shape) == (1, S) and tuple(res['residual'].shape) == (n, 1)
-      _eq(res['values'][0], alone['values'], (S, path, 'values'))
-      _eq(res['q'][0], alone['q'], (S, path, 'q'))
-      _eq(res['residual'][:, 0], alone['residual'], (S, path, 'residual'))
+      _eq_member(res, alone, (S, path))
+    kw = dict(reward=torch.from_numpy(over).cuda())
+    values = torch.from_numpy(start).cuda()
+    want = plan_ref.sweeps(g.st_next, g.st_reward, g.st_done, g.st_discount, np.float32(0.99), n, policy=w,
+                           values=start, reward_override=over)
+    for solo_path in (1, 2, 0):
+      alone = f.evaluate_policy(policy, 0.99, n, values=values, path=solo_path, **kw)
+      for k in ('values', 'q', 'residual'):
+        _eq(alone[k], want[k], (S, solo_path, k, 'evaluate_policy() against the reference'))
+      for path in (1, 2, 0):
+        res = f.evaluate_population(policy[None], 0.99, n, values=values[None], want_q=True, path=path, **kw)
+        _eq_member(res, alone, (S, solo_path, path, 'override, start'))
+    _eq(values, start, 'the values given are left as they are')
+    for path in (1, 2):
+      out = f.population_sweep_buffers(1, n, want_q=True)
+      out['values'].copy_(values[None])
+      res = f.evaluate_population(policy[None], 0.99, n, values=out['values'], want_q=True, out=out, path=path, **kw)
+      assert res['values'] is out['values']
+      _eq_member(res, want, (S, path, 'values is out[values]'))
+      solo = f.sweep_buffers(n, greedy=False)
+      solo['values'].copy_(values)
+      alone = f.evaluate_policy(policy, 0.99, n, values=solo['values'], out=solo, path=path, **kw)
+      _eq_member(res, alone, (S, path, 'both aliased'))
+
+
+def test_one_member_with_a_gamma_of_its_own():
+  """P = 1 with `gamma` as a float32 [1] tensor: the same bits as evaluate_policy() with that number
+  on both paths; the tensor is not read on the host, so a NaN in it is not refused and the result is
+  the reference's (NaN in the same places - the payload of a generated NaN is defined by no rule -
+  and the same bits everywhere else)."""
+  import float_edges as fe
+  for S, n in ONE_MEMBER:
+    g, f, w, over, start = _one_member(S)
+    policy = torch.from_numpy(w).cuda()
+    values = torch.from_numpy(start).cuda()
+    for gamma in (np.float32(0.99), np.float32(0.3)):
+      gammas = torch.from_numpy(np.array([gamma])).cuda()
+      alone = f.evaluate_policy(policy, float(gamma), n, values=values)
+      for path in (1, 2):
+        res = f.evaluate_population(policy[None], gammas, n, values=values[None], want_q=True, path=path)
+        _eq_member(res, alone, (S, float(gamma), path))
+    nan = torch.full((1,), float('nan'), device='cuda')
+    want = plan_ref.sweeps(g.st_next, g.st_reward, g.st_done, g.st_discount, np.float32(np.nan), n, policy=w,
+                           values=start)
+    assert np.isnan(want['values']).any() and np.isnan(want['residual']).any()
+    for path in (1, 2):
+      res = f.evaluate_population(policy[None], nan, n, values=values[None], want_q=True, path=path)
+      assert fe.same_bits_or_nan(res['values'][0].cpu().numpy(), want['values']), (S, path, 'values')
+      assert fe.same_bits_or_nan(res['q'][0].cpu().numpy(), want['q']), (S, path, 'q')
+      assert fe.same_bits_or_nan(res['residual'][:, 0].cpu().numpy(), want['residual']), (S, path, 'residual')
+
+
+def test_bad_rows_of_one_member_land_on_the_call_s_own_counter():
+  """The same kernels from either call: the rows are counted where the call says, and named by it."""
+  S, n = 37, 2
+  g = _table(S)
+  f = _game(g)
+  f.validate_actions = 'sync'
+  w, n_bad = _policy(S, 'bad', 9)
+  assert n_bad == 3
+  policy = torch.from_numpy(w).cuda()
+  for path in (1, 2):
+    with pytest.raises(ValueError) as e:
+      f.evaluate_population(policy[None], 0.5, n, path=path)
+    assert str(e.value).startswith('3 rows of the policies given to evaluate_population()')
+    assert 'evaluate_policy()' not in str(e.value)
+    assert int(f._bad_plan_rows.item()) == 0 and int(f._bad_population_rows.item()) == 0
+    f.check_actions()                            # nothing is left counted
+    with pytest.raises(ValueError) as e:
+      f.evaluate_policy(policy, 0.5, n, path=path)
+    assert str(e.value).startswith('3 rows of the policy given to evaluate_policy()')
+    assert 'evaluate_population()' not in str(e.value)
+    assert int(f._bad_plan_rows.item()) == 0 and int(f._bad_population_rows.item()) == 0
+    f.check_actions()
+  # not validated: neither counter moves
+  f.validate_actions = False
+  f.evaluate_population(policy[None], 0.5, n)
+  f.evaluate_policy(policy, 0.5, n)
+  torch.cuda.synchronize()
+  assert int(f._bad_plan_rows.item()) == 0 and int(f._bad_population_rows.item()) == 0
 
 
 def test_a_member_does_not_depend_on_the_others_or_on_its_place():
