@@ -43,6 +43,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_sweeps_plan', 'campx_wide_sweeps_launch',
            'campx_wide_population_sweeps_plan', 'campx_wide_population_sweeps_launch',
            'campx_wide_visit_plan', 'campx_wide_visit_launch',
+           'campx_wide_visit_population_plan', 'campx_wide_visit_population_launch',
            'campx_check_actions_launch',
            'campx_onehot_to_ids_launch', 'campx_config_set', 'campx_config_get',
            'campx_config_string', 'campx_write_probe_launch', 'campx_strerror',
@@ -283,6 +284,11 @@ def _load():
   lib.campx_wide_visit_launch.restype = i32
   lib.campx_wide_visit_launch.argtypes = [wide_p, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp,
                                           i32, vp]
+  lib.campx_wide_visit_population_plan.restype = i32
+  lib.campx_wide_visit_population_plan.argtypes = [i64, i64, i64, i64, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_visit_population_launch.restype = i32
+  lib.campx_wide_visit_population_launch.argtypes = [wide_p, vp, vp, i64, vp, i32, i32, i32, vp, vp, vp, vp,
+                                                     vp, vp, vp, vp, i32, vp]
   lib.campx_render_gather_plan.restype = i32
   lib.campx_render_gather_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_check_actions_launch.restype = i32
@@ -335,7 +341,7 @@ ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps',
-            'wide_population_sweeps', 'wide_visit', 'onehot_to_ids', 'check_actions')
+            'wide_population_sweeps', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

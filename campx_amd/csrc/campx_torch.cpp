@@ -27,6 +27,7 @@
 //   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
 //   campx::wide_population_sweeps   the policy-evaluation sweeps for a population of policies
 //   campx::wide_visit               exact state visitation of a policy over the state table
+//   campx::wide_visit_population    the same for a population of policies
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
 //
 // Contract: every tensor is caller-owned and contiguous; outputs are written in
@@ -1299,6 +1300,53 @@ void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& pol
            "campx_wide_visit_launch");
 }
 
+// Exact state visitation of a population of policies (campx_wide_visit_population_launch):
+// `policies` float32 [P, n_states, 5], as many frames as `finished` [frames, P] has rows, from
+// `start` - int64 [P, n_states] per member, which may be `final_mass`, or [n_states] shared by
+// all; None: one environment in state 0 for every member.
+void wide_visit_population(const Tensor& spec_host, const Tensor& tables, const Tensor& policies,
+                           const OptTensor& start, bool restart, Tensor& visits, Tensor& finished,
+                           Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
+                           const OptTensor& scratch, const OptTensor& bad_rows,
+                           const OptTensor& bad_flag, int64_t path) {
+  const char* what = "campx::wide_visit_population";
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  TORCH_CHECK(visits.device().is_cuda(), what, ": visits must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = visits.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  want_wide_tables(tables, hs, dev);
+  TORCH_CHECK(policies.dim() == 3 && policies.size(0) >= 1, what,
+              ": policies must be float32 [P, n_states, 5], P >= 1");
+  const int64_t P = policies.size(0);
+  want(policies, "policies", at::kFloat, dev, {P, S, A});
+  const bool per_member = start.has_value() && start->dim() == 2;
+  if (start.has_value()) {
+    if (per_member) want(*start, "start", at::kLong, dev, {P, S});
+    else want(*start, "start", at::kLong, dev, {S});
+  }
+  want(visits, "visits", at::kLong, dev, {P, S, A});
+  TORCH_CHECK(finished.dim() == 2 && finished.size(0) >= 1 && finished.size(0) <= (1 << 20), what,
+              ": finished must be int64 [frames, P], 1 <= frames <= 2^20");
+  const int64_t T = finished.size(0);
+  want(finished, "finished", at::kLong, dev, {T, P});
+  want(final_mass, "final_mass", at::kLong, dev, {P, S});
+  if (per_frame.has_value()) want(*per_frame, "per_frame", at::kLong, dev, {T + 1, P, S});
+  want(counts, "counts", at::kInt, dev, {P, S, A});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, {P, S});
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  const DeviceGuard guard(dev);
+  check_ok(campx_wide_visit_population_launch(
+               hs, tables.data_ptr(), reinterpret_cast<const float*>(policies.data_ptr()), P,
+               opt_ptr<const int64_t>(start), per_member ? 1 : 0, restart ? 1 : 0, (int32_t)T,
+               reinterpret_cast<int64_t*>(visits.data_ptr()),
+               reinterpret_cast<int64_t*>(finished.data_ptr()),
+               reinterpret_cast<int64_t*>(final_mass.data_ptr()), opt_ptr<int64_t>(per_frame),
+               reinterpret_cast<int32_t*>(counts.data_ptr()), opt_ptr<int64_t>(scratch),
+               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path, current_stream()),
+           "campx_wide_visit_population_launch");
+}
+
 void onehot_to_ids(const Tensor& onehot, Tensor& ids_out, Tensor& bad_count) {
   TORCH_CHECK(onehot.device().is_cuda(), "campx::onehot_to_ids: HIP tensors only");
   const c10::Device dev = onehot.device();
@@ -1364,7 +1412,8 @@ const char* const kOps[] = {
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
     "wide_learn", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
-    "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "onehot_to_ids",
+    "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "wide_visit_population",
+    "onehot_to_ids",
     "check_actions"};
 
 }  // namespace
@@ -1474,6 +1523,11 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(a!) visits, Tensor(b!) finished, Tensor(c!) final_mass, Tensor(d!)? per_frame, "
       "Tensor(e!) counts, Tensor(f!)? scratch, Tensor(g!)? bad_rows, Tensor(h!)? bad_flag, "
       "int path) -> ()");
+  m.def(
+      "wide_visit_population(Tensor spec_host, Tensor tables, Tensor policies, Tensor? start, "
+      "bool restart, Tensor(a!) visits, Tensor(b!) finished, Tensor(c!) final_mass, "
+      "Tensor(d!)? per_frame, Tensor(e!) counts, Tensor(f!)? scratch, Tensor(g!)? bad_rows, "
+      "Tensor(h!)? bad_flag, int path) -> ()");
   m.def("onehot_to_ids(Tensor onehot, Tensor(a!) ids, Tensor(b!) bad_count) -> ()");
   m.def("check_actions(Tensor actions, Tensor(a!) bad_count) -> ()");
 }
@@ -1502,6 +1556,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_sweeps", &wide_sweeps);
   m.impl("wide_population_sweeps", &wide_population_sweeps);
   m.impl("wide_visit", &wide_visit);
+  m.impl("wide_visit_population", &wide_visit_population);
   m.impl("onehot_to_ids", &onehot_to_ids);
   m.impl("check_actions", &check_actions);
 }

@@ -579,6 +579,20 @@ class Engine(object):
     `wide.WideGame.visitation_buffers`."""
     return self._batched('visitation_buffers').visitation_buffers(frames, want_frames)
 
+  def visit_population_buffers(self, P, frames, want_frames=False):
+    """State-table tier only: the dict of `visit_population(out=...)`, allocated once.  See
+    `wide.WideGame.visit_population_buffers`."""
+    return self._batched('visit_population_buffers').visit_population_buffers(P, frames, want_frames)
+
+  def visit_population(self, policies, frames, **kwargs):
+    """State-table tier only: `state_visitation()` for P policies in one launch, `policies` float32
+    `[P, n_states, 5]`; member m of 'visits' `[P, n_states, 5]`, 'finished' `[frames, P]`, 'final'
+    `[P, n_states]`, 'per_frame' `[frames + 1, P, n_states]`, 'counts' and 'probs' is bit for bit
+    what `state_visitation()` gives for `policies[m]` alone.  See `wide.WideGame.visit_population`;
+    the other batched tiers raise NotImplementedError (`use_state_table()` before `its_showtime()`
+    puts a game on this one)."""
+    return self._batched('visit_population').visit_population(policies, frames, **kwargs)
+
   def render_frames(self, trace, t_idx, e_idx, obs_dtype=torch.int8, out=None):
     """Batched tiers only: the observations `[N, L, H, W]` of the (frame, environment) pairs
     `(t_idx[i], e_idx[i])` of a trace, bit for bit what `rollout()` writes for them.  See

@@ -32,7 +32,7 @@ STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
     'learner_buffers', 'learn_tabular', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'visitation_buffers',
-    'state_visitation', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
+    'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
 
 def refuse_state_table_only(tier, answers=None):
@@ -129,6 +129,8 @@ class WideGame(fused.FusedGame):
     self._n_cus = None                # compute units of the device, asked when a plan first needs them
     # bad rows of the policies given to state_visitation() (raised under the same flag)
     self._bad_visit_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    # the same of visit_population(), summed over the members
+    self._bad_visit_member_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     # ids of render_states() outside the table (raised with the rows of render_frames(), under
     # their flag), and the one-frame trace of its out= calls: the last block is the largest; the
     # smaller ones before it stay alive, a captured graph may still write into them
@@ -176,6 +178,9 @@ class WideGame(fused.FusedGame):
          '; they were evaluated as taking action {}'),
         (self._bad_visit_rows, acts,
          '{} rows of the policy given to state_visitation() are bad ' + bad_row +
+         '; all their mass took action {}'),
+        (self._bad_visit_member_rows, acts,
+         '{} rows of the policies given to visit_population() are bad ' + bad_row +
          '; all their mass took action {}'),
         (self._bad_window_rows, idx,
          '{} rows of render_frame_windows() named a frame or an environment outside the trace (their '
@@ -812,13 +817,13 @@ class WideGame(fused.FusedGame):
 
   POPULATION_MAX_ELEMENTS = (1 << 31) - 1      # P * n_states * 5 of evaluate_population()
 
-  def _check_members(self, P):
+  def _check_members(self, P, call='evaluate_population', verb='evaluate'):
     S, A = self.n_states, gamespec.N_ACTIONS
     if isinstance(P, bool) or not isinstance(P, int) or P < 1:
       raise ValueError('P must be an int >= 1, got {!r}'.format(P))
     if P * S * A > self.POPULATION_MAX_ELEMENTS:
-      raise ValueError('evaluate_population(): P * n_states * 5 = {} x {} x 5 must be at most '
-                       '2^31 - 1; evaluate the population in parts'.format(P, S))
+      raise ValueError('{}(): P * n_states * 5 = {} x {} x 5 must be at most '
+                       '2^31 - 1; {} the population in parts'.format(call, P, S, verb))
 
   def population_sweep_buffers(self, P, sweeps, want_q=False):
     """Allocate the dict of `evaluate_population(out=...)` once: 'values' float32 [P, S], 'residual'
@@ -994,6 +999,151 @@ class WideGame(fused.FusedGame):
     if want_frames:
       res['per_frame'] = out['per_frame']
     return res
+
+  # ------------------------------------------------------------ exact visitation of a population
+
+  VISIT_MAX_FRAME_ELEMENTS = (1 << 31) - 1     # (frames + 1) * P * n_states of visit_population()'s 'per_frame'
+
+  def _check_frame_elements(self, P, frames):
+    if (frames + 1) * P * self.n_states > self.VISIT_MAX_FRAME_ELEMENTS:
+      raise ValueError('visit_population(): (frames + 1) * P * n_states = {} x {} x {} must be at most '
+                       '2^31 - 1 with want_frames; split the frames or the population over several '
+                       'calls'.format(frames + 1, P, self.n_states))
+
+  def visit_population_buffers(self, P, frames, want_frames=False):
+    """Allocate the dict of `visit_population(out=...)` once: 'visits' int64 [P, S, 5], 'finished'
+    int64 [frames, P], 'final' int64 [P, S], 'counts' int32 [P, S, 5], 'probs' float64 [P, S, 5],
+    'scratch' int64 [P, S] (the second mass array of the one-launch-per-frame path) and -
+    `want_frames` - 'per_frame' int64 [frames + 1, P, S]."""
+    self._check_members(P, 'visit_population', 'visit')
+    self._check_count('frames', frames)
+    if want_frames:
+      self._check_frame_elements(P, frames)
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    out = {'visits': torch.zeros((P, S, A), dtype=torch.int64, device=dev),
+           'finished': torch.zeros((frames, P), dtype=torch.int64, device=dev),
+           'final': torch.zeros((P, S), dtype=torch.int64, device=dev),
+           'counts': torch.zeros((P, S, A), dtype=torch.int32, device=dev),
+           'probs': torch.zeros((P, S, A), dtype=torch.float64, device=dev),
+           'scratch': torch.zeros((P, S), dtype=torch.int64, device=dev)}
+    if want_frames:
+      out['per_frame'] = torch.zeros((frames + 1, P, S), dtype=torch.int64, device=dev)
+    return out
+
+  def visit_population(self, policies, frames, start=None, restart=True, want_frames=False, out=None,
+                       path=0):
+    """`state_visitation()` for a POPULATION of P policies in one launch: member m of every result
+    is, bit for bit, `state_visitation(policies[m], frames, start_m, restart)` - the forward half
+    of the exact policy gradient for every member of a population, a sweep of learning rates or a
+    set of seeds, without a launch per member (csrc/k_visit.hip, `campx::wide_visit_population`).
+    The rule is `state_visitation()`'s and is stated there; no result depends on P, on the order of
+    the members or on the path.
+
+    Args:
+      policies: what `evaluate_population()` takes, checked by the same helpers - contiguous
+          float32 `[P, n_states, 5]` on the game's device, P need not divide the batch,
+          `P * n_states * 5 <= 2^31 - 1`.  A bad row sends all its mass to action 4 and raises
+          ValueError with the count of such rows, summed over the members, lazily as
+          `state_visitation()`'s do, in a message that names this call.
+      frames: how many frames to run, 1 .. 2^20.
+      start: where the mass starts.  None: one environment in state 0 for every member.
+          `[P, n_states]`: member m starts from row m; `[n_states]`: every member starts from it.
+          int64 units - contiguous, every entry >= 0, each member's total at most 2^38 - or float
+          probabilities, quantised HERE row by row exactly as `state_visitation()` quantises its
+          float `start`.  Validated eagerly, with a few synchronising reads; `start=None` reads
+          nothing.  An int64 `[P, n_states]` start may BE `out['final']`: the call then continues
+          in place.  A shared `[n_states]` start must not overlap 'final', and no start may be
+          `out['scratch']`.
+      restart, want_frames: as in `state_visitation()`.  With `want_frames`,
+          `(frames + 1) * P * n_states <= 2^31 - 1`; split a larger call.
+      out: a dict from `visit_population_buffers(P, frames, want_frames)`, overwritten; with it
+          (and `start` None or already int64) the call allocates nothing, and it synchronises only
+          to validate a `start` ('scratch' is needed on path 2 only).
+      path: 0 - a workgroup keeps the table and several members' vectors in LDS and runs all
+          frames in the one launch whenever one member fits there (exactly the tables that fit
+          `state_visitation()`'s LDS path), else one launch per frame for all members; 1 / 2 force
+          either (1 raises ValueError for a table that does not fit).  Both give the same bits.
+
+    Returns a dict, time-major where there is a frame axis: 'visits' int64 `[P, n_states, 5]`;
+    'finished' int64 `[frames, P]`; 'final' int64 `[P, n_states]`; 'counts' int32
+    `[P, n_states, 5]`; 'probs' float64 `[P, n_states, 5]` = counts / 2^24; 'unit' = 2^38; with
+    `want_frames` 'per_frame' int64 `[frames + 1, P, n_states]`.  Argument errors raise ValueError
+    before anything is launched.
+    """
+    P = self._check_population(policies, split=False)
+    self._check_members(P, 'visit_population', 'visit')
+    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    unit = self.VISIT_UNIT
+    self._check_count('frames', frames)
+    if want_frames:
+      self._check_frame_elements(P, frames)
+    if self._n_cus is None:
+      self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+    planned = self._planned_path(path, _hip.lib.campx_wide_visit_population_plan, P, n_cus=self._n_cus,
+                                 words=5)
+    if start is not None:
+      if (not torch.is_tensor(start) or tuple(start.shape) not in ((S,), (P, S)) or start.device != dev
+          or not (start.dtype == torch.int64 or start.is_floating_point())):
+        raise ValueError('start must be None, an int64 tensor of units of 2^-38 or a float tensor of '
+                         'probabilities, [{0}, {1}] (per member) or [{1}] (shared), on {2}'.format(P, S, dev))
+      start = start.detach()
+      if start.dtype == torch.int64:
+        if not start.is_contiguous():
+          raise ValueError('an int64 start must be contiguous')
+        if (bool((start < 0).any()) or int(start.sum(-1).max()) > unit or int(start.max()) > unit):
+          raise ValueError('an int64 start must hold entries >= 0 that total at most 2^38 per member')
+      else:
+        p = start.double()
+        if (not bool(torch.isfinite(p).all()) or bool((p < 0).any())
+            or float((p.sum(-1) - 1.0).abs().max()) > 1e-4):
+          raise ValueError('a float start must hold finite probabilities >= 0 that sum to 1 (within '
+                           '1e-4) per member')
+        rows = p.reshape(-1, S)
+        units = torch.floor(rows * float(unit)).long()
+        largest = torch.argmax(rows, dim=1, keepdim=True)
+        units.scatter_add_(1, largest, (unit - units.sum(1, keepdim=True)))
+        if bool((units.gather(1, largest) < 0).any()):
+          raise ValueError('a float start sums to more than 1 by more than its largest entry')
+        start = units.reshape(p.shape).contiguous()
+    want = [('visits', torch.int64, (P, S, A)), ('finished', torch.int64, (frames, P)),
+            ('final', torch.int64, (P, S)), ('counts', torch.int32, (P, S, A)),
+            ('probs', torch.float64, (P, S, A))]
+    if planned == 2:
+      want.append(('scratch', torch.int64, (P, S)))
+    if want_frames:
+      want.append(('per_frame', torch.int64, (frames + 1, P, S)))
+    made_by = 'visit_population_buffers({}, {}, want_frames={})'.format(P, frames, bool(want_frames))
+    if out is None:
+      out = self.visit_population_buffers(P, frames, want_frames)
+    else:
+      self._check_out(out, want, made_by)
+    if start is not None:
+      if out.get('scratch') is not None and self._shares_bytes(start, out['scratch']):
+        raise ValueError('start must not be out[\'scratch\']')
+      in_place = start.dim() == 2 and start.data_ptr() == out['final'].data_ptr()
+      if not in_place and self._shares_bytes(start, out['final']):
+        raise ValueError('start must not overlap out[\'final\'] (a [P, n_states] start may BE it)')
+    validate = self.validate_actions
+    _hip.ops.wide_visit_population(
+        self._spec_host, self._tables, policies.detach(), start, bool(restart), out['visits'],
+        out['finished'], out['final'], out['per_frame'] if want_frames else None, out['counts'],
+        out.get('scratch'), self._bad_visit_member_rows if validate else None,
+        self._bad_flag if validate else None, path)
+    if validate:
+      self._after_launch()
+    out['probs'].copy_(out['counts'])
+    out['probs'].mul_(1.0 / float(1 << 24))
+    res = {'visits': out['visits'], 'finished': out['finished'], 'final': out['final'],
+           'counts': out['counts'], 'probs': out['probs'], 'unit': unit}
+    if want_frames:
+      res['per_frame'] = out['per_frame']
+    return res
+
+  @staticmethod
+  def _shares_bytes(a, b):
+    """Two contiguous tensors share a byte."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
 
   # ------------------------------------------------------------ observations by state
 

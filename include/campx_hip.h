@@ -1330,6 +1330,59 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* spec_host, const void* tabl
                                 int64_t* final_mass, int64_t* per_frame, int32_t* counts,
                                 int64_t* scratch, int32_t* bad_rows, int32_t* bad_flag,
                                 int32_t path, void* stream);
+/*
+ * ---- The same for a population of policies, in one launch --------------------------------------
+ * Member m of campx_wide_visit_population_launch() IS campx_wide_visit_launch() of the policy
+ * `policies[m]` from member m's start: the rule above, steps 1 to 4, word for word - int64 units
+ * of 2^-38, the bisection counts, the floor(m * N / 2^24) splits, integer additions only - and so
+ * the same bits, whatever `members` is, whichever workgroup or lane takes the member, however
+ * members are packed, in whatever order they come, on either path.  Members share the table and
+ * nothing they write.
+ *   policies          DEVICE float32 [members][n_states][5]; members * n_states * 5 <= 2^31 - 1
+ *   start             DEVICE int64, NULL for 2^38 in state 0 of every member; with
+ *                     start_per_member = 1 [members][n_states], member m's d_0 (it may BE `final`:
+ *                     a call continued in place); with 0 [n_states], every member's d_0, read with
+ *                     member stride 0, which must not overlap `final`.  Per member: entries >= 0,
+ *                     total <= 2^38
+ *   visits, counts    [members][n_states][5];  final, scratch  [members][n_states]
+ *   finished          [n_frames][members];  per_frame  [n_frames + 1][members][n_states] or NULL:
+ *                     time-major, as campx_wide_population_sweeps_launch()'s residual is
+ *   bad_rows          bad rows summed over the members, once per call (as above)
+ * Path 1: after the kernel that makes `counts`, a lane per (member, state) row, a workgroup stages
+ * the entries' second words in LDS once and takes G consecutive members - N, two mass vectors and
+ * two slots of finished[t] each, in LDS too - through all n_frames in the ONE launch, one
+ * workgroup barrier per frame; ceil(members / G) workgroups.  The LDS is the single call's 64-byte
+ * header, 16 more bytes for each member after the first, 20 bytes a state once and 32 bytes a
+ * state per member, each part rounded up to 16: at G = 1 exactly campx_wide_visit_plan()'s, so
+ * the tables that fit are the same.  Path 2: one launch per frame for all members, a workgroup per
+ * 256 states of one member, all members' blocks along grid.x, between `final` and `scratch`.
+ * 0 = path 1 whenever ONE member fits.  Either grid stops at 2^20 workgroups, each then taking
+ * several groups in turn.
+ *
+ * campx_wide_visit_population_plan() is the choice as host-only arithmetic: plan_out[5] = the
+ * path; dynamic LDS bytes; threads of a workgroup; workgroups launched; G (1 on path 2).  G is the
+ * rule of campx_wide_population_sweeps_plan(), taken over and not tuned for these kernels: the
+ * least of what fits wide_lds_max, floor(256 / n_states) or 1, and ceil(members / n_cus).  With
+ * G > 1 the G * n_states <= 256 pairs have a lane each, in whole waves.  CAMPX_EINVAL: plan_out
+ * NULL, n_states outside 1 .. CAMPX_WIDE_MAX_STATES, members < 1, members * n_states * 5 above
+ * 2^31 - 1, n_cus < 1, wide_lds_max < 0, a `path` outside 0 .. 2, path 1 where one member does not
+ * fit.  The launch returns CAMPX_EINVAL, before anything is launched, for the same and for: NULL
+ * where it is not allowed (as above), pointers that are not aligned (as above), n_frames outside
+ * 1 .. 2^20, a `restart` or a `start_per_member` that is not 0 / 1, a start per member that
+ * overlaps `final` without being equal to it, a shared start that overlaps `final`, on path 2 a
+ * `scratch` that is NULL or overlaps `final` or `start`.  Asynchronous on `stream`, no
+ * synchronisation, no allocation, no library state.
+ */
+int32_t campx_wide_visit_population_plan(int64_t n_states, int64_t members, int64_t wide_lds_max,
+                                         int64_t n_cus, int32_t path, int64_t* plan_out);
+int32_t campx_wide_visit_population_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                           const float* policies, int64_t members,
+                                           const int64_t* start, int32_t start_per_member,
+                                           int32_t restart, int32_t n_frames, int64_t* visits,
+                                           int64_t* finished, int64_t* final_mass,
+                                           int64_t* per_frame, int32_t* counts, int64_t* scratch,
+                                           int32_t* bad_rows, int32_t* bad_flag, int32_t path,
+                                           void* stream);
 /* The gather launch's arithmetic for N rows of R bytes written at address `dst_addr`, pure host
  * code (tests restate it): plan_out[8] = the division-by-R constants m, sh1, sh2; N * R; the
  * bytes (16-bit formats: elements) from the first memory-aligned window's start to the output;
