@@ -206,9 +206,16 @@ __global__ __launch_bounds__(kWindowWaves * kWave) void window_kernel(WindowPara
   for (int j = 0; j < kWin; ++j) {
     const uint32_t off = woff0 + j * 1024u + (uint32_t)lane * 16u;
     uint32_t word[4] = {0u, 0u, 0u, 0u};
-    if (off < wp.total) {      // (chunks before the output wrap to huge offsets and fail this too)
-      const uint32_t row = div_r(off);
-      const uint32_t k = off - row * wp.R;
+    // A chunk that starts before the output: offsets are multiples of 16 with int8 (the output is
+    // 16-byte aligned), so there the chunk before the output holds none of it; with the 16-bit
+    // formats they are multiples of 8 ELEMENTS, and for an output at 16 (mod 32) bytes the chunk
+    // at -8 holds row 0's first 8 bytes in its upper half - which the store loop's half at
+    // element 0 reads.  It is filled as the chunk at 0 and moved up below.
+    const bool before = kFmt != 0 && off == 0u - 8u;
+    const uint32_t from = before ? 0u : off;
+    if (from < wp.total) {     // (other chunks before the output wrap to huge offsets and fail this too)
+      const uint32_t row = div_r(from);
+      const uint32_t k = from - row * wp.R;
       uint32_t i = row - first_row;
       uint32_t l = k / (uint32_t)wp.hw;
       const uint32_t rem = k - l * (uint32_t)wp.hw;
@@ -240,6 +247,11 @@ __global__ __launch_bounds__(kWindowWaves * kWave) void window_kernel(WindowPara
           anchor = row_anchor[i];
         }
       }
+    }
+    if (before) {
+      word[2] = word[0];
+      word[3] = word[1];
+      word[0] = word[1] = 0u;
     }
     *reinterpret_cast<u32x4*>(win0 + j * 1024 + lane * 16) = u32x4{word[0], word[1], word[2], word[3]};
   }
