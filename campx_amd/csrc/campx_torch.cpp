@@ -1260,6 +1260,77 @@ void wide_population_sweeps(const Tensor& spec_host, const Tensor& tables, const
          values_in, values_out, scratch, q, std::nullopt, residual, bad_rows, bad_flag, path);
 }
 
+// Both visitation ops.  `what` names the op in its messages; `members`: `policy` is a population's
+// [P, n_states, 5], every per-member shape has that leading P, and `start` may also be one
+// [n_states] shared by all.
+void visit(const char* what, bool members, const Tensor& spec_host, const Tensor& tables,
+           const Tensor& policy, const OptTensor& start, bool restart, Tensor& visits,
+           Tensor& finished, Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
+           const OptTensor& scratch, const OptTensor& bad_rows, const OptTensor& bad_flag,
+           int64_t path) {
+  const CampxWideSpec* hs = wide_spec(spec_host);
+  TORCH_CHECK(visits.device().is_cuda(), what, ": visits must be on a HIP device (no CPU implementation)");
+  const c10::Device dev = visits.device();
+  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
+  want_wide_tables(tables, hs, dev);
+  TORCH_CHECK(!members || (policy.dim() == 3 && policy.size(0) >= 1), what,
+              ": policies must be float32 [P, n_states, 5], P >= 1");
+  const int64_t P = members ? policy.size(0) : 1;
+  const auto each = [&](std::initializer_list<int64_t> shape) {      // ... of every member
+    std::vector<int64_t> all(members ? 1 : 0, P);
+    all.insert(all.end(), shape);
+    return all;
+  };
+  want(policy, members ? "policies" : "policy", at::kFloat, dev, each({S, A}));
+  const bool per_member = !members || (start.has_value() && start->dim() == 2);
+  if (start.has_value()) {
+    if (per_member) want(*start, "start", at::kLong, dev, each({S}));
+    else want(*start, "start", at::kLong, dev, {S});
+  }
+  want(visits, "visits", at::kLong, dev, each({S, A}));
+  if (members) {
+    TORCH_CHECK(finished.dim() == 2 && finished.size(0) >= 1 && finished.size(0) <= (1 << 20), what,
+                ": finished must be int64 [frames, P], 1 <= frames <= 2^20");
+    want(finished, "finished", at::kLong, dev, {finished.size(0), P});
+  } else {
+    TORCH_CHECK(finished.device() == dev && finished.scalar_type() == at::kLong && finished.dim() == 1 &&
+                    finished.is_contiguous() && finished.numel() >= 1 && finished.numel() <= (1 << 20),
+                what, ": finished must be a contiguous int64 [frames] tensor on ", dev,
+                ", 1 <= frames <= 2^20");
+  }
+  const int64_t T = finished.size(0);
+  want(final_mass, "final_mass", at::kLong, dev, each({S}));
+  if (per_frame.has_value()) {
+    std::vector<int64_t> frames = each({S});
+    frames.insert(frames.begin(), T + 1);
+    want(*per_frame, "per_frame", at::kLong, dev, frames);
+  }
+  want(counts, "counts", at::kInt, dev, each({S, A}));
+  if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, each({S}));
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  const DeviceGuard guard(dev);
+  const float* w = reinterpret_cast<const float*>(policy.data_ptr());
+  int64_t* d_visits = reinterpret_cast<int64_t*>(visits.data_ptr());
+  int64_t* d_finished = reinterpret_cast<int64_t*>(finished.data_ptr());
+  int64_t* d_final = reinterpret_cast<int64_t*>(final_mass.data_ptr());
+  int32_t* d_counts = reinterpret_cast<int32_t*>(counts.data_ptr());
+  if (members)
+    check_ok(campx_wide_visit_population_launch(
+                 hs, tables.data_ptr(), w, P, opt_ptr<const int64_t>(start), per_member ? 1 : 0,
+                 restart ? 1 : 0, (int32_t)T, d_visits, d_finished, d_final, opt_ptr<int64_t>(per_frame),
+                 d_counts, opt_ptr<int64_t>(scratch), opt_ptr<int32_t>(bad_rows),
+                 flag_ptr(bad_flag, dev), (int32_t)path, current_stream()),
+             "campx_wide_visit_population_launch");
+  else
+    check_ok(campx_wide_visit_launch(
+                 hs, tables.data_ptr(), w, opt_ptr<const int64_t>(start), restart ? 1 : 0, (int32_t)T,
+                 d_visits, d_finished, d_final, opt_ptr<int64_t>(per_frame), d_counts,
+                 opt_ptr<int64_t>(scratch), opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev),
+                 (int32_t)path, current_stream()),
+             "campx_wide_visit_launch");
+}
+
 // Exact state visitation of a policy over the state table (campx_wide_visit_launch): as many
 // frames as `finished` has elements, from `start` (int64 [n_states] units of 2^-38; None: one
 // environment in state 0), which may be `final_mass`.
@@ -1268,36 +1339,8 @@ void wide_visit(const Tensor& spec_host, const Tensor& tables, const Tensor& pol
                 Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
                 const OptTensor& scratch, const OptTensor& bad_rows, const OptTensor& bad_flag,
                 int64_t path) {
-  const CampxWideSpec* hs = wide_spec(spec_host);
-  TORCH_CHECK(visits.device().is_cuda(),
-              "campx::wide_visit: visits must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = visits.device();
-  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  want_wide_tables(tables, hs, dev);
-  want(policy, "policy", at::kFloat, dev, {S, A});
-  if (start.has_value()) want(*start, "start", at::kLong, dev, {S});
-  want(visits, "visits", at::kLong, dev, {S, A});
-  TORCH_CHECK(finished.device() == dev && finished.scalar_type() == at::kLong && finished.dim() == 1 &&
-                  finished.is_contiguous() && finished.numel() >= 1 && finished.numel() <= (1 << 20),
-              "campx::wide_visit: finished must be a contiguous int64 [frames] tensor on ", dev,
-              ", 1 <= frames <= 2^20");
-  const int64_t T = finished.numel();
-  want(final_mass, "final_mass", at::kLong, dev, {S});
-  if (per_frame.has_value()) want(*per_frame, "per_frame", at::kLong, dev, {T + 1, S});
-  want(counts, "counts", at::kInt, dev, {S, A});
-  if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, {S});
-  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
-  TORCH_CHECK(path >= 0 && path <= 2, "campx::wide_visit: path must be 0, 1 or 2");
-  const DeviceGuard guard(dev);
-  check_ok(campx_wide_visit_launch(
-               hs, tables.data_ptr(), reinterpret_cast<const float*>(policy.data_ptr()),
-               opt_ptr<const int64_t>(start), restart ? 1 : 0, (int32_t)T,
-               reinterpret_cast<int64_t*>(visits.data_ptr()),
-               reinterpret_cast<int64_t*>(finished.data_ptr()),
-               reinterpret_cast<int64_t*>(final_mass.data_ptr()), opt_ptr<int64_t>(per_frame),
-               reinterpret_cast<int32_t*>(counts.data_ptr()), opt_ptr<int64_t>(scratch),
-               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path, current_stream()),
-           "campx_wide_visit_launch");
+  visit("campx::wide_visit", false, spec_host, tables, policy, start, restart, visits, finished,
+        final_mass, per_frame, counts, scratch, bad_rows, bad_flag, path);
 }
 
 // Exact state visitation of a population of policies (campx_wide_visit_population_launch):
@@ -1309,42 +1352,8 @@ void wide_visit_population(const Tensor& spec_host, const Tensor& tables, const 
                            Tensor& final_mass, const OptTensor& per_frame, Tensor& counts,
                            const OptTensor& scratch, const OptTensor& bad_rows,
                            const OptTensor& bad_flag, int64_t path) {
-  const char* what = "campx::wide_visit_population";
-  const CampxWideSpec* hs = wide_spec(spec_host);
-  TORCH_CHECK(visits.device().is_cuda(), what, ": visits must be on a HIP device (no CPU implementation)");
-  const c10::Device dev = visits.device();
-  const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
-  want_wide_tables(tables, hs, dev);
-  TORCH_CHECK(policies.dim() == 3 && policies.size(0) >= 1, what,
-              ": policies must be float32 [P, n_states, 5], P >= 1");
-  const int64_t P = policies.size(0);
-  want(policies, "policies", at::kFloat, dev, {P, S, A});
-  const bool per_member = start.has_value() && start->dim() == 2;
-  if (start.has_value()) {
-    if (per_member) want(*start, "start", at::kLong, dev, {P, S});
-    else want(*start, "start", at::kLong, dev, {S});
-  }
-  want(visits, "visits", at::kLong, dev, {P, S, A});
-  TORCH_CHECK(finished.dim() == 2 && finished.size(0) >= 1 && finished.size(0) <= (1 << 20), what,
-              ": finished must be int64 [frames, P], 1 <= frames <= 2^20");
-  const int64_t T = finished.size(0);
-  want(finished, "finished", at::kLong, dev, {T, P});
-  want(final_mass, "final_mass", at::kLong, dev, {P, S});
-  if (per_frame.has_value()) want(*per_frame, "per_frame", at::kLong, dev, {T + 1, P, S});
-  want(counts, "counts", at::kInt, dev, {P, S, A});
-  if (scratch.has_value()) want(*scratch, "scratch", at::kLong, dev, {P, S});
-  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, dev, {1});
-  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
-  const DeviceGuard guard(dev);
-  check_ok(campx_wide_visit_population_launch(
-               hs, tables.data_ptr(), reinterpret_cast<const float*>(policies.data_ptr()), P,
-               opt_ptr<const int64_t>(start), per_member ? 1 : 0, restart ? 1 : 0, (int32_t)T,
-               reinterpret_cast<int64_t*>(visits.data_ptr()),
-               reinterpret_cast<int64_t*>(finished.data_ptr()),
-               reinterpret_cast<int64_t*>(final_mass.data_ptr()), opt_ptr<int64_t>(per_frame),
-               reinterpret_cast<int32_t*>(counts.data_ptr()), opt_ptr<int64_t>(scratch),
-               opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), (int32_t)path, current_stream()),
-           "campx_wide_visit_population_launch");
+  visit("campx::wide_visit_population", true, spec_host, tables, policies, start, restart, visits,
+        finished, final_mass, per_frame, counts, scratch, bad_rows, bad_flag, path);
 }
 
 void onehot_to_ids(const Tensor& onehot, Tensor& ids_out, Tensor& bad_count) {

@@ -90,22 +90,9 @@ inline int64_t sweeps_lds(int64_t S, int64_t G, bool policy, bool slots, SweepsP
 }
 
 // The plan of P members; `slots`: the LDS layout of a population (a single policy or value
-// iteration is P = 1 on one compute unit without them).  Path 1 whenever one member fits.  How
-// many members a workgroup of the LDS path takes - the least of
-//   (a) what fits lds_max;
-//   (b) floor(kPlanPackThreads / S), at least 1: members are packed until the workgroup has about
-//       four waves of (member, state) pairs, no further;
-//   (c) ceil(P / n_cus): a population smaller than G * n_cus would leave CUs idle, so it is spread
-//       one workgroup per CU first and packed only beyond that.
-// (b) is not the rule this started from, ceil(kTableLdsThreads / S) - pack until every one of the
-// workgroup's 1 024 threads has a pair.  One run on an MI355X at P = 65 536, 64 sweeps, G bounded
-// through (a) (NOTES.md has the table): the maze's 159 states 5.77 ms at G = 7 (1 113 pairs: a second
-// round for 89 of them), 5.32 at 6, 3.71 at 3, 3.40 at G = 1; the boat race's 8 states 0.226 ms at
-// G = 128 (1 024 threads), 0.185-0.199 from 64 down to 8, 0.319 at 4 and 1.15 at G = 1, where most
-// of a wave idles.  Several small workgroups to a CU beat one large one, and a part-filled wave
-// costs more than either: 256 threads is the size that is best or within a tenth of it at both,
-// and a floor keeps a table of up to 256 states to one pair per thread.  Two sizes, one run: a
-// choice with a reason, not a tuned one.  (c) has not been measured at all.
+// iteration is P = 1 on one compute unit without them).  Path 1 whenever one member fits; how
+// many members a workgroup of it takes is members_per_workgroup()'s rule (wide_table.hip.h, with
+// the measurement behind it, which was made on these kernels).
 inline int32_t plan_sweeps(int64_t S, int64_t P, int32_t policy, bool slots, int32_t has_override,
                            int64_t lds_max, int64_t n_cus, int32_t path, SweepsPlan* p) {
   if (S < 1 || S > CAMPX_WIDE_MAX_STATES || P < 1 || (policy & ~1) || (has_override & ~1) ||
@@ -116,19 +103,9 @@ inline int32_t plan_sweeps(int64_t S, int64_t P, int32_t policy, bool slots, int
   const bool fits = sweeps_lds(S, 1, policy, slots, nullptr) <= lds_max;
   if (path == 1 && !fits) return CAMPX_EINVAL;
   if (path == 1 || (path == 0 && fits)) {
-    int64_t G = kPlanPackThreads / S;                                 // (b)
-    if (G < 1) G = 1;
-    const int64_t spread = (P + n_cus - 1) / n_cus;                   // (c)
-    if (spread < G) G = spread;
-    if (sweeps_lds(S, G, policy, slots, nullptr) > lds_max) {         // (a): the largest that fits
-      int64_t lo = 1, hi = G - 1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi + 1) / 2;
-        if (sweeps_lds(S, mid, policy, slots, nullptr) <= lds_max) lo = mid;
-        else hi = mid - 1;
-      }
-      G = lo;
-    }
+    const int64_t G = members_per_workgroup(S, P, n_cus, lds_max, kPlanPackThreads, [&](int64_t g) {
+      return sweeps_lds(S, g, policy, slots, nullptr);
+    });
     p->path = 1;
     p->G = (int32_t)G;
     p->lds_bytes = sweeps_lds(S, G, policy, slots, p);
@@ -422,17 +399,6 @@ __global__ __launch_bounds__(kPlanThreads) void wide_sweep_kernel(
     if (kMembers) __syncthreads();   // `partial` is written again by the next block
   } while (kMembers && (block += gridDim.x) < sp.groups);
   report_bad(bad_rows, bad_flag, bad);
-}
-
-// Compute units of the current device (256 where it cannot be asked): rule (c) of the plan.
-inline int64_t device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-    (void)hipGetLastError();
-    return 256;
-  }
-  return cus;
 }
 
 // Both entry points, their own NULL checks behind them: `members` policies (`policy` NULL: value

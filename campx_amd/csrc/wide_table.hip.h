@@ -2,7 +2,8 @@
 // k_plan, k_visit, k_sums, k_states, k_window) and their launchers agree on, each said once: the
 // table entry's format, the policy-row rule, the sampler's Philox block, the lazy error report -
 // and, host side, the table blob's layout and the view a launcher takes of it, the discount list,
-// and the choice between one LDS workgroup and one launch per step.
+// the choice between one LDS workgroup and one launch per step, and how many members of a
+// population a workgroup takes.
 #ifndef CAMPX_WIDE_TABLE_HIP_H_
 #define CAMPX_WIDE_TABLE_HIP_H_
 
@@ -105,6 +106,23 @@ inline bool ranges_overlap(const void* a, const void* b, int64_t bytes) {
   return x < y ? y - x < n : x - y < n;
 }
 
+// [a, a + na) and [b, b + nb) share a byte
+inline bool spans_overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// Compute units of the current device (256 where it cannot be asked): rule (c) below.
+inline int64_t device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  return cus;
+}
+
 // Where the parts of the state-table blob are: [entries uint2 x 5S, padded to 16][cells 8 x uint16
 // x S][perf int8 x 5S, padded to 16][rot_obs][rot_board][pieces: 16 words for the layered rows, 16
 // for the flat board].  wide_layout() (k_wide.hip) is the one place that computes the offsets;
@@ -189,6 +207,42 @@ inline int32_t plan_lds_or_launch(int64_t S, int64_t lds_bytes, bool fits_too, i
     plan_out[3] = p->grid;
   }
   return CAMPX_OK;
+}
+
+// The same work for a population of P members that share the table (k_plan.hip, k_visit.hip): how
+// many members G a workgroup of the LDS path takes - the least of
+//   (a) what fits lds_max (`lds_of(G)`: the LDS bytes of G members; one member fits);
+//   (b) floor(pack / S), at least 1: members are packed until the workgroup has about four waves
+//       of (member, state) pairs (pack = 256), no further;
+//   (c) ceil(P / n_cus): a population smaller than G * n_cus would leave CUs idle, so it is spread
+//       one workgroup per CU first and packed only beyond that.
+// (b) is not the rule this started from, ceil(kTableLdsThreads / S) - pack until every one of the
+// workgroup's 1 024 threads has a pair.  One run of k_plan.hip's sweeps on an MI355X at P = 65 536,
+// 64 sweeps, G bounded through (a) (NOTES.md has the table): the maze's 159 states 5.77 ms at G = 7
+// (1 113 pairs: a second round for 89 of them), 5.32 at 6, 3.71 at 3, 3.40 at G = 1; the boat race's
+// 8 states 0.226 ms at G = 128 (1 024 threads), 0.185-0.199 from 64 down to 8, 0.319 at 4 and 1.15
+// at G = 1, where most of a wave idles.  Several small workgroups to a CU beat one large one, and a
+// part-filled wave costs more than either: 256 threads is the size that is best or within a tenth
+// of it at both, and a floor keeps a table of up to 256 states to one pair per thread.  Two sizes,
+// one run: a choice with a reason, not a tuned one.  (c) has not been measured at all, and the
+// visitation takes the rule over as it stands, NOT tuned for its kernel.
+template <class LdsOf>
+inline int64_t members_per_workgroup(int64_t S, int64_t P, int64_t n_cus, int64_t lds_max,
+                                     int64_t pack, LdsOf lds_of) {
+  int64_t G = pack / S;                                               // (b)
+  if (G < 1) G = 1;
+  const int64_t spread = (P + n_cus - 1) / n_cus;                     // (c)
+  if (spread < G) G = spread;
+  if (lds_of(G) > lds_max) {                                          // (a): the largest that fits
+    int64_t lo = 1, hi = G - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      if (lds_of(mid) <= lds_max) lo = mid;
+      else hi = mid - 1;
+    }
+    G = lo;
+  }
+  return G;
 }
 
 }  // namespace campx_impl

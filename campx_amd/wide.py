@@ -886,15 +886,18 @@ class WideGame(fused.FusedGame):
     int64 [frames], 'final' int64 [S], 'counts' int32 [S, 5], 'scratch' int64 [S] (the second mass
     vector of the one-launch-per-frame path) and - `want_frames` - 'per_frame' int64
     [frames + 1, S]."""
+    return self._visit_buffers((), int(frames), want_frames)
+
+  def _visit_buffers(self, lead, frames, want_frames):
+    """What both dicts of buffers share; `lead`: the leading dimensions of a member's, () or (P,)."""
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
-    frames = int(frames)
-    out = {'visits': torch.zeros((S, A), dtype=torch.int64, device=dev),
-           'finished': torch.zeros((frames,), dtype=torch.int64, device=dev),
-           'final': torch.zeros((S,), dtype=torch.int64, device=dev),
-           'counts': torch.zeros((S, A), dtype=torch.int32, device=dev),
-           'scratch': torch.zeros((S,), dtype=torch.int64, device=dev)}
+    out = {'visits': torch.zeros(lead + (S, A), dtype=torch.int64, device=dev),
+           'finished': torch.zeros((frames,) + lead, dtype=torch.int64, device=dev),
+           'final': torch.zeros(lead + (S,), dtype=torch.int64, device=dev),
+           'counts': torch.zeros(lead + (S, A), dtype=torch.int32, device=dev),
+           'scratch': torch.zeros(lead + (S,), dtype=torch.int64, device=dev)}
     if want_frames:
-      out['per_frame'] = torch.zeros((frames + 1, S), dtype=torch.int64, device=dev)
+      out['per_frame'] = torch.zeros((frames + 1,) + lead + (S,), dtype=torch.int64, device=dev)
     return out
 
   def state_visitation(self, policy, frames, start=None, restart=True, want_frames=False, out=None,
@@ -948,54 +951,98 @@ class WideGame(fused.FusedGame):
     before anything is launched.
     """
     self._check_policy(policy)
+    return self._visit(None, policy, frames, start, restart, want_frames, out, path)
+
+  def _visit(self, P, policy, frames, start, restart, want_frames, out, path):
+    """The body of `state_visitation()` and - `P` not None, every per-member shape with that
+    leading P, a `start` per member or shared - of `visit_population()`, their policy checked."""
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
+    members = P is not None
+    lead = (P,) if members else ()
+    per_member = ' per member' if members else ''
     unit = self.VISIT_UNIT
     self._check_count('frames', frames)
-    planned = self._planned_path(path, _hip.lib.campx_wide_visit_plan)
+    if members:
+      if want_frames:
+        self._check_frame_elements(P, frames)
+      if self._n_cus is None:
+        self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+      planned = self._planned_path(path, _hip.lib.campx_wide_visit_population_plan, P, n_cus=self._n_cus,
+                                   words=5)
+    else:
+      planned = self._planned_path(path, _hip.lib.campx_wide_visit_plan)
     if start is not None:
-      if (not torch.is_tensor(start) or tuple(start.shape) != (S,) or start.device != dev
+      if (not torch.is_tensor(start) or tuple(start.shape) not in ((S,), lead + (S,)) or start.device != dev
           or not (start.dtype == torch.int64 or start.is_floating_point())):
+        if members:
+          raise ValueError('start must be None, an int64 tensor of units of 2^-38 or a float tensor of '
+                           'probabilities, [{0}, {1}] (per member) or [{1}] (shared), on {2}'.format(P, S, dev))
         raise ValueError('start must be None, an int64 [{0}] tensor of units of 2^-38 or a float '
                          '[{0}] tensor of probabilities, on {1}'.format(S, dev))
       start = start.detach()
+      # row by row: a single call's [S] and a shared start are one row
       if start.dtype == torch.int64:
         if not start.is_contiguous():
           raise ValueError('an int64 start must be contiguous')
-        if bool((start < 0).any()) or int(start.sum()) > unit or int(start.max()) > unit:
-          raise ValueError('an int64 start must hold entries >= 0 that total at most 2^38')
+        totals = start.sum(-1)                   # (one row: its total, and no launch to find the largest)
+        if (bool((start < 0).any()) or int(totals.max() if totals.dim() else totals) > unit
+            or int(start.max()) > unit):
+          raise ValueError('an int64 start must hold entries >= 0 that total at most 2^38' + per_member)
       else:
         p = start.double()
-        if not bool(torch.isfinite(p).all()) or bool((p < 0).any()) or abs(float(p.sum()) - 1.0) > 1e-4:
-          raise ValueError('a float start must hold finite probabilities >= 0 that sum to 1 (within 1e-4)')
-        start = torch.floor(p * float(unit)).long()
-        largest = int(torch.argmax(p))
-        start[largest] += unit - int(start.sum())
-        if int(start[largest]) < 0:
+        if (not bool(torch.isfinite(p).all()) or bool((p < 0).any())
+            or float((p.sum(-1) - 1.0).abs().max()) > 1e-4):
+          raise ValueError('a float start must hold finite probabilities >= 0 that sum to 1 (within '
+                           '1e-4)' + per_member)
+        rows = p.reshape(-1, S)
+        units = torch.floor(rows * float(unit)).long()
+        largest = torch.argmax(rows, dim=1, keepdim=True)
+        units.scatter_add_(1, largest, (unit - units.sum(1, keepdim=True)))
+        if bool((units.gather(1, largest) < 0).any()):
           raise ValueError('a float start sums to more than 1 by more than its largest entry')
-    want = [('visits', torch.int64, (S, A)), ('finished', torch.int64, (frames,)),
-            ('final', torch.int64, (S,)), ('counts', torch.int32, (S, A))]
+        start = units.reshape(p.shape).contiguous()
+    want = [('visits', torch.int64, lead + (S, A)), ('finished', torch.int64, (frames,) + lead),
+            ('final', torch.int64, lead + (S,)), ('counts', torch.int32, lead + (S, A))]
+    if members:
+      want.append(('probs', torch.float64, lead + (S, A)))
     if planned == 2:
-      want.append(('scratch', torch.int64, (S,)))
+      want.append(('scratch', torch.int64, lead + (S,)))
     if want_frames:
-      want.append(('per_frame', torch.int64, (frames + 1, S)))
-    if out is None:
-      out = self.visitation_buffers(frames, want_frames)
+      want.append(('per_frame', torch.int64, (frames + 1,) + lead + (S,)))
+    given = out is not None
+    if not given:
+      out = (self.visit_population_buffers(P, frames, want_frames) if members
+             else self.visitation_buffers(frames, want_frames))
     else:
-      self._check_out(out, want, 'visitation_buffers({}, want_frames={})'.format(
-          frames, bool(want_frames)))
-      if start is not None and out.get('scratch') is not None and \
-          start.data_ptr() == out['scratch'].data_ptr():
+      self._check_out(out, want,
+                      'visit_population_buffers({}, {}, want_frames={})'.format(P, frames, bool(want_frames))
+                      if members else
+                      'visitation_buffers({}, want_frames={})'.format(frames, bool(want_frames)))
+    scratch = out.get('scratch')
+    if members and start is not None:
+      if scratch is not None and self._shares_bytes(start, scratch):
         raise ValueError('start must not be out[\'scratch\']')
+      in_place = start.dim() == 2 and start.data_ptr() == out['final'].data_ptr()
+      if not in_place and self._shares_bytes(start, out['final']):
+        raise ValueError('start must not overlap out[\'final\'] (a [P, n_states] start may BE it)')
+    elif given and start is not None and scratch is not None and start.data_ptr() == scratch.data_ptr():
+      raise ValueError('start must not be out[\'scratch\']')
     validate = self.validate_actions
-    _hip.ops.wide_visit(self._spec_host, self._tables, policy.detach(), start, bool(restart),
-                        out['visits'], out['finished'], out['final'],
-                        out['per_frame'] if want_frames else None, out['counts'], out.get('scratch'),
-                        self._bad_visit_rows if validate else None,
-                        self._bad_flag if validate else None, path)
+    bad_rows = self._bad_visit_member_rows if members else self._bad_visit_rows
+    (_hip.ops.wide_visit_population if members else _hip.ops.wide_visit)(
+        self._spec_host, self._tables, policy.detach(), start, bool(restart), out['visits'],
+        out['finished'], out['final'], out['per_frame'] if want_frames else None, out['counts'],
+        scratch, bad_rows if validate else None, self._bad_flag if validate else None, path)
     if validate:
       self._after_launch()
+    if members:
+      probs = out['probs']
+      probs.copy_(out['counts'])
+      probs.mul_(1.0 / float(1 << 24))
+    else:
+      probs = out['counts'].double() / float(1 << 24)
     res = {'visits': out['visits'], 'finished': out['finished'], 'final': out['final'],
-           'counts': out['counts'], 'probs': out['counts'].double() / float(1 << 24), 'unit': unit}
+           'counts': out['counts'], 'probs': probs, 'unit': unit}
     if want_frames:
       res['per_frame'] = out['per_frame']
     return res
@@ -1019,15 +1066,9 @@ class WideGame(fused.FusedGame):
     self._check_count('frames', frames)
     if want_frames:
       self._check_frame_elements(P, frames)
-    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
-    out = {'visits': torch.zeros((P, S, A), dtype=torch.int64, device=dev),
-           'finished': torch.zeros((frames, P), dtype=torch.int64, device=dev),
-           'final': torch.zeros((P, S), dtype=torch.int64, device=dev),
-           'counts': torch.zeros((P, S, A), dtype=torch.int32, device=dev),
-           'probs': torch.zeros((P, S, A), dtype=torch.float64, device=dev),
-           'scratch': torch.zeros((P, S), dtype=torch.int64, device=dev)}
-    if want_frames:
-      out['per_frame'] = torch.zeros((frames + 1, P, S), dtype=torch.int64, device=dev)
+    out = self._visit_buffers((P,), frames, want_frames)
+    out['probs'] = torch.zeros((P, self.n_states, gamespec.N_ACTIONS), dtype=torch.float64,
+                               device=self.device)
     return out
 
   def visit_population(self, policies, frames, start=None, restart=True, want_frames=False, out=None,
@@ -1072,72 +1113,7 @@ class WideGame(fused.FusedGame):
     """
     P = self._check_population(policies, split=False)
     self._check_members(P, 'visit_population', 'visit')
-    S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
-    unit = self.VISIT_UNIT
-    self._check_count('frames', frames)
-    if want_frames:
-      self._check_frame_elements(P, frames)
-    if self._n_cus is None:
-      self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-    planned = self._planned_path(path, _hip.lib.campx_wide_visit_population_plan, P, n_cus=self._n_cus,
-                                 words=5)
-    if start is not None:
-      if (not torch.is_tensor(start) or tuple(start.shape) not in ((S,), (P, S)) or start.device != dev
-          or not (start.dtype == torch.int64 or start.is_floating_point())):
-        raise ValueError('start must be None, an int64 tensor of units of 2^-38 or a float tensor of '
-                         'probabilities, [{0}, {1}] (per member) or [{1}] (shared), on {2}'.format(P, S, dev))
-      start = start.detach()
-      if start.dtype == torch.int64:
-        if not start.is_contiguous():
-          raise ValueError('an int64 start must be contiguous')
-        if (bool((start < 0).any()) or int(start.sum(-1).max()) > unit or int(start.max()) > unit):
-          raise ValueError('an int64 start must hold entries >= 0 that total at most 2^38 per member')
-      else:
-        p = start.double()
-        if (not bool(torch.isfinite(p).all()) or bool((p < 0).any())
-            or float((p.sum(-1) - 1.0).abs().max()) > 1e-4):
-          raise ValueError('a float start must hold finite probabilities >= 0 that sum to 1 (within '
-                           '1e-4) per member')
-        rows = p.reshape(-1, S)
-        units = torch.floor(rows * float(unit)).long()
-        largest = torch.argmax(rows, dim=1, keepdim=True)
-        units.scatter_add_(1, largest, (unit - units.sum(1, keepdim=True)))
-        if bool((units.gather(1, largest) < 0).any()):
-          raise ValueError('a float start sums to more than 1 by more than its largest entry')
-        start = units.reshape(p.shape).contiguous()
-    want = [('visits', torch.int64, (P, S, A)), ('finished', torch.int64, (frames, P)),
-            ('final', torch.int64, (P, S)), ('counts', torch.int32, (P, S, A)),
-            ('probs', torch.float64, (P, S, A))]
-    if planned == 2:
-      want.append(('scratch', torch.int64, (P, S)))
-    if want_frames:
-      want.append(('per_frame', torch.int64, (frames + 1, P, S)))
-    made_by = 'visit_population_buffers({}, {}, want_frames={})'.format(P, frames, bool(want_frames))
-    if out is None:
-      out = self.visit_population_buffers(P, frames, want_frames)
-    else:
-      self._check_out(out, want, made_by)
-    if start is not None:
-      if out.get('scratch') is not None and self._shares_bytes(start, out['scratch']):
-        raise ValueError('start must not be out[\'scratch\']')
-      in_place = start.dim() == 2 and start.data_ptr() == out['final'].data_ptr()
-      if not in_place and self._shares_bytes(start, out['final']):
-        raise ValueError('start must not overlap out[\'final\'] (a [P, n_states] start may BE it)')
-    validate = self.validate_actions
-    _hip.ops.wide_visit_population(
-        self._spec_host, self._tables, policies.detach(), start, bool(restart), out['visits'],
-        out['finished'], out['final'], out['per_frame'] if want_frames else None, out['counts'],
-        out.get('scratch'), self._bad_visit_member_rows if validate else None,
-        self._bad_flag if validate else None, path)
-    if validate:
-      self._after_launch()
-    out['probs'].copy_(out['counts'])
-    out['probs'].mul_(1.0 / float(1 << 24))
-    res = {'visits': out['visits'], 'finished': out['finished'], 'final': out['final'],
-           'counts': out['counts'], 'probs': out['probs'], 'unit': unit}
-    if want_frames:
-      res['per_frame'] = out['per_frame']
-    return res
+    return self._visit(P, policies, frames, start, restart, want_frames, out, path)
 
   @staticmethod
   def _shares_bytes(a, b):

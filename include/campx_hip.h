@@ -1357,7 +1357,8 @@ int32_t campx_wide_visit_launch(const CampxWideSpec* spec_host, const void* tabl
  * the tables that fit are the same.  Path 2: one launch per frame for all members, a workgroup per
  * 256 states of one member, all members' blocks along grid.x, between `final` and `scratch`.
  * 0 = path 1 whenever ONE member fits.  Either grid stops at 2^20 workgroups, each then taking
- * several groups in turn.
+ * several groups in turn.  Both launches run one set of kernels, compiled with the members and
+ * without: members = 1 runs campx_wide_visit_launch()'s instances, from either entry point.
  *
  * campx_wide_visit_population_plan() is the choice as host-only arithmetic: plan_out[5] = the
  * path; dynamic LDS bytes; threads of a workgroup; workgroups launched; G (1 on path 2).  G is the

@@ -8,7 +8,10 @@ Tables: the boat race's own (8 states) and synthetic ones of 1, 37, 257 and 1 02
 states a lane), of the plan's largest table in LDS and of the next.  The populations are chosen so
 that the LDS path packs G = 1, 2 and 32 members of 8 states and 6 of 37 into a workgroup, each of
 the packed ones with a short last workgroup; every case ASSERTS the G the plan gives, read back
-from the plan call with the device's own number of compute units.  The reference does not depend
+from the plan call with the device's own number of compute units.  A population of ONE runs the
+kernels compiled without members - `state_visitation()`'s - through this call's entry point: at
+every one of the sizes it is held, path by path, against the reference and against
+`state_visitation()` on the same path.  The reference does not depend
 on the path: it is computed once per (table, P, frames, restart, start) and every path is held
 against it.
 """
@@ -127,10 +130,13 @@ def _cases():
   cus = _cus()
   return [('boat', 1, 1), ('boat', min(cus, 5), 1), ('boat', cus + 1, 2), ('boat', 32 * cus + 8, 32),
           ('1', 3, 1), ('1', 3 * cus + 2, 4), ('37', 5 * cus + 1, 6), ('257', 5, 1), ('1025', 5, 1), ('fits', 5, 1),
-          ('next', 5, None)]
+          ('next', 5, None),
+          ('37', 1, 1), ('257', 1, 1), ('1025', 1, 1), ('fits', 1, 1), ('next', 1, None)]
 
 
-CASE_IDS = ['boat-1', 'boat-few', 'boat-G2', 'boat-G32', 'one-state', 'one-state-G4', '37-G6', '257', '1025', 'fits', 'next']
+CASE_IDS = ['boat-1', 'boat-few', 'boat-G2', 'boat-G32', 'one-state', 'one-state-G4', '37-G6', '257', '1025', 'fits', 'next',
+            '37-solo', '257-solo', '1025-solo', 'fits-solo', 'next-solo']
+SOLO_KEYS = KEYS + ('probs',)
 
 
 @pytest.mark.parametrize('case', range(len(CASE_IDS)), ids=CASE_IDS)
@@ -151,6 +157,8 @@ def test_every_path_equals_the_reference_and_every_member_the_single_call(case):
       assert G * S % 64 != 0 and S < 64                            # members share a wave, the last wave is part idle
     if name == '1025':
       assert plan[2] == 1024                                       # two states a lane
+    if name == 'fits':
+      assert S == 2834 and plan[2] == 1024                         # three states a lane
   w = _weights(P, S, 100 + case)
   policies = torch.from_numpy(w).cuda()
   members = _members_to_check(P, G or 1)
@@ -173,6 +181,12 @@ def test_every_path_equals_the_reference_and_every_member_the_single_call(case):
             bare = f.visit_population(policies, frames, start=arg, restart=restart, path=path)
             assert 'per_frame' not in bare
             _eq(bare, want, what + (path, 'no per_frame'), NO_ROWS)
+          if P == 1:                             # the same instances from the other entry point, path by path
+            own = None if arg is None else arg.reshape(-1)[:S].reshape(S)
+            one = f.state_visitation(policies[0], frames, start=own, restart=restart, want_frames=True, path=path)
+            for k in SOLO_KEYS:
+              got = res[k][:, 0] if k in ('finished', 'per_frame') else res[k][0]
+              assert got.dtype == one[k].dtype and torch.equal(got, one[k]), what + (path, k)
         if restart:                              # the invariant: the total stays put
           assert np.array_equal(want['final'].sum(axis=1), want['per_frame'][0].sum(axis=1))
           assert torch.equal(res['final'].sum(1), res['per_frame'][0].sum(1))
@@ -207,7 +221,7 @@ def test_through_the_engine_and_into_reused_buffers():
   assert 'per_frame' not in game.visit_population_buffers(3, 7)
 
 
-@pytest.mark.parametrize('name,P', [('boat', 70), ('37', 13), ('next', 4)])
+@pytest.mark.parametrize('name,P', [('boat', 70), ('37', 13), ('next', 4), ('boat', 1), ('1025', 1), ('next', 1)])
 def test_continuation_in_place_with_reused_buffers(name, P):
   f, nxt, done = _game(name)
   S = f.n_states
@@ -281,6 +295,97 @@ def test_bad_rows_give_the_reference_s_bits_and_raise_lazily_with_their_count(na
     f.state_visitation(policies[0], 3)
     f.check_actions()
   f.check_actions()
+
+
+@pytest.mark.parametrize('name', ['boat', 'next'])
+def test_bad_rows_of_one_member_land_on_the_counter_of_the_function_called(name):
+  """P = 1 runs one set of kernels from both entry points; whose counter and message a bad row
+  lands on is the caller's, both ways, each with the exact count."""
+  f, nxt, done = _game(name)
+  S = f.n_states
+  bad = [(0, 0), (0, S - 1), (0, S // 2)]
+  w = _weights(1, S, 57, bad)
+  want = pop_ref.visitation(nxt, done, w, 5)
+  assert want['bad_rows'] == 3
+  policies = torch.from_numpy(w).cuda()
+  f.check_actions()
+  f.validate_actions = 'sync'                    # the call itself raises, with the count
+  try:
+    for path in _paths(S)[:2]:
+      res = f.visit_population_buffers(1, 5, want_frames=True)
+      with pytest.raises(ValueError) as caught:
+        f.visit_population(policies, 5, want_frames=True, out=res, path=path)
+      text = str(caught.value)
+      assert text.startswith('3 rows of the policies given to visit_population() are bad')
+      assert 'state_visitation' not in text and text.count('rows of') == 1
+      assert int(f._bad_visit_rows) == 0 and int(f._bad_visit_member_rows) == 0
+      _eq(res, want, (name, path, 'bad rows of one member'))
+      f.check_actions()                          # nothing is left counted
+      one = f.visitation_buffers(5, want_frames=True)
+      with pytest.raises(ValueError) as caught:
+        f.state_visitation(policies[0], 5, want_frames=True, out=one, path=path)
+      text = str(caught.value)
+      assert text.startswith('3 rows of the policy given to state_visitation() are bad')
+      assert 'visit_population' not in text and text.count('rows of') == 1
+      assert int(f._bad_visit_rows) == 0 and int(f._bad_visit_member_rows) == 0
+      assert torch.equal(one['visits'], res['visits'][0]) and torch.equal(one['final'], res['final'][0])
+      f.check_actions()
+    # not validated: neither counter moves
+    f.validate_actions = False
+    f.visit_population(policies, 5)
+    f.state_visitation(policies[0], 5)
+    torch.cuda.synchronize()
+    assert int(f._bad_visit_rows) == 0 and int(f._bad_visit_member_rows) == 0
+  finally:
+    f.validate_actions = True
+  f.check_actions()
+
+
+def test_a_shared_start_that_is_final_is_refused_for_one_member_too():
+  """A [S] start is SHARED, whatever P is: at P = 1 it still must not be 'final' - only a
+  [1, S] start continues in place - and the refusal comes before any launch, from the method and
+  from the C entry."""
+  from campx_amd import _hip
+  f, nxt, done = _game('37')
+  S = f.n_states
+  w = _weights(1, S, 81)
+  policies = torch.from_numpy(w).cuda()
+  given = _start(1, S, 'member', 82)
+  out = f.visit_population_buffers(1, 3)
+  launched = []
+  real = _hip.ops.wide_visit_population
+  try:
+    _hip.ops.wide_visit_population = lambda *a: launched.append(a) or real(*a)
+    for path in (1, 2, 0):
+      out['final'].copy_(torch.from_numpy(given))
+      with pytest.raises(ValueError, match='start must not overlap out'):
+        f.visit_population(policies, 3, start=out['final'][0], out=out, path=path)
+      assert not launched
+  finally:
+    del _hip.ops.wide_visit_population
+  spec = (ctypes.c_char * f._spec_host.numel()).from_buffer(f._spec_host.numpy())
+  vp = ctypes.c_void_p
+  launch = _hip.lib.campx_wide_visit_population_launch
+  for t in out.values():
+    t.fill_(-3)
+  for path in (1, 2, 0):
+    for per_member, refused in ((0, True), (1, False)):
+      out['final'].copy_(torch.from_numpy(given))
+      code = launch(ctypes.cast(spec, launch.argtypes[0]), vp(f._tables.data_ptr()), vp(policies.data_ptr()), 1,
+                    vp(out['final'].data_ptr()), per_member, 1, 3, vp(out['visits'].data_ptr()),
+                    vp(out['finished'].data_ptr()), vp(out['final'].data_ptr()), None,
+                    vp(out['counts'].data_ptr()), vp(out['scratch'].data_ptr()), None, None, path,
+                    vp(torch.cuda.current_stream().cuda_stream))
+      torch.cuda.synchronize()
+      if refused:
+        assert code != 0
+        assert bool((out['visits'] == -3).all()) and bool((out['counts'] == -3).all())   # nothing ran
+        assert np.array_equal(out['final'].cpu().numpy(), given)
+      else:                                      # the same pointers as a start per member: in place
+        assert code == 0
+        _eq(out, pop_ref.visitation(nxt, done, w, 3, start=given), ('in place', path), NO_ROWS)
+        out['visits'].fill_(-3)
+        out['counts'].fill_(-3)
 
 
 def test_path_1_on_a_table_that_does_not_fit_raises():

@@ -199,6 +199,48 @@ def test_at_one_member_per_workgroup_the_account_is_the_single_call_s():
   assert _plan(THREADS * PER_LANE + 1, 3, lds_max=1 << 20, path=1)[0] != 0
 
 
+def test_the_single_plan_is_the_first_four_words_of_one_member_s_at_every_input():
+  """campx_wide_visit_plan(S, lds_max, path) against campx_wide_visit_population_plan(S, 1, lds_max,
+  n_cus, path): the same return code and the same first four words for every input, refused ones
+  included - the words are pre-filled, so that one a call leaves untouched shows as the canary."""
+  from campx_amd import _hip
+  single_fn, members_fn = _hip.lib.campx_wide_visit_plan, _hip.lib.campx_wide_visit_population_plan
+  canary = -0x5a5a5a5a5a5a5a5b
+  most = 1 << 24                                 # CAMPX_WIDE_MAX_STATES
+
+  def largest(lds_max):
+    S = 1
+    while _lds_bytes(S + 1, 1) <= lds_max:
+      S += 1
+    return S
+
+  sizes = set(range(1, 4097)) | {0, -1}
+  for centre in (largest(64 * 1024), largest(LDS_MAX), most):
+    sizes |= set(range(centre - 2, centre + 3))
+  assert largest(LDS_MAX) == 2834 and max(sizes) == most + 2
+  one, five = (ctypes.c_int64 * 4)(), (ctypes.c_int64 * 5)()
+  calls = refused = 0
+  for S in sorted(sizes):
+    for lds_max in (-1, 0, _lds_bytes(1, 1), 64 * 1024, LDS_MAX):
+      for path in (-1, 0, 1, 2, 3):
+        one[:] = [canary] * 4
+        code = single_fn(S, lds_max, path, one)
+        words = list(one)
+        assert (code == 0) == (canary not in words), (S, lds_max, path, code, words)
+        for n_cus in (1, 256):
+          five[:] = [canary] * 5
+          got = members_fn(S, 1, lds_max, n_cus, path, five)
+          assert got == code and list(five)[:4] == words, (S, lds_max, path, n_cus, code, got, words, list(five))
+          assert five[4] == (1 if code == 0 else canary), (S, lds_max, path, n_cus, list(five))
+        calls += 1
+        refused += code != 0
+  assert calls == len(sizes) * 25 and 0 < refused < calls
+  # fewer than one compute unit is the population's alone to refuse
+  five[:] = [canary] * 5
+  assert members_fn(8, 1, LDS_MAX, 0, 0, five) != 0 and list(five) == [canary] * 5
+  assert single_fn(8, LDS_MAX, 0, one) == 0
+
+
 def test_a_lowered_wide_lds_max_bounds_the_members():
   # S = 8, P = 65536, one CU: (b) says 32; LDS says less
   for G in (1, 2, 3, 17, 31):
