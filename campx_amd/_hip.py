@@ -38,7 +38,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
            'campx_wide_render_windows_launch', 'campx_wide_render_windows_plan',
-           'campx_returns_launch',
+           'campx_returns_launch', 'campx_vtrace_launch', 'campx_vtrace_plan',
            'campx_state_sums_launch', 'campx_state_sums_plan', 'campx_table_lookup_launch',
            'campx_wide_sweeps_plan', 'campx_wide_sweeps_launch',
            'campx_wide_population_sweeps_plan', 'campx_wide_population_sweeps_launch',
@@ -112,6 +112,24 @@ class CampxReturns(ctypes.Structure):
               ('discount_pitch', ctypes.c_int64), ('values_pitch', ctypes.c_int64),
               ('returns_pitch', ctypes.c_int64), ('advantages_pitch', ctypes.c_int64),
               ('gamma', ctypes.c_float), ('lam', ctypes.c_float)]
+
+
+class CampxVtrace(ctypes.Structure):
+  """include/campx_hip.h: the streams, tables and scalars of one campx_vtrace_launch() call."""
+  _fields_ = [('reward', ctypes.c_void_p), ('done', ctypes.c_void_p), ('discount', ctypes.c_void_p),
+              ('values', ctypes.c_void_p), ('bootstrap', ctypes.c_void_p), ('ratio', ctypes.c_void_p),
+              ('target', ctypes.c_void_p), ('behaviour', ctypes.c_void_p),
+              ('states', ctypes.c_void_p), ('actions', ctypes.c_void_p),
+              ('vs', ctypes.c_void_p), ('advantages', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
+              ('reward_pitch', ctypes.c_int64), ('done_pitch', ctypes.c_int64),
+              ('discount_pitch', ctypes.c_int64), ('values_pitch', ctypes.c_int64),
+              ('ratio_pitch', ctypes.c_int64), ('states_pitch', ctypes.c_int64),
+              ('actions_pitch', ctypes.c_int64), ('vs_pitch', ctypes.c_int64),
+              ('advantages_pitch', ctypes.c_int64),
+              ('n_target_states', ctypes.c_int64), ('n_behaviour_states', ctypes.c_int64),
+              ('n_actions', ctypes.c_int32), ('path', ctypes.c_int32),
+              ('gamma', ctypes.c_float), ('lam', ctypes.c_float), ('rho_bar', ctypes.c_float),
+              ('c_bar', ctypes.c_float), ('pg_rho_bar', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
 class CampxStateSums(ctypes.Structure):
@@ -263,6 +281,10 @@ def _load():
   lib.campx_wide_render_windows_plan.argtypes = [i64, i32, i32, ctypes.c_uint64, ctypes.POINTER(i64)]
   lib.campx_returns_launch.restype = i32
   lib.campx_returns_launch.argtypes = [ctypes.POINTER(CampxReturns), i64, i32, vp]
+  lib.campx_vtrace_launch.restype = i32
+  lib.campx_vtrace_launch.argtypes = [ctypes.POINTER(CampxVtrace), i64, i32, vp]
+  lib.campx_vtrace_plan.restype = i32
+  lib.campx_vtrace_plan.argtypes = [i64, i64, i32, i64, i32, i32, ctypes.POINTER(i64)]
   lib.campx_state_sums_launch.restype = i32
   lib.campx_state_sums_launch.argtypes = [ctypes.POINTER(CampxStateSums), i64, i32, vp]
   lib.campx_state_sums_plan.restype = i32
@@ -340,7 +362,7 @@ def _load_ops():
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'render_gather', 'wide_render_gather', 'wide_render_states',
-            'wide_render_windows', 'returns', 'state_sums', 'table_lookup', 'wide_sweeps',
+            'wide_render_windows', 'returns', 'vtrace', 'state_sums', 'table_lookup', 'wide_sweeps',
             'wide_population_sweeps', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
 
 

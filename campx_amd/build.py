@@ -23,7 +23,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # kernel rebuilds one object (tools/build_variants.py).
 UNITS = ('campx_api', 'k_interp', 'k_rollout_table', 'k_step', 'k_update', 'k_render',
          'k_shape', 'k_wide', 'k_policy', 'k_learn', 'k_gather', 'k_states', 'k_window', 'k_returns',
-         'k_sums', 'k_plan', 'k_visit', 'k_misc')
+         'k_vtrace', 'k_sums', 'k_plan', 'k_visit', 'k_misc')
 SRCS = [os.path.join(CSRC, u + '.hip') for u in UNITS]
 HEADERS = [os.path.join(CSRC, 'campx_common.hip.h'), os.path.join(CSRC, 'wide_table.hip.h'),
            os.path.join(REPO, 'include', 'campx_hip.h')]

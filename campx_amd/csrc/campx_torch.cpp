@@ -22,6 +22,7 @@
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
 //   campx::returns                  discounted returns / GAE advantages of a rollout's streams
+//   campx::vtrace                   V-trace targets / advantages of off-policy streams
 //   campx::state_sums               per-(state, action) fixed-point sums of a rollout's streams
 //   campx::table_lookup             table[states, actions] of a rollout's streams
 //   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
@@ -1092,6 +1093,76 @@ void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTe
   check_ok(campx_returns_launch(&r, B, (int32_t)T, current_stream()), "campx_returns_launch");
 }
 
+// V-trace targets and advantages of [T, B] streams (campx_vtrace_launch): the streams as in
+// campx::returns; `ratio` exactly when the table set (target [Nt, A], behaviour [Nb, A], states,
+// actions) is not given.
+void vtrace(const Tensor& reward, const Tensor& done, double gamma, const Tensor& values,
+            const OptTensor& ratio, const OptTensor& target, const OptTensor& behaviour,
+            const OptTensor& states, const OptTensor& actions, const OptTensor& discount,
+            const OptTensor& bootstrap, double lam, double rho_bar, double c_bar, double pg_rho_bar,
+            const OptTensor& bad_count, int64_t path, Tensor& vs, Tensor& advantages) {
+  TORCH_CHECK(reward.device().is_cuda() && reward.dim() == 2,
+              "campx::vtrace: reward must be a float32 [T, B] tensor on a HIP device (no CPU "
+              "implementation)");
+  const c10::Device dev = reward.device();
+  const int64_t T = reward.size(0), B = reward.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::vtrace: bad shape [", T, ", ", B, "]");
+  const bool table = target.has_value();
+  TORCH_CHECK(behaviour.has_value() == table && states.has_value() == table &&
+                  actions.has_value() == table && ratio.has_value() != table,
+              "campx::vtrace: give ratio, or target, behaviour, states and actions together");
+  TORCH_CHECK(path >= 0 && path <= 2, "campx::vtrace: bad path ", path);
+  CampxVtrace v{};
+  v.reward_pitch = stream_rows(reward, "reward", at::kFloat, dev, T, B);
+  v.done_pitch = stream_rows(done, "done", at::kByte, dev, T, B);
+  v.values_pitch = stream_rows(values, "values", at::kFloat, dev, T, B);
+  if (discount.has_value()) v.discount_pitch = stream_rows(*discount, "discount", at::kFloat, dev, T, B);
+  if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, dev, {B});
+  if (table) {
+    TORCH_CHECK(target->dim() == 2 && behaviour->dim() == 2 && target->size(0) >= 1 &&
+                    target->size(1) >= 1 && target->size(1) <= 128 &&
+                    behaviour->size(0) <= 0x7fffffff && behaviour->size(0) % target->size(0) == 0,
+                "campx::vtrace: target must be [Nt, A <= 128] and behaviour [Nb, A], Nb a multiple "
+                "of Nt; they are ", target->sizes(), " and ", behaviour->sizes());
+    want(*target, "target", at::kFloat, dev, {target->size(0), target->size(1)});
+    want(*behaviour, "behaviour", at::kFloat, dev, {behaviour->size(0), target->size(1)});
+    v.states_pitch = stream_rows(*states, "states", at::kInt, dev, T, B);
+    v.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
+    v.n_target_states = target->size(0);
+    v.n_behaviour_states = behaviour->size(0);
+    v.n_actions = (int32_t)target->size(1);
+  } else {
+    v.ratio_pitch = stream_rows(*ratio, "ratio", at::kFloat, dev, T, B);
+  }
+  if (bad_count.has_value())
+    TORCH_CHECK(bad_count->device() == dev && bad_count->scalar_type() == at::kLong &&
+                    bad_count->numel() == 1,
+                "campx::vtrace: bad_count must be an int64 tensor of one element on ", dev);
+  v.vs_pitch = stream_rows(vs, "vs", at::kFloat, dev, T, B);
+  v.advantages_pitch = stream_rows(advantages, "advantages", at::kFloat, dev, T, B);
+  v.reward = reinterpret_cast<const float*>(reward.data_ptr());
+  v.done = reinterpret_cast<const uint8_t*>(done.data_ptr());
+  v.values = reinterpret_cast<const float*>(values.data_ptr());
+  v.discount = opt_ptr<const float>(discount);
+  v.bootstrap = opt_ptr<const float>(bootstrap);
+  v.ratio = opt_ptr<const float>(ratio);
+  v.target = opt_ptr<const float>(target);
+  v.behaviour = opt_ptr<const float>(behaviour);
+  v.states = opt_ptr<const int32_t>(states);
+  v.actions = opt_ptr<const int8_t>(actions);
+  v.vs = reinterpret_cast<float*>(vs.data_ptr());
+  v.advantages = reinterpret_cast<float*>(advantages.data_ptr());
+  v.bad_count = opt_ptr<int64_t>(bad_count);
+  v.path = (int32_t)path;
+  v.gamma = (float)gamma;
+  v.lam = (float)lam;
+  v.rho_bar = (float)rho_bar;
+  v.c_bar = (float)c_bar;
+  v.pg_rho_bar = (float)pg_rho_bar;
+  const DeviceGuard guard(dev);
+  check_ok(campx_vtrace_launch(&v, B, (int32_t)T, current_stream()), "campx_vtrace_launch");
+}
+
 // Per-(state, action) fixed-point sums of [T, B] streams (campx_state_sums_launch): `raw` int64
 // [1 + K, n_states * n_actions] in any shape that is contiguous, the counters int64 of one element.
 void state_sums(const Tensor& states, const OptTensor& actions, at::TensorList values,
@@ -1420,7 +1491,7 @@ const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
     "wide_learn", "render_gather",
-    "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "state_sums",
+    "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "wide_visit_population",
     "onehot_to_ids",
     "check_actions"};
@@ -1511,6 +1582,11 @@ TORCH_LIBRARY(campx, m) {
       "returns(Tensor reward, Tensor done, float gamma, Tensor? discount, Tensor? values, "
       "Tensor? bootstrap, float lam, Tensor(a!) returns, Tensor(b!)? advantages) -> ()");
   m.def(
+      "vtrace(Tensor reward, Tensor done, float gamma, Tensor values, Tensor? ratio, Tensor? target, "
+      "Tensor? behaviour, Tensor? states, Tensor? actions, Tensor? discount, Tensor? bootstrap, "
+      "float lam, float rho_bar, float c_bar, float pg_rho_bar, Tensor(a!)? bad_count, int path, "
+      "Tensor(b!) vs, Tensor(c!) advantages) -> ()");
+  m.def(
       "state_sums(Tensor states, Tensor? actions, Tensor[] values, int n_states, int n_actions, "
       "int frac_bits, bool accumulate, int path, Tensor(a!) raw, Tensor(b!) skipped, "
       "Tensor(c!) clamped) -> ()");
@@ -1560,6 +1636,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_render_states", &wide_render_states);
   m.impl("wide_render_windows", &wide_render_windows);
   m.impl("returns", &returns);
+  m.impl("vtrace", &vtrace);
   m.impl("state_sums", &state_sums);
   m.impl("table_lookup", &table_lookup);
   m.impl("wide_sweeps", &wide_sweeps);

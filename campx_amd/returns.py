@@ -14,6 +14,11 @@ is tier-agnostic: it takes the `[T, B]` streams of `rollout()`, `rollout_trace()
 The rule is in include/campx_hip.h next to the sampling rule; tests/returns_reference.py restates
 it in numpy float32, bit for bit.  No CPU path.
 
+`vtrace_returns()` is that pass for streams that OTHER policies sampled - the stale actors of a
+`rollout_population()` feeding one learner: V-trace targets and advantages, the importance ratio a
+stream or looked up from the two policies' tables inside the kernel (csrc/k_vtrace.hip,
+`campx::vtrace`; tests/vtrace_reference.py restates the rule).
+
 The learner's half of such an episode is here too.  Everything a tabular loss needs from the
 `[T, B]` streams is a sum per (state, action): `sum_by_state()` is that reduction in one launch, in
 64-bit fixed point - order-independent, so bitwise reproducible - and `table_lookup()` is the
@@ -110,6 +115,128 @@ def discounted_returns(reward, done, gamma, discount=None, values=None, bootstra
       _rows(out.get(k), "out['{}']".format(k), torch.float32, T, B, device)
   _hip.ops.returns(reward, done, float(gamma), discount, values, bootstrap, float(lam),
                    out['returns'], out['advantages'] if values is not None else None)
+  return out if set(out) == set(want) else {k: out[k] for k in want}
+
+
+# ------------------------------------------------------------------ off-policy returns
+
+def _bar(x, name):
+  if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+    raise ValueError('{} must be a finite number >= 0, got {!r}'.format(name, x))
+  return float(x)
+
+
+def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behaviour=None, states=None,
+                   actions=None, discount=None, bootstrap=None, lam=1.0, rho_bar=1.0, c_bar=1.0,
+                   pg_rho_bar=None, bad_count=None, out=None, path=0):
+  """V-trace targets and advantages of `[T, B]` streams that OTHER policies sampled: one launch.
+
+  The off-policy counterpart of `discounted_returns()` (Espeholt et al. 2018, IMPALA): a learner
+  fed by stale or perturbed actors, population-based training, one rollout used for several
+  gradient steps.  For t = T-1 down to 0, per environment e, in float32 with every operation
+  rounded on its own (include/campx_hip.h has the rule in full):
+
+      r, c     as in discounted_returns()
+      w        = ratio[t]                                             (ratio mode), or
+                 target[states[t] % Nt, actions[t]] / behaviour[states[t], actions[t]]   (table mode)
+      w        = w if w > 0 else +0           (NaN, negatives and -0 count as 0; +inf stays)
+      rho, cs, rpg = min(w, rho_bar), min(w, c_bar), min(w, pg_rho_bar)
+      delta    = rho * ((r if done[t] else r + c * V[t+1]) - V[t])    (V[T] = bootstrap[e], or 0)
+      D[t]     = delta if done[t] else delta + ((c * lam) * cs) * D[t+1]       (D[T] = 0)
+      vs[t]    = V[t] + D[t]
+      adv[t]   = rpg * ((r if done[t] else r + c * vs[t+1]) - V[t])   (vs[T] = bootstrap[e], or 0)
+
+  With every ratio 1 and every bar 1, `vs` is bit for bit `values + discounted_returns(...)
+  ['advantages']` at the same `lam`.
+
+  Args:
+    reward, done, gamma, discount, bootstrap, lam: as in `discounted_returns()`.
+    values: float32 `[T, B]`, the critic at the state each frame STARTS in.
+    ratio: float32 `[T, B]`, pi(a|s) / mu(a|s) per frame - ratio mode, any tier's streams.
+    target, behaviour, states, actions: table mode, the four together and no `ratio`.  `target` is
+        the learner's float32 `[Nt, A]` of action probabilities, `behaviour` the float32 `[Nb, A]`
+        the data was sampled with, Nb a multiple of Nt, A <= 128; `states` int32 and `actions` int8
+        `[T, B]`.  For `rollout_population()`, whose states are `member * S + state`:
+        `behaviour = probabilities.view(-1, 5)`, `target` the learner's `[S, 5]`; for
+        `rollout_policy()` both are `[S, 5]`.  A frame whose state is outside [0, Nb) or whose
+        action is outside [0, A) gets w = 0 and is added to `bad_count`; the tables are not read
+        for it.
+    rho_bar, c_bar, pg_rho_bar: the truncation levels, finite and >= 0; `pg_rho_bar=None` means
+        `rho_bar`.
+    bad_count: an int64 tensor of one element on the device, or None.
+    out: a dict of float32 `[T, B]` tensors to write into, 'vs' and 'advantages'.  The call then
+        allocates nothing and is capturable in a HIP graph.
+    path: table mode, where the tables are read from: 0 lets the library choose, 1 forces both
+        into LDS (ValueError when they do not fit), 2 reads them through the caches.  By the rule
+        no bit of the result depends on it.
+
+  Every `[T, B]` tensor lives on one HIP device with `stride(1) == 1` and any row pitch >= B, each
+  its own.  Inputs are used through `.detach()`: the outputs are targets.  Returns a dict: 'vs',
+  the critic's regression target, and 'advantages', the policy-gradient weight with the truncated
+  ratio already inside.  Argument errors raise ValueError before anything is launched.  No CPU path.
+  """
+  for name, x in (('gamma', gamma), ('lam', lam)):
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+      raise ValueError('{} must be a finite number, got {!r}'.format(name, x))
+  rho_bar, c_bar = _bar(rho_bar, 'rho_bar'), _bar(c_bar, 'c_bar')
+  pg_rho_bar = rho_bar if pg_rho_bar is None else _bar(pg_rho_bar, 'pg_rho_bar')
+  _count_arg(path, 'path', 0, 2)
+  tables = (target, behaviour, states, actions)
+  given = sum(x is not None for x in tables)
+  if given not in (0, 4) or (given == 4) == (ratio is not None):
+    raise ValueError('give ratio, or target, behaviour, states and actions together - not both, not neither')
+  _rows(reward, 'reward', torch.float32, None, None, None)
+  T, B = int(reward.shape[0]), int(reward.shape[1])
+  device = reward.device
+  if device.type != 'cuda':
+    raise ValueError('reward must be on a HIP device, it is on {} (there is no CPU path)'.format(device))
+  if T > 0x7fffffff or B > 1 << 31:
+    raise ValueError('vtrace_returns: [T, B] = {} is too large'.format([T, B]))
+  _rows(done, 'done', torch.uint8, T, B, device)
+  _rows(values, 'values', torch.float32, T, B, device)
+  if discount is not None:
+    _rows(discount, 'discount', torch.float32, T, B, device)
+    discount = discount.detach()
+  if bootstrap is not None:
+    if (not torch.is_tensor(bootstrap) or bootstrap.dtype != torch.float32
+        or tuple(bootstrap.shape) != (B,) or bootstrap.device != device
+        or not bootstrap.is_contiguous()):
+      raise ValueError('bootstrap must be a contiguous float32 [{}] tensor on {}'.format(B, device))
+    bootstrap = bootstrap.detach()
+  if ratio is not None:
+    _rows(ratio, 'ratio', torch.float32, T, B, device)
+    ratio = ratio.detach()
+  else:
+    for name, x in (('target', target), ('behaviour', behaviour)):
+      if (not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or x.device != device
+          or not x.is_contiguous() or x.shape[0] < 1 or not 1 <= x.shape[1] <= 128):
+        raise ValueError('{} must be a contiguous float32 [n_states, n_actions <= 128] tensor on {}, got {}'.format(
+            name, device, '{} {} on {}'.format(x.dtype, list(x.shape), x.device) if torch.is_tensor(x)
+            else type(x).__name__))
+    Nt, Nb, A = int(target.shape[0]), int(behaviour.shape[0]), int(target.shape[1])
+    if behaviour.shape[1] != A or Nb % Nt != 0 or Nb > 0x7fffffff:
+      raise ValueError('behaviour must be [Nb, {}] with Nb a multiple of target\'s {} rows and at most '
+                       '2^31 - 1, it is {}'.format(A, Nt, list(behaviour.shape)))
+    _rows(states, 'states', torch.int32, T, B, device)
+    _rows(actions, 'actions', torch.int8, T, B, device)
+    if path == 1 and (Nt + Nb) * A * 4 > _hip.SUMS_LDS_BUDGET:
+      raise ValueError('path=1: tables of {} + {} entries of 4 bytes do not fit the LDS budget of {} bytes'.format(
+          Nt * A, Nb * A, _hip.SUMS_LDS_BUDGET))
+    target, behaviour = target.detach(), behaviour.detach()
+  if bad_count is not None and (not torch.is_tensor(bad_count) or bad_count.dtype != torch.int64
+                                or bad_count.numel() != 1 or bad_count.device != device):
+    raise ValueError('bad_count must be an int64 tensor of one element on {}'.format(device))
+  want = ('vs', 'advantages')
+  if out is None:
+    out = {k: torch.empty((T, B), dtype=torch.float32, device=device) for k in want}
+  else:
+    if not isinstance(out, dict):
+      raise ValueError('out must be a dict of float32 [T, B] tensors: {}'.format(list(want)))
+    for k in want:
+      _rows(out.get(k), "out['{}']".format(k), torch.float32, T, B, device)
+  _hip.ops.vtrace(reward.detach(), done, float(gamma), values.detach(), ratio, target, behaviour, states,
+                  actions, discount, bootstrap, float(lam), rho_bar, c_bar, pg_rho_bar, bad_count,
+                  int(path), out['vs'], out['advantages'])
   return out if set(out) == set(want) else {k: out[k] for k in want}
 
 

@@ -1038,6 +1038,90 @@ typedef struct CampxReturns {
 } CampxReturns;
 int32_t campx_returns_launch(const CampxReturns* returns, int64_t B, int32_t T, void* stream);
 /*
+ * ---- Off-policy returns: V-trace targets and advantages, episode-aware ------------------------
+ * The same backward pass for data that OTHER policies sampled (csrc/k_vtrace.hip): a learner fed
+ * by stale or perturbed actors, population-based training, one rollout used for several gradient
+ * steps.  V-trace (Espeholt et al. 2018, IMPALA) corrects with importance ratios truncated per
+ * frame.  No reference counterpart.
+ *
+ * The rule.  f32 throughout, every operation rounded on its own (no fused multiply-add), the one
+ * division IEEE-rounded, so that a float32 restatement is bit-exact (tests/vtrace_reference.py is
+ * one, in numpy).  Per environment e, for t = T-1 down to 0:
+ *     r      = isnan(reward[t]) ? 0 : reward[t]
+ *     c      = gamma * discount[t]                       (gamma when `discount` is NULL)
+ *   ratio mode:  w0 = ratio[t]
+ *   table mode:  s = states[t], a = actions[t]
+ *                in range  <=>  0 <= s < Nb  and  0 <= a < A
+ *                w0 = in range ? target[(s % Nt) * A + a] / behaviour[s * A + a] : 0
+ *                (a frame out of range is added to *bad_count; the tables are not read for it)
+ *     w      = w0 > 0 ? w0 : +0                          (NaN, negatives and -0 count as 0; +Inf stays)
+ *     rho    = w < rho_bar    ? w : rho_bar
+ *     cs     = w < c_bar      ? w : c_bar
+ *     rpg    = w < pg_rho_bar ? w : pg_rho_bar
+ *     v      = values[t]
+ *     v_next = t == T-1 ? bootstrap[e] : values[t+1]     (0 when `bootstrap` is NULL)
+ *     q      = done[t] ? r : r + c * v_next
+ *     delta  = rho * (q - v)
+ *     k      = (c * lam) * cs
+ *     D[t]   = done[t] ? delta : delta + k * D[t+1]      (D[T] = 0)
+ *     vs[t]  = v + D[t]
+ *     vs_nx  = t == T-1 ? bootstrap[e] : vs[t+1]
+ *     qs     = done[t] ? r : r + c * vs_nx
+ *     adv[t] = rpg * (qs - v)
+ * vs goes to `vs` (the critic's regression target), adv to `advantages` (the policy-gradient
+ * weight, the truncated ratio already inside).  Nb = n_behaviour_states is a multiple of Nt =
+ * n_target_states: with the flat states `member * S + state` of
+ * campx_wide_policy_population_launch(), `behaviour` is the population's [P * S][A] and `target`
+ * the learner's [S][A]; Nb == Nt is the one-policy case.  As in the returns rule subnormals are
+ * kept, zeros keep their sign, only a NaN REWARD counts as 0, and a NaN or an infinity in `values`
+ * or `bootstrap` propagates up to the next frame whose `done` is set.  No ratio reaches the outputs
+ * as a NaN.  Two consequences: with w == 1 everywhere and all three bars 1, D is bit for bit
+ * campx_returns_launch()'s A at the same lam (a multiplication by 1.0 is exact); with c_bar = 0,
+ * D equals delta.
+ *
+ * Streams and pitches as above.  `ratio` is given exactly when none of `target`, `behaviour`,
+ * `states`, `actions` is: those four come together.  `target` is DEVICE float32 [Nt * A],
+ * `behaviour` [Nb * A]; `bad_count` a DEVICE int64, 8-byte aligned, added to, may be NULL.
+ * `path` says where the tables are read from: 1 = both staged in LDS once per workgroup, 2 =
+ * through the caches, 0 = campx_table_lookup_launch()'s rule for both tables together - staged
+ * when their bytes fit CAMPX_SUMS_LDS_BUDGET and their entries are no more than the frames a
+ * workgroup looks up (256 * T).  By the rule no bit of the result depends on it.
+ *
+ * campx_vtrace_plan() is that arithmetic, pure host code: plan_out[3] = the path taken (1 / 2);
+ * dynamic LDS bytes (0 on path 2); workgroups.  CAMPX_EINVAL: Nt < 1, Nb % Nt != 0, Nb above
+ * 2^31 - 1, n_actions outside 1..128, B <= 0 or above 2^31, T <= 0, a `path` outside 0..2, path 1
+ * for tables that do not fit.  campx_vtrace_launch() returns CAMPX_EINVAL for the same (in table
+ * mode) and for: NULL `reward`, `done`, `values`, `vs` or `advantages`; both or neither of `ratio`
+ * and the table set; a pitch below B; float or int32 pointers that are not 4-byte aligned, a
+ * `bad_count` that is not 8-byte aligned; gamma or lam not finite; a bar that is not finite or is
+ * negative.  Asynchronous on `stream`, no synchronisation, no library state.
+ */
+typedef struct CampxVtrace {
+  const float* reward;        /* [T][reward_pitch] */
+  const uint8_t* done;        /* [T][done_pitch] */
+  const float* discount;      /* [T][discount_pitch], or NULL */
+  const float* values;        /* [T][values_pitch] */
+  const float* bootstrap;     /* [B], or NULL */
+  const float* ratio;         /* [T][ratio_pitch]: ratio mode; NULL in table mode */
+  const float* target;        /* [n_target_states * n_actions]: table mode */
+  const float* behaviour;     /* [n_behaviour_states * n_actions] */
+  const int32_t* states;      /* [T][states_pitch] */
+  const int8_t* actions;      /* [T][actions_pitch] */
+  float* vs;                  /* [T][vs_pitch] */
+  float* advantages;          /* [T][advantages_pitch] */
+  int64_t* bad_count;         /* or NULL */
+  int64_t reward_pitch, done_pitch, discount_pitch, values_pitch, ratio_pitch, states_pitch,
+      actions_pitch, vs_pitch, advantages_pitch;
+  int64_t n_target_states, n_behaviour_states;
+  int32_t n_actions;
+  int32_t path;               /* 0 = by arithmetic, 1 = LDS, 2 = global */
+  float gamma, lam, rho_bar, c_bar, pg_rho_bar;
+  int32_t reserved;
+} CampxVtrace;
+int32_t campx_vtrace_launch(const CampxVtrace* vtrace, int64_t B, int32_t T, void* stream);
+int32_t campx_vtrace_plan(int64_t n_target_states, int64_t n_behaviour_states, int32_t n_actions,
+                          int64_t B, int32_t T, int32_t path, int64_t* plan_out);
+/*
  * ---- Per-state sums of a rollout's streams: the learner's gradient in one launch -------------
  * Everything a tabular loss needs from the [T][B] streams of a rollout is a sum per (state,
  * action): the gradient of  sum_t f(table[s_t, a_t]) * w_t  with respect to `table` is
