@@ -18,6 +18,7 @@
 //                                   policy over the game's states (closed-loop rollouts)
 //   campx::wide_policy_population   wide_policy_update for P policies, each over its block of environments
 //   campx::wide_learn               online tabular learners: a Q-table per environment, T frames per launch
+//   campx::wide_learn_shared        shared learners: n environments feed one Q-table, T frames per launch
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -871,6 +872,70 @@ void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Te
            "campx_wide_learn_launch");
 }
 
+// Wide tier, shared online learners (campx_wide_shared_launch): the P = q.size(0) learners are each
+// fed by B / P consecutive environments; `q` float32 [P, n_states, 5], `alpha`, `gamma`, `epsilon`
+// float32 [P], `clamped` int64 [P] (written), the window sums [ceil(frames / window), B] per
+// environment.  `scratch` int32 [3 * P * n_states * 5], zero on entry and left zero: the global
+// path's accumulators (may be None when the launch takes the LDS path).
+void wide_learn_shared(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                       const OptTensor& ret, Tensor& q, const Tensor& alpha, const Tensor& gamma,
+                       const Tensor& epsilon, int64_t rule, int64_t seed, int64_t first_frame,
+                       int64_t frames, int64_t window, Tensor& reward_sum, const OptTensor& perf_sum,
+                       Tensor& episodes, Tensor& clamped, const OptTensor& scratch,
+                       const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                       int64_t path) {
+  const char* what = "campx::wide_learn_shared";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  const int64_t S = g.hs->n_states, A = CAMPX_N_ACTIONS;
+  TORCH_CHECK(q.dim() == 3 && q.size(0) >= 1, what, ": q must be float32 [P, n_states, 5] with P >= 1");
+  const int64_t P = q.size(0);
+  TORCH_CHECK(g.B % P == 0, what, ": the ", g.B, " environments do not split into ", P, " equal blocks");
+  TORCH_CHECK(g.B / P <= 1024, what, ": ", g.B / P, " environments per learner are more than one "
+              "workgroup holds (1024)");
+  TORCH_CHECK(P * S * A < (1ll << 31), what, ": P * n_states * 5 must be below 2^31");
+  want(q, "q", at::kFloat, g.dev, {P, S, A});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": q must be 16-byte aligned");
+  want(alpha, "alpha", at::kFloat, g.dev, {P});
+  want(gamma, "gamma", at::kFloat, g.dev, {P});
+  want(epsilon, "epsilon", at::kFloat, g.dev, {P});
+  TORCH_CHECK(rule == CAMPX_LEARN_Q || rule == CAMPX_LEARN_EXPECTED_SARSA, what,
+              ": rule must be 0 (Q-learning) or 1 (expected SARSA)");
+  TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
+  TORCH_CHECK(frames >= 1 && frames <= 0x7fffffff, what, ": bad frame count");
+  TORCH_CHECK(window >= 1 && window <= 0x7fffffff, what, ": window must be 1 .. 2^31 - 1");
+  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
+  const int64_t W = (frames + window - 1) / window;
+  want(reward_sum, "reward_sum", at::kFloat, g.dev, {W, g.B});
+  if (perf_sum.has_value()) want(*perf_sum, "perf_sum", at::kInt, g.dev, {W, g.B});
+  want(episodes, "episodes", at::kInt, g.dev, {W, g.B});
+  want(clamped, "clamped", at::kLong, g.dev, {P});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kInt, g.dev, {3 * P * S * A});
+  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
+  CampxSharedLearner l{};
+  l.q = reinterpret_cast<float*>(q.data_ptr());
+  l.alpha = reinterpret_cast<const float*>(alpha.data_ptr());
+  l.gamma = reinterpret_cast<const float*>(gamma.data_ptr());
+  l.epsilon = reinterpret_cast<const float*>(epsilon.data_ptr());
+  l.reward_sum = reinterpret_cast<float*>(reward_sum.data_ptr());
+  l.perf_sum = opt_ptr<int32_t>(perf_sum);
+  l.episodes = reinterpret_cast<int32_t*>(episodes.data_ptr());
+  l.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
+  l.scratch = scratch.has_value() ? scratch->data_ptr() : nullptr;
+  l.scratch_bytes = scratch.has_value() ? 12 * P * S * A : 0;
+  l.bad_count = opt_ptr<int32_t>(bad_count);
+  l.bad_flag = flag_ptr(bad_flag, g.dev);
+  l.seed = (uint64_t)seed;
+  l.first_frame = first_frame;
+  l.n_learners = P;
+  l.window = (int32_t)window;
+  l.rule = (int32_t)rule;
+  l.path = (int32_t)path;
+  l.reset_first = reset_first ? 1 : 0;
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_shared_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
+           "campx_wide_shared_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1490,7 +1555,7 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
-    "wide_learn", "render_gather",
+    "wide_learn", "wide_learn_shared", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "wide_visit_population",
     "onehot_to_ids",
@@ -1566,6 +1631,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(g!) episodes, Tensor(h!)? bad_count, Tensor(i!)? bad_flag, bool reset_first, "
       "int path=0) -> ()");
   m.def(
+      "wide_learn_shared(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) q, Tensor alpha, Tensor gamma, Tensor epsilon, int rule, int seed, "
+      "int first_frame, int frames, int window, Tensor(e!) reward_sum, Tensor(f!)? perf_sum, "
+      "Tensor(g!) episodes, Tensor(h!) clamped, Tensor(i!)? scratch, Tensor(j!)? bad_count, "
+      "Tensor(k!)? bad_flag, bool reset_first, int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1631,6 +1702,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_policy_update", &wide_policy_update);
   m.impl("wide_policy_population", &wide_policy_population);
   m.impl("wide_learn", &wide_learn);
+  m.impl("wide_learn_shared", &wide_learn_shared);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

@@ -497,6 +497,22 @@ class Engine(object):
     """State-table tier only: the dict of `learn_tabular(out=...)`, allocated once."""
     return self._batched('learner_buffers').learner_buffers(T, window=window)
 
+  def learn_shared(self, T, q, *args, **kwargs):
+    """State-table tier only: T frames of online tabular learning for P SHARED learners in one
+    launch, learner m owning `q[m]` of `q` float32 `[P, n_states, 5]` (updated in place) and fed by
+    the n = B / P environments `[m * n, (m + 1) * n)`, 1 <= n <= 1024; `alpha`, `gamma` and
+    `epsilon` are numbers or float32 `[P]` tensors.  Synchronous and reproducible bit for bit: per
+    frame the TD errors of a learner's environments are summed in fixed point per (state, action)
+    and the table moves once, by alpha times their mean.  Returns 'q', the per-environment window
+    sums 'reward_sum', 'perf_sum' and 'episodes', `[W, B]`, and 'clamped' int64 `[P]`.  See
+    `wide.WideGame.learn_shared`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    return self._batched('learn_shared').learn_shared(T, q, *args, **kwargs)
+
+  def shared_learner_buffers(self, P, T, window=None, path=0):
+    """State-table tier only: the dict of `learn_shared(out=...)` for P learners, allocated once."""
+    return self._batched('shared_learner_buffers').shared_learner_buffers(P, T, window=window, path=path)
+
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
     game's table (None: all of them), bit for bit what `play()` / `rollout()` show for an

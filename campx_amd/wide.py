@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'learner_buffers', 'learn_tabular', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
@@ -143,6 +143,9 @@ class WideGame(fused.FusedGame):
     # flag of the action ids), and the [3, B] tensor its Python-float hyper-parameters are filled into
     self._bad_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._learn_floats = None
+    # the same two of learn_shared(): bad learners, and its [3, P] tensors by P
+    self._bad_shared_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._shared_floats = {}
     self._layer_of_cell = None        # the window kernel's scenery table
     self._window_table()
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
@@ -191,7 +194,11 @@ class WideGame(fused.FusedGame):
         (self._bad_learners, acts,
          '{} learners of learn_tabular() have bad hyper-parameters (alpha, gamma or epsilon not '
          'finite, or epsilon outside [0, 1]); they took action {} at every frame and their tables were '
-         'left untouched')]
+         'left untouched'),
+        (self._bad_shared_learners, acts,
+         '{} learners of learn_shared() have bad hyper-parameters (alpha, gamma or epsilon not '
+         'finite, or epsilon outside [0, 1]); their environments took action {} at every frame and '
+         'their tables were left untouched')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -497,11 +504,11 @@ class WideGame(fused.FusedGame):
       out['perf_sum'] = torch.zeros((W, B), dtype=torch.int32, device=dev)
     return out
 
-  def _hyper_parameter(self, name, value, row):
+  def _hyper_parameter(self, name, value, row, learners=None):
     """float32 [B] on the device of `alpha`, `gamma` or `epsilon`: a tensor as given, a Python
     number checked here and filled into row `row` of a tensor the game keeps (no allocation after
-    the first call)."""
-    B = self.batch
+    the first call).  `learners`: float32 [learners] for the P learners of `learn_shared()`."""
+    B = self.batch if learners is None else learners
     if torch.is_tensor(value):
       if not self._tensor_ok(value, torch.float32, (B,)):
         raise ValueError('{} must be a number or a contiguous float32 [{}] tensor (one per learner) '
@@ -515,6 +522,10 @@ class WideGame(fused.FusedGame):
         or (name == 'epsilon' and not 0.0 <= value <= 1.0)):
       raise ValueError('{} must be a finite number (as a float32){}, got {!r}'.format(
           name, ' in [0, 1]' if name == 'epsilon' else '', value))
+    if learners is not None:
+      if learners not in self._shared_floats:
+        self._shared_floats[learners] = torch.zeros((3, B), dtype=torch.float32, device=self.device)
+      return self._shared_floats[learners][row].fill_(float(value))
     if self._learn_floats is None:
       self._learn_floats = torch.zeros((3, B), dtype=torch.float32, device=self.device)
     return self._learn_floats[row].fill_(float(value))
@@ -547,7 +558,7 @@ class WideGame(fused.FusedGame):
           `q[e, s, a] += alpha * (target - q[e, s, a])`.  Expected SARSA is the on-policy form
           that needs nothing carried between frames; SARSA proper needs the NEXT frame's committed
           action, across launches too, and is not offered.  Several environments feeding ONE
-          learner would need atomics and would not repeat bit for bit: out of scope as well.
+          learner are `learn_shared()`: its atomics add integers, so it repeats bit for bit too.
       seed, first_frame: exploration is counter-based - learner e at absolute frame f draws from
           the Philox4x32-10 block of key `seed`, counter (e, f >> 1, 1) - a stream unrelated to
           `rollout_policy()`'s for the same seed.  `first_frame=None` continues the per-game frame
@@ -613,6 +624,142 @@ class WideGame(fused.FusedGame):
     if validate:
       self._after_launch()
     res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes']}
+    if self.has_perf:
+      res['perf_sum'] = out['perf_sum']
+    return res
+
+  # ------------------------------------------------------------ shared online learners
+
+  def _shared_plan(self, P, path):
+    """The six words of campx_wide_shared_plan() for P learners of this game - path, learners per
+    workgroup, threads, LDS bytes, entries in LDS, accumulator copies - after the checks of P that
+    have a message of their own."""
+    S, A, B = self.n_states, gamespec.N_ACTIONS, self.batch
+    if isinstance(P, bool) or not isinstance(P, int) or P < 1 or P > B or B % P != 0:
+      raise ValueError('learn_shared(): the {} environments do not split into P = {!r} equal blocks '
+                       '(P must divide the batch)'.format(B, P))
+    if B // P > 1024:
+      raise ValueError('learn_shared(): {} environments per learner are more than one workgroup '
+                       'holds: n = B / P must be at most 1024'.format(B // P))
+    if P * S * A >= 1 << 31:
+      raise ValueError('learn_shared(): P * n_states * 5 = {} x {} x 5 must be below 2^31'.format(P, S))
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    plan = (ctypes.c_int64 * 6)()
+    lds_max = _hip.config_get('wide_lds_max')
+    code = _hip.lib.campx_wide_shared_plan(S, 1 if self.has_perf else 0, B, P, lds_max, path, plan)
+    if code != 0 and path == 1:
+      raise ValueError('path=1: a table of {} states with the Q-table and the accumulators of one '
+                       'learner does not fit the LDS of one workgroup (library setting '
+                       'wide_lds_max); use path=0 or path=2'.format(S))
+    if code != 0:
+      raise ValueError('path={}: the library refused the plan (code {}; library setting '
+                       'wide_lds_max = {})'.format(path, code, lds_max))
+    return list(plan)
+
+  def shared_learner_buffers(self, P, T, window=None, path=0):
+    """Allocate the dict of `learn_shared(out=...)` once, for P learners: `learner_buffers(T,
+    window)`'s tensors, 'clamped' int64 [P] and - when a call with this `path` goes through global
+    memory (path 2) - 'scratch', its accumulators: int32 [3 * P * n_states * 5], zero, and left
+    zero by every call."""
+    plan = self._shared_plan(P, path)
+    out = self.learner_buffers(T, window)
+    out['clamped'] = torch.zeros((P,), dtype=torch.int64, device=self.device)
+    if plan[0] == 2:
+      out['scratch'] = torch.zeros((3 * P * self.n_states * gamespec.N_ACTIONS,), dtype=torch.int32,
+                                   device=self.device)
+    return out
+
+  def learn_shared(self, T, q, alpha=0.1, gamma=0.99, epsilon=0.1, rule='q', seed=0,
+                   first_frame=None, reset_first=False, window=None, out=None, path=0):
+    """T frames of online tabular learning for P SHARED learners in ONE launch: learner m owns the
+    table `q[m]` and is fed by the n = B / P environments `[m * n, (m + 1) * n)` - one agent that
+    learns from n parallel actors, `rollout_population()`'s split of the batch (csrc/k_learn.hip,
+    `campx::wide_learn_shared`).
+
+    The learner is synchronous.  Within a frame every environment of a learner acts
+    epsilon-greedily on the same table - the table as the frame found it - and computes its own TD
+    error, `learn_tabular()`'s, with the learner's alpha, gamma and epsilon.  The errors are
+    quantised to 64-bit fixed point (32 fractional bits) and summed per (state, action) as
+    integers, and each visited `q[m, s, a]` moves once, by alpha times the MEAN error of its
+    visitors: the step size does not depend on n, and the run repeats bit for bit whatever the
+    order in which environments arrive (include/campx_hip.h has the rule in full;
+    tests/shared_learner_reference.py restates it in numpy).
+
+    Args:
+      q: contiguous float32 `[P, n_states, 5]` on the game's device (16-byte aligned,
+          `P * n_states * 5 < 2^31`), updated IN PLACE; P is read from it, so None is not allowed.
+          P must divide the batch, and 1 <= n = B / P <= 1024, the largest workgroup: a learner's
+          environments sit in one workgroup, whose barrier is the per-frame synchronisation.  More
+          actors than one workgroup holds would need a grid-wide barrier per frame: out of scope.
+      alpha, gamma, epsilon: each a Python number or a float32 `[P]` tensor - a tensor is a sweep.
+          A learner whose alpha, gamma or epsilon is not finite, or whose epsilon is outside
+          [0, 1], is BAD: all its environments take action 4 at every frame, its table is left
+          untouched, and it raises ValueError - counted once per learner and call - lazily, as bad
+          learners of `learn_tabular()` do.  Python numbers are checked at once.
+      rule: 'q' or 'expected_sarsa', with `learn_tabular()`'s meaning.
+      seed, first_frame, reset_first, window: exactly as in `learn_tabular()`; the Philox counter
+          is (absolute environment, frame >> 1, 1), the same stream.
+      out: a dict from `shared_learner_buffers(P, T, window, path)`, overwritten.  With `out` (and
+          tensors, or the same numbers as before, for the hyper-parameters) the call allocates
+          nothing and is capturable in a HIP graph.
+      path: 0 - a workgroup keeps the table, its learners' Q-tables and their accumulators in LDS
+          whenever enough of them fit (library setting wide_lds_max), else Q-tables and
+          accumulators are in global memory; 1 / 2 force either (1 raises ValueError when not even
+          one learner fits).  Both give the same bits.
+
+    Returns a dict: 'q'; 'reward_sum' float32, 'episodes' int32 and - games with hidden
+    performance - 'perf_sum' int32, `[W, B]` each and PER ENVIRONMENT as `learn_tabular()` writes
+    them (`.view(W, P, n)` gives a learner's curves); 'clamped' int64 `[P]`, written by the call:
+    the TD errors of this call that were NaN (counted as 0) or beyond +-2^20 (counted as that).
+    `state`, `done`, `ret` and `frame` carry over exactly as `learn_tabular()` leaves them.
+    Argument errors raise ValueError before anything is launched.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    T, window, W = self._windows_of(T, window)
+    if rule not in _hip.LEARN_RULES:
+      raise ValueError('rule must be \'q\' or \'expected_sarsa\', got {!r}'.format(rule))
+    if (not torch.is_tensor(q) or q.dtype != torch.float32 or q.dim() != 3 or q.shape[0] < 1
+        or tuple(q.shape[1:]) != (S, A) or q.device != dev or not q.is_contiguous()
+        or q.data_ptr() % 16):
+      got = ('{} {} on {}'.format(q.dtype, list(q.shape), q.device) if torch.is_tensor(q)
+             else type(q).__name__)
+      raise ValueError('q must be a contiguous, 16-byte aligned float32 [P, {}, {}] tensor (learners '
+                       'x n_states x actions) on {}; got {}'.format(S, A, dev, got))
+    P = int(q.shape[0])
+    plan = self._shared_plan(P, path)
+    first = self._policy_frame if first_frame is None else int(first_frame)
+    if first < 0 or first + T >= 1 << 63:
+      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
+    seed = int(seed) & ((1 << 64) - 1)
+    want = [('reward_sum', torch.float32, (W, B)), ('episodes', torch.int32, (W, B)),
+            ('clamped', torch.int64, (P,))]
+    if self.has_perf:
+      want.append(('perf_sum', torch.int32, (W, B)))
+    if plan[0] == 2:
+      want.append(('scratch', torch.int32, (3 * P * S * A,)))
+    if out is None:
+      out = self.shared_learner_buffers(P, T, window, path)
+    else:
+      self._check_out(out, want, 'shared_learner_buffers({}, {}, window={}, path={})'.format(
+          P, T, window, path))
+    hyper = [self._hyper_parameter(name, value, row, learners=P) for row, (name, value) in
+             enumerate((('alpha', alpha), ('gamma', gamma), ('epsilon', epsilon)))]
+    validate = self.validate_actions
+    _hip.ops.wide_learn_shared(
+        self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), hyper[0],
+        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed - (1 << 64) if seed >= 1 << 63 else seed,
+        first, T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
+        out['episodes'], out['clamped'], out.get('scratch') if plan[0] == 2 else None,
+        self._bad_shared_learners if validate else None, self._bad_flag if validate else None,
+        bool(reset_first), path)
+    self._policy_frame = first + T
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if validate:
+      self._after_launch()
+    res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes'],
+           'clamped': out['clamped']}
     if self.has_perf:
       res['perf_sum'] = out['perf_sum']
     return res

@@ -895,6 +895,94 @@ int32_t campx_wide_learn_launch(const CampxWideSpec* spec_host, const void* tabl
                                 CampxState state, const CampxLearner* learner, int64_t B, int32_t T,
                                 void* stream);
 /*
+ * ---- Shared online learners: n environments feed one Q-table, a whole run per launch ----------
+ * The common shape of tabular RL on a vectorised engine: P learners, learner m fed by the
+ * n = B / P consecutive environments [m * n, (m + 1) * n) - campx_wide_policy_population_launch()'s
+ * split.  `q` is DEVICE float32 [P][n_states][5] (16-byte aligned, P * n_states * 5 < 2^31,
+ * updated in place), alpha / gamma / epsilon DEVICE float32 [P].  P divides B and 1 <= n <= 1024,
+ * the largest workgroup: a learner's environments sit in ONE workgroup, so that the per-frame
+ * synchronisation is a workgroup barrier and T frames are one launch (csrc/k_learn.hip).  More
+ * actors per learner would need a grid-wide barrier per frame: not offered.
+ *
+ * The learner is SYNCHRONOUS, and repeats bit for bit whatever the order in which its
+ * environments arrive.  Frame f of learner m, every float32 operation rounded on its own:
+ *   1. TD error per environment.  Every environment e of the learner does steps 1 - 6 of the rule
+ *      above with q[m] in place of q[e] and alpha[m], gamma[m], epsilon[m]; the Philox counter is
+ *      (ABSOLUTE environment e, g & 0xffffffff, g >> 32, 1), the stream of the per-environment
+ *      learners.  It reads q[m] as it stands at the START of the frame - no environment sees
+ *      another's update of the same frame.  delta_e = target - q[m][s_e][a_e].
+ *   2. Quantise.  d = double(delta_e) * 2^32; z_e = llrint(d) (round half to even); a NaN gives 0
+ *      and |d| > 2^52 (an infinity too) gives +-2^52, and both are counted in clamped[m].  1 024
+ *      values of at most 2^52 cannot overflow an int64.
+ *   3. Update per bin.  For every (s, a) that c >= 1 of the learner's environments visited in this
+ *      frame: Z = the sum of their z_e (integers: any order), g = double(Z) / double(c),
+ *      mean = float32(g * 2^-32), step = alpha[m] * mean, q[m][s][a] = q[m][s][a] + step.
+ *      Bins nobody visited are not touched.  The mean makes the step size independent of n.
+ *   4. The next frame starts from the updated table.
+ *   5. reward_sum / perf_sum / episodes [W][B], `ret`, state and done are PER ENVIRONMENT, exactly
+ *      as campx_wide_learn_launch() writes them.
+ *   6. A learner whose alpha, gamma or epsilon is not finite, or whose epsilon is outside [0, 1],
+ *      is BAD: all its environments take action 4 at every frame, its table is untouched, nothing
+ *      is accumulated or clamped, and it is counted ONCE per learner and launch into *bad_count.
+ * clamped DEVICE int64 [P] is WRITTEN, not added to: the TD errors of this launch that step 2 could
+ * not hold.
+ *
+ * A workgroup holds G consecutive whole learners, G * n threads.  A frame is two phases with a
+ * barrier after each: (A) every lane adds 1 to its bin's count and z to its bin's sum with
+ * workgroup-scope atomics - the lane whose count-add returned 0 owns the bin; (B) the owner
+ * exchanges both for 0 and writes q[m][s][a].  The cost of (B) does not grow with n_states.  One
+ * accumulator per bin: the adds are not privatised (`copies` = 1).
+ * Path 1: the entries, the perf bytes, the G tables and their accumulators in LDS:
+ *     table = up16(n_states * 40) + (has_perf ? up16(n_states * 5) : 0)
+ *     most  = min(P, n <= 256 ? 256 / n : 1)       G = min(most, (wide_lds_max - table) / (n_states * 80))
+ *     LDS bytes = table + G * n_states * 80        (per entry: sum 8, q 4, count 4)
+ * Path 2: q and the accumulators in global memory, G = most; `scratch` (DEVICE, 8-byte aligned, at
+ * least campx_wide_shared_scratch_bytes() = P * n_states * 5 * 12 bytes) must be ZERO on entry and
+ * is left zero; the entries (and perf bytes) are in LDS when `table` alone is within wide_lds_max.
+ * `path` 0 takes path 1 when G >= 1 and G == most or G * n >= 64 (a workgroup that its LDS cuts
+ * below a wave idles most of one at every frame); 1 forces it (refused when not even one learner
+ * fits), 2 forces path 2.  No path, G or order of arrival changes a bit of any result: only
+ * integers are added.
+ *
+ * campx_wide_shared_plan() is the choice as host-only arithmetic: plan_out[6] = path (1 / 2); G;
+ * threads of a workgroup (G * n); dynamic LDS bytes; 1 when the entries are staged in LDS;
+ * accumulator copies per bin (1).  CAMPX_EINVAL: n_states outside 1 .. CAMPX_WIDE_MAX_STATES, a
+ * has_perf that is not 0 / 1, B outside 1 .. 2^32 - 1, P < 1, P not dividing B, B / P > 1024,
+ * P * n_states * 5 >= 2^31, wide_lds_max < 0, a `path` outside 0 .. 2, path 1 for what does not
+ * fit, plan_out NULL.  campx_wide_shared_launch() returns CAMPX_EINVAL, before anything touches a
+ * device, for the same and for what campx_wide_learn_launch() refuses, a clamped that is NULL or
+ * not 8-byte aligned, and - on path 2 - a scratch that is NULL, misaligned or too small.
+ * Asynchronous on `stream`, no synchronisation, no allocation, no library state.
+ */
+typedef struct CampxSharedLearner {
+  float* q;               /* DEVICE [P][n_states][5], 16-byte aligned; updated in place */
+  const float* alpha;     /* DEVICE [P] each */
+  const float* gamma;
+  const float* epsilon;
+  float* reward_sum;      /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;      /* DEVICE [W][B], or NULL */
+  int32_t* episodes;      /* DEVICE [W][B] */
+  int64_t* clamped;       /* DEVICE [P]: written */
+  void* scratch;          /* path 2: zero on entry, left zero; may be NULL on path 1 */
+  int64_t scratch_bytes;
+  int32_t* bad_count;     /* optional device int32: += bad learners */
+  int32_t* bad_flag;      /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;    /* absolute number of the launch's frame 0 */
+  int64_t n_learners;     /* P */
+  int32_t window;         /* frames per window, >= 1 (may exceed T) */
+  int32_t rule;           /* CAMPX_LEARN_Q / CAMPX_LEARN_EXPECTED_SARSA */
+  int32_t path;           /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+} CampxSharedLearner;
+
+int32_t campx_wide_shared_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t P,
+                               int64_t wide_lds_max, int32_t path, int64_t* plan_out);
+int64_t campx_wide_shared_scratch_bytes(int64_t n_states, int64_t P);
+int32_t campx_wide_shared_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                 CampxState state, const CampxSharedLearner* learner, int64_t B,
+                                 int32_t T, void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
