@@ -822,24 +822,21 @@ void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tenso
               step_done, perf, trace, actions_out, states_out, bad_count, bad_flag, reset_first);
 }
 
-// Wide tier, online tabular learners (campx_wide_learn_launch): environment e learns on its own
-// table `q[e]` float32 [B, n_states, 5] for `frames` frames; `alpha`, `gamma`, `epsilon` float32 [B];
-// the window sums are [ceil(frames / window), B].  `rule`: 0 Q-learning, 1 expected SARSA.
-void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
-                const OptTensor& ret, Tensor& q, const Tensor& alpha, const Tensor& gamma,
-                const Tensor& epsilon, int64_t rule, int64_t seed, int64_t first_frame, int64_t frames,
-                int64_t window, Tensor& reward_sum, const OptTensor& perf_sum, Tensor& episodes,
-                const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
-                int64_t path) {
-  const char* what = "campx::wide_learn";
-  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
-  const int64_t S = g.hs->n_states, A = CAMPX_N_ACTIONS;
-  TORCH_CHECK(g.B * S * A < (1ll << 31), what, ": B * n_states * 5 must be below 2^31");
-  want(q, "q", at::kFloat, g.dev, {g.B, S, A});
+// Wide tier, online learners: what campx::wide_learn (`n` = B learners) and campx::wide_learn_shared
+// (`n` = P) share - the checks of `q` float32 [n, n_states, 5], of `alpha`, `gamma`, `epsilon`
+// float32 [n], of the scalars and of the window sums [ceil(frames / window), B] - and the fields
+// that CampxLearner and CampxSharedLearner have in common, which carry the same names.
+template <typename Learner>
+Learner learner_fields(const char* what, const WideGame& g, int64_t n, Tensor& q, const Tensor& alpha,
+                       const Tensor& gamma, const Tensor& epsilon, int64_t rule, int64_t seed,
+                       int64_t first_frame, int64_t frames, int64_t window, Tensor& reward_sum,
+                       const OptTensor& perf_sum, Tensor& episodes, const OptTensor& bad_count,
+                       const OptTensor& bad_flag, bool reset_first, int64_t path) {
+  want(q, "q", at::kFloat, g.dev, {n, g.hs->n_states, CAMPX_N_ACTIONS});
   TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": q must be 16-byte aligned");
-  want(alpha, "alpha", at::kFloat, g.dev, {g.B});
-  want(gamma, "gamma", at::kFloat, g.dev, {g.B});
-  want(epsilon, "epsilon", at::kFloat, g.dev, {g.B});
+  want(alpha, "alpha", at::kFloat, g.dev, {n});
+  want(gamma, "gamma", at::kFloat, g.dev, {n});
+  want(epsilon, "epsilon", at::kFloat, g.dev, {n});
   TORCH_CHECK(rule == CAMPX_LEARN_Q || rule == CAMPX_LEARN_EXPECTED_SARSA, what,
               ": rule must be 0 (Q-learning) or 1 (expected SARSA)");
   TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
@@ -851,7 +848,7 @@ void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Te
   if (perf_sum.has_value()) want(*perf_sum, "perf_sum", at::kInt, g.dev, {W, g.B});
   want(episodes, "episodes", at::kInt, g.dev, {W, g.B});
   if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
-  CampxLearner l{};
+  Learner l{};
   l.q = reinterpret_cast<float*>(q.data_ptr());
   l.alpha = reinterpret_cast<const float*>(alpha.data_ptr());
   l.gamma = reinterpret_cast<const float*>(gamma.data_ptr());
@@ -867,13 +864,32 @@ void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Te
   l.rule = (int32_t)rule;
   l.path = (int32_t)path;
   l.reset_first = reset_first ? 1 : 0;
+  return l;
+}
+
+// Online tabular learners (campx_wide_learn_launch): environment e learns on its own table `q[e]`
+// float32 [B, n_states, 5] for `frames` frames; `alpha`, `gamma`, `epsilon` float32 [B]; the window
+// sums are [ceil(frames / window), B].  `rule`: 0 Q-learning, 1 expected SARSA.
+void wide_learn(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                const OptTensor& ret, Tensor& q, const Tensor& alpha, const Tensor& gamma,
+                const Tensor& epsilon, int64_t rule, int64_t seed, int64_t first_frame, int64_t frames,
+                int64_t window, Tensor& reward_sum, const OptTensor& perf_sum, Tensor& episodes,
+                const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                int64_t path) {
+  const char* what = "campx::wide_learn";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  TORCH_CHECK(g.B * g.hs->n_states * CAMPX_N_ACTIONS < (1ll << 31), what,
+              ": B * n_states * 5 must be below 2^31");
+  const CampxLearner l = learner_fields<CampxLearner>(
+      what, g, g.B, q, alpha, gamma, epsilon, rule, seed, first_frame, frames, window, reward_sum,
+      perf_sum, episodes, bad_count, bad_flag, reset_first, path);
   const DeviceGuard guard(g.dev);
   check_ok(campx_wide_learn_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
            "campx_wide_learn_launch");
 }
 
-// Wide tier, shared online learners (campx_wide_shared_launch): the P = q.size(0) learners are each
-// fed by B / P consecutive environments; `q` float32 [P, n_states, 5], `alpha`, `gamma`, `epsilon`
+// Shared online learners (campx_wide_shared_launch): the P = q.size(0) learners are each fed by
+// B / P consecutive environments; `q` float32 [P, n_states, 5], `alpha`, `gamma`, `epsilon`
 // float32 [P], `clamped` int64 [P] (written), the window sums [ceil(frames / window), B] per
 // environment.  `scratch` int32 [3 * P * n_states * 5], zero on entry and left zero: the global
 // path's accumulators (may be None when the launch takes the LDS path).
@@ -893,44 +909,15 @@ void wide_learn_shared(const Tensor& spec_host, const Tensor& tables, Tensor& st
   TORCH_CHECK(g.B / P <= 1024, what, ": ", g.B / P, " environments per learner are more than one "
               "workgroup holds (1024)");
   TORCH_CHECK(P * S * A < (1ll << 31), what, ": P * n_states * 5 must be below 2^31");
-  want(q, "q", at::kFloat, g.dev, {P, S, A});
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": q must be 16-byte aligned");
-  want(alpha, "alpha", at::kFloat, g.dev, {P});
-  want(gamma, "gamma", at::kFloat, g.dev, {P});
-  want(epsilon, "epsilon", at::kFloat, g.dev, {P});
-  TORCH_CHECK(rule == CAMPX_LEARN_Q || rule == CAMPX_LEARN_EXPECTED_SARSA, what,
-              ": rule must be 0 (Q-learning) or 1 (expected SARSA)");
-  TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
-  TORCH_CHECK(frames >= 1 && frames <= 0x7fffffff, what, ": bad frame count");
-  TORCH_CHECK(window >= 1 && window <= 0x7fffffff, what, ": window must be 1 .. 2^31 - 1");
-  TORCH_CHECK(path >= 0 && path <= 2, what, ": path must be 0, 1 or 2");
-  const int64_t W = (frames + window - 1) / window;
-  want(reward_sum, "reward_sum", at::kFloat, g.dev, {W, g.B});
-  if (perf_sum.has_value()) want(*perf_sum, "perf_sum", at::kInt, g.dev, {W, g.B});
-  want(episodes, "episodes", at::kInt, g.dev, {W, g.B});
+  CampxSharedLearner l = learner_fields<CampxSharedLearner>(
+      what, g, P, q, alpha, gamma, epsilon, rule, seed, first_frame, frames, window, reward_sum,
+      perf_sum, episodes, bad_count, bad_flag, reset_first, path);
   want(clamped, "clamped", at::kLong, g.dev, {P});
   if (scratch.has_value()) want(*scratch, "scratch", at::kInt, g.dev, {3 * P * S * A});
-  if (bad_count.has_value()) want(*bad_count, "bad_count", at::kInt, g.dev, {1});
-  CampxSharedLearner l{};
-  l.q = reinterpret_cast<float*>(q.data_ptr());
-  l.alpha = reinterpret_cast<const float*>(alpha.data_ptr());
-  l.gamma = reinterpret_cast<const float*>(gamma.data_ptr());
-  l.epsilon = reinterpret_cast<const float*>(epsilon.data_ptr());
-  l.reward_sum = reinterpret_cast<float*>(reward_sum.data_ptr());
-  l.perf_sum = opt_ptr<int32_t>(perf_sum);
-  l.episodes = reinterpret_cast<int32_t*>(episodes.data_ptr());
   l.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
   l.scratch = scratch.has_value() ? scratch->data_ptr() : nullptr;
   l.scratch_bytes = scratch.has_value() ? 12 * P * S * A : 0;
-  l.bad_count = opt_ptr<int32_t>(bad_count);
-  l.bad_flag = flag_ptr(bad_flag, g.dev);
-  l.seed = (uint64_t)seed;
-  l.first_frame = first_frame;
   l.n_learners = P;
-  l.window = (int32_t)window;
-  l.rule = (int32_t)rule;
-  l.path = (int32_t)path;
-  l.reset_first = reset_first ? 1 : 0;
   const DeviceGuard guard(g.dev);
   check_ok(campx_wide_shared_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
            "campx_wide_shared_launch");

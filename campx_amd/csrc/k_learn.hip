@@ -1,29 +1,22 @@
 // k_learn.hip - online tabular learners of the state-table tier: Q-learning and expected SARSA,
-// a whole run of T frames for B independent learners in ONE launch.  Environment e IS learner e:
-// it owns the table q[e][S][5], acts epsilon-greedily on it, and updates q[e][s][a] after every
-// single frame - the next frame's action is chosen from the updated table.  Nothing is shared
-// between lanes: no atomics, and the run is reproducible bit for bit (include/campx_hip.h has the
-// rule in full; tests/learner_reference.py restates it in numpy).
+// a whole run of T frames in ONE launch, reproducible bit for bit (include/campx_hip.h has the
+// rules in full; tests/learner_reference.py and tests/shared_learner_reference.py restate them in
+// numpy).  Two kernels, two schedules, each with its own account below: wide_learn_kernel, a table
+// per environment, updated after every single frame, nothing shared between lanes; and
+// wide_learn_shared_kernel, n environments feeding one table, two barriers a frame.
 //
-// The walk is k_policy.hip's - a lane per environment, chunks that start on a multiple of four
-// ABSOLUTE frames - with the policy row replaced by the lane's own, writable, row of Q-values.  No
-// trace and no per-frame stream is written: what leaves the kernel is q, three [W][B] rows per
-// window of frames (reward, hidden performance, episodes that ended; environment innermost, hence
-// coalesced) and the state at the end.
+// What they have in common is written ONCE and called by both - a change of the rule is made
+// there.  "The frame step": stage_table() (entries and perf bytes into LDS), Hyper (alpha, gamma,
+// epsilon, `keep`, the `good` test), Carried (a lane's state / done / ret), Chunks (the Philox
+// blocks of four ABSOLUTE frames), frame_action() (rule step 3), decode_entry() (step 4),
+// td_error() (steps 5 - 7's delta), WindowSums (step 8).  "Launch set-up": plan_args_ok() and
+// table_bytes() behind both plans; screen_learner(), learn_params() and pick_kernel() behind both
+// launchers.  What a kernel does with delta, and when it reads the bootstrap row, is its own.
 //
-// The chain per frame is  row -> action -> entry -> next row -> one write.  The next frame's row is
-// read BEFORE this frame's write, so it is also the bootstrap row (q[n] as it stands before the
-// update); when the frame stays in its state the one element just written is patched in registers.
-//
-// Two paths (campx_wide_learn_plan()).  Path 1: the workgroup stages the entries, the hidden
-// performance and its 256 learners' tables in LDS, the tables lane-innermost -
-// (s * 5 + a) * 256 + lane - so that the five reads of a row, and the write, go to 32 consecutive
-// banks per half wave: conflict-free.  They are copied in and out with 16-byte global accesses.
-// Path 2: each lane reads and writes its own 20-byte rows of q through L1 / L2; the entries stay
-// in LDS when they alone fit.
-//
-// Below it, the SHARED learners: n environments feed one table (wide_learn_shared_kernel has its
-// own account).
+// The walk is k_policy.hip's - a lane per environment - with the policy row replaced by a writable
+// row of Q-values.  No trace and no per-frame stream is written: what leaves a kernel is q, three
+// [W][B] rows per window of frames (reward, hidden performance, episodes that ended; environment
+// innermost, hence coalesced) and the state at the end.
 
 #include "wide_table.hip.h"
 
@@ -40,36 +33,96 @@ struct LearnParams {
   int64_t first_frame;         // absolute number of the launch's frame 0
 };
 
-// What a launch takes: campx_wide_learn_plan()'s four words.
-struct LearnPlan {
-  int32_t path;                // 1 tables and q in LDS, 2 q through L1 / L2
-  int64_t lds_bytes;
-  int32_t threads;
-  int32_t table_in_lds;        // the entries (and the perf bytes) are staged: always on path 1
+// ---------------------------------------------------------------------------------------------
+// The frame step: what wide_learn_kernel and wide_learn_shared_kernel share.  No helper holds a
+// barrier, or a return that depends on the lane.
+
+// The entries and the perf bytes as a kernel reads them, and the first free, 16-byte aligned LDS
+// address after them: a kernel lays out its own q and accumulators there.  kTableLds: thread `tid`
+// of `stride` copies its share to the dynamic LDS at `lds` (16-byte aligned), entries first, then -
+// kPerf - the perf bytes from the next 16-byte boundary; the caller's barrier makes them visible.
+struct StagedTable { const uint2* entries; const int8_t* perf_tab; unsigned char* free; };
+template <bool kTableLds, bool kPerf>
+__device__ __forceinline__ StagedTable stage_table(uint2* lds, const uint2* g_entries,
+                                                   const int8_t* g_perf, int n_entries, int tid,
+                                                   int stride) {
+  if (!kTableLds) return {g_entries, g_perf, reinterpret_cast<unsigned char*>(lds)};
+  int8_t* l_perf = reinterpret_cast<int8_t*>(lds + n_entries + (n_entries & 1));
+  for (int i = tid; i < n_entries; i += stride) lds[i] = g_entries[i];
+  if (kPerf)
+    for (int i = tid; i < n_entries; i += stride) l_perf[i] = g_perf[i];
+  return {lds, l_perf, reinterpret_cast<unsigned char*>(l_perf + (kPerf ? (n_entries + 15) & ~15 : 0))};
+}
+
+// A learner's hyper-parameters.  As constructed: those of a lane that has none (it is not `good`).
+struct Hyper {
+  float alpha = 0.0f, gamma = 0.0f, epsilon = 0.0f, keep = 0.0f;
+  bool good = false;
+  __device__ __forceinline__ void load(const float* alphas, const float* gammas, const float* epsilons,
+                                       int64_t learner) {
+    alpha = alphas[learner];
+    gamma = gammas[learner];
+    epsilon = epsilons[learner];
+    // (x - x is 0 exactly for a finite x, NaN for an infinity or a NaN)
+    good = (alpha - alpha) == 0.0f && (gamma - gamma) == 0.0f && epsilon >= 0.0f && epsilon <= 1.0f;
+    keep = 1.0f - epsilon;
+  }
 };
 
-inline int32_t plan_learn(int64_t S, int32_t has_perf, int64_t B, int64_t lds_max, int32_t path,
-                          LearnPlan* p, int64_t* plan_out) {
-  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || (has_perf & ~1) || B < 1 || B > 0xffffffffll ||
-      B * S * CAMPX_N_ACTIONS >= (1ll << 31) || lds_max < 0 || path < 0 || path > 2)
-    return CAMPX_EINVAL;
-  const int64_t n_entries = S * CAMPX_N_ACTIONS;
-  const int64_t table = up16(n_entries * (int64_t)sizeof(uint2)) + (has_perf ? up16(n_entries) : 0);
-  const int64_t want = table + kLearnThreads * n_entries * (int64_t)sizeof(float);
-  const bool fits = want <= lds_max;
-  if (path == 1 && !fits) return CAMPX_EINVAL;
-  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
-  p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
-  p->lds_bytes = p->path == 1 ? want : (p->table_in_lds ? table : 0);
-  p->threads = kLearnThreads;
-  if (plan_out) {
-    plan_out[0] = p->path;
-    plan_out[1] = p->lds_bytes;
-    plan_out[2] = p->threads;
-    plan_out[3] = p->table_in_lds;
-  }
-  return CAMPX_OK;
+// One table entry, decoded: the state it leads to, the state the next frame starts from (0 after
+// `done`), the frame's discount and its reward, None counted as 0.
+struct Entry { uint32_t now, next, done; float D, r; };
+__device__ __forceinline__ Entry decode_entry(uint2 e, int S, const float* discounts) {
+  const uint32_t now = entry_target(e.y, (uint32_t)S), done = entry_done(e.y);
+  return {now, done ? 0u : now, done, __uint_as_float(discount_bits(discounts, entry_dcode(e.y), done)),
+          real_reward(__uint_as_float(e.x))};
 }
+
+// What a lane carries from frame to frame, and from launch to launch in state / done / ret.  As
+// constructed: a new episode (`reset_first`, and a lane without an environment).
+struct Carried {
+  uint32_t now = 0, from = 0;  // the state as stored; the state the frame starts from
+  int over = 0;
+  float ret = 0.0f;
+  __device__ __forceinline__ void load(const int32_t* state, const CampxState& st, int64_t env, int S,
+                                       int32_t reset_first) {
+    if (!reset_first) {
+      now = (uint32_t)state[env];
+      now = now < (uint32_t)S ? now : 0u;      // (a state index from outside: start over)
+      over = st.done[env];
+      if (st.ret) ret = st.ret[env];
+    }
+    from = over ? 0u : now;
+  }
+  __device__ __forceinline__ void advance(const Entry& e) {
+    now = e.now;
+    from = e.next;
+    ret = (over ? 0.0f : ret) + e.r;
+    over = (int)e.done;
+  }
+  __device__ __forceinline__ void store(int32_t* state, const CampxState& st, int64_t env) const {
+    state[env] = (int32_t)now;
+    st.done[env] = (uint8_t)over;
+    if (st.ret) st.ret[env] = ret;
+  }
+};
+
+// Chunks start on a multiple of four ABSOLUTE frames, as in wide_policy_update_kernel: t0 runs from
+// -lead in steps of kLearnChunk, and frame j of a chunk takes words 2 * (j & 1), 2 * (j & 1) + 1 of
+// block j >> 1 - x[2 * j] and x[2 * j + 1] of words() - whatever first_frame is.
+struct Chunks {
+  int lead;                    // frames of the first chunk that lie before the launch's frame 0
+  uint64_t pair0;              // the first chunk's first pair of frames
+  __device__ __forceinline__ explicit Chunks(int64_t first_frame)
+      : lead((int)(first_frame & 3)), pair0((uint64_t)(first_frame - lead) >> 1) {}
+  __device__ __forceinline__ void words(const LearnParams& pp, int64_t env, int t0,
+                                        uint32_t (&x)[2 * kLearnChunk]) const {
+    const uint64_t g = pair0 + (uint64_t)((t0 + lead) >> 1);
+    philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 1u, pp.key0, pp.key1, x);
+    philox4x32_10((uint32_t)env, (uint32_t)(g + 1), (uint32_t)((g + 1) >> 32), 1u, pp.key0, pp.key1,
+                  x + 4);
+  }
+};
 
 // The greedy reduction of a row: best = q0; for a = 1 .. 4: if (q[a] > best) ... - the lowest
 // index wins ties, NaN never wins (k_plan.hip's, with the action kept).
@@ -81,6 +134,196 @@ __device__ __forceinline__ void greedy_of(const float (&r)[5], float& best, uint
     const bool better = r[a] > best;
     best = better ? r[a] : best;
     arg = better ? (uint32_t)a : arg;
+  }
+}
+
+// A frame's action: the row's greedy one, or - the frame's first word below epsilon - the one its
+// second word draws; action 4 for a learner that is not good.
+__device__ __forceinline__ uint32_t frame_action(const float (&row)[5], uint32_t x0, uint32_t x1,
+                                                 float epsilon, bool good) {
+  float best;
+  uint32_t arg;
+  greedy_of(row, best, arg);
+  const float u = (float)(x0 >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
+  const uint32_t any = ((x1 >> 8) * 5u) >> 24;                     // 0 .. 4
+  const uint32_t a = u < epsilon ? any : arg;
+  return good ? a : 4u;
+}
+
+// The TD error of a frame that met entry `e`; `old` is the element of its row that the action it
+// took picks and the kernel goes on to update, `nrow` the bootstrap row (a frame that ends the
+// episode bootstraps from nothing, its target is r).  (`old` is picked in the kernel: the same
+// selection in a helper, on a row passed by reference, becomes an indexed load before it is inlined,
+// and the row then lives in scratch.  The entry is read before the choice: a select, no branch.)
+template <bool kSarsa>
+__device__ __forceinline__ float td_error(float old, const float (&nrow)[5], const Entry& e,
+                                          float gamma, float keep, float epsilon) {
+  float b;
+  uint32_t unused;
+  greedy_of(nrow, b, unused);
+  if (kSarsa) {
+    const float m = ((((nrow[0] + nrow[1]) + nrow[2]) + nrow[3]) + nrow[4]) * 0.2f;
+    b = (keep * b) + (epsilon * m);
+  }
+  const float r = e.r, discounted = (gamma * e.D) * b;
+  const float target = e.done ? r : r + discounted;
+  return target - old;
+}
+
+// The sums of the window of frames a lane is in, and where they go: element `at` = (window, env)
+// of the three [W][B] rows of pitch B (perf_sum, and add()'s `perf`, only when kPerf).  Every lane
+// is at the same frame: the flush is uniform.  flush_short(): the last window may be short.
+template <bool kPerf>
+struct WindowSums {
+  float* reward_sum;
+  int32_t *perf_sum, *episodes;
+  int64_t at;
+  float r_sum = 0.0f;
+  int32_t p_sum = 0, n_done = 0;
+  int in_window = 0;
+  __device__ __forceinline__ void write() const {
+    reward_sum[at] = r_sum;
+    if (kPerf) perf_sum[at] = p_sum;
+    episodes[at] = n_done;
+  }
+  __device__ __forceinline__ void add(const LearnParams& pp, float r, int32_t perf, uint32_t done,
+                                      int64_t B) {
+    r_sum += r;
+    if (kPerf) p_sum += perf;
+    n_done += (int32_t)done;
+    if (++in_window == pp.window) {
+      write();
+      at += B;
+      r_sum = 0.0f, p_sum = n_done = in_window = 0;
+    }
+  }
+  __device__ __forceinline__ void flush_short() const { if (in_window) write(); }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Launch set-up: what the two plans and the two launchers share.
+
+// The LDS bytes of the staged entries and perf bytes.
+inline int64_t table_bytes(int64_t S, int32_t has_perf) {
+  const int64_t n_entries = S * CAMPX_N_ACTIONS;
+  return up16(n_entries * (int64_t)sizeof(uint2)) + (has_perf ? up16(n_entries) : 0);
+}
+
+// A plan's arguments; the `tables` <= B Q-tables of S x 5 floats are indexed with 32 bits.
+inline bool plan_args_ok(int64_t S, int32_t has_perf, int64_t B, int64_t tables, int64_t lds_max,
+                         int32_t path) {
+  return !(S < 1 || S > CAMPX_WIDE_MAX_STATES || (has_perf & ~1) || B < 1 || B > 0xffffffffll ||
+           tables * S * CAMPX_N_ACTIONS >= (1ll << 31) || lds_max < 0 || path < 0 || path > 2);
+}
+
+// What a launcher refuses before anything touches a device, for CampxLearner and CampxSharedLearner
+// alike (their common fields carry the same names); `own_ok`: the caller's checks of its own fields.
+template <typename Learner>
+int32_t screen_learner(const CampxWideSpec* s, const void* tables_dev, const CampxState& st,
+                       const Learner* l, int64_t B, int32_t T, bool own_ok) {
+  if (!s || !tables_dev || !st.pos || !st.done || !l || B <= 0 || T <= 0 || !own_ok || !l->q ||
+      !l->alpha || !l->gamma || !l->epsilon || !l->reward_sum || !l->episodes)
+    return CAMPX_EINVAL;
+  if (!aligned_to(l->q, 16) || !aligned_to(st.pos, 4) || !aligned_to(st.ret, 4) ||
+      !aligned_to(l->alpha, 4) || !aligned_to(l->gamma, 4) || !aligned_to(l->epsilon, 4) ||
+      !aligned_to(l->reward_sum, 4) || !aligned_to(l->perf_sum, 4) || !aligned_to(l->episodes, 4) ||
+      !aligned_to(l->bad_count, 4) || !aligned_to(l->bad_flag, 4))
+    return CAMPX_EINVAL;
+  // (the environment is one 32-bit word of the Philox counter; frames count up to 2^63 - 1)
+  if (B > 0xffffffffll || l->first_frame < 0 || l->first_frame > INT64_MAX - T || l->window < 1 ||
+      (l->rule != CAMPX_LEARN_Q && l->rule != CAMPX_LEARN_EXPECTED_SARSA) || l->path < 0 || l->path > 2)
+    return CAMPX_EINVAL;
+  const int32_t v = wide_validate_plain(s);
+  if (v != CAMPX_OK) return v;
+  if (l->perf_sum && !s->has_perf) return CAMPX_EINVAL;
+  return CAMPX_OK;
+}
+
+template <typename Learner>
+LearnParams learn_params(const CampxWideSpec& s, const Learner& l) {
+  LearnParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.n_states = s.n_states;
+  pp.window = l.window;
+  wide_discounts(s, pp.discounts);
+  pp.key0 = (uint32_t)l.seed;
+  pp.key1 = (uint32_t)(l.seed >> 32);
+  pp.first_frame = l.first_frame;
+  return pp;
+}
+
+// The twelve instances of a kernel template <kQLds, kTableLds, kPerf, kSarsa>, at
+// [where q and the table are][kPerf][kSarsa]: 0 both read through the caches, 1 the table in LDS,
+// 2 q and the table in LDS.  (q in LDS without the table does not exist.)
+#define CAMPX_LEARN_INSTANCES(K)                                                  \
+  {{{K<0, 0, 0, 0>, K<0, 0, 0, 1>}, {K<0, 0, 1, 0>, K<0, 0, 1, 1>}},              \
+   {{K<0, 1, 0, 0>, K<0, 1, 0, 1>}, {K<0, 1, 1, 0>, K<0, 1, 1, 1>}},              \
+   {{K<1, 1, 0, 0>, K<1, 1, 0, 1>}, {K<1, 1, 1, 0>, K<1, 1, 1, 1>}}}
+
+template <typename Kernel, typename Plan, typename Learner>
+Kernel pick_kernel(const Kernel (&instances)[3][2][2], const Plan& plan, const Learner& l) {
+  return instances[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)][l.perf_sum != nullptr]
+                  [l.rule == CAMPX_LEARN_EXPECTED_SARSA];
+}
+
+// ---------------------------------------------------------------------------------------------
+// A table per environment.  The chain per frame is  row -> action -> entry -> next row -> one
+// write.  The next frame's row is read BEFORE this frame's write, so it is also the bootstrap row
+// (q[n] as it stands before the update); when the frame stays in its state the one element just
+// written is patched in registers.
+//
+// Two paths (campx_wide_learn_plan()).  Path 1: the workgroup stages the entries, the hidden
+// performance and its 256 learners' tables in LDS, the tables lane-innermost -
+// (s * 5 + a) * 256 + lane - so that the five reads of a row, and the write, go to 32 consecutive
+// banks per half wave: conflict-free.  They are copied in and out with 16-byte global accesses.
+// Path 2: each lane reads and writes its own 20-byte rows of q through L1 / L2; the entries stay
+// in LDS when they alone fit.
+
+// campx_wide_learn_plan()'s four words, in their order.  path: 1 tables and q in LDS, 2 q through
+// L1 / L2; table_in_lds: the entries (and the perf bytes) are staged, always on path 1.
+struct LearnPlan { int64_t path, lds_bytes, threads, table_in_lds; };
+
+inline int32_t plan_learn(int64_t S, int32_t has_perf, int64_t B, int64_t lds_max, int32_t path,
+                          LearnPlan* p, int64_t* plan_out) {
+  if (!plan_args_ok(S, has_perf, B, B, lds_max, path)) return CAMPX_EINVAL;
+  const int64_t table = table_bytes(S, has_perf);
+  const int64_t want = table + kLearnThreads * S * CAMPX_N_ACTIONS * (int64_t)sizeof(float);
+  const bool fits = want <= lds_max;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
+  p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
+  p->lds_bytes = p->path == 1 ? want : (p->table_in_lds ? table : 0);
+  p->threads = kLearnThreads;
+  if (plan_out) memcpy(plan_out, p, sizeof(*p));
+  return CAMPX_OK;
+}
+
+// Path 1's tables between q - element i of the workgroup's piece is learner i / n_entries, entry
+// i % n_entries - and LDS (kIn: into it, else back out): four elements and one 16-byte global access
+// at a time, one division per group.
+template <bool kIn>
+__device__ __forceinline__ void move_q(float* l_q, float* q_block, int n_q, int n_entries, int lane) {
+  const int whole = n_q & ~3;
+  for (int i = lane * 4; i < whole; i += kLearnThreads * 4) {
+    u32x4* piece = reinterpret_cast<u32x4*>(q_block + i);
+    u32x4 v = kIn ? *piece : u32x4{};
+    int who = i / n_entries, k = i - who * n_entries;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float& cell = l_q[k * kLearnThreads + who];
+      if (kIn) cell = __uint_as_float(v[j]);
+      else v[j] = __float_as_uint(cell);
+      if (++k == n_entries) {
+        k = 0;
+        ++who;
+      }
+    }
+    if (!kIn) *piece = v;
+  }
+  for (int i = whole + lane; i < n_q; i += kLearnThreads) {
+    float& cell = l_q[(i % n_entries) * kLearnThreads + i / n_entries];
+    if (kIn) cell = q_block[i];
+    else q_block[i] = cell;
   }
 }
 
@@ -100,197 +343,85 @@ __global__ __launch_bounds__(kLearnThreads) void wide_learn_kernel(
   const int lane = threadIdx.x;
   const int64_t env_lo = (int64_t)blockIdx.x * kLearnThreads;
   const int64_t env = env_lo + lane;
-  const uint2* entries = g_entries;
-  const int8_t* perf_tab = g_perf;
-  float* l_q = nullptr;
   // this workgroup's learners and their piece of q: contiguous, 16-byte aligned (q is, and a
   // workgroup's piece starts a multiple of 256 * 20 bytes in)
   const int n_lanes = (int)(B - env_lo < kLearnThreads ? B - env_lo : kLearnThreads);
   const int n_q = n_lanes * n_entries;                 // floats: B * S * 5 < 2^31
   float* q_block = q + env_lo * n_entries;
-  if (kTableLds) {
-    uint2* l_entries = lds_tables;
-    int8_t* l_perf = reinterpret_cast<int8_t*>(l_entries + n_entries + (n_entries & 1));   // 16-byte aligned
-    for (int i = lane; i < n_entries; i += kLearnThreads) l_entries[i] = g_entries[i];
-    if (kPerf)
-      for (int i = lane; i < n_entries; i += kLearnThreads) l_perf[i] = g_perf[i];
-    entries = l_entries;
-    perf_tab = l_perf;
-    if (kQLds) {
-      l_q = reinterpret_cast<float*>(l_perf + (kPerf ? (n_entries + 15) & ~15 : 0));
-      // element i of the piece is learner i / n_entries, entry i % n_entries: four at a time,
-      // one division per group
-      const int whole = n_q & ~3;
-      for (int i = lane * 4; i < whole; i += kLearnThreads * 4) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(q_block + i);
-        int who = i / n_entries, k = i - who * n_entries;
-        const float w[4] = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z),
-                            __uint_as_float(v.w)};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          l_q[k * kLearnThreads + who] = w[j];
-          if (++k == n_entries) {
-            k = 0;
-            ++who;
-          }
-        }
-      }
-      for (int i = whole + lane; i < n_q; i += kLearnThreads)
-        l_q[(i % n_entries) * kLearnThreads + i / n_entries] = q_block[i];
-    }
-  }
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, lane, kLearnThreads);
+  float* l_q = reinterpret_cast<float*>(tab.free);
+  if (kQLds) move_q<true>(l_q, q_block, n_q, n_entries, lane);
   if (lane < 16) discounts[lane] = pp.discounts[lane];
   __syncthreads();
 
   if (env < B) {
-    const float alpha = alphas[env], gamma = gammas[env], epsilon = epsilons[env];
-    // (x - x is 0 exactly for a finite x, NaN for an infinity or a NaN)
-    const bool good = (alpha - alpha) == 0.0f && (gamma - gamma) == 0.0f && epsilon >= 0.0f &&
-                      epsilon <= 1.0f;
-    const float keep = 1.0f - epsilon;
+    Hyper h;
+    h.load(alphas, gammas, epsilons, env);
     // the lane's table: row s is five floats at own[(s * 5 + a) * step]
     float* own = kQLds ? l_q + lane : q + env * n_entries;
     constexpr int step = kQLds ? kLearnThreads : 1;
-    uint32_t now = 0;
-    int over = 0;
-    float ret = 0.0f;
-    if (!reset_first) {
-      now = (uint32_t)state[env];
-      now = now < (uint32_t)S ? now : 0u;      // (a state index from outside: start over)
-      over = st.done[env];
-      if (st.ret) ret = st.ret[env];
-    }
-    uint32_t from = over ? 0u : now;
+    Carried c;
+    c.load(state, st, env, S, reset_first);
     float row[5];
 #pragma unroll
-    for (int a = 0; a < 5; ++a) row[a] = own[(from * CAMPX_N_ACTIONS + a) * step];
-    float r_sum = 0.0f;
-    int32_t p_sum = 0, n_done = 0;
-    int in_window = 0;
-    int64_t at = env;                          // element (window, env) of the [W][B] sums
-    // Chunks start on a multiple of four ABSOLUTE frames, as in wide_policy_update_kernel: frame j
-    // of a chunk takes words 2 * (j & 1), 2 * (j & 1) + 1 of block j >> 1 whatever first_frame is.
-    const int lead = (int)(pp.first_frame & 3);
-    const uint64_t pair0 = (uint64_t)(pp.first_frame - lead) >> 1;
-    for (int t0 = -lead; t0 < T; t0 += kLearnChunk) {
+    for (int a = 0; a < 5; ++a) row[a] = own[(c.from * CAMPX_N_ACTIONS + a) * step];
+    WindowSums<kPerf> sums{reward_sum, perf_sum, episodes, env};
+    const Chunks chunks(pp.first_frame);
+    for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
       uint32_t x[2 * kLearnChunk];
-      const uint64_t g = pair0 + (uint64_t)((t0 + lead) >> 1);
-      philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 1u, pp.key0, pp.key1, x);
-      philox4x32_10((uint32_t)env, (uint32_t)(g + 1), (uint32_t)((g + 1) >> 32), 1u, pp.key0, pp.key1,
-                    x + 4);
+      chunks.words(pp, env, t0, x);
 #pragma unroll
       for (int j = 0; j < kLearnChunk; ++j) {
         if (t0 + j >= 0 && t0 + j < T) {
-          float best;
-          uint32_t arg;
-          greedy_of(row, best, arg);
-          const float u = (float)(x[2 * j] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
-          const uint32_t any = ((x[2 * j + 1] >> 8) * 5u) >> 24;                 // 0 .. 4
-          uint32_t a = u < epsilon ? any : arg;
-          a = good ? a : 4u;
-          const uint32_t idx = from * CAMPX_N_ACTIONS + a;
-          const uint2 e = entries[idx];
-          now = entry_target(e.y, (uint32_t)S);
-          const uint32_t done = entry_done(e.y);
-          const float D = __uint_as_float(discount_bits(discounts, entry_dcode(e.y), done));
-          const float r = real_reward(__uint_as_float(e.x));
-          const uint32_t next = done ? 0u : now;
-          // the next frame's row, as it stands BEFORE this frame's update: the bootstrap row too
-          // (a frame that ends the episode bootstraps from nothing, its target is r)
+          const uint32_t a = frame_action(row, x[2 * j], x[2 * j + 1], h.epsilon, h.good);
+          const uint32_t idx = c.from * CAMPX_N_ACTIONS + a;
+          const Entry e = decode_entry(tab.entries[idx], S, discounts);
+          // the next frame's row, as it stands BEFORE this frame's update: the bootstrap row too.
+          // It is read for a bad learner as well: it is the row its next frame acts from.
           float nrow[5];
 #pragma unroll
-          for (int k = 0; k < 5; ++k) nrow[k] = own[(next * CAMPX_N_ACTIONS + k) * step];
-          float b;
-          uint32_t unused;
-          greedy_of(nrow, b, unused);
-          if (kSarsa) {
-            const float m = ((((nrow[0] + nrow[1]) + nrow[2]) + nrow[3]) + nrow[4]) * 0.2f;
-            b = (keep * b) + (epsilon * m);
-          }
-          const float target = done ? r : r + (gamma * D) * b;
+          for (int k = 0; k < 5; ++k) nrow[k] = own[(e.next * CAMPX_N_ACTIONS + k) * step];
           float old = row[0];
 #pragma unroll
           for (int k = 1; k < 5; ++k) old = a == (uint32_t)k ? row[k] : old;
-          const float delta = target - old;
-          const float fresh = old + alpha * delta;
-          if (good) {
+          const float delta = td_error<kSarsa>(old, nrow, e, h.gamma, h.keep, h.epsilon);
+          const float fresh = old + h.alpha * delta;
+          if (h.good) {
             own[idx * step] = fresh;
-            if (next == from) {
+            if (e.next == c.from) {
 #pragma unroll
               for (int k = 0; k < 5; ++k) nrow[k] = a == (uint32_t)k ? fresh : nrow[k];
             }
           }
 #pragma unroll
           for (int k = 0; k < 5; ++k) row[k] = nrow[k];
-          from = next;
-          r_sum += r;
-          if (kPerf) p_sum += perf_tab[idx];
-          n_done += (int32_t)done;
-          ret = (over ? 0.0f : ret) + r;
-          over = (int)done;
-          if (++in_window == pp.window) {      // (uniform: every lane is at the same frame)
-            reward_sum[at] = r_sum;
-            if (kPerf) perf_sum[at] = p_sum;
-            episodes[at] = n_done;
-            at += B;
-            r_sum = 0.0f;
-            p_sum = 0;
-            n_done = 0;
-            in_window = 0;
-          }
+          c.advance(e);
+          sums.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
         }
       }
     }
-    if (in_window) {                           // the last window is short
-      reward_sum[at] = r_sum;
-      if (kPerf) perf_sum[at] = p_sum;
-      episodes[at] = n_done;
-    }
-    state[env] = (int32_t)now;
-    st.done[env] = (uint8_t)over;
-    if (st.ret) st.ret[env] = ret;
-    report_bad(bad_count, bad_flag, good ? 0 : 1);     // bad LEARNERS, once per launch
+    sums.flush_short();
+    c.store(state, st, env);
+    report_bad(bad_count, bad_flag, h.good ? 0 : 1);     // bad LEARNERS, once per launch
   }
 
   if (kQLds) {
     __syncthreads();
-    const int whole = n_q & ~3;
-    for (int i = lane * 4; i < whole; i += kLearnThreads * 4) {
-      int who = i / n_entries, k = i - who * n_entries;
-      float w[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        w[j] = l_q[k * kLearnThreads + who];
-        if (++k == n_entries) {
-          k = 0;
-          ++who;
-        }
-      }
-      *reinterpret_cast<u32x4*>(q_block + i) = u32x4{__float_as_uint(w[0]), __float_as_uint(w[1]),
-                                                     __float_as_uint(w[2]), __float_as_uint(w[3])};
-    }
-    for (int i = whole + lane; i < n_q; i += kLearnThreads)
-      q_block[i] = l_q[(i % n_entries) * kLearnThreads + i / n_entries];
+    move_q<false>(l_q, q_block, n_q, n_entries, lane);
   }
 }
 
-// The twelve instances, at [where q and the table are][kPerf][kSarsa]: 0 both read through the
-// caches, 1 the table in LDS, 2 q and the table in LDS.  (q in LDS without the table does not exist.)
 using LearnKernel = decltype(&wide_learn_kernel<false, false, false, false>);
-static const LearnKernel kLearnKernels[3][2][2] = {
-    {{wide_learn_kernel<false, false, false, false>, wide_learn_kernel<false, false, false, true>},
-     {wide_learn_kernel<false, false, true, false>, wide_learn_kernel<false, false, true, true>}},
-    {{wide_learn_kernel<false, true, false, false>, wide_learn_kernel<false, true, false, true>},
-     {wide_learn_kernel<false, true, true, false>, wide_learn_kernel<false, true, true, true>}},
-    {{wide_learn_kernel<true, true, false, false>, wide_learn_kernel<true, true, false, true>},
-     {wide_learn_kernel<true, true, true, false>, wide_learn_kernel<true, true, true, true>}}};
+static const LearnKernel kLearnKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_kernel);
 
 // ---------------------------------------------------------------------------------------------
 // Shared learners: P tables, each fed by the n = B / P consecutive environments of its block
 // (include/campx_hip.h, "Shared online learners", has the rule; tests/shared_learner_reference.py
 // restates it in numpy).  Within a frame every environment of a learner reads the table as the
-// frame found it; the TD errors are quantised to 64-bit fixed point and added per (state, action)
-// as INTEGERS, and the table moves once per visited bin: no order of arrival changes a bit.
+// frame found it; the TD errors - td_error(), the per-environment learners' - are quantised to
+// 64-bit fixed point and added per (state, action) as INTEGERS, and the table moves once per
+// visited bin: no order of arrival changes a bit.
 //
 // A workgroup holds G whole learners, G * n threads, thread tid being environment
 // blockIdx.x * G * n + tid.  A frame is
@@ -315,24 +446,19 @@ constexpr double kSharedScale = 4294967296.0;          // 2^32
 constexpr double kSharedLimit = 4503599627370496.0;    // 2^52
 constexpr long long kSharedLimitQ = 1ll << 52;
 
-struct SharedPlan {
-  int32_t path;                // 1 tables, q and accumulators in LDS, 2 q and accumulators global
-  int32_t learners;            // G: whole learners of a workgroup
-  int32_t threads;             // G * n
-  int64_t lds_bytes;
-  int32_t table_in_lds;
-  int32_t copies;              // accumulators per bin: 1, the adds are not privatised
-};
+// campx_wide_shared_plan()'s six words, in their order.  path: 1 tables, q and accumulators in LDS,
+// 2 q and accumulators global; learners: G, whole learners of a workgroup; threads: G * n; copies:
+// accumulators per bin - 1, the adds are not privatised.
+struct SharedPlan { int64_t path, learners, threads, lds_bytes, table_in_lds, copies; };
 
 inline int32_t plan_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
                            int32_t path, SharedPlan* p, int64_t* plan_out) {
-  if (S < 1 || S > CAMPX_WIDE_MAX_STATES || (has_perf & ~1) || B < 1 || B > 0xffffffffll || P < 1 ||
-      P > B || B % P != 0 || B / P > kSharedMaxThreads || P * S * CAMPX_N_ACTIONS >= (1ll << 31) ||
-      lds_max < 0 || path < 0 || path > 2)
+  if (P < 1 || P > B || !plan_args_ok(S, has_perf, B, P, lds_max, path) || B % P != 0 ||
+      B / P > kSharedMaxThreads)
     return CAMPX_EINVAL;
-  const int64_t n = B / P, n_entries = S * CAMPX_N_ACTIONS;
-  const int64_t table = up16(n_entries * (int64_t)sizeof(uint2)) + (has_perf ? up16(n_entries) : 0);
-  const int64_t per = n_entries * kSharedBytesPerEntry;
+  const int64_t n = B / P;
+  const int64_t table = table_bytes(S, has_perf);
+  const int64_t per = S * CAMPX_N_ACTIONS * kSharedBytesPerEntry;
   int64_t most = n <= kSharedPack ? kSharedPack / n : 1;       // what a workgroup would hold
   if (most > P) most = P;
   const int64_t room = lds_max >= table ? (lds_max - table) / per : 0;
@@ -342,19 +468,12 @@ inline int32_t plan_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, in
   // a few lanes by its LDS leaves most of a wave idle at every frame.
   const bool pays = held >= 1 && (held == most || held * n >= 64);
   p->path = (path == 1 || (path == 0 && pays)) ? 1 : 2;
-  p->learners = (int32_t)(p->path == 1 ? held : most);
-  p->threads = (int32_t)(p->learners * n);
+  p->learners = p->path == 1 ? held : most;
+  p->threads = p->learners * n;
   p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
   p->lds_bytes = p->path == 1 ? table + p->learners * per : (p->table_in_lds ? table : 0);
   p->copies = 1;
-  if (plan_out) {
-    plan_out[0] = p->path;
-    plan_out[1] = p->learners;
-    plan_out[2] = p->threads;
-    plan_out[3] = p->lds_bytes;
-    plan_out[4] = p->table_in_lds;
-    plan_out[5] = p->copies;
-  }
+  if (plan_out) memcpy(plan_out, p, sizeof(*p));
   return CAMPX_OK;
 }
 
@@ -381,116 +500,65 @@ __global__ __launch_bounds__(kSharedMaxThreads) void wide_learn_shared_kernel(
   const int who = tid / n;                                   // learner of the workgroup
   const bool active = who < n_here;                          // (an absent lane: last workgroup only)
   const int64_t m = first_learner + who;
-  const uint2* entries = g_entries;
-  const int8_t* perf_tab = g_perf;
   const int n_q = n_here * n_entries;                        // floats: P * S * 5 < 2^31
   float* q_block = q + first_learner * n_entries;
   float* tables = q_block;                                   // [learner][s][a], wherever they are
   long long* sums = kQLds ? nullptr : acc_sum + first_learner * n_entries;
   uint32_t* counts = kQLds ? nullptr : acc_count + first_learner * n_entries;
-  if (kTableLds) {
-    uint2* l_entries = lds_tables;
-    int8_t* l_perf = reinterpret_cast<int8_t*>(l_entries + n_entries + (n_entries & 1));   // 16-byte aligned
-    for (int i = tid; i < n_entries; i += threads) l_entries[i] = g_entries[i];
-    if (kPerf)
-      for (int i = tid; i < n_entries; i += threads) l_perf[i] = g_perf[i];
-    entries = l_entries;
-    perf_tab = l_perf;
-    if (kQLds) {
-      // [sums G x entries x 8][tables G x entries x 4][counts G x entries x 4], 16-byte aligned
-      sums = reinterpret_cast<long long*>(l_perf + (kPerf ? (n_entries + 15) & ~15 : 0));
-      float* l_q = reinterpret_cast<float*>(sums + (int64_t)G * n_entries);
-      counts = reinterpret_cast<uint32_t*>(l_q + (int64_t)G * n_entries);
-      for (int i = tid; i < n_q; i += threads) {
-        l_q[i] = q_block[i];
-        sums[i] = 0;
-        counts[i] = 0u;
-      }
-      tables = l_q;
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, tid, threads);
+  if (kQLds) {
+    // [sums G x entries x 8][tables G x entries x 4][counts G x entries x 4], 16-byte aligned
+    sums = reinterpret_cast<long long*>(tab.free);
+    float* l_q = reinterpret_cast<float*>(sums + (int64_t)G * n_entries);
+    counts = reinterpret_cast<uint32_t*>(l_q + (int64_t)G * n_entries);
+    for (int i = tid; i < n_q; i += threads) {
+      l_q[i] = q_block[i];
+      sums[i] = 0;
+      counts[i] = 0u;
     }
+    tables = l_q;
   }
   if (tid < 16) discounts[tid] = pp.discounts[tid];
   if (tid < kSharedPack) l_clamped[tid] = 0ull;
   __syncthreads();
 
-  // What stays in registers for the run.  An absent lane keeps these values and does nothing
-  // between the barriers below.
-  float alpha = 0.0f, gamma = 0.0f, epsilon = 0.0f, keep = 0.0f;
-  bool good = false;
-  uint32_t now = 0, from = 0;
-  int over = 0;
-  float ret = 0.0f, r_sum = 0.0f;
-  int32_t p_sum = 0, n_done = 0;
-  int in_window = 0;
-  int64_t at = env;                            // element (window, env) of the [W][B] sums
+  // What stays in registers for the run.  An absent lane keeps these values - no learner, a new
+  // episode, empty sums - and does nothing between the barriers below.
+  Hyper h;
+  Carried c;
+  WindowSums<kPerf> win{reward_sum, perf_sum, episodes, env};
   unsigned long long n_clamped = 0ull;
   const int own = who * n_entries;             // the learner's table, sums and counts start here
   if (active) {
-    alpha = alphas[m];
-    gamma = gammas[m];
-    epsilon = epsilons[m];
-    // (x - x is 0 exactly for a finite x, NaN for an infinity or a NaN)
-    good = (alpha - alpha) == 0.0f && (gamma - gamma) == 0.0f && epsilon >= 0.0f && epsilon <= 1.0f;
-    keep = 1.0f - epsilon;
-    if (!reset_first) {
-      now = (uint32_t)state[env];
-      now = now < (uint32_t)S ? now : 0u;      // (a state index from outside: start over)
-      over = st.done[env];
-      if (st.ret) ret = st.ret[env];
-    }
-    from = over ? 0u : now;
+    h.load(alphas, gammas, epsilons, m);
+    c.load(state, st, env, S, reset_first);
   }
-  // Chunks start on a multiple of four ABSOLUTE frames, as in wide_learn_kernel.  t0, lead and T
-  // are the same in every lane of the grid.
-  const int lead = (int)(pp.first_frame & 3);
-  const uint64_t pair0 = (uint64_t)(pp.first_frame - lead) >> 1;
-  for (int t0 = -lead; t0 < T; t0 += kLearnChunk) {
+  const Chunks chunks(pp.first_frame);
+  for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
     uint32_t x[2 * kLearnChunk];
-    if (active) {
-      const uint64_t g = pair0 + (uint64_t)((t0 + lead) >> 1);
-      philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 1u, pp.key0, pp.key1, x);
-      philox4x32_10((uint32_t)env, (uint32_t)(g + 1), (uint32_t)((g + 1) >> 32), 1u, pp.key0, pp.key1,
-                    x + 4);
-    }
+    if (active) chunks.words(pp, env, t0, x);
 #pragma unroll
     for (int j = 0; j < kLearnChunk; ++j) {
       if (t0 + j < 0 || t0 + j >= T) continue;               // (uniform: kernel arguments alone)
       int bin = 0;                                           // own + s * 5 + a
       bool owner = false;
       if (active) {                                          // ---- (A)
-        float row[5], nrow[5];
+        float row[5];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) row[k] = tables[own + from * CAMPX_N_ACTIONS + k];
-        float best;
-        uint32_t arg;
-        greedy_of(row, best, arg);
-        const float u = (float)(x[2 * j] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
-        const uint32_t any = ((x[2 * j + 1] >> 8) * 5u) >> 24;                 // 0 .. 4
-        uint32_t a = u < epsilon ? any : arg;
-        a = good ? a : 4u;
-        const uint32_t idx = from * CAMPX_N_ACTIONS + a;
-        const uint2 e = entries[idx];
-        now = entry_target(e.y, (uint32_t)S);
-        const uint32_t done = entry_done(e.y);
-        const float D = __uint_as_float(discount_bits(discounts, entry_dcode(e.y), done));
-        const float r = real_reward(__uint_as_float(e.x));
-        const uint32_t next = done ? 0u : now;
-        if (good) {
+        for (int k = 0; k < 5; ++k) row[k] = tables[own + c.from * CAMPX_N_ACTIONS + k];
+        const uint32_t a = frame_action(row, x[2 * j], x[2 * j + 1], h.epsilon, h.good);
+        const uint32_t idx = c.from * CAMPX_N_ACTIONS + a;
+        const Entry e = decode_entry(tab.entries[idx], S, discounts);
+        if (h.good) {
           // the bootstrap row: the table as the frame found it, for every lane of the learner
+          float nrow[5];
 #pragma unroll
-          for (int k = 0; k < 5; ++k) nrow[k] = tables[own + next * CAMPX_N_ACTIONS + k];
-          float b;
-          uint32_t unused;
-          greedy_of(nrow, b, unused);
-          if (kSarsa) {
-            const float mean = ((((nrow[0] + nrow[1]) + nrow[2]) + nrow[3]) + nrow[4]) * 0.2f;
-            b = (keep * b) + (epsilon * mean);
-          }
-          const float target = done ? r : r + (gamma * D) * b;
+          for (int k = 0; k < 5; ++k) nrow[k] = tables[own + e.next * CAMPX_N_ACTIONS + k];
           float old = row[0];
 #pragma unroll
           for (int k = 1; k < 5; ++k) old = a == (uint32_t)k ? row[k] : old;
-          const float delta = target - old;
+          const float delta = td_error<kSarsa>(old, nrow, e, h.gamma, h.keep, h.epsilon);
           const double d = (double)delta * kSharedScale;
           long long z;
           if (!(fabs(d) <= kSharedLimit)) {                  // NaN, +-Inf, past the limit
@@ -504,49 +572,29 @@ __global__ __launch_bounds__(kSharedMaxThreads) void wide_learn_shared_kernel(
                                          __HIP_MEMORY_SCOPE_WORKGROUP) == 0u;
           __hip_atomic_fetch_add(&sums[bin], z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        from = next;
-        r_sum += r;
-        if (kPerf) p_sum += perf_tab[idx];
-        n_done += (int32_t)done;
-        ret = (over ? 0.0f : ret) + r;
-        over = (int)done;
-        if (++in_window == pp.window) {
-          reward_sum[at] = r_sum;
-          if (kPerf) perf_sum[at] = p_sum;
-          episodes[at] = n_done;
-          at += B;
-          r_sum = 0.0f;
-          p_sum = 0;
-          n_done = 0;
-          in_window = 0;
-        }
+        c.advance(e);
+        win.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
       }
       __syncthreads();
       if (owner) {                                           // ---- (B)
         const long long Z = __hip_atomic_exchange(&sums[bin], 0ll, __ATOMIC_RELAXED,
                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint32_t c = __hip_atomic_exchange(&counts[bin], 0u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_WORKGROUP);
-        const double g = (double)Z / (double)c;
+        const uint32_t visits = __hip_atomic_exchange(&counts[bin], 0u, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_WORKGROUP);
+        const double g = (double)Z / (double)visits;
         const float mean = (float)(g * (1.0 / kSharedScale));
-        const float step = alpha * mean;
+        const float step = h.alpha * mean;
         tables[bin] = tables[bin] + step;
       }
       __syncthreads();
     }
   }
   if (active) {
-    if (in_window) {                           // the last window is short
-      reward_sum[at] = r_sum;
-      if (kPerf) perf_sum[at] = p_sum;
-      episodes[at] = n_done;
-    }
-    state[env] = (int32_t)now;
-    st.done[env] = (uint8_t)over;
-    if (st.ret) st.ret[env] = ret;
+    win.flush_short();
+    c.store(state, st, env);
     if (n_clamped)
       __hip_atomic_fetch_add(&l_clamped[who], n_clamped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (tid == who * n) report_bad(bad_count, bad_flag, good ? 0 : 1);     // bad LEARNERS, once
+    if (tid == who * n) report_bad(bad_count, bad_flag, h.good ? 0 : 1);     // bad LEARNERS, once
   }
   __syncthreads();
   if (active && tid == who * n) clamped[m] = (long long)l_clamped[who];
@@ -555,13 +603,7 @@ __global__ __launch_bounds__(kSharedMaxThreads) void wide_learn_shared_kernel(
 }
 
 using SharedKernel = decltype(&wide_learn_shared_kernel<false, false, false, false>);
-static const SharedKernel kSharedKernels[3][2][2] = {
-    {{wide_learn_shared_kernel<false, false, false, false>, wide_learn_shared_kernel<false, false, false, true>},
-     {wide_learn_shared_kernel<false, false, true, false>, wide_learn_shared_kernel<false, false, true, true>}},
-    {{wide_learn_shared_kernel<false, true, false, false>, wide_learn_shared_kernel<false, true, false, true>},
-     {wide_learn_shared_kernel<false, true, true, false>, wide_learn_shared_kernel<false, true, true, true>}},
-    {{wide_learn_shared_kernel<true, true, false, false>, wide_learn_shared_kernel<true, true, false, true>},
-     {wide_learn_shared_kernel<true, true, true, false>, wide_learn_shared_kernel<true, true, true, true>}}};
+static const SharedKernel kSharedKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_shared_kernel);
 
 }  // namespace campx_impl
 
@@ -578,44 +620,21 @@ int32_t campx_wide_learn_plan(int64_t n_states, int32_t has_perf, int64_t B, int
 
 int32_t campx_wide_learn_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
                                 const CampxLearner* l, int64_t B, int32_t T, void* stream) {
-  if (!s || !tables_dev || !st.pos || !st.done || !l || B <= 0 || T <= 0) return CAMPX_EINVAL;
-  if (!l->q || !l->alpha || !l->gamma || !l->epsilon || !l->reward_sum || !l->episodes)
-    return CAMPX_EINVAL;
-  if (!aligned_to(l->q, 16) || !aligned_to(st.pos, 4) || !aligned_to(st.ret, 4) ||
-      !aligned_to(l->alpha, 4) || !aligned_to(l->gamma, 4) || !aligned_to(l->epsilon, 4) ||
-      !aligned_to(l->reward_sum, 4) || !aligned_to(l->perf_sum, 4) || !aligned_to(l->episodes, 4) ||
-      !aligned_to(l->bad_count, 4) || !aligned_to(l->bad_flag, 4))
-    return CAMPX_EINVAL;
-  // (the environment is one 32-bit word of the Philox counter; frames count up to 2^63 - 1)
-  if (B > 0xffffffffll || l->first_frame < 0 || l->first_frame > INT64_MAX - T) return CAMPX_EINVAL;
-  if (l->window < 1 || (l->rule != CAMPX_LEARN_Q && l->rule != CAMPX_LEARN_EXPECTED_SARSA) ||
-      l->path < 0 || l->path > 2)
-    return CAMPX_EINVAL;
-  const int32_t v = wide_validate_plain(s);
-  if (v != CAMPX_OK) return v;
-  if (l->perf_sum && !s->has_perf) return CAMPX_EINVAL;
+  const int32_t screened = screen_learner(s, tables_dev, st, l, B, T, true);
+  if (screened != CAMPX_OK) return screened;
   LearnPlan plan;      // (refuses B * n_states * 5 >= 2^31, and path 1 for what does not fit)
   const int32_t planned = plan_learn(s->n_states, l->perf_sum ? 1 : 0, B, knob(K_WIDE_LDS_MAX),
                                      l->path, &plan, nullptr);
   if (planned != CAMPX_OK) return planned;
   const WideTables t = wide_tables(*s, tables_dev);
-  LearnParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.n_states = s->n_states;
-  pp.window = l->window;
-  wide_discounts(*s, pp.discounts);
-  pp.key0 = (uint32_t)l->seed;
-  pp.key1 = (uint32_t)(l->seed >> 32);
-  pp.first_frame = l->first_frame;
   const size_t lds = (size_t)plan.lds_bytes;
-  const LearnKernel kernel = kLearnKernels[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)]
-                                          [l->perf_sum != nullptr][l->rule == CAMPX_LEARN_EXPECTED_SARSA];
+  const LearnKernel kernel = pick_kernel(kLearnKernels, plan, *l);
   CAMPX_ALLOW_LDS(kernel, lds);
   hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kLearnThreads - 1) / kLearnThreads)),
-                     dim3(kLearnThreads), lds, static_cast<hipStream_t>(stream), pp, t.entries, t.perf,
-                     l->q, l->alpha, l->gamma, l->epsilon, reinterpret_cast<int32_t*>(st.pos), st,
-                     l->reward_sum, l->perf_sum, l->episodes, l->bad_count, l->bad_flag, B, T,
-                     l->reset_first);
+                     dim3(kLearnThreads), lds, static_cast<hipStream_t>(stream), learn_params(*s, *l),
+                     t.entries, t.perf, l->q, l->alpha, l->gamma, l->epsilon,
+                     reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
+                     l->bad_count, l->bad_flag, B, T, l->reset_first);
   return launch_status();
 }
 
@@ -627,7 +646,7 @@ int32_t campx_wide_shared_plan(int64_t n_states, int32_t has_perf, int64_t B, in
 }
 
 int64_t campx_wide_shared_scratch_bytes(int64_t n_states, int64_t P) {
-  if (n_states < 1 || n_states > CAMPX_WIDE_MAX_STATES || P < 1 ||
+  if (n_states < 1 || n_states > CAMPX_WIDE_MAX_STATES || P < 1 || P > 0xffffffffll ||
       P * n_states * CAMPX_N_ACTIONS >= (1ll << 31))
     return 0;
   return P * n_states * CAMPX_N_ACTIONS * 12;
@@ -635,22 +654,10 @@ int64_t campx_wide_shared_scratch_bytes(int64_t n_states, int64_t P) {
 
 int32_t campx_wide_shared_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
                                  const CampxSharedLearner* l, int64_t B, int32_t T, void* stream) {
-  if (!s || !tables_dev || !st.pos || !st.done || !l || B <= 0 || T <= 0) return CAMPX_EINVAL;
-  if (!l->q || !l->alpha || !l->gamma || !l->epsilon || !l->reward_sum || !l->episodes || !l->clamped)
-    return CAMPX_EINVAL;
-  if (!aligned_to(l->q, 16) || !aligned_to(st.pos, 4) || !aligned_to(st.ret, 4) ||
-      !aligned_to(l->alpha, 4) || !aligned_to(l->gamma, 4) || !aligned_to(l->epsilon, 4) ||
-      !aligned_to(l->reward_sum, 4) || !aligned_to(l->perf_sum, 4) || !aligned_to(l->episodes, 4) ||
-      !aligned_to(l->clamped, 8) || !aligned_to(l->scratch, 8) || !aligned_to(l->bad_count, 4) ||
-      !aligned_to(l->bad_flag, 4))
-    return CAMPX_EINVAL;
-  if (B > 0xffffffffll || l->first_frame < 0 || l->first_frame > INT64_MAX - T) return CAMPX_EINVAL;
-  if (l->window < 1 || (l->rule != CAMPX_LEARN_Q && l->rule != CAMPX_LEARN_EXPECTED_SARSA) ||
-      l->path < 0 || l->path > 2 || l->n_learners < 1 || l->scratch_bytes < 0)
-    return CAMPX_EINVAL;
-  const int32_t v = wide_validate_plain(s);
-  if (v != CAMPX_OK) return v;
-  if (l->perf_sum && !s->has_perf) return CAMPX_EINVAL;
+  const bool own_ok = l && l->clamped && aligned_to(l->clamped, 8) && aligned_to(l->scratch, 8) &&
+                      l->n_learners >= 1 && l->scratch_bytes >= 0;
+  const int32_t screened = screen_learner(s, tables_dev, st, l, B, T, own_ok);
+  if (screened != CAMPX_OK) return screened;
   const int64_t P = l->n_learners;
   SharedPlan plan;     // (refuses a P that does not divide B, n > 1024, P * n_states * 5 >= 2^31)
   const int32_t planned = plan_shared(s->n_states, l->perf_sum ? 1 : 0, B, P, knob(K_WIDE_LDS_MAX),
@@ -659,27 +666,19 @@ int32_t campx_wide_shared_launch(const CampxWideSpec* s, const void* tables_dev,
   const int64_t n_bins = P * s->n_states * CAMPX_N_ACTIONS;
   if (plan.path == 2 && (!l->scratch || l->scratch_bytes < n_bins * 12)) return CAMPX_EINVAL;
   const WideTables t = wide_tables(*s, tables_dev);
-  LearnParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.n_states = s->n_states;
-  pp.window = l->window;
-  wide_discounts(*s, pp.discounts);
-  pp.key0 = (uint32_t)l->seed;
-  pp.key1 = (uint32_t)(l->seed >> 32);
-  pp.first_frame = l->first_frame;
   const size_t lds = (size_t)plan.lds_bytes;
-  const SharedKernel kernel = kSharedKernels[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)]
-                                            [l->perf_sum != nullptr][l->rule == CAMPX_LEARN_EXPECTED_SARSA];
+  const SharedKernel kernel = pick_kernel(kSharedKernels, plan, *l);
   CAMPX_ALLOW_LDS(kernel, lds);
   // path 2's accumulators: [sums int64 x bins][counts uint32 x bins]
   long long* acc_sum = plan.path == 2 ? static_cast<long long*>(l->scratch) : nullptr;
   uint32_t* acc_count = plan.path == 2 ? reinterpret_cast<uint32_t*>(acc_sum + n_bins) : nullptr;
   const int64_t G = plan.learners;
   hipLaunchKernelGGL(kernel, dim3((unsigned)((P + G - 1) / G)), dim3((unsigned)plan.threads), lds,
-                     static_cast<hipStream_t>(stream), pp, t.entries, t.perf, l->q, l->alpha, l->gamma,
-                     l->epsilon, reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum,
-                     l->episodes, reinterpret_cast<long long*>(l->clamped), acc_sum, acc_count,
-                     l->bad_count, l->bad_flag, B, P, (int32_t)(B / P), (int32_t)G, T, l->reset_first);
+                     static_cast<hipStream_t>(stream), learn_params(*s, *l), t.entries, t.perf, l->q,
+                     l->alpha, l->gamma, l->epsilon, reinterpret_cast<int32_t*>(st.pos), st,
+                     l->reward_sum, l->perf_sum, l->episodes, reinterpret_cast<long long*>(l->clamped),
+                     acc_sum, acc_count, l->bad_count, l->bad_flag, B, P, (int32_t)(B / P), (int32_t)G,
+                     T, l->reset_first);
   return launch_status();
 }
 

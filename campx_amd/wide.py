@@ -139,13 +139,12 @@ class WideGame(fused.FusedGame):
     # the same two of the window calls, counted apart so that the error says where they came from
     self._bad_window_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_window_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
-    # learners of learn_tabular() with bad hyper-parameters, once per launch (raised under the
-    # flag of the action ids), and the [3, B] tensor its Python-float hyper-parameters are filled into
+    # learners of learn_tabular() and of learn_shared() with bad hyper-parameters, once per launch
+    # (raised under the flag of the action ids), and the [3, learners] tensors that Python-float
+    # hyper-parameters are filled into, by (method, learners)
     self._bad_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
-    self._learn_floats = None
-    # the same two of learn_shared(): bad learners, and its [3, P] tensors by P
     self._bad_shared_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
-    self._shared_floats = {}
+    self._hyper_floats = {}
     self._layer_of_cell = None        # the window kernel's scenery table
     self._window_table()
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
@@ -504,11 +503,11 @@ class WideGame(fused.FusedGame):
       out['perf_sum'] = torch.zeros((W, B), dtype=torch.int32, device=dev)
     return out
 
-  def _hyper_parameter(self, name, value, row, learners=None):
-    """float32 [B] on the device of `alpha`, `gamma` or `epsilon`: a tensor as given, a Python
-    number checked here and filled into row `row` of a tensor the game keeps (no allocation after
-    the first call).  `learners`: float32 [learners] for the P learners of `learn_shared()`."""
-    B = self.batch if learners is None else learners
+  def _hyper_parameter(self, name, value, row, call, B):
+    """float32 [B] on the device of `alpha`, `gamma` or `epsilon` for the B learners of method
+    `call`: a tensor as given, a Python number checked here and filled into row `row` of a tensor
+    the game keeps per (call, B) - no allocation after the first call, and a captured call of one
+    method never sees the numbers of the other."""
     if torch.is_tensor(value):
       if not self._tensor_ok(value, torch.float32, (B,)):
         raise ValueError('{} must be a number or a contiguous float32 [{}] tensor (one per learner) '
@@ -522,13 +521,49 @@ class WideGame(fused.FusedGame):
         or (name == 'epsilon' and not 0.0 <= value <= 1.0)):
       raise ValueError('{} must be a finite number (as a float32){}, got {!r}'.format(
           name, ' in [0, 1]' if name == 'epsilon' else '', value))
-    if learners is not None:
-      if learners not in self._shared_floats:
-        self._shared_floats[learners] = torch.zeros((3, B), dtype=torch.float32, device=self.device)
-      return self._shared_floats[learners][row].fill_(float(value))
-    if self._learn_floats is None:
-      self._learn_floats = torch.zeros((3, B), dtype=torch.float32, device=self.device)
-    return self._learn_floats[row].fill_(float(value))
+    if (call, B) not in self._hyper_floats:
+      self._hyper_floats[call, B] = torch.zeros((3, B), dtype=torch.float32, device=self.device)
+    return self._hyper_floats[call, B][row].fill_(float(value))
+
+  def _learner_prologue(self, call, learners, T, window, rule, first_frame, seed, alpha, gamma,
+                        epsilon, out, own, made_by, make_out):
+    """What learn_tabular() and learn_shared() do after their own checks of q and P: returns T,
+    window, the first frame, the seed as the op's signed int64, the checked (or made) `out` and
+    alpha, gamma, epsilon as float32 [learners].  `own`: the call's own entries of `out`;
+    `made_by(T, window)`: the call that makes `out`, for the message; `make_out(T, window)`."""
+    B = self.batch
+    T, window, W = self._windows_of(T, window)
+    if rule not in _hip.LEARN_RULES:
+      raise ValueError('rule must be \'q\' or \'expected_sarsa\', got {!r}'.format(rule))
+    first = self._policy_frame if first_frame is None else int(first_frame)
+    if first < 0 or first + T >= 1 << 63:
+      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
+    seed = int(seed) & ((1 << 64) - 1)
+    want = [('reward_sum', torch.float32, (W, B)), ('episodes', torch.int32, (W, B))] + own
+    if self.has_perf:
+      want.append(('perf_sum', torch.int32, (W, B)))
+    if out is None:
+      out = make_out(T, window)
+    else:
+      self._check_out(out, want, made_by(T, window))
+    hyper = (self._hyper_parameter('alpha', alpha, 0, call, learners),
+             self._hyper_parameter('gamma', gamma, 1, call, learners),
+             self._hyper_parameter('epsilon', epsilon, 2, call, learners))
+    return T, window, first, seed - (1 << 64) if seed >= 1 << 63 else seed, out, hyper
+
+  def _learner_epilogue(self, first, T, reset_first, q, out, own=()):
+    """The frame counters, the lazy errors and the result dict of a learner call."""
+    self._policy_frame = first + T
+    self.frame = T if reset_first else self.frame + T
+    self.check_ok()
+    if self.validate_actions:
+      self._after_launch()
+    res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes']}
+    for k in own:
+      res[k] = out[k]
+    if self.has_perf:
+      res['perf_sum'] = out['perf_sum']
+    return res
 
   def learn_tabular(self, T, q=None, alpha=0.1, gamma=0.99, epsilon=0.1, rule='q', seed=0,
                     first_frame=None, reset_first=False, window=None, out=None, path=0):
@@ -582,16 +617,9 @@ class WideGame(fused.FusedGame):
     `rollout_policy()` leaves them.  Argument errors raise ValueError before anything is launched.
     """
     S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
-    T, window, W = self._windows_of(T, window)
-    if rule not in _hip.LEARN_RULES:
-      raise ValueError('rule must be \'q\' or \'expected_sarsa\', got {!r}'.format(rule))
     if B * S * A >= 1 << 31:
       raise ValueError('learn_tabular(): B * n_states * 5 = {} x {} x 5 must be below 2^31; use a '
                        'smaller batch'.format(B, S))
-    first = self._policy_frame if first_frame is None else int(first_frame)
-    if first < 0 or first + T >= 1 << 63:
-      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
-    seed = int(seed) & ((1 << 64) - 1)
     if q is not None and (not self._tensor_ok(q, torch.float32, (B, S, A)) or q.data_ptr() % 16):
       got = ('{} {} on {}'.format(q.dtype, list(q.shape), q.device) if torch.is_tensor(q)
              else type(q).__name__)
@@ -600,33 +628,19 @@ class WideGame(fused.FusedGame):
     self._planned_path(path, _hip.lib.campx_wide_learn_plan, 1 if self.has_perf else 0, B,
                        what='a table of {} states with the Q-tables of a workgroup\'s 256 '
                             'learners'.format(S))
-    want = [('reward_sum', torch.float32, (W, B)), ('episodes', torch.int32, (W, B))]
-    if self.has_perf:
-      want.append(('perf_sum', torch.int32, (W, B)))
-    if out is None:
-      out = self.learner_buffers(T, window)
-    else:
-      self._check_out(out, want, 'learner_buffers({}, window={})'.format(T, window))
-    hyper = [self._hyper_parameter(name, value, row) for row, (name, value) in
-             enumerate((('alpha', alpha), ('gamma', gamma), ('epsilon', epsilon)))]
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_tabular', B, T, window, rule, first_frame, seed, alpha, gamma, epsilon, out, [],
+        'learner_buffers({}, window={})'.format, self.learner_buffers)
     if q is None:
       q = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
     validate = self.validate_actions
     _hip.ops.wide_learn(
         self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), hyper[0],
-        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed - (1 << 64) if seed >= 1 << 63 else seed,
-        first, T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
-        out['episodes'], self._bad_learners if validate else None,
-        self._bad_flag if validate else None, bool(reset_first), path)
-    self._policy_frame = first + T
-    self.frame = T if reset_first else self.frame + T
-    self.check_ok()
-    if validate:
-      self._after_launch()
-    res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes']}
-    if self.has_perf:
-      res['perf_sum'] = out['perf_sum']
-    return res
+        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed, first, T, window, out['reward_sum'],
+        out.get('perf_sum') if self.has_perf else None, out['episodes'],
+        self._bad_learners if validate else None, self._bad_flag if validate else None,
+        bool(reset_first), path)
+    return self._learner_epilogue(first, T, reset_first, q, out)
 
   # ------------------------------------------------------------ shared online learners
 
@@ -716,9 +730,6 @@ class WideGame(fused.FusedGame):
     Argument errors raise ValueError before anything is launched.
     """
     S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
-    T, window, W = self._windows_of(T, window)
-    if rule not in _hip.LEARN_RULES:
-      raise ValueError('rule must be \'q\' or \'expected_sarsa\', got {!r}'.format(rule))
     if (not torch.is_tensor(q) or q.dtype != torch.float32 or q.dim() != 3 or q.shape[0] < 1
         or tuple(q.shape[1:]) != (S, A) or q.device != dev or not q.is_contiguous()
         or q.data_ptr() % 16):
@@ -728,41 +739,22 @@ class WideGame(fused.FusedGame):
                        'x n_states x actions) on {}; got {}'.format(S, A, dev, got))
     P = int(q.shape[0])
     plan = self._shared_plan(P, path)
-    first = self._policy_frame if first_frame is None else int(first_frame)
-    if first < 0 or first + T >= 1 << 63:
-      raise ValueError('first_frame must be >= 0 and first_frame + T below 2^63')
-    seed = int(seed) & ((1 << 64) - 1)
-    want = [('reward_sum', torch.float32, (W, B)), ('episodes', torch.int32, (W, B)),
-            ('clamped', torch.int64, (P,))]
-    if self.has_perf:
-      want.append(('perf_sum', torch.int32, (W, B)))
+    own = [('clamped', torch.int64, (P,))]
     if plan[0] == 2:
-      want.append(('scratch', torch.int32, (3 * P * S * A,)))
-    if out is None:
-      out = self.shared_learner_buffers(P, T, window, path)
-    else:
-      self._check_out(out, want, 'shared_learner_buffers({}, {}, window={}, path={})'.format(
-          P, T, window, path))
-    hyper = [self._hyper_parameter(name, value, row, learners=P) for row, (name, value) in
-             enumerate((('alpha', alpha), ('gamma', gamma), ('epsilon', epsilon)))]
+      own.append(('scratch', torch.int32, (3 * P * S * A,)))
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_shared', P, T, window, rule, first_frame, seed, alpha, gamma, epsilon, out, own,
+        lambda T, window: 'shared_learner_buffers({}, {}, window={}, path={})'.format(P, T, window, path),
+        lambda T, window: self.shared_learner_buffers(P, T, window, path))
     validate = self.validate_actions
     _hip.ops.wide_learn_shared(
         self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), hyper[0],
-        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed - (1 << 64) if seed >= 1 << 63 else seed,
-        first, T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
-        out['episodes'], out['clamped'], out.get('scratch') if plan[0] == 2 else None,
+        hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed, first, T, window, out['reward_sum'],
+        out.get('perf_sum') if self.has_perf else None, out['episodes'], out['clamped'],
+        out.get('scratch') if plan[0] == 2 else None,
         self._bad_shared_learners if validate else None, self._bad_flag if validate else None,
         bool(reset_first), path)
-    self._policy_frame = first + T
-    self.frame = T if reset_first else self.frame + T
-    self.check_ok()
-    if validate:
-      self._after_launch()
-    res = {'q': q, 'reward_sum': out['reward_sum'], 'episodes': out['episodes'],
-           'clamped': out['clamped']}
-    if self.has_perf:
-      res['perf_sum'] = out['perf_sum']
-    return res
+    return self._learner_epilogue(first, T, reset_first, q, out, ('clamped',))
 
   # ------------------------------------------------------------ planning on the table
 

@@ -847,6 +847,9 @@ int32_t campx_wide_policy_population_launch(const CampxWideSpec* spec_host, cons
  * BAD: it takes action 4 at every frame, its table is left untouched (its sums are still written),
  * and it is counted ONCE per launch into *bad_count (DEVICE int32, added to, may be NULL);
  * *bad_flag (device or mapped pinned int32, may be NULL) is set to 1.
+ * In csrc/k_learn.hip the steps are the helpers of "The frame step", which the shared learners
+ * below call too: Chunks (1), Carried (2), frame_action() (3), decode_entry() (4), td_error()
+ * (5 - 7's delta) and WindowSums (8); Hyper holds the test of a BAD learner.
  *
  * A lane per learner, 256 to a workgroup.  Two paths, `path`: 1 = a workgroup stages the entries,
  * the perf bytes (when perf_sum is given) and its 256 learners' tables in LDS, the tables
@@ -907,7 +910,8 @@ int32_t campx_wide_learn_launch(const CampxWideSpec* spec_host, const void* tabl
  * The learner is SYNCHRONOUS, and repeats bit for bit whatever the order in which its
  * environments arrive.  Frame f of learner m, every float32 operation rounded on its own:
  *   1. TD error per environment.  Every environment e of the learner does steps 1 - 6 of the rule
- *      above with q[m] in place of q[e] and alpha[m], gamma[m], epsilon[m]; the Philox counter is
+ *      above - the same functions of csrc/k_learn.hip, not a restatement of them - with q[m] in
+ *      place of q[e] and alpha[m], gamma[m], epsilon[m]; the Philox counter is
  *      (ABSOLUTE environment e, g & 0xffffffff, g >> 32, 1), the stream of the per-environment
  *      learners.  It reads q[m] as it stands at the START of the frame - no environment sees
  *      another's update of the same frame.  delta_e = target - q[m][s_e][a_e].

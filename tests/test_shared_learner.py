@@ -411,3 +411,79 @@ def test_a_captured_call_replays_to_the_same_bits(path):
   if path == 2:
     assert not bool(bufs['scratch'].any())
   f.check_actions()
+
+
+@pytest.mark.parametrize('rule,epsilon', [('q', 0.5), ('expected_sarsa', 0.5), ('expected_sarsa', 0.0)])
+def test_one_actor_per_learner_gives_the_bits_of_learn_tabular(rule, epsilon):
+  """The one place where both kernels of csrc/k_learn.hip run on the same input: B = P = 65 (n = 1;
+  one short workgroup with absent lanes in either kernel), the integer-valued table of
+  test_shared_learner_cpu.py with alpha = gamma = 0.5 and q0 = 0, T = 13 from frame 3 (a chunk with
+  a lead and a tail) in windows of 4 (a short last window), each kernel on paths 1 and 2, and a
+  second call with `reset_first`.  Each kernel gives the bits of its own reference, `clamped` is all
+  zeros, and the window sums, state, done and ret are the same bits across the two kernels.
+
+  q is the same bits across the kernels wherever the quantiser is exact - every delta a multiple
+  of 2^-32, which the references show here: under 'q', and under 'expected_sarsa' with epsilon = 0,
+  where the bootstrap is (1 * max) + (0 * mean).  Expected SARSA with epsilon = 0.5 rounds: its mean
+  is a sum times float32(0.2), so the deltas have bits below 2^-32, the quantised step differs from
+  the per-environment learner's by design, and the two REFERENCES disagree on q (asserted below) -
+  there each kernel is held to its own.
+
+  The table has 12 states: a workgroup's piece of q is 65 x 60 floats, a multiple of four (any piece
+  of it is, 60 being one), so path 1 of learn_tabular() copies it in whole 16-byte groups here."""
+  import learner_reference as learn_ref
+  from campx_amd import _hip, wide
+  from wide_table_reference import integer_table
+  B = P = 65
+  g = integer_table()
+  S = g.n_states
+  assert S == 12 and (B * S * 5) % 4 == 0
+  kw = dict(alpha=0.5, gamma=0.5, epsilon=epsilon, rule=rule, seed=11, first_frame=3, window=4)
+  T = 13
+
+  # the references, once: [call] -> (outputs, q, state, over, ret)
+  def walk(L):
+    calls = []
+    for reset in (False, True):
+      L.q[:] = 0
+      out = L.learn(T, reset_first=reset, record=True, **kw)
+      calls.append((out, L.q.copy(), L.state.copy(), L.over.copy(), L.ret.copy()))
+    return calls
+
+  alone = walk(learn_ref.Learners(g, B))
+  shared = walk(shared_ref.SharedLearners(g, B, np.zeros((P, S, 5), np.float32)))
+  exact = all(np.array_equal(np.ldexp(out['delta'].astype(np.float64), 32),
+                             np.rint(np.ldexp(out['delta'].astype(np.float64), 32))) for out, *_ in shared)
+  assert exact == (rule == 'q' or epsilon == 0.0)
+  for (a, aq, *a_end), (s, sq, *s_end) in zip(alone, shared):
+    assert s['clamped'].tolist() == [0] * P and np.abs(aq).max() > 0
+    assert _same(aq, sq) == exact
+    assert _same(a['reward_sum'], s['reward_sum']) and np.array_equal(a['episodes'], s['episodes'])
+    assert np.array_equal(a['perf_sum'], s['perf_sum'])
+    assert np.array_equal(a_end[0], s_end[0]) and np.array_equal(a_end[1], s_end[1]) and _same(a_end[2], s_end[2])
+
+  f = wide.WideGame(types.SimpleNamespace(rows=4, cols=5), B, 'cuda', g)
+  f.showtime()
+  plan = (ctypes.c_int64 * 4)()
+  for path in (1, 2):
+    assert _hip.lib.campx_wide_learn_plan(S, 1, B, _hip.config_get('wide_lds_max'), path, plan) == 0
+    assert plan[0] == path and _plan(f, P, path)[1][0] == path
+  for method, want in (('learn_tabular', alone), ('learn_shared', shared)):
+    for path in (1, 2):
+      f.state.zero_()
+      f.done.zero_()
+      f.ret.zero_()
+      for reset, (out, q_end, state, over, ret) in zip((False, True), want):
+        q = torch.zeros((P, S, 5), device='cuda')
+        res = getattr(f, method)(T, q, reset_first=reset, path=path, **kw)
+        where = '{} path {} reset_first={}'.format(method, path, reset)
+        assert _same(q.cpu().numpy(), q_end), where
+        assert _same(res['reward_sum'].cpu().numpy(), out['reward_sum']), where
+        assert np.array_equal(res['perf_sum'].cpu().numpy(), out['perf_sum']), where
+        assert np.array_equal(res['episodes'].cpu().numpy(), out['episodes']), where
+        assert np.array_equal(f.state.cpu().numpy(), state), where
+        assert np.array_equal(f.done.cpu().numpy(), over.astype(np.uint8)), where
+        assert _same(f.ret.cpu().numpy(), ret), where
+        if method == 'learn_shared':
+          assert not bool(res['clamped'].any()), where
+  f.check_actions()

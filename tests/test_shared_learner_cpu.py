@@ -12,6 +12,7 @@ import pytest
 import learner_reference as learn_ref
 import shared_learner_reference as shared_ref
 from test_population_cpu import _Table, _same, _valid_spec
+from wide_table_reference import integer_table
 
 F = np.float32
 LDS_MAX = 144 * 1024
@@ -374,24 +375,11 @@ def test_a_bad_learner_takes_action_4_keeps_its_table_and_is_counted_once():
   assert _same(L.q[[0, 3]], alone.q[[0, 3]])
 
 
-def _integer_table():
-  """A synthetic table of tests/wide_table_reference.py with discounts of 1 (no discount codes; an
-  entry that ends the episode bootstraps from nothing), its rewards - 0.1 and 1e6 among them -
-  replaced by small integers: 0.1 becomes 2 and 1e6 becomes 3 (None stays None)."""
-  import wide_table_reference as table_ref
-  g = table_ref.make_table(77, 4, 5, 4, 2, 12, dcodes=False, perf=True)
-  r = g.st_reward
-  g.st_reward = np.where(r == F(0.1), F(2), np.where(np.abs(r) == F(1e6), np.sign(r) * F(3), r)).astype(F)
-  reward = np.where(np.isnan(g.st_reward), 0, g.st_reward)
-  assert np.array_equal(reward, np.rint(reward)) and (g.st_discount[g.st_done == 0] == 1).all()
-  return g
-
-
 def test_one_actor_per_learner_is_learn_tabular_when_nothing_is_rounded_away():
   """n = 1, alpha = gamma = 0.5, q0 = 0, integer rewards, discounts of 1, eight frames: every
   delta is a multiple of 2^-32 below 2^20, so the quantiser is exact, the mean of one value is the
   value, and q is `learner_reference`'s bit for bit."""
-  g = _integer_table()
+  g = integer_table()
   B = 16
   kw = dict(alpha=0.5, gamma=0.5, epsilon=0.5, seed=11, reset_first=True)
   shared = shared_ref.SharedLearners(g, B, np.zeros((B, g.n_states, 5), F))

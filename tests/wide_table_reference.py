@@ -175,6 +175,20 @@ class View(object):
   """A table in the header's terms (module docstring)."""
 
 
+def integer_table():
+  """A synthetic table with discounts of 1 (no discount codes; an entry that ends the episode
+  bootstraps from nothing), its rewards - 0.1 and 1e6 among them - replaced by small integers: 0.1
+  becomes 2 and 1e6 becomes 3 (None stays None).  With alpha = gamma = epsilon = 0.5 and q0 = 0 a
+  learner's first frames round nothing away."""
+  F = np.float32
+  g = make_table(77, 4, 5, 4, 2, 12, dcodes=False, perf=True)
+  r = g.st_reward
+  g.st_reward = np.where(r == F(0.1), F(2), np.where(np.abs(r) == F(1e6), np.sign(r) * F(3), r)).astype(F)
+  reward = np.where(np.isnan(g.st_reward), 0, g.st_reward)
+  assert np.array_equal(reward, np.rint(reward)) and (g.st_discount[g.st_done == 0] == 1).all()
+  return g
+
+
 def _scenery(table, v):
   """Character codes [rows*cols] of picture v of the scenery: the backdrop's picture, then the things
   that never move (and the several-cell drapes this picture holds), back to front."""
