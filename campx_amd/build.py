@@ -26,7 +26,7 @@ UNITS = ('campx_api', 'k_interp', 'k_rollout_table', 'k_step', 'k_update', 'k_re
          'k_vtrace', 'k_sums', 'k_plan', 'k_visit', 'k_misc')
 SRCS = [os.path.join(CSRC, u + '.hip') for u in UNITS]
 HEADERS = [os.path.join(CSRC, 'campx_common.hip.h'), os.path.join(CSRC, 'wide_table.hip.h'),
-           os.path.join(REPO, 'include', 'campx_hip.h')]
+           os.path.join(CSRC, 'streams.hip.h'), os.path.join(REPO, 'include', 'campx_hip.h')]
 OBJ_DIR = os.path.join(REPO, 'build', 'obj')
 OUT = os.path.join(CSRC, 'libcampx_hip.so')
 INCLUDE = os.path.join(REPO, 'include')

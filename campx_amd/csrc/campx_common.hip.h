@@ -470,6 +470,8 @@ inline int32_t launch_status() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? CAMPX_OK : hip_failed(e);
 }
+// `p` is a multiple of `n`, a power of two (NULL is).
+inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 // The library's settings (campx_api.hip holds the table: name, default, range, what each selects;
 // campx_config_set / _get / _string in include/campx_hip.h).  Read at every use - a plain load.
 enum Knob : int {

@@ -151,16 +151,6 @@ void want_row_stream(const Tensor& t, const char* name, at::ScalarType dtype, co
   TORCH_CHECK(B == 1 || t.stride(1) == 1, "campx: ", name, " must be contiguous within a row");
 }
 
-// ... of campx::returns / state_sums / table_lookup: rows any pitch >= B apart, each stream its
-// own; returns the pitch.
-int64_t stream_rows(const Tensor& t, const char* name, at::ScalarType dtype, const c10::Device& dev,
-                    int64_t T, int64_t B) {
-  want_row_stream(t, name, dtype, dev, T, B);
-  TORCH_CHECK(T == 1 || t.stride(0) >= B, "campx: ", name, " has row pitch ", t.stride(0),
-              ", below its ", B, " columns");
-  return T == 1 ? B : t.stride(0);
-}
-
 // ... of a rollout.  The per-frame scalar streams [T, B] and the trace [K, T, B] may be PADDED:
 // contiguous within a row, rows `pitch` >= B elements apart, the same pitch for every stream of a
 // call (the planes of the trace then T * pitch apart).  rollout_buffers() pads to a multiple of
@@ -1109,67 +1099,95 @@ void wide_render_windows(const Tensor& spec_host, const Tensor& tables, const Te
            "campx_wide_render_windows_launch");
 }
 
-// Discounted returns and GAE advantages of [T, B] streams (campx_returns_launch): every stream
-// contiguous within a row, rows any pitch >= B apart, each stream its own (stream_rows()).
+// ---- campx::returns / vtrace / state_sums / table_lookup: the ops over [T, B] streams, every
+// stream contiguous within a row, rows any pitch >= B apart, each stream its own.
+
+// The first stream of such an op tells the device and the shape.  `kind`: "a float32", "an int32".
+struct StreamShape {
+  c10::Device dev;
+  int64_t T, B;
+};
+StreamShape first_stream(const char* op, const Tensor& t, const char* name, const char* kind) {
+  TORCH_CHECK(t.device().is_cuda() && t.dim() == 2, op, ": ", name, " must be ", kind,
+              " [T, B] tensor on a HIP device (no CPU implementation)");
+  const int64_t T = t.size(0), B = t.size(1);
+  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, op, ": bad shape [", T, ", ", B, "]");
+  return {t.device(), T, B};
+}
+
+// One stream into the launch's struct: its pointer and its pitch.
+template <typename P>
+void stream_rows(const Tensor& t, const char* name, at::ScalarType dtype, const StreamShape& s, P*& p,
+                 int64_t& pitch) {
+  want_row_stream(t, name, dtype, s.dev, s.T, s.B);
+  TORCH_CHECK(s.T == 1 || t.stride(0) >= s.B, "campx: ", name, " has row pitch ", t.stride(0),
+              ", below its ", s.B, " columns");
+  p = reinterpret_cast<P*>(t.data_ptr());
+  pitch = s.T == 1 ? s.B : t.stride(0);
+}
+template <typename P>
+void stream_rows(const OptTensor& t, const char* name, at::ScalarType dtype, const StreamShape& s, P*& p,
+                 int64_t& pitch) {
+  if (t.has_value()) stream_rows(*t, name, dtype, s, p, pitch);
+}
+
+// A device counter: int64, one element.  `what`: "bad_count must be an int64 tensor".
+int64_t* counter(const char* op, const char* what, const Tensor& c, const c10::Device& dev) {
+  TORCH_CHECK(c.device() == dev && c.scalar_type() == at::kLong && c.numel() == 1, op, ": ", what,
+              " of one element on ", dev);
+  return reinterpret_cast<int64_t*>(c.data_ptr());
+}
+int64_t* counter(const char* op, const char* what, const OptTensor& c, const c10::Device& dev) {
+  return c.has_value() ? counter(op, what, *c, dev) : nullptr;
+}
+
+// float32 [B], or none.
+const float* bootstrap_row(const OptTensor& bootstrap, const StreamShape& s) {
+  if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, s.dev, {s.B});
+  return opt_ptr<const float>(bootstrap);
+}
+
+// Discounted returns and GAE advantages of [T, B] streams (campx_returns_launch).
 void returns(const Tensor& reward, const Tensor& done, double gamma, const OptTensor& discount,
              const OptTensor& values, const OptTensor& bootstrap, double lam, Tensor& returns_out,
              const OptTensor& advantages) {
-  TORCH_CHECK(reward.device().is_cuda() && reward.dim() == 2,
-              "campx::returns: reward must be a float32 [T, B] tensor on a HIP device (no CPU "
-              "implementation)");
-  const c10::Device dev = reward.device();
-  const int64_t T = reward.size(0), B = reward.size(1);
-  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::returns: bad shape [", T, ", ", B, "]");
+  const StreamShape s = first_stream("campx::returns", reward, "reward", "a float32");
   TORCH_CHECK(values.has_value() == advantages.has_value(),
               "campx::returns: values and advantages come together");
   CampxReturns r{};
-  r.reward_pitch = stream_rows(reward, "reward", at::kFloat, dev, T, B);
-  r.done_pitch = stream_rows(done, "done", at::kByte, dev, T, B);
-  if (discount.has_value()) r.discount_pitch = stream_rows(*discount, "discount", at::kFloat, dev, T, B);
-  if (values.has_value()) {
-    r.values_pitch = stream_rows(*values, "values", at::kFloat, dev, T, B);
-    r.advantages_pitch = stream_rows(*advantages, "advantages", at::kFloat, dev, T, B);
-  }
-  r.returns_pitch = stream_rows(returns_out, "returns", at::kFloat, dev, T, B);
-  if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, dev, {B});
-  r.reward = reinterpret_cast<const float*>(reward.data_ptr());
-  r.done = reinterpret_cast<const uint8_t*>(done.data_ptr());
-  r.discount = opt_ptr<const float>(discount);
-  r.values = opt_ptr<const float>(values);
-  r.bootstrap = opt_ptr<const float>(bootstrap);
-  r.returns = reinterpret_cast<float*>(returns_out.data_ptr());
-  r.advantages = opt_ptr<float>(advantages);
+  stream_rows(reward, "reward", at::kFloat, s, r.reward, r.reward_pitch);
+  stream_rows(done, "done", at::kByte, s, r.done, r.done_pitch);
+  stream_rows(discount, "discount", at::kFloat, s, r.discount, r.discount_pitch);
+  stream_rows(values, "values", at::kFloat, s, r.values, r.values_pitch);
+  stream_rows(advantages, "advantages", at::kFloat, s, r.advantages, r.advantages_pitch);
+  stream_rows(returns_out, "returns", at::kFloat, s, r.returns, r.returns_pitch);
+  r.bootstrap = bootstrap_row(bootstrap, s);
   r.gamma = (float)gamma;
   r.lam = (float)lam;
-  const DeviceGuard guard(dev);
-  check_ok(campx_returns_launch(&r, B, (int32_t)T, current_stream()), "campx_returns_launch");
+  const DeviceGuard guard(s.dev);
+  check_ok(campx_returns_launch(&r, s.B, (int32_t)s.T, current_stream()), "campx_returns_launch");
 }
 
-// V-trace targets and advantages of [T, B] streams (campx_vtrace_launch): the streams as in
-// campx::returns; `ratio` exactly when the table set (target [Nt, A], behaviour [Nb, A], states,
-// actions) is not given.
+// V-trace targets and advantages of [T, B] streams (campx_vtrace_launch): `ratio` exactly when the
+// table set (target [Nt, A], behaviour [Nb, A], states, actions) is not given.
 void vtrace(const Tensor& reward, const Tensor& done, double gamma, const Tensor& values,
             const OptTensor& ratio, const OptTensor& target, const OptTensor& behaviour,
             const OptTensor& states, const OptTensor& actions, const OptTensor& discount,
             const OptTensor& bootstrap, double lam, double rho_bar, double c_bar, double pg_rho_bar,
             const OptTensor& bad_count, int64_t path, Tensor& vs, Tensor& advantages) {
-  TORCH_CHECK(reward.device().is_cuda() && reward.dim() == 2,
-              "campx::vtrace: reward must be a float32 [T, B] tensor on a HIP device (no CPU "
-              "implementation)");
-  const c10::Device dev = reward.device();
-  const int64_t T = reward.size(0), B = reward.size(1);
-  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::vtrace: bad shape [", T, ", ", B, "]");
+  const StreamShape s = first_stream("campx::vtrace", reward, "reward", "a float32");
+  const c10::Device dev = s.dev;
   const bool table = target.has_value();
   TORCH_CHECK(behaviour.has_value() == table && states.has_value() == table &&
                   actions.has_value() == table && ratio.has_value() != table,
               "campx::vtrace: give ratio, or target, behaviour, states and actions together");
   TORCH_CHECK(path >= 0 && path <= 2, "campx::vtrace: bad path ", path);
   CampxVtrace v{};
-  v.reward_pitch = stream_rows(reward, "reward", at::kFloat, dev, T, B);
-  v.done_pitch = stream_rows(done, "done", at::kByte, dev, T, B);
-  v.values_pitch = stream_rows(values, "values", at::kFloat, dev, T, B);
-  if (discount.has_value()) v.discount_pitch = stream_rows(*discount, "discount", at::kFloat, dev, T, B);
-  if (bootstrap.has_value()) want(*bootstrap, "bootstrap", at::kFloat, dev, {B});
+  stream_rows(reward, "reward", at::kFloat, s, v.reward, v.reward_pitch);
+  stream_rows(done, "done", at::kByte, s, v.done, v.done_pitch);
+  stream_rows(values, "values", at::kFloat, s, v.values, v.values_pitch);
+  stream_rows(discount, "discount", at::kFloat, s, v.discount, v.discount_pitch);
+  v.bootstrap = bootstrap_row(bootstrap, s);
   if (table) {
     TORCH_CHECK(target->dim() == 2 && behaviour->dim() == 2 && target->size(0) >= 1 &&
                     target->size(1) >= 1 && target->size(1) <= 128 &&
@@ -1178,33 +1196,18 @@ void vtrace(const Tensor& reward, const Tensor& done, double gamma, const Tensor
                 "of Nt; they are ", target->sizes(), " and ", behaviour->sizes());
     want(*target, "target", at::kFloat, dev, {target->size(0), target->size(1)});
     want(*behaviour, "behaviour", at::kFloat, dev, {behaviour->size(0), target->size(1)});
-    v.states_pitch = stream_rows(*states, "states", at::kInt, dev, T, B);
-    v.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
+    v.target = opt_ptr<const float>(target);
+    v.behaviour = opt_ptr<const float>(behaviour);
     v.n_target_states = target->size(0);
     v.n_behaviour_states = behaviour->size(0);
     v.n_actions = (int32_t)target->size(1);
-  } else {
-    v.ratio_pitch = stream_rows(*ratio, "ratio", at::kFloat, dev, T, B);
   }
-  if (bad_count.has_value())
-    TORCH_CHECK(bad_count->device() == dev && bad_count->scalar_type() == at::kLong &&
-                    bad_count->numel() == 1,
-                "campx::vtrace: bad_count must be an int64 tensor of one element on ", dev);
-  v.vs_pitch = stream_rows(vs, "vs", at::kFloat, dev, T, B);
-  v.advantages_pitch = stream_rows(advantages, "advantages", at::kFloat, dev, T, B);
-  v.reward = reinterpret_cast<const float*>(reward.data_ptr());
-  v.done = reinterpret_cast<const uint8_t*>(done.data_ptr());
-  v.values = reinterpret_cast<const float*>(values.data_ptr());
-  v.discount = opt_ptr<const float>(discount);
-  v.bootstrap = opt_ptr<const float>(bootstrap);
-  v.ratio = opt_ptr<const float>(ratio);
-  v.target = opt_ptr<const float>(target);
-  v.behaviour = opt_ptr<const float>(behaviour);
-  v.states = opt_ptr<const int32_t>(states);
-  v.actions = opt_ptr<const int8_t>(actions);
-  v.vs = reinterpret_cast<float*>(vs.data_ptr());
-  v.advantages = reinterpret_cast<float*>(advantages.data_ptr());
-  v.bad_count = opt_ptr<int64_t>(bad_count);
+  stream_rows(states, "states", at::kInt, s, v.states, v.states_pitch);
+  stream_rows(actions, "actions", at::kChar, s, v.actions, v.actions_pitch);
+  stream_rows(ratio, "ratio", at::kFloat, s, v.ratio, v.ratio_pitch);
+  v.bad_count = counter("campx::vtrace", "bad_count must be an int64 tensor", bad_count, dev);
+  stream_rows(vs, "vs", at::kFloat, s, v.vs, v.vs_pitch);
+  stream_rows(advantages, "advantages", at::kFloat, s, v.advantages, v.advantages_pitch);
   v.path = (int32_t)path;
   v.gamma = (float)gamma;
   v.lam = (float)lam;
@@ -1212,7 +1215,7 @@ void vtrace(const Tensor& reward, const Tensor& done, double gamma, const Tensor
   v.c_bar = (float)c_bar;
   v.pg_rho_bar = (float)pg_rho_bar;
   const DeviceGuard guard(dev);
-  check_ok(campx_vtrace_launch(&v, B, (int32_t)T, current_stream()), "campx_vtrace_launch");
+  check_ok(campx_vtrace_launch(&v, s.B, (int32_t)s.T, current_stream()), "campx_vtrace_launch");
 }
 
 // Per-(state, action) fixed-point sums of [T, B] streams (campx_state_sums_launch): `raw` int64
@@ -1220,12 +1223,8 @@ void vtrace(const Tensor& reward, const Tensor& done, double gamma, const Tensor
 void state_sums(const Tensor& states, const OptTensor& actions, at::TensorList values,
                 int64_t n_states, int64_t n_actions, int64_t frac_bits, bool accumulate,
                 int64_t path, Tensor& raw, Tensor& skipped, Tensor& clamped) {
-  TORCH_CHECK(states.device().is_cuda() && states.dim() == 2,
-              "campx::state_sums: states must be an int32 [T, B] tensor on a HIP device (no CPU "
-              "implementation)");
-  const c10::Device dev = states.device();
-  const int64_t T = states.size(0), B = states.size(1);
-  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::state_sums: bad shape [", T, ", ", B, "]");
+  const StreamShape sh = first_stream("campx::state_sums", states, "states", "an int32");
+  const c10::Device dev = sh.dev;
   const int64_t K = (int64_t)values.size();
   TORCH_CHECK(K <= CAMPX_SUMS_MAX_VALUES, "campx::state_sums: at most ", CAMPX_SUMS_MAX_VALUES,
               " value streams, got ", K);
@@ -1233,44 +1232,33 @@ void state_sums(const Tensor& states, const OptTensor& actions, at::TensorList v
                   frac_bits >= 0 && frac_bits <= 62 && path >= 0 && path <= 2,
               "campx::state_sums: bad n_states / n_actions / frac_bits / path");
   CampxStateSums s{};
-  s.states_pitch = stream_rows(states, "states", at::kInt, dev, T, B);
-  if (actions.has_value()) s.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
-  for (int64_t k = 0; k < K; ++k) {
-    s.values_pitch[k] = stream_rows(values[k], "values", at::kFloat, dev, T, B);
-    s.values[k] = reinterpret_cast<const float*>(values[k].data_ptr());
-  }
+  stream_rows(states, "states", at::kInt, sh, s.states, s.states_pitch);
+  stream_rows(actions, "actions", at::kChar, sh, s.actions, s.actions_pitch);
+  for (int64_t k = 0; k < K; ++k)
+    stream_rows(values[k], "values", at::kFloat, sh, s.values[k], s.values_pitch[k]);
   TORCH_CHECK(raw.device() == dev && raw.scalar_type() == at::kLong && raw.is_contiguous() &&
                   raw.numel() == (K + 1) * n_states * n_actions,
               "campx::state_sums: raw must be a contiguous int64 tensor of ", K + 1, " x ", n_states,
               " x ", n_actions, " elements on ", dev);
-  for (const Tensor* c : {&skipped, &clamped})
-    TORCH_CHECK(c->device() == dev && c->scalar_type() == at::kLong && c->numel() == 1,
-                "campx::state_sums: skipped and clamped must be int64 tensors of one element on ", dev);
-  s.states = reinterpret_cast<const int32_t*>(states.data_ptr());
-  s.actions = opt_ptr<const int8_t>(actions);
+  s.acc = reinterpret_cast<int64_t*>(raw.data_ptr());
+  s.skipped = counter("campx::state_sums", "skipped and clamped must be int64 tensors", skipped, dev);
+  s.clamped = counter("campx::state_sums", "skipped and clamped must be int64 tensors", clamped, dev);
   s.n_states = n_states;
   s.n_actions = (int32_t)n_actions;
   s.n_values = (int32_t)K;
   s.frac_bits = (int32_t)frac_bits;
   s.accumulate = accumulate ? 1 : 0;
   s.path = (int32_t)path;
-  s.acc = reinterpret_cast<int64_t*>(raw.data_ptr());
-  s.skipped = reinterpret_cast<int64_t*>(skipped.data_ptr());
-  s.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
   const DeviceGuard guard(dev);
-  check_ok(campx_state_sums_launch(&s, B, (int32_t)T, current_stream()), "campx_state_sums_launch");
+  check_ok(campx_state_sums_launch(&s, sh.B, (int32_t)sh.T, current_stream()), "campx_state_sums_launch");
 }
 
 // out[t, e] = table[states[t, e] * n_actions + actions[t, e]] (campx_table_lookup_launch); `table`
 // float32 [n_states] without actions, [n_states, n_actions] with.
 void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& actions, Tensor& out,
                   const OptTensor& bad_count) {
-  TORCH_CHECK(states.device().is_cuda() && states.dim() == 2,
-              "campx::table_lookup: states must be an int32 [T, B] tensor on a HIP device (no CPU "
-              "implementation)");
-  const c10::Device dev = states.device();
-  const int64_t T = states.size(0), B = states.size(1);
-  TORCH_CHECK(T >= 1 && T <= 0x7fffffff && B >= 1, "campx::table_lookup: bad shape [", T, ", ", B, "]");
+  const StreamShape s = first_stream("campx::table_lookup", states, "states", "an int32");
+  const c10::Device dev = s.dev;
   TORCH_CHECK(table.device() == dev && table.scalar_type() == at::kFloat && table.is_contiguous() &&
                   table.dim() == (actions.has_value() ? 2 : 1) && table.numel() >= 1,
               "campx::table_lookup: table must be a contiguous float32 [n_states",
@@ -1278,22 +1266,15 @@ void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& ac
   const int64_t S = table.size(0), A = actions.has_value() ? table.size(1) : 1;
   TORCH_CHECK(S <= 0x7fffffff && A <= 128, "campx::table_lookup: table too large: ", table.sizes());
   CampxTableLookup l{};
-  l.states_pitch = stream_rows(states, "states", at::kInt, dev, T, B);
-  if (actions.has_value()) l.actions_pitch = stream_rows(*actions, "actions", at::kChar, dev, T, B);
-  l.out_pitch = stream_rows(out, "out", at::kFloat, dev, T, B);
-  if (bad_count.has_value())
-    TORCH_CHECK(bad_count->device() == dev && bad_count->scalar_type() == at::kLong &&
-                    bad_count->numel() == 1,
-                "campx::table_lookup: bad_count must be an int64 tensor of one element on ", dev);
+  stream_rows(states, "states", at::kInt, s, l.states, l.states_pitch);
+  stream_rows(actions, "actions", at::kChar, s, l.actions, l.actions_pitch);
+  stream_rows(out, "out", at::kFloat, s, l.out, l.out_pitch);
+  l.bad_count = counter("campx::table_lookup", "bad_count must be an int64 tensor", bad_count, dev);
   l.table = reinterpret_cast<const float*>(table.data_ptr());
-  l.states = reinterpret_cast<const int32_t*>(states.data_ptr());
-  l.actions = opt_ptr<const int8_t>(actions);
-  l.out = reinterpret_cast<float*>(out.data_ptr());
   l.n_states = S;
   l.n_actions = (int32_t)A;
-  l.bad_count = opt_ptr<int64_t>(bad_count);
   const DeviceGuard guard(dev);
-  check_ok(campx_table_lookup_launch(&l, B, (int32_t)T, current_stream()),
+  check_ok(campx_table_lookup_launch(&l, s.B, (int32_t)s.T, current_stream()),
            "campx_table_lookup_launch");
 }
 

@@ -10,7 +10,8 @@
 // and counted.
 //
 // state_sums_kernel: a lane per environment walks a slice of the frames (the grid is B / 256 x
-// slices of T, so that a batch of a few thousand still fills the chip).  Like returns_kernel it is
+// slices of T, so that a batch of a few thousand still fills the chip; streams.hip.h has
+// walk_forward() and its Chunk, the id test and bin, table staging and the counters).  The walk is
 // bound by latency, so a chunk of eight frames issues all its loads - coalesced along B, each
 // stream with its own pitch - before its first atomic.  Two ways to accumulate:
 //   LDS     (K + 1) * bins int64 accumulators in LDS, `copies` of them interleaved so that copy c
@@ -24,26 +25,18 @@
 //
 // table_lookup_kernel: out[t, e] = table[state * A + action], the same walk without atomics.
 
-#include "wide_table.hip.h"
-
-#include <type_traits>
+#include "streams.hip.h"
 
 namespace campx_impl {
 
-constexpr int kSumsThreads = 256;
-constexpr int kSumsChunk = 8;
 constexpr int kSumsMaxCopies = 64;
-// dynamic LDS of a workgroup: below the 64 KiB a launch may have without an attribute (the
-// counters are static LDS on top), and three workgroups of it still share a CU's 160 KiB
-constexpr int64_t kSumsLdsBudget = CAMPX_SUMS_LDS_BUDGET;
 constexpr int64_t kSumsTargetBlocks = 2048;       // 256 CUs x 8 workgroups
-typedef unsigned long long u64;
 
 struct SumsPlan {
   int32_t path;            // 1 LDS, 2 global
   int32_t copies;
   int64_t grid_b, grid_t;
-  int32_t frames;          // per workgroup along T, a multiple of kSumsChunk
+  int32_t frames;          // per workgroup along T, a multiple of kStreamChunk
   int64_t lds_bytes;
   int32_t n2;
 };
@@ -51,18 +44,18 @@ struct SumsPlan {
 // How [T, B] is cut into workgroups: 256 environments x `frames` frames each, the frames a whole
 // number of chunks, as many slices of T as bring the grid to about kSumsTargetBlocks.
 inline void cut_frames(int64_t B, int32_t T, int64_t* grid_b, int64_t* grid_t, int32_t* frames) {
-  const int64_t nb = (B + kSumsThreads - 1) / kSumsThreads;
-  const int64_t chunks = ((int64_t)T + kSumsChunk - 1) / kSumsChunk;
+  const int64_t nb = stream_blocks(B);
+  const int64_t chunks = ((int64_t)T + kStreamChunk - 1) / kStreamChunk;
   int64_t slices = kSumsTargetBlocks / nb;
   slices = slices < 1 ? 1 : (slices > chunks ? chunks : slices);
   const int64_t per = (chunks + slices - 1) / slices;      // chunks per slice
-  *frames = (int32_t)(per * kSumsChunk > 0x7ffffff8ll ? 0x7ffffff8ll : per * kSumsChunk);
+  *frames = (int32_t)(per * kStreamChunk > 0x7ffffff8ll ? 0x7ffffff8ll : per * kStreamChunk);
   *grid_t = ((int64_t)T + *frames - 1) / *frames;
   *grid_b = nb;
 }
 
 inline bool sums_shape_ok(int64_t S, int32_t A, int64_t B, int32_t T) {
-  return S >= 1 && S <= 0x7fffffffll && A >= 1 && A <= 128 && B >= 1 && B <= (1ll << 31) && T >= 1;
+  return S >= 1 && S <= 0x7fffffffll && A >= 1 && A <= 128 && stream_shape_ok(B, T);
 }
 
 inline int32_t plan_sums(int64_t S, int32_t A, int32_t K, int64_t B, int32_t T, int32_t frac_bits,
@@ -77,12 +70,12 @@ inline int32_t plan_sums(int64_t S, int32_t A, int32_t K, int64_t B, int32_t T, 
   p->n2 = n2;
   cut_frames(B, T, &p->grid_b, &p->grid_t, &p->frames);
   const int64_t accs = S * A * (K + 1);                    // <= 2^31 * 128 * 5
-  const int64_t room = kSumsLdsBudget / 8;                 // accumulators the budget holds
+  const int64_t room = kStreamLdsBudget / 8;                 // accumulators the budget holds
   const bool fits = accs <= room;
   if (path == 1 && !fits) return CAMPX_EINVAL;
   // the flush is one global atomic per non-zero accumulator: "small" is a quarter of the frames
   // the workgroup reduces (each of which would otherwise cost K + 1 global atomics)
-  const int64_t block_frames = (int64_t)kSumsThreads * p->frames;
+  const int64_t block_frames = (int64_t)kStreamThreads * p->frames;
   const bool lds = path == 1 || (path == 0 && fits && accs * 4 <= block_frames);
   p->path = lds ? 1 : 2;
   p->copies = 1;
@@ -122,24 +115,13 @@ __device__ __forceinline__ long long quantise(float x, double scale, double lim,
   return __double2ll_rn(d);
 }
 
-// What both kernels end with: the workgroup's two counters, summed in LDS, added to the global ones.
-__device__ __forceinline__ void add_counters(u64* block, u64 a, u64 b, u64* ga, u64* gb) {
-  if (a) __hip_atomic_fetch_add(&block[0], a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  if (b) __hip_atomic_fetch_add(&block[1], b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (ga && block[0]) __hip_atomic_fetch_add(ga, block[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (gb && block[1]) __hip_atomic_fetch_add(gb, block[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
 // What a launch that does not accumulate starts with: the accumulators and both counters to zero,
 // as one kernel on the launch's stream.
-__global__ __launch_bounds__(kSumsThreads) void sums_zero_kernel(u64* __restrict__ acc, int64_t n,
+__global__ __launch_bounds__(kStreamThreads) void sums_zero_kernel(u64* __restrict__ acc, int64_t n,
                                                                  u64* __restrict__ skipped,
                                                                  u64* __restrict__ clamped) {
-  const int64_t first = (int64_t)blockIdx.x * kSumsThreads + threadIdx.x;
-  const int64_t step = (int64_t)gridDim.x * kSumsThreads;
+  const int64_t first = (int64_t)blockIdx.x * kStreamThreads + threadIdx.x;
+  const int64_t step = (int64_t)gridDim.x * kStreamThreads;
   for (int64_t i = first; i < n; i += step) acc[i] = 0;
   if (first == 0) {
     *skipped = 0;
@@ -148,76 +130,70 @@ __global__ __launch_bounds__(kSumsThreads) void sums_zero_kernel(u64* __restrict
 }
 
 template <int K, bool kActions, bool kLds>
-__global__ __launch_bounds__(kSumsThreads) void state_sums_kernel(
+__global__ __launch_bounds__(kStreamThreads) void state_sums_kernel(
     SumsParams sp, const int32_t* __restrict__ states, const int8_t* __restrict__ actions,
     u64* __restrict__ acc, u64* __restrict__ skipped, u64* __restrict__ clamped) {
   extern __shared__ __align__(16) u64 lds_acc[];     // kLds: [accs][copies]
   __shared__ u64 counters[2];
   const int tid = threadIdx.x;
   if (kLds)
-    for (int i = tid; i < sp.accs * sp.copies; i += kSumsThreads) lds_acc[i] = 0;
+    for (int i = tid; i < sp.accs * sp.copies; i += kStreamThreads) lds_acc[i] = 0;
   if (tid < 2) counters[tid] = 0;
   __syncthreads();
-  const int64_t env = (int64_t)blockIdx.x * kSumsThreads + tid;
+  const int64_t env = (int64_t)blockIdx.x * kStreamThreads + tid;
   const bool live = env < sp.B;
   const int64_t col = live ? env : 0;                // any valid column
   const int32_t t_begin = (int32_t)blockIdx.y * sp.frames;
   const int32_t t_end = sp.T - t_begin < sp.frames ? sp.T : t_begin + sp.frames;
   const uint32_t copy = (uint32_t)tid & (uint32_t)(sp.copies - 1);
   u64 n_skipped = 0, n_clamped = 0;
-  auto add = [&](int plane, uint32_t state, uint32_t action, u64 v) {
+  auto add = [&](int plane, int32_t state, int8_t action, u64 v) {
     if (kLds) {
-      const uint32_t i = (uint32_t)plane * (uint32_t)sp.bins + state * sp.A + action;
+      const uint32_t i = (uint32_t)plane * (uint32_t)sp.bins + bin_of<uint32_t>(state, action, sp.A);
       __hip_atomic_fetch_add(&lds_acc[i * (uint32_t)sp.copies + copy], v, __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_WORKGROUP);
     } else {
-      const int64_t i = plane * sp.bins + (int64_t)state * sp.A + action;
+      const int64_t i = plane * sp.bins + bin_of<int64_t>(state, action, sp.A);
       __hip_atomic_fetch_add(&acc[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   };
-  // One chunk: frames t0 .. t0 + 7.  kFull: all of them are this workgroup's; else those from
-  // t_end on are loaded from frame t_end - 1 (no branch between the loads) and left out.
-  auto chunk = [&](auto full_tag, int32_t t0) {
-    constexpr bool kFull = decltype(full_tag)::value;
-    int32_t s[kSumsChunk];
-    int8_t a[kSumsChunk];
-    float x[K ? K : 1][kSumsChunk];
+  walk_forward(t_begin, t_end, [&](auto chunk) {
+    int32_t s[kStreamChunk];
+    int8_t a[kStreamChunk];
+    float x[K ? K : 1][kStreamChunk];
 #pragma unroll
-    for (int j = 0; j < kSumsChunk; ++j) {
-      int32_t t = t0 + j;
-      if (!kFull) t = t < t_end ? t : t_end - 1;
-      s[j] = states[(int64_t)t * sp.p_states + col];
-      a[j] = kActions ? actions[(int64_t)t * sp.p_actions + col] : (int8_t)0;
+    for (int j = 0; j < kStreamChunk; ++j) {
+      const int64_t t = chunk.load_t(j);
+      s[j] = states[t * sp.p_states + col];
+      a[j] = kActions ? actions[t * sp.p_actions + col] : (int8_t)0;
 #pragma unroll
-      for (int k = 0; k < K; ++k) x[k][j] = sp.values[k][(int64_t)t * sp.p_values[k] + col];
+      for (int k = 0; k < K; ++k) x[k][j] = sp.values[k][t * sp.p_values[k] + col];
     }
 #pragma unroll
-    for (int j = 0; j < kSumsChunk; ++j) {
-      if (live && (kFull || t0 + j < t_end)) {
-        const uint32_t state = (uint32_t)s[j], action = (uint32_t)(int32_t)a[j];
-        if (state < sp.S && action < sp.A) {         // (negative ids are large as unsigned)
-          add(0, state, action, 1ull);
+    for (int j = 0; j < kStreamChunk; ++j) {
+      if (live && chunk.has(j)) {
+        if (ids_in_range(s[j], a[j], sp.S, sp.A)) {
+          add(0, s[j], a[j], 1ull);
 #pragma unroll
           for (int k = 0; k < K; ++k)
-            add(1 + k, state, action, (u64)quantise(x[k][j], sp.scale, sp.lim, sp.lim_q, n_clamped));
+            add(1 + k, s[j], a[j], (u64)quantise(x[k][j], sp.scale, sp.lim, sp.lim_q, n_clamped));
         } else {
           ++n_skipped;
         }
       }
     }
-  };
-  int32_t t = t_begin;
-  for (; t_end - t >= kSumsChunk; t += kSumsChunk) chunk(std::true_type{}, t);
-  if (t < t_end) chunk(std::false_type{}, t);
+  });
   if (kLds) {
     __syncthreads();
-    for (int i = tid; i < sp.accs; i += kSumsThreads) {
+    for (int i = tid; i < sp.accs; i += kStreamThreads) {
       u64 sum = 0;
       for (int c = 0; c < sp.copies; ++c) sum += lds_acc[i * sp.copies + c];
       if (sum) __hip_atomic_fetch_add(&acc[i], sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  add_counters(counters, n_skipped, n_clamped, skipped, clamped);
+  count_in_block(counters, n_skipped, n_clamped);
+  __syncthreads();
+  report_block_counts(counters, skipped, clamped);
 }
 
 struct LookupParams {
@@ -229,55 +205,50 @@ struct LookupParams {
 };
 
 template <bool kActions, bool kLds>
-__global__ __launch_bounds__(kSumsThreads) void table_lookup_kernel(
+__global__ __launch_bounds__(kStreamThreads) void table_lookup_kernel(
     LookupParams lp, const float* __restrict__ table, const int32_t* __restrict__ states,
     const int8_t* __restrict__ actions, float* __restrict__ out, u64* __restrict__ bad_count) {
   extern __shared__ __align__(16) float lds_table[];
   __shared__ u64 counters[2];
   const int tid = threadIdx.x;
-  if (kLds)
-    for (int i = tid; i < lp.entries; i += kSumsThreads) lds_table[i] = table[i];
+  if (kLds) stage_table(lds_table, table, (uint32_t)lp.entries);
   if (tid < 2) counters[tid] = 0;
   __syncthreads();
-  const int64_t env = (int64_t)blockIdx.x * kSumsThreads + tid;
+  const int64_t env = (int64_t)blockIdx.x * kStreamThreads + tid;
   const bool live = env < lp.B;
   const int64_t col = live ? env : 0;
   const int32_t t_begin = (int32_t)blockIdx.y * lp.frames;
   const int32_t t_end = lp.T - t_begin < lp.frames ? lp.T : t_begin + lp.frames;
   u64 n_bad = 0;
-  auto chunk = [&](auto full_tag, int32_t t0) {
-    constexpr bool kFull = decltype(full_tag)::value;
-    int32_t s[kSumsChunk];
-    int8_t a[kSumsChunk];
+  walk_forward(t_begin, t_end, [&](auto chunk) {
+    int32_t s[kStreamChunk];
+    int8_t a[kStreamChunk];
 #pragma unroll
-    for (int j = 0; j < kSumsChunk; ++j) {
-      int32_t t = t0 + j;
-      if (!kFull) t = t < t_end ? t : t_end - 1;
-      s[j] = states[(int64_t)t * lp.p_states + col];
-      a[j] = kActions ? actions[(int64_t)t * lp.p_actions + col] : (int8_t)0;
+    for (int j = 0; j < kStreamChunk; ++j) {
+      const int64_t t = chunk.load_t(j);
+      s[j] = states[t * lp.p_states + col];
+      a[j] = kActions ? actions[t * lp.p_actions + col] : (int8_t)0;
     }
     // every read of the table before the first store; a bad index reads entry 0 and shows 0.0
-    float v[kSumsChunk];
-    bool ok[kSumsChunk];
+    float v[kStreamChunk];
+    bool ok[kStreamChunk];
 #pragma unroll
-    for (int j = 0; j < kSumsChunk; ++j) {
-      const uint32_t state = (uint32_t)s[j], action = (uint32_t)(int32_t)a[j];
-      ok[j] = state < lp.S && action < lp.A;
-      const int64_t i = ok[j] ? (int64_t)state * lp.A + action : 0;
+    for (int j = 0; j < kStreamChunk; ++j) {
+      ok[j] = ids_in_range(s[j], a[j], lp.S, lp.A);
+      const int64_t i = ok[j] ? bin_of<int64_t>(s[j], a[j], lp.A) : 0;
       v[j] = kLds ? lds_table[(uint32_t)i] : table[i];
     }
 #pragma unroll
-    for (int j = 0; j < kSumsChunk; ++j) {
-      if (live && (kFull || t0 + j < t_end)) {
-        out[(int64_t)(t0 + j) * lp.p_out + env] = ok[j] ? v[j] : 0.0f;
+    for (int j = 0; j < kStreamChunk; ++j) {
+      if (live && chunk.has(j)) {
+        out[(int64_t)chunk.t(j) * lp.p_out + env] = ok[j] ? v[j] : 0.0f;
         n_bad += ok[j] ? 0 : 1;
       }
     }
-  };
-  int32_t t = t_begin;
-  for (; t_end - t >= kSumsChunk; t += kSumsChunk) chunk(std::true_type{}, t);
-  if (t < t_end) chunk(std::false_type{}, t);
-  add_counters(counters, n_bad, 0, bad_count, nullptr);
+  });
+  count_in_block(counters, n_bad, 0);
+  __syncthreads();
+  report_block_counts(counters, bad_count, nullptr);
 }
 
 // The instances, at [K][kActions][kLds] and [kActions][kLds].
@@ -328,15 +299,11 @@ int32_t campx_state_sums_launch(const CampxStateSums* s, int64_t B, int32_t T, v
   if (e != CAMPX_OK) return e;
   const int K = s->n_values;
   if (!s->actions && s->n_actions != 1) return CAMPX_EINVAL;
-  if (!aligned_to(s->states, 4) || !aligned_to(s->acc, 8) || !aligned_to(s->skipped, 8) ||
-      !aligned_to(s->clamped, 8))
-    return CAMPX_EINVAL;
-  // (a single frame never uses its pitch)
-  const int64_t least = T > 1 ? B : 0, most = (1ll << 40) / T;
-  auto pitch_ok = [&](int64_t pitch) { return pitch >= least && pitch <= most; };
-  if (!pitch_ok(s->states_pitch) || (s->actions && !pitch_ok(s->actions_pitch))) return CAMPX_EINVAL;
+  if (!aligned_to(s->states, 4) || !all_aligned(8, {s->acc, s->skipped, s->clamped})) return CAMPX_EINVAL;
+  if (!pitches_ok(B, T, {{s->states, s->states_pitch}, {s->actions, s->actions_pitch}})) return CAMPX_EINVAL;
   for (int k = 0; k < K; ++k)
-    if (!s->values[k] || !aligned_to(s->values[k], 4) || !pitch_ok(s->values_pitch[k])) return CAMPX_EINVAL;
+    if (!s->values[k] || !aligned_to(s->values[k], 4) || !pitches_ok(B, T, {{s->values[k], s->values_pitch[k]}}))
+      return CAMPX_EINVAL;
   SumsParams sp;
   memset(&sp, 0, sizeof(sp));
   sp.T = T;
@@ -363,13 +330,13 @@ int32_t campx_state_sums_launch(const CampxStateSums* s, int64_t B, int32_t T, v
   u64* clamped = reinterpret_cast<u64*>(s->clamped);
   if (!s->accumulate) {
     const int64_t n = sp.bins * (K + 1);
-    const int64_t blocks = (n + 4 * kSumsThreads - 1) / (4 * kSumsThreads);
+    const int64_t blocks = (n + 4 * kStreamThreads - 1) / (4 * kStreamThreads);
     hipLaunchKernelGGL(sums_zero_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)),
-                       dim3(kSumsThreads), 0, hs, acc, n, skipped, clamped);
+                       dim3(kStreamThreads), 0, hs, acc, n, skipped, clamped);
     const int32_t launched = launch_status();
     if (launched != CAMPX_OK) return launched;
   }
-  hipLaunchKernelGGL(kSumsKernels[K][s->actions != nullptr][plan.path == 1], grid, dim3(kSumsThreads),
+  hipLaunchKernelGGL(kSumsKernels[K][s->actions != nullptr][plan.path == 1], grid, dim3(kStreamThreads),
                      (size_t)plan.lds_bytes, hs, sp, s->states, s->actions, acc, skipped, clamped);
   return launch_status();
 }
@@ -378,12 +345,8 @@ int32_t campx_table_lookup_launch(const CampxTableLookup* l, int64_t B, int32_t 
   if (!l || !l->table || !l->states || !l->out) return CAMPX_EINVAL;
   if (!sums_shape_ok(l->n_states, l->n_actions, B, T)) return CAMPX_EINVAL;
   if (!l->actions && l->n_actions != 1) return CAMPX_EINVAL;
-  if (!aligned_to(l->table, 4) || !aligned_to(l->states, 4) || !aligned_to(l->out, 4) ||
-      !aligned_to(l->bad_count, 8))
-    return CAMPX_EINVAL;
-  const int64_t least = T > 1 ? B : 0, most = (1ll << 40) / T;
-  auto pitch_ok = [&](int64_t pitch) { return pitch >= least && pitch <= most; };
-  if (!pitch_ok(l->states_pitch) || !pitch_ok(l->out_pitch) || (l->actions && !pitch_ok(l->actions_pitch)))
+  if (!all_aligned(4, {l->table, l->states, l->out}) || !aligned_to(l->bad_count, 8)) return CAMPX_EINVAL;
+  if (!pitches_ok(B, T, {{l->states, l->states_pitch}, {l->out, l->out_pitch}, {l->actions, l->actions_pitch}}))
     return CAMPX_EINVAL;
   LookupParams lp;
   memset(&lp, 0, sizeof(lp));
@@ -396,14 +359,13 @@ int32_t campx_table_lookup_launch(const CampxTableLookup* l, int64_t B, int32_t 
   lp.p_states = l->states_pitch;
   lp.p_actions = l->actions_pitch;
   lp.p_out = l->out_pitch;
-  // staged when it fits AND costs a workgroup no more loads than the frames it looks up
   const int64_t entries = l->n_states * l->n_actions;
-  const bool lds = entries * 4 <= kSumsLdsBudget && entries <= (int64_t)kSumsThreads * lp.frames;
+  const bool lds = table_staged(entries, lp.frames);
   lp.entries = lds ? (int32_t)entries : 0;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)grid_b, (unsigned)grid_t);
   u64* bad = reinterpret_cast<u64*>(l->bad_count);
-  hipLaunchKernelGGL(kLookupKernels[l->actions != nullptr][lds], grid, dim3(kSumsThreads),
+  hipLaunchKernelGGL(kLookupKernels[l->actions != nullptr][lds], grid, dim3(kStreamThreads),
                      (size_t)(lds ? entries * 4 : 0), hs, lp, l->table, l->states, l->actions, l->out, bad);
   return launch_status();
 }

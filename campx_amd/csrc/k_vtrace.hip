@@ -11,11 +11,12 @@
 //     D = done ? delta : delta + ((c * lam) * cs) * D_next
 //     vs = v + D                  adv = rpg * ((done ? r : r + c * vs_next) - v)
 //
-// The shape is returns_kernel's: a lane per environment walks its column backwards in chunks of
-// eight frames, a chunk issues ALL its loads - coalesced along B - before its arithmetic, and
-// everything that does not depend on the frame after (r, c, w, the three clips, delta, the factor
-// of D_next) is computed off the chain, which stays one multiply and one add per frame (D).  vs
-// and adv hang off it and feed nothing back.  Stores are plain: the learner reads them next.
+// A lane per environment walks its column backwards in chunks of eight frames (streams.hip.h:
+// walk_back() and its Chunk, the head of the rule, the id test, table staging, the counters), a
+// chunk issues ALL its loads - coalesced along B - before its arithmetic, and everything that does
+// not depend on the frame after (r, c, w, the three clips, delta, the factor of D_next) is
+// computed off the chain, which stays one multiply and one add per frame (D).  vs and adv hang
+// off it and feed nothing back.  Stores are plain: the learner reads them next.
 //
 // Table mode: the ratio is a function of (state, action) on two small tables, so it is looked up
 // and divided here instead of being written as a stream (two lookups, a division: three launches
@@ -24,19 +25,13 @@
 // arithmetic.  A frame whose ids are out of range forms no address from them: its gathers are
 // not executed, its w is 0 and it is counted.  Two places for the tables: both staged in LDS once
 // per workgroup (path 1) or read through L1 / L2 (path 2); plan_vtrace() chooses by
-// table_lookup's rule and campx_vtrace_plan() shows the choice to a test without a GPU.
+// table_staged() and campx_vtrace_plan() shows the choice to a test without a GPU.
 
-#include "wide_table.hip.h"
+#include "streams.hip.h"
 
 #include <cmath>
-#include <type_traits>
 
 namespace campx_impl {
-
-constexpr int kVtraceThreads = 256;
-constexpr int kVtraceChunk = 8;
-constexpr int64_t kVtraceLdsBudget = CAMPX_SUMS_LDS_BUDGET;
-typedef unsigned long long u64;
 
 enum VtraceMode : int { kVtraceRatio = 0, kVtraceLds = 1, kVtraceGlobal = 2 };
 
@@ -46,20 +41,19 @@ struct VtracePlan {
   int64_t grid;
 };
 
-// Where the tables of a launch live.  table_lookup's rule, for both tables together: staged when
-// their bytes fit the budget AND they cost a workgroup no more loads than the frames it looks up.
+// Where the tables of a launch live: table_staged()'s rule for both tables together, a workgroup
+// looking up all T frames.
 inline int32_t plan_vtrace(int64_t Nt, int64_t Nb, int32_t A, int64_t B, int32_t T, int32_t path,
                            VtracePlan* p) {
-  if (Nt < 1 || Nb < Nt || Nb > 0x7fffffffll || Nb % Nt != 0 || A < 1 || A > 128 || B < 1 ||
-      B > (1ll << 31) || T < 1 || path < 0 || path > 2)
+  if (Nt < 1 || Nb < Nt || Nb > 0x7fffffffll || Nb % Nt != 0 || A < 1 || A > 128 ||
+      !stream_shape_ok(B, T) || path < 0 || path > 2)
     return CAMPX_EINVAL;
   const int64_t entries = (Nt + Nb) * A;                   // <= 2^32 * 128
-  const bool fits = entries * 4 <= kVtraceLdsBudget;
-  if (path == 1 && !fits) return CAMPX_EINVAL;
-  const bool lds = path == 1 || (path == 0 && fits && entries <= (int64_t)kVtraceThreads * T);
+  if (path == 1 && !table_fits_lds(entries)) return CAMPX_EINVAL;
+  const bool lds = path == 1 || (path == 0 && table_staged(entries, T));
   p->path = lds ? 1 : 2;
   p->lds_bytes = lds ? entries * 4 : 0;
-  p->grid = (B + kVtraceThreads - 1) / kVtraceThreads;
+  p->grid = stream_blocks(B);
   return CAMPX_OK;
 }
 
@@ -83,7 +77,7 @@ struct VtraceParams {
 };
 
 template <bool kDiscount, int kMode>
-__global__ __launch_bounds__(kVtraceThreads) void vtrace_kernel(
+__global__ __launch_bounds__(kStreamThreads) void vtrace_kernel(
     VtraceParams vp, const float* __restrict__ reward, const uint8_t* __restrict__ done,
     const float* __restrict__ discount, const float* __restrict__ values,
     const float* __restrict__ bootstrap, const float* __restrict__ ratio,
@@ -93,76 +87,68 @@ __global__ __launch_bounds__(kVtraceThreads) void vtrace_kernel(
   constexpr bool kTable = kMode != kVtraceRatio;
   constexpr bool kLds = kMode == kVtraceLds;
   extern __shared__ __align__(16) float lds_tables[];       // kLds: target [Nt * A], behaviour [Nb * A]
-  __shared__ u64 block_bad;
+  __shared__ u64 counters[2];                               // [0]: the frames with a bad id
   const int tid = threadIdx.x;
   const uint32_t n_target = vp.Nt * vp.A;                   // (fits 32 bits whenever it is used)
   if (kLds) {
-    const uint32_t n_all = n_target + vp.Nb * vp.A;
-    for (uint32_t i = tid; i < n_target; i += kVtraceThreads) lds_tables[i] = target[i];
-    for (uint32_t i = n_target + tid; i < n_all; i += kVtraceThreads) lds_tables[i] = behaviour[i - n_target];
+    stage_table(lds_tables, target, n_target);
+    stage_table(lds_tables + n_target, behaviour, vp.Nb * vp.A);
   }
   if (kTable) {
-    if (tid == 0) block_bad = 0;
+    if (tid < 2) counters[tid] = 0;
     __syncthreads();
   }
-  const int64_t env = (int64_t)blockIdx.x * kVtraceThreads + tid;
+  const int64_t env = (int64_t)blockIdx.x * kStreamThreads + tid;
   u64 n_bad = 0;
   if (env < vp.B) {
     const float boot = bootstrap ? bootstrap[env] : 0.0f;
     const float gamma = vp.gamma, lam = vp.lam;
     const float rho_bar = vp.rho_bar, c_bar = vp.c_bar, pg_rho_bar = vp.pg_rho_bar;
     float D = 0.0f, v_after = boot, vs_after = boot;        // of the frame after the one in hand
-    // One chunk: frames t1 - 1 down to t1 - 8.  kFull: all of them exist; else those below 0 are
-    // loaded from frame 0 (no branch between the loads; the indices too) and skipped.
-    auto chunk = [&](auto full_tag, int t1) {
-      constexpr bool kFull = decltype(full_tag)::value;
-      float r[kVtraceChunk], c[kVtraceChunk], v[kVtraceChunk], w[kVtraceChunk];
-      uint8_t d[kVtraceChunk];
-      int32_t s[kVtraceChunk];
-      int8_t a[kVtraceChunk];
-      auto frame = [&](int j) {
-        const int t = t1 - 1 - j;
-        return (int64_t)(kFull || t >= 0 ? t : 0);
-      };
+    walk_back(vp.T, [&](auto chunk) {
+      float r[kStreamChunk], c[kStreamChunk], v[kStreamChunk], w[kStreamChunk];
+      uint8_t d[kStreamChunk];
+      int32_t s[kStreamChunk];
+      int8_t a[kStreamChunk];
       // the index loads first: the gathers wait for them alone (the wait counter is in order)
       if (kTable) {
 #pragma unroll
-        for (int j = 0; j < kVtraceChunk; ++j) {
-          s[j] = states[frame(j) * vp.p_states + env];
-          a[j] = actions[frame(j) * vp.p_actions + env];
+        for (int j = 0; j < kStreamChunk; ++j) {
+          s[j] = states[chunk.load_t(j) * vp.p_states + env];
+          a[j] = actions[chunk.load_t(j) * vp.p_actions + env];
         }
       }
 #pragma unroll
-      for (int j = 0; j < kVtraceChunk; ++j) {
-        if (!kTable) w[j] = ratio[frame(j) * vp.p_ratio + env];
-        r[j] = reward[frame(j) * vp.p_reward + env];
-        d[j] = done[frame(j) * vp.p_done + env];
-        c[j] = kDiscount ? discount[frame(j) * vp.p_discount + env] : 1.0f;
-        v[j] = values[frame(j) * vp.p_values + env];
+      for (int j = 0; j < kStreamChunk; ++j) {
+        const int64_t t = chunk.load_t(j);
+        if (!kTable) w[j] = ratio[t * vp.p_ratio + env];
+        r[j] = reward[t * vp.p_reward + env];
+        d[j] = done[t * vp.p_done + env];
+        c[j] = kDiscount ? discount[t * vp.p_discount + env] : 1.0f;
+        v[j] = values[t * vp.p_values + env];
       }
       // (the scheduler otherwise pulls each index load and its range check to the front, waits
       // for them one by one, and issues the rest of the chunk's loads behind that)
       __builtin_amdgcn_sched_barrier(0);
       if (kTable) {
         // the sixteen gathers, before any arithmetic; an id out of range forms no address
-        float tg[kVtraceChunk], bh[kVtraceChunk];
-        bool ok[kVtraceChunk], all_ok = true;
+        float tg[kStreamChunk], bh[kStreamChunk];
+        bool ok[kStreamChunk], all_ok = true;
 #pragma unroll
-        for (int j = 0; j < kVtraceChunk; ++j) {
-          // (negative ids are large as unsigned; `&`: no load may hide behind a short circuit)
-          ok[j] = ((uint32_t)s[j] < vp.Nb) & ((uint32_t)(int32_t)a[j] < vp.A);
+        for (int j = 0; j < kStreamChunk; ++j) {
+          ok[j] = ids_in_range(s[j], a[j], vp.Nb, vp.A);
           all_ok = all_ok & ok[j];
         }
         auto gather = [&](int j) {
-          const uint32_t state = (uint32_t)s[j], action = (uint32_t)(int32_t)a[j];
+          const uint32_t state = (uint32_t)s[j];
           // state % Nt for a state below 2^31, by the multiplier of the launch (vtrace_modulus())
           const uint32_t member_state = state - (uint32_t)(((uint64_t)state * vp.mod_m) >> vp.mod_shift) * vp.Nt;
           if (kLds) {
-            tg[j] = lds_tables[member_state * vp.A + action];
-            bh[j] = lds_tables[n_target + state * vp.A + action];
+            tg[j] = lds_tables[bin_of<uint32_t>(member_state, a[j], vp.A)];
+            bh[j] = lds_tables[n_target + bin_of<uint32_t>(s[j], a[j], vp.A)];
           } else {
-            tg[j] = target[(int64_t)member_state * vp.A + action];
-            bh[j] = behaviour[(int64_t)state * vp.A + action];
+            tg[j] = target[bin_of<int64_t>(member_state, a[j], vp.A)];
+            bh[j] = behaviour[bin_of<int64_t>(s[j], a[j], vp.A)];
           }
         };
         // A wave whose chunk holds no bad id - every wave of a sound rollout - issues the sixteen
@@ -171,17 +157,17 @@ __global__ __launch_bounds__(kVtraceThreads) void vtrace_kernel(
         // a frame at a time, and finishes with them before it goes on.
         if (__all(all_ok)) {
 #pragma unroll
-          for (int j = 0; j < kVtraceChunk; ++j) gather(j);
+          for (int j = 0; j < kStreamChunk; ++j) gather(j);
 #pragma unroll
-          for (int j = 0; j < kVtraceChunk; ++j) w[j] = __fdiv_rn(tg[j], bh[j]);
+          for (int j = 0; j < kStreamChunk; ++j) w[j] = __fdiv_rn(tg[j], bh[j]);
         } else {
 #pragma unroll
-          for (int j = 0; j < kVtraceChunk; ++j) {
+          for (int j = 0; j < kStreamChunk; ++j) {
             w[j] = 0.0f;
             if (ok[j]) {
               gather(j);
               w[j] = __fdiv_rn(tg[j], bh[j]);
-            } else if (kFull || t1 - 1 - j >= 0) {
+            } else if (chunk.has(j)) {
               ++n_bad;
             }
           }
@@ -189,45 +175,39 @@ __global__ __launch_bounds__(kVtraceThreads) void vtrace_kernel(
       }
       // off the chain: the reward that counts, the factor, the clipped ratios, delta and the
       // factor of D_next
-      float delta[kVtraceChunk], k[kVtraceChunk], rpg[kVtraceChunk];
+      float delta[kStreamChunk], k[kStreamChunk], rpg[kStreamChunk];
 #pragma unroll
-      for (int j = 0; j < kVtraceChunk; ++j) {
-        r[j] = r[j] == r[j] ? r[j] : 0.0f;
-        c[j] = kDiscount ? __fmul_rn(gamma, c[j]) : gamma;
+      for (int j = 0; j < kStreamChunk; ++j) {
+        r[j] = reward_that_counts(r[j]);
+        c[j] = frame_factor<kDiscount>(gamma, c[j]);
         const float wj = w[j] > 0.0f ? w[j] : 0.0f;         // NaN, negatives and -0 count as +0
         const float rho = wj < rho_bar ? wj : rho_bar;
         const float cs = wj < c_bar ? wj : c_bar;
         rpg[j] = wj < pg_rho_bar ? wj : pg_rho_bar;
-        const float v_next = j == 0 ? v_after : v[j - 1];
-        const float q = d[j] ? r[j] : __fadd_rn(r[j], __fmul_rn(c[j], v_next));
+        const float q = CAMPX_UNLESS_DONE(d[j], r[j], c[j], j == 0 ? v_after : v[j - 1]);
         delta[j] = __fmul_rn(rho, __fsub_rn(q, v[j]));
         k[j] = __fmul_rn(__fmul_rn(c[j], lam), cs);
       }
       // the chain: a multiply and an add per frame; vs and adv hang off it
 #pragma unroll
-      for (int j = 0; j < kVtraceChunk; ++j) {
-        const int t = t1 - 1 - j;
-        if (kFull || t >= 0) {
-          D = d[j] ? delta[j] : __fadd_rn(delta[j], __fmul_rn(k[j], D));
+      for (int j = 0; j < kStreamChunk; ++j) {
+        if (chunk.has(j)) {
+          D = CAMPX_UNLESS_DONE(d[j], delta[j], k[j], D);
           const float vs = __fadd_rn(v[j], D);
-          const float qs = d[j] ? r[j] : __fadd_rn(r[j], __fmul_rn(c[j], vs_after));
-          vs_out[(int64_t)t * vp.p_vs + env] = vs;
-          adv_out[(int64_t)t * vp.p_adv + env] = __fmul_rn(rpg[j], __fsub_rn(qs, v[j]));
+          const float qs = CAMPX_UNLESS_DONE(d[j], r[j], c[j], vs_after);
+          vs_out[(int64_t)chunk.t(j) * vp.p_vs + env] = vs;
+          adv_out[(int64_t)chunk.t(j) * vp.p_adv + env] = __fmul_rn(rpg[j], __fsub_rn(qs, v[j]));
           vs_after = vs;
           v_after = v[j];
         }
       }
-    };
-    int t1 = vp.T;
-    for (; t1 >= kVtraceChunk; t1 -= kVtraceChunk) chunk(std::true_type{}, t1);
-    if (t1 > 0) chunk(std::false_type{}, t1);
+    });
   }
   if (kTable) {
     // counted per lane, summed in LDS, one global atomic per workgroup that met a bad frame
-    if (n_bad) __hip_atomic_fetch_add(&block_bad, n_bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    count_in_block(counters, n_bad, 0);
     __syncthreads();
-    if (tid == 0 && bad_count && block_bad)
-      __hip_atomic_fetch_add(bad_count, block_bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    report_block_counts(counters, bad_count, nullptr);
   }
 }
 
@@ -258,8 +238,7 @@ int32_t campx_vtrace_plan(int64_t n_target_states, int64_t n_behaviour_states, i
 }
 
 int32_t campx_vtrace_launch(const CampxVtrace* v, int64_t B, int32_t T, void* stream) {
-  if (!v || !v->reward || !v->done || !v->values || !v->vs || !v->advantages || B <= 0 ||
-      B > (1ll << 31) || T <= 0)
+  if (!v || !v->reward || !v->done || !v->values || !v->vs || !v->advantages || !stream_shape_ok(B, T))
     return CAMPX_EINVAL;
   const int n_table = (v->target != nullptr) + (v->behaviour != nullptr) + (v->states != nullptr) +
                       (v->actions != nullptr);
@@ -270,55 +249,32 @@ int32_t campx_vtrace_launch(const CampxVtrace* v, int64_t B, int32_t T, void* st
   if (!std::isfinite(v->gamma) || !std::isfinite(v->lam)) return CAMPX_EINVAL;
   for (const float bar : {v->rho_bar, v->c_bar, v->pg_rho_bar})
     if (!std::isfinite(bar) || bar < 0.0f) return CAMPX_EINVAL;
-  if (!aligned_to(v->reward, 4) || !aligned_to(v->discount, 4) || !aligned_to(v->values, 4) ||
-      !aligned_to(v->bootstrap, 4) || !aligned_to(v->ratio, 4) || !aligned_to(v->target, 4) ||
-      !aligned_to(v->behaviour, 4) || !aligned_to(v->states, 4) || !aligned_to(v->vs, 4) ||
-      !aligned_to(v->advantages, 4) || !aligned_to(v->bad_count, 8))
+  if (!all_aligned(4, {v->reward, v->discount, v->values, v->bootstrap, v->ratio, v->target, v->behaviour,
+                       v->states, v->vs, v->advantages}) ||
+      !aligned_to(v->bad_count, 8))
     return CAMPX_EINVAL;
-  // (a single frame never uses its pitch)
-  const int64_t least = T > 1 ? B : 0, most = (1ll << 40) / T;
-  auto pitch_ok = [&](const void* p, int64_t pitch) { return !p || (pitch >= least && pitch <= most); };
-  if (!pitch_ok(v->reward, v->reward_pitch) || !pitch_ok(v->done, v->done_pitch) ||
-      !pitch_ok(v->discount, v->discount_pitch) || !pitch_ok(v->values, v->values_pitch) ||
-      !pitch_ok(v->ratio, v->ratio_pitch) || !pitch_ok(v->states, v->states_pitch) ||
-      !pitch_ok(v->actions, v->actions_pitch) || !pitch_ok(v->vs, v->vs_pitch) ||
-      !pitch_ok(v->advantages, v->advantages_pitch))
+  if (!pitches_ok(B, T, {{v->reward, v->reward_pitch}, {v->done, v->done_pitch},
+                         {v->discount, v->discount_pitch}, {v->values, v->values_pitch},
+                         {v->ratio, v->ratio_pitch}, {v->states, v->states_pitch},
+                         {v->actions, v->actions_pitch}, {v->vs, v->vs_pitch},
+                         {v->advantages, v->advantages_pitch}}))
     return CAMPX_EINVAL;
-  VtracePlan plan;
-  memset(&plan, 0, sizeof(plan));
-  plan.grid = (B + kVtraceThreads - 1) / kVtraceThreads;
+  VtracePlan plan{kVtraceRatio, 0, stream_blocks(B)};
+  VtraceParams vp{v->gamma, v->lam, v->rho_bar, v->c_bar, v->pg_rho_bar, T, B, 0, 0, 0, 0, 0,
+                  v->reward_pitch, v->done_pitch, v->discount_pitch, v->values_pitch, v->ratio_pitch,
+                  v->states_pitch, v->actions_pitch, v->vs_pitch, v->advantages_pitch};
   if (table) {
     const int32_t e = plan_vtrace(v->n_target_states, v->n_behaviour_states, v->n_actions, B, T,
                                   v->path, &plan);
     if (e != CAMPX_OK) return e;
-  }
-  VtraceParams vp;
-  memset(&vp, 0, sizeof(vp));
-  vp.gamma = v->gamma;
-  vp.lam = v->lam;
-  vp.rho_bar = v->rho_bar;
-  vp.c_bar = v->c_bar;
-  vp.pg_rho_bar = v->pg_rho_bar;
-  vp.T = T;
-  vp.B = B;
-  if (table) {
     vp.Nt = (uint32_t)v->n_target_states;
     vp.Nb = (uint32_t)v->n_behaviour_states;
     vp.A = (uint32_t)v->n_actions;
     vtrace_modulus(vp.Nt, &vp.mod_m, &vp.mod_shift);
   }
-  vp.p_reward = v->reward_pitch;
-  vp.p_done = v->done_pitch;
-  vp.p_discount = v->discount_pitch;
-  vp.p_values = v->values_pitch;
-  vp.p_ratio = v->ratio_pitch;
-  vp.p_states = v->states_pitch;
-  vp.p_actions = v->actions_pitch;
-  vp.p_vs = v->vs_pitch;
-  vp.p_adv = v->advantages_pitch;
   hipStream_t hs = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(kVtraceKernels[v->discount != nullptr][plan.path], dim3((unsigned)plan.grid),
-                     dim3(kVtraceThreads), (size_t)plan.lds_bytes, hs, vp, v->reward, v->done,
+                     dim3(kStreamThreads), (size_t)plan.lds_bytes, hs, vp, v->reward, v->done,
                      v->discount, v->values, v->bootstrap, v->ratio, v->target, v->behaviour,
                      v->states, v->actions, v->vs, v->advantages,
                      reinterpret_cast<u64*>(v->bad_count));

@@ -1,5 +1,5 @@
 // wide_table.hip.h - what the kernels of the state-table tier (k_wide, k_policy, k_learn,
-// k_plan, k_visit, k_sums, k_states, k_window) and their launchers agree on, each said once: the
+// k_plan, k_visit, k_states, k_window) and their launchers agree on, each said once: the
 // table entry's format, the policy-row rule, the sampler's Philox block, the lazy error report -
 // and, host side, the table blob's layout and the view a launcher takes of it, the discount list,
 // the choice between one LDS workgroup and one launch per step, and how many members of a
@@ -96,8 +96,6 @@ __device__ __forceinline__ void report_bad(int32_t* count, int32_t* flag, int n)
 // ---------------------------------------------------------------------------- host side
 
 inline int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
-inline bool aligned_to(const void* p, uintptr_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 // [a, a + bytes) and [b, b + bytes) share a byte
 inline bool ranges_overlap(const void* a, const void* b, int64_t bytes) {

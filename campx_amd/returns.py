@@ -54,6 +54,53 @@ def _rows(t, name, dtype, T, B, device):
     raise ValueError('{} has row pitch {}, below its {} columns'.format(name, t.stride(0), t.shape[1]))
 
 
+def _first_stream(t, name, dtype, fn):
+  """The stream that tells a call its shape and device; returns (T, B, device)."""
+  _rows(t, name, dtype, None, None, None)
+  T, B = int(t.shape[0]), int(t.shape[1])
+  if t.device.type != 'cuda':
+    raise ValueError('{} must be on a HIP device, it is on {} (there is no CPU path)'.format(name, t.device))
+  if T > 0x7fffffff or B > 1 << 31:
+    raise ValueError('{}: [T, B] = {} is too large'.format(fn, [T, B]))
+  return T, B, t.device
+
+
+def _got(x):
+  return '{} {} on {}'.format(x.dtype, list(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__
+
+
+def _finite(x, name):
+  if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
+    raise ValueError('{} must be a finite number, got {!r}'.format(name, x))
+  return float(x)
+
+
+def _bootstrap(bootstrap, B, device):
+  if bootstrap is None:
+    return None
+  if (not torch.is_tensor(bootstrap) or bootstrap.dtype != torch.float32
+      or tuple(bootstrap.shape) != (B,) or bootstrap.device != device
+      or not bootstrap.is_contiguous()):
+    raise ValueError('bootstrap must be a contiguous float32 [{}] tensor on {}'.format(B, device))
+  return bootstrap.detach()
+
+
+def _counter(c, name, device):
+  if not torch.is_tensor(c) or c.dtype != torch.int64 or c.numel() != 1 or c.device != device:
+    raise ValueError('{} must be an int64 tensor of one element on {}'.format(name, device))
+
+
+def _out_streams(out, want, T, B, device):
+  """The dict of float32 `[T, B]` streams a call writes: a new one, or the caller's, checked."""
+  if out is None:
+    return {k: torch.empty((T, B), dtype=torch.float32, device=device) for k in want}
+  if not isinstance(out, dict):
+    raise ValueError('out must be a dict of float32 [T, B] tensors: {}'.format(list(want)))
+  for k in want:
+    _rows(out.get(k), "out['{}']".format(k), torch.float32, T, B, device)
+  return out
+
+
 def discounted_returns(reward, done, gamma, discount=None, values=None, bootstrap=None, lam=1.0,
                        out=None):
   """Returns - and, with `values`, GAE advantages - of `[T, B]` rollout streams: one launch.
@@ -85,35 +132,18 @@ def discounted_returns(reward, done, gamma, discount=None, values=None, bootstra
   Returns a dict: 'returns' float32 `[T, B]`, and 'advantages' float32 `[T, B]` only when `values`
   is given.  Argument errors raise ValueError before anything is launched.
   """
-  _rows(reward, 'reward', torch.float32, None, None, None)
-  T, B = int(reward.shape[0]), int(reward.shape[1])
-  device = reward.device
-  if device.type != 'cuda':
-    raise ValueError('reward must be on a HIP device, it is on {} (there is no CPU path)'.format(device))
+  T, B, device = _first_stream(reward, 'reward', torch.float32, 'discounted_returns')
   _rows(done, 'done', torch.uint8, T, B, device)
   if discount is not None:
     _rows(discount, 'discount', torch.float32, T, B, device)
   if values is not None:
     _rows(values, 'values', torch.float32, T, B, device)
     values = values.detach()
-  if bootstrap is not None:
-    if (not torch.is_tensor(bootstrap) or bootstrap.dtype != torch.float32
-        or tuple(bootstrap.shape) != (B,) or bootstrap.device != device
-        or not bootstrap.is_contiguous()):
-      raise ValueError('bootstrap must be a contiguous float32 [{}] tensor on {}'.format(B, device))
-    bootstrap = bootstrap.detach()
-  for name, x in (('gamma', gamma), ('lam', lam)):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
-      raise ValueError('{} must be a finite number, got {!r}'.format(name, x))
+  bootstrap = _bootstrap(bootstrap, B, device)
+  gamma, lam = _finite(gamma, 'gamma'), _finite(lam, 'lam')
   want = ('returns',) + (('advantages',) if values is not None else ())
-  if out is None:
-    out = {k: torch.empty((T, B), dtype=torch.float32, device=device) for k in want}
-  else:
-    if not isinstance(out, dict):
-      raise ValueError('out must be a dict of float32 [T, B] tensors: {}'.format(list(want)))
-    for k in want:
-      _rows(out.get(k), "out['{}']".format(k), torch.float32, T, B, device)
-  _hip.ops.returns(reward, done, float(gamma), discount, values, bootstrap, float(lam),
+  out = _out_streams(out, want, T, B, device)
+  _hip.ops.returns(reward, done, gamma, discount, values, bootstrap, lam,
                    out['returns'], out['advantages'] if values is not None else None)
   return out if set(out) == set(want) else {k: out[k] for k in want}
 
@@ -175,9 +205,7 @@ def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behavio
   the critic's regression target, and 'advantages', the policy-gradient weight with the truncated
   ratio already inside.  Argument errors raise ValueError before anything is launched.  No CPU path.
   """
-  for name, x in (('gamma', gamma), ('lam', lam)):
-    if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
-      raise ValueError('{} must be a finite number, got {!r}'.format(name, x))
+  gamma, lam = _finite(gamma, 'gamma'), _finite(lam, 'lam')
   rho_bar, c_bar = _bar(rho_bar, 'rho_bar'), _bar(c_bar, 'c_bar')
   pg_rho_bar = rho_bar if pg_rho_bar is None else _bar(pg_rho_bar, 'pg_rho_bar')
   _count_arg(path, 'path', 0, 2)
@@ -185,24 +213,13 @@ def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behavio
   given = sum(x is not None for x in tables)
   if given not in (0, 4) or (given == 4) == (ratio is not None):
     raise ValueError('give ratio, or target, behaviour, states and actions together - not both, not neither')
-  _rows(reward, 'reward', torch.float32, None, None, None)
-  T, B = int(reward.shape[0]), int(reward.shape[1])
-  device = reward.device
-  if device.type != 'cuda':
-    raise ValueError('reward must be on a HIP device, it is on {} (there is no CPU path)'.format(device))
-  if T > 0x7fffffff or B > 1 << 31:
-    raise ValueError('vtrace_returns: [T, B] = {} is too large'.format([T, B]))
+  T, B, device = _first_stream(reward, 'reward', torch.float32, 'vtrace_returns')
   _rows(done, 'done', torch.uint8, T, B, device)
   _rows(values, 'values', torch.float32, T, B, device)
   if discount is not None:
     _rows(discount, 'discount', torch.float32, T, B, device)
     discount = discount.detach()
-  if bootstrap is not None:
-    if (not torch.is_tensor(bootstrap) or bootstrap.dtype != torch.float32
-        or tuple(bootstrap.shape) != (B,) or bootstrap.device != device
-        or not bootstrap.is_contiguous()):
-      raise ValueError('bootstrap must be a contiguous float32 [{}] tensor on {}'.format(B, device))
-    bootstrap = bootstrap.detach()
+  bootstrap = _bootstrap(bootstrap, B, device)
   if ratio is not None:
     _rows(ratio, 'ratio', torch.float32, T, B, device)
     ratio = ratio.detach()
@@ -211,8 +228,7 @@ def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behavio
       if (not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or x.device != device
           or not x.is_contiguous() or x.shape[0] < 1 or not 1 <= x.shape[1] <= 128):
         raise ValueError('{} must be a contiguous float32 [n_states, n_actions <= 128] tensor on {}, got {}'.format(
-            name, device, '{} {} on {}'.format(x.dtype, list(x.shape), x.device) if torch.is_tensor(x)
-            else type(x).__name__))
+            name, device, _got(x)))
     Nt, Nb, A = int(target.shape[0]), int(behaviour.shape[0]), int(target.shape[1])
     if behaviour.shape[1] != A or Nb % Nt != 0 or Nb > 0x7fffffff:
       raise ValueError('behaviour must be [Nb, {}] with Nb a multiple of target\'s {} rows and at most '
@@ -223,19 +239,12 @@ def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behavio
       raise ValueError('path=1: tables of {} + {} entries of 4 bytes do not fit the LDS budget of {} bytes'.format(
           Nt * A, Nb * A, _hip.SUMS_LDS_BUDGET))
     target, behaviour = target.detach(), behaviour.detach()
-  if bad_count is not None and (not torch.is_tensor(bad_count) or bad_count.dtype != torch.int64
-                                or bad_count.numel() != 1 or bad_count.device != device):
-    raise ValueError('bad_count must be an int64 tensor of one element on {}'.format(device))
+  if bad_count is not None:
+    _counter(bad_count, 'bad_count', device)
   want = ('vs', 'advantages')
-  if out is None:
-    out = {k: torch.empty((T, B), dtype=torch.float32, device=device) for k in want}
-  else:
-    if not isinstance(out, dict):
-      raise ValueError('out must be a dict of float32 [T, B] tensors: {}'.format(list(want)))
-    for k in want:
-      _rows(out.get(k), "out['{}']".format(k), torch.float32, T, B, device)
-  _hip.ops.vtrace(reward.detach(), done, float(gamma), values.detach(), ratio, target, behaviour, states,
-                  actions, discount, bootstrap, float(lam), rho_bar, c_bar, pg_rho_bar, bad_count,
+  out = _out_streams(out, want, T, B, device)
+  _hip.ops.vtrace(reward.detach(), done, gamma, values.detach(), ratio, target, behaviour, states,
+                  actions, discount, bootstrap, lam, rho_bar, c_bar, pg_rho_bar, bad_count,
                   int(path), out['vs'], out['advantages'])
   return out if set(out) == set(want) else {k: out[k] for k in want}
 
@@ -244,13 +253,7 @@ def vtrace_returns(reward, done, gamma, values, ratio=None, target=None, behavio
 
 def _sums_streams(states, actions, fn):
   """Checks the index streams of `sum_by_state()` / `table_lookup()`; returns (T, B, device)."""
-  _rows(states, 'states', torch.int32, None, None, None)
-  T, B = int(states.shape[0]), int(states.shape[1])
-  device = states.device
-  if device.type != 'cuda':
-    raise ValueError('states must be on a HIP device, it is on {} (there is no CPU path)'.format(device))
-  if T > 0x7fffffff or B > 1 << 31:
-    raise ValueError('{}: [T, B] = {} is too large'.format(fn, [T, B]))
+  T, B, device = _first_stream(states, 'states', torch.int32, fn)
   if actions is not None:
     _rows(actions, 'actions', torch.int8, T, B, device)
   return T, B, device
@@ -342,13 +345,9 @@ def sum_by_state(states, actions=None, values=(), n_states=None, n_actions=5, fr
     if (not torch.is_tensor(raw) or raw.dtype != torch.int64 or tuple(raw.shape) != shape
         or raw.device != device or not raw.is_contiguous()):
       raise ValueError("out['raw'] must be a contiguous int64 {} tensor on {}, got {}".format(
-          list(shape), device,
-          '{} {} on {}'.format(raw.dtype, list(raw.shape), raw.device) if torch.is_tensor(raw)
-          else type(raw).__name__))
+          list(shape), device, _got(raw)))
     for k in ('skipped', 'clamped'):
-      c = out.get(k)
-      if (not torch.is_tensor(c) or c.dtype != torch.int64 or c.numel() != 1 or c.device != device):
-        raise ValueError("out['{}'] must be an int64 tensor of one element on {}".format(k, device))
+      _counter(out.get(k), "out['{}']".format(k), device)
   raw = out['raw']
   _hip.ops.state_sums(states, actions, values, S, A, int(frac_bits), bool(accumulate), int(path),
                       raw, out['skipped'], out['clamped'])
@@ -412,10 +411,7 @@ def table_lookup(table, states, actions=None, bad_count=None):
       or table.device != device or not table.is_contiguous() or table.numel() < 1
       or table.shape[0] > 0x7fffffff or (want_dim == 2 and table.shape[1] > 128)):
     raise ValueError('table must be a contiguous float32 {} tensor on {}, got {}'.format(
-        '[n_states]' if actions is None else '[n_states, n_actions <= 128]', device,
-        '{} {} on {}'.format(table.dtype, list(table.shape), table.device) if torch.is_tensor(table)
-        else type(table).__name__))
-  if bad_count is not None and (not torch.is_tensor(bad_count) or bad_count.dtype != torch.int64
-                                or bad_count.numel() != 1 or bad_count.device != device):
-    raise ValueError('bad_count must be an int64 tensor of one element on {}'.format(device))
+        '[n_states]' if actions is None else '[n_states, n_actions <= 128]', device, _got(table)))
+  if bad_count is not None:
+    _counter(bad_count, 'bad_count', device)
   return _TableLookup.apply(table, states, actions, bad_count)
