@@ -43,6 +43,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_state_sums_launch', 'campx_state_sums_plan', 'campx_table_lookup_launch',
            'campx_wide_sweeps_plan', 'campx_wide_sweeps_launch',
            'campx_wide_population_sweeps_plan', 'campx_wide_population_sweeps_launch',
+           'campx_wide_population_solve_plan', 'campx_wide_population_solve_launch',
            'campx_wide_visit_plan', 'campx_wide_visit_launch',
            'campx_wide_visit_population_plan', 'campx_wide_visit_population_launch',
            'campx_check_actions_launch',
@@ -323,6 +324,11 @@ def _load():
   lib.campx_wide_population_sweeps_launch.restype = i32
   lib.campx_wide_population_sweeps_launch.argtypes = [wide_p, vp, vp, i64, vp, ctypes.c_float, vp, vp, vp,
                                                       vp, vp, vp, vp, vp, i32, i32, vp]
+  lib.campx_wide_population_solve_plan.restype = i32
+  lib.campx_wide_population_solve_plan.argtypes = [i64, i64, i32, i32, i64, i64, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_population_solve_launch.restype = i32
+  lib.campx_wide_population_solve_launch.argtypes = [wide_p, vp, vp, vp, i64, vp, ctypes.c_float, vp, vp, vp,
+                                                     vp, vp, vp, vp, vp, vp, i32, i32, vp]
   lib.campx_wide_visit_plan.restype = i32
   lib.campx_wide_visit_plan.argtypes = [i64, i64, i32, ctypes.POINTER(i64)]
   lib.campx_wide_visit_launch.restype = i32
@@ -385,7 +391,7 @@ ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
             'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'wide_learn_shared', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'vtrace', 'state_sums', 'table_lookup', 'wide_sweeps',
-            'wide_population_sweeps', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
+            'wide_population_sweeps', 'wide_population_solve', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
 
 
 def check(code, what):

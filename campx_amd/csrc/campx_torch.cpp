@@ -28,6 +28,7 @@
 //   campx::table_lookup             table[states, actions] of a rollout's streams
 //   campx::wide_sweeps              policy evaluation / value iteration sweeps over the state table
 //   campx::wide_population_sweeps   the policy-evaluation sweeps for a population of policies
+//   campx::wide_population_solve    either reduction for a population, a reward table per member
 //   campx::wide_visit               exact state visitation of a policy over the state table
 //   campx::wide_visit_population    the same for a population of policies
 //   campx::onehot_to_ids / campx::check_actions   action-format helpers
@@ -1278,11 +1279,12 @@ void table_lookup(const Tensor& table, const Tensor& states, const OptTensor& ac
            "campx_table_lookup_launch");
 }
 
-// Both sweeps ops.  `what` names the op in its messages; `members`: `policy` is a population's
-// [P, n_states, 5] and every per-member shape has that leading P.
-void sweeps(const char* what, bool members, const Tensor& spec_host, const Tensor& tables,
-            const OptTensor& policy, const OptTensor& reward, double gamma, const OptTensor& gammas,
-            const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
+// The sweeps ops.  `what` names the op in its messages; `members`: `policy` is a population's
+// [P, n_states, 5] and every per-member shape has that leading P; `solve`: the population's
+// policies may be missing (the greedy reduction, P from `values_out`) and `rewards` given.
+void sweeps(const char* what, bool members, bool solve, const Tensor& spec_host, const Tensor& tables,
+            const OptTensor& policy, const OptTensor& rewards, const OptTensor& reward, double gamma,
+            const OptTensor& gammas, const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
             const OptTensor& q, const OptTensor& greedy, Tensor& residual,
             const OptTensor& bad_rows, const OptTensor& bad_flag, int64_t path) {
   const CampxWideSpec* hs = wide_spec(spec_host);
@@ -1291,9 +1293,15 @@ void sweeps(const char* what, bool members, const Tensor& spec_host, const Tenso
   const c10::Device dev = values_out.device();
   const int64_t S = hs->n_states, A = CAMPX_N_ACTIONS;
   want_wide_tables(tables, hs, dev);
-  TORCH_CHECK(!members || (policy->dim() == 3 && policy->size(0) >= 1), what,
+  TORCH_CHECK(!members || solve || (policy->dim() == 3 && policy->size(0) >= 1), what,
               ": policies must be float32 [P, n_states, 5], P >= 1");
-  const int64_t P = members ? policy->size(0) : 1;
+  TORCH_CHECK(!solve || (values_out.dim() == 2 && values_out.size(0) >= 1), what,
+              ": values_out must be float32 [P, n_states], P >= 1");
+  TORCH_CHECK(!rewards.has_value() || !reward.has_value(), what,
+              ": give rewards (one table per member) or reward (one for all), not both");
+  TORCH_CHECK(!solve || !policy.has_value() || !greedy.has_value(), what,
+              ": greedy is written by the greedy reduction only (policies None)");
+  const int64_t P = solve ? values_out.size(0) : members ? policy->size(0) : 1;
   const auto each = [&](std::initializer_list<int64_t> shape) {      // ... of every member
     std::vector<int64_t> all(members ? 1 : 0, P);
     all.insert(all.end(), shape);
@@ -1301,12 +1309,13 @@ void sweeps(const char* what, bool members, const Tensor& spec_host, const Tenso
   };
   if (policy.has_value()) want(*policy, members ? "policies" : "policy", at::kFloat, dev, each({S, A}));
   if (reward.has_value()) want(*reward, "reward", at::kFloat, dev, {S, A});
+  if (rewards.has_value()) want(*rewards, "rewards", at::kFloat, dev, each({S, A}));
   if (gammas.has_value()) want(*gammas, "gammas", at::kFloat, dev, {P});
   want(values_in, "values_in", at::kFloat, dev, each({S}));
   want(values_out, "values_out", at::kFloat, dev, each({S}));
   if (scratch.has_value()) want(*scratch, "scratch", at::kFloat, dev, each({S}));
   if (q.has_value()) want(*q, "q", at::kFloat, dev, each({S, A}));
-  if (greedy.has_value()) want(*greedy, "greedy", at::kChar, dev, {S});
+  if (greedy.has_value()) want(*greedy, "greedy", at::kChar, dev, each({S}));
   if (members) {
     TORCH_CHECK(residual.dim() == 2 && residual.size(0) >= 1 && residual.size(0) <= (1 << 20), what,
                 ": residual must be float32 [sweeps, P], 1 <= sweeps <= 2^20");
@@ -1324,7 +1333,15 @@ void sweeps(const char* what, bool members, const Tensor& spec_host, const Tenso
   float* v_out = reinterpret_cast<float*>(values_out.data_ptr());
   float* res = reinterpret_cast<float*>(residual.data_ptr());
   const int32_t n_sweeps = (int32_t)residual.size(0);
-  if (members)
+  if (solve)
+    check_ok(campx_wide_population_solve_launch(
+                 hs, tables.data_ptr(), opt_ptr<const float>(policy), opt_ptr<const float>(rewards), P,
+                 opt_ptr<const float>(reward), (float)gamma, opt_ptr<const float>(gammas), v_in, v_out,
+                 opt_ptr<float>(scratch), opt_ptr<float>(q), opt_ptr<int8_t>(greedy), res,
+                 opt_ptr<int32_t>(bad_rows), flag_ptr(bad_flag, dev), n_sweeps, (int32_t)path,
+                 current_stream()),
+             "campx_wide_population_solve_launch");
+  else if (members)
     check_ok(campx_wide_population_sweeps_launch(
                  hs, tables.data_ptr(), opt_ptr<const float>(policy), P, opt_ptr<const float>(reward),
                  (float)gamma, opt_ptr<const float>(gammas), v_in, v_out, opt_ptr<float>(scratch),
@@ -1348,8 +1365,8 @@ void wide_sweeps(const Tensor& spec_host, const Tensor& tables, const OptTensor&
                  const OptTensor& scratch, const OptTensor& q, const OptTensor& greedy,
                  Tensor& residual, const OptTensor& bad_rows, const OptTensor& bad_flag,
                  int64_t path) {
-  sweeps("campx::wide_sweeps", false, spec_host, tables, policy, reward, gamma, std::nullopt, values_in,
-         values_out, scratch, q, greedy, residual, bad_rows, bad_flag, path);
+  sweeps("campx::wide_sweeps", false, false, spec_host, tables, policy, std::nullopt, reward, gamma,
+         std::nullopt, values_in, values_out, scratch, q, greedy, residual, bad_rows, bad_flag, path);
 }
 
 // The policy-evaluation sweeps for a population (campx_wide_population_sweeps_launch): `policies`
@@ -1360,8 +1377,23 @@ void wide_population_sweeps(const Tensor& spec_host, const Tensor& tables, const
                             const Tensor& values_in, Tensor& values_out, const OptTensor& scratch,
                             const OptTensor& q, Tensor& residual, const OptTensor& bad_rows,
                             const OptTensor& bad_flag, int64_t path) {
-  sweeps("campx::wide_population_sweeps", true, spec_host, tables, policies, reward, gamma, gammas,
-         values_in, values_out, scratch, q, std::nullopt, residual, bad_rows, bad_flag, path);
+  sweeps("campx::wide_population_sweeps", true, false, spec_host, tables, policies, std::nullopt, reward,
+         gamma, gammas, values_in, values_out, scratch, q, std::nullopt, residual, bad_rows, bad_flag,
+         path);
+}
+
+// Either reduction for a population (campx_wide_population_solve_launch): `policies` float32
+// [P, n_states, 5] or None for value iteration, `rewards` float32 [P, n_states, 5] - a reward table
+// per member - or None, `reward` the one table for all or None (not beside `rewards`), `greedy` int8
+// [P, n_states] or None (not beside `policies`); the rest as campx::wide_population_sweeps.
+void wide_population_solve(const Tensor& spec_host, const Tensor& tables, const OptTensor& policies,
+                           const OptTensor& rewards, const OptTensor& reward, double gamma,
+                           const OptTensor& gammas, const Tensor& values_in, Tensor& values_out,
+                           const OptTensor& scratch, const OptTensor& q, const OptTensor& greedy,
+                           Tensor& residual, const OptTensor& bad_rows, const OptTensor& bad_flag,
+                           int64_t path) {
+  sweeps("campx::wide_population_solve", true, true, spec_host, tables, policies, rewards, reward, gamma,
+         gammas, values_in, values_out, scratch, q, greedy, residual, bad_rows, bad_flag, path);
 }
 
 // Both visitation ops.  `what` names the op in its messages; `members`: `policy` is a population's
@@ -1525,7 +1557,8 @@ const char* const kOps[] = {
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
     "wide_learn", "wide_learn_shared", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
-    "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_visit", "wide_visit_population",
+    "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_population_solve", "wide_visit",
+    "wide_visit_population",
     "onehot_to_ids",
     "check_actions"};
 
@@ -1643,6 +1676,11 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(c!)? q, Tensor(d!) residual, Tensor(e!)? bad_rows, Tensor(f!)? bad_flag, "
       "int path) -> ()");
   m.def(
+      "wide_population_solve(Tensor spec_host, Tensor tables, Tensor? policies, Tensor? rewards, "
+      "Tensor? reward, float gamma, Tensor? gammas, Tensor values_in, Tensor(a!) values_out, "
+      "Tensor(b!)? scratch, Tensor(c!)? q, Tensor(d!)? greedy, Tensor(e!) residual, "
+      "Tensor(f!)? bad_rows, Tensor(g!)? bad_flag, int path) -> ()");
+  m.def(
       "wide_visit(Tensor spec_host, Tensor tables, Tensor policy, Tensor? start, bool restart, "
       "Tensor(a!) visits, Tensor(b!) finished, Tensor(c!) final_mass, Tensor(d!)? per_frame, "
       "Tensor(e!) counts, Tensor(f!)? scratch, Tensor(g!)? bad_rows, Tensor(h!)? bad_flag, "
@@ -1681,6 +1719,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("table_lookup", &table_lookup);
   m.impl("wide_sweeps", &wide_sweeps);
   m.impl("wide_population_sweeps", &wide_population_sweeps);
+  m.impl("wide_population_solve", &wide_population_solve);
   m.impl("wide_visit", &wide_visit);
   m.impl("wide_visit_population", &wide_visit_population);
   m.impl("onehot_to_ids", &onehot_to_ids);

@@ -558,10 +558,21 @@ class Engine(object):
     NotImplementedError (`use_state_table()` before `its_showtime()` puts a game on this one)."""
     return self._batched('evaluate_policy').evaluate_policy(policy, gamma, sweeps, **kwargs)
 
-  def population_sweep_buffers(self, P, sweeps, want_q=False):
-    """State-table tier only: the dict of `evaluate_population(out=...)`, allocated once.  See
+  def population_sweep_buffers(self, P, sweeps, want_q=False, greedy=False):
+    """State-table tier only: the dict of `evaluate_population(out=...)` or (`greedy=True`) of
+    `value_iteration_population(out=...)`, allocated once.  See
     `wide.WideGame.population_sweep_buffers`."""
-    return self._batched('population_sweep_buffers').population_sweep_buffers(P, sweeps, want_q=want_q)
+    return self._batched('population_sweep_buffers').population_sweep_buffers(
+        P, sweeps, want_q=want_q, greedy=greedy)
+
+  def value_iteration_population(self, gamma, sweeps, **kwargs):
+    """State-table tier only: `value_iteration()` for P rewards (`rewards` float32
+    `[P, n_states, 5]`) or P gammas (a float32 `[P]` tensor) in one launch; member m of 'values',
+    'greedy' `[P, n_states]`, 'residual' `[sweeps, P]` and 'q' is bit for bit what
+    `value_iteration()` gives for `rewards[m]` and `gamma[m]` alone.  See
+    `wide.WideGame.value_iteration_population`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    return self._batched('value_iteration_population').value_iteration_population(gamma, sweeps, **kwargs)
 
   def evaluate_population(self, policies, gamma, sweeps, **kwargs):
     """State-table tier only: `evaluate_policy()` for P policies in one launch, `policies` float32

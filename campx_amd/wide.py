@@ -31,7 +31,8 @@ from . import tabulate
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
     'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
-    'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'visitation_buffers',
+    'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'value_iteration_population',
+    'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
 
 
@@ -804,11 +805,15 @@ class WideGame(fused.FusedGame):
       out['greedy'] = torch.zeros((self.n_states,), dtype=torch.int8, device=self.device)
     return out
 
-  def _sweeps(self, P, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path):
+  def _sweeps(self, P, policy, gamma, sweeps, values, reward, want_q, tol, check_every, out, path,
+              rewards=None):
     """The body of `evaluate_policy()`, of `value_iteration()` (`policy` None) and - `P` not None,
-    every per-member shape with that leading P - of `evaluate_population()`, their policy checked."""
+    every per-member shape with that leading P - of `evaluate_population()` and of
+    `value_iteration_population()` (`policy` None), their policy checked.  `rewards`: a reward
+    table per member, a population's only."""
     S, A, dev = self.n_states, gamespec.N_ACTIONS, self.device
     greedy, members = policy is None, P is not None
+    solve = members and (greedy or rewards is not None)     # campx::wide_population_solve's forms
     lead = (P,) if members else ()
     gammas = None
     if members and torch.is_tensor(gamma):
@@ -828,6 +833,11 @@ class WideGame(fused.FusedGame):
     if reward is not None and not self._tensor_ok(reward, torch.float32, (S, A)):
       raise ValueError('reward must be a contiguous float32 [{}, {}] tensor (n_states x actions) on '
                        '{}, or None for the table\'s own'.format(S, A, dev))
+    if rewards is not None and reward is not None:
+      raise ValueError('give rewards (one table per member) or reward (one for all members), not both')
+    if rewards is not None and not self._tensor_ok(rewards, torch.float32, (P, S, A)):
+      raise ValueError('rewards must be a contiguous float32 [{}, {}, {}] tensor (members x n_states x '
+                       'actions) on {}, or None'.format(P, S, A, dev))
     if tol is not None and (isinstance(tol, bool) or not isinstance(tol, (int, float))
                             or not math.isfinite(tol) or tol < 0):
       raise ValueError('tol must be a finite number >= 0 or None, got {!r}'.format(tol))
@@ -837,8 +847,14 @@ class WideGame(fused.FusedGame):
     if members:
       if self._n_cus is None:
         self._n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
-      planned = self._planned_path(path, _hip.lib.campx_wide_population_sweeps_plan, P, override,
-                                   n_cus=self._n_cus, words=5)
+      if solve:
+        planned = self._planned_path(path, _hip.lib.campx_wide_population_solve_plan, P,
+                                     0 if greedy else 1, 0 if rewards is None else 1,
+                                     what='one member of {} states with its rewards'.format(S)
+                                     if rewards is not None else None, n_cus=self._n_cus, words=5)
+      else:
+        planned = self._planned_path(path, _hip.lib.campx_wide_population_sweeps_plan, P, override,
+                                     n_cus=self._n_cus, words=5)
     else:
       planned = self._planned_path(path, _hip.lib.campx_wide_sweeps_plan, 0 if greedy else 1, override)
     want = [('values', torch.float32, lead + (S,)), ('residual', torch.float32, (sweeps,) + lead)]
@@ -847,13 +863,14 @@ class WideGame(fused.FusedGame):
     if want_q:
       want.append(('q', torch.float32, lead + (S, A)))
     if greedy:
-      want.append(('greedy', torch.int8, (S,)))
+      want.append(('greedy', torch.int8, lead + (S,)))
     if out is None:
-      out = (self.population_sweep_buffers(P, sweeps, want_q) if members
+      out = (self.population_sweep_buffers(P, sweeps, want_q, greedy=greedy) if members
              else self.sweep_buffers(sweeps, want_q, greedy))
     else:
       self._check_out(out, want,
-                      'population_sweep_buffers({}, {}, want_q={})'.format(P, sweeps, bool(want_q))
+                      'population_sweep_buffers({}, {}, want_q={}{})'.format(
+                          P, sweeps, bool(want_q), ', greedy=True' if greedy else '')
                       if members else
                       'sweep_buffers({}, want_q={}, greedy={})'.format(sweeps, bool(want_q), greedy))
       if values is not None and out.get('scratch') is not None and \
@@ -861,6 +878,8 @@ class WideGame(fused.FusedGame):
         raise ValueError('values must not be out[\'scratch\']')
     if reward is not None:
       reward = reward.detach()
+    if rewards is not None:
+      rewards = rewards.detach()
     v_out = out['values']
     if values is None:
       v_out.zero_()
@@ -878,7 +897,11 @@ class WideGame(fused.FusedGame):
       tail = (residual[ran:ran + n], bad_rows if count else None, self._bad_flag if count else None,
               path)
       q = out['q'] if want_q else None
-      if members:
+      if solve:
+        _hip.ops.wide_population_solve(self._spec_host, self._tables, policy, rewards, reward, float(gamma),
+                                       gammas, v_in, v_out, out.get('scratch'), q,
+                                       out['greedy'] if greedy else None, *tail)
+      elif members:
         _hip.ops.wide_population_sweeps(*head, gammas, v_in, v_out, out.get('scratch'), q, *tail)
       else:
         _hip.ops.wide_sweeps(*head, v_in, v_out, out.get('scratch'), q,
@@ -964,19 +987,26 @@ class WideGame(fused.FusedGame):
       raise ValueError('{}(): P * n_states * 5 = {} x {} x 5 must be at most '
                        '2^31 - 1; {} the population in parts'.format(call, P, S, verb))
 
-  def population_sweep_buffers(self, P, sweeps, want_q=False):
-    """Allocate the dict of `evaluate_population(out=...)` once: 'values' float32 [P, S], 'residual'
+  def population_sweep_buffers(self, P, sweeps, want_q=False, greedy=False):
+    """Allocate the dict of `evaluate_population(out=...)` or - `greedy=True` - of
+    `value_iteration_population(out=...)` once: 'values' float32 [P, S], 'residual'
     float32 [sweeps, P], 'scratch' float32 [P, S] (the second value array of the
     one-launch-per-sweep path), 'gamma' float32 [P] (for the caller to fill and pass as `gamma`; a
-    number needs none) and with `want_q` 'q' float32 [P, S, 5]."""
+    number needs none), with `want_q` 'q' float32 [P, S, 5] and with `greedy` 'greedy' int8 [P, S]
+    and 'rewards' float32 [P, S, 5] (for the caller to fill and pass as `rewards`; neither call
+    reads it from here)."""
     self._check_members(P)
     self._check_count('sweeps', sweeps)
     out = self._sweep_buffers((P,), sweeps, want_q)
     out['gamma'] = torch.zeros((P,), dtype=torch.float32, device=self.device)
+    if greedy:
+      out['greedy'] = torch.zeros((P, self.n_states), dtype=torch.int8, device=self.device)
+      out['rewards'] = torch.zeros((P, self.n_states, gamespec.N_ACTIONS), dtype=torch.float32,
+                                   device=self.device)
     return out
 
   def evaluate_population(self, policies, gamma, sweeps, values=None, reward=None, want_q=False,
-                          out=None, path=0):
+                          out=None, path=0, rewards=None):
     """`evaluate_policy()` for a POPULATION of P policies in one launch: member m of every result
     is, bit for bit, `evaluate_policy(policies[m], gamma[m], sweeps, ...)` - the exact score that
     population-based training, an evolution strategy, a sweep over gammas or a set of seeds selects
@@ -999,6 +1029,13 @@ class WideGame(fused.FusedGame):
       values: float32 `[P, n_states]` to start from, or None for zeros.  n sweeps and then m more
           from the returned 'values' equal n + m sweeps, bit for bit.
       reward: float32 `[n_states, 5]` used instead of the table's rewards by ALL members.
+      rewards: contiguous float32 `[P, n_states, 5]`, a reward table PER MEMBER (NaN counts as 0):
+          member m is then `evaluate_policy(policies[m], gamma[m], sweeps, reward=rewards[m])`, bit
+          for bit (`campx::wide_population_solve`).  Not beside `reward`.  One policy under P
+          rewards - its successor representation from S one-hot rewards, its reward value and its
+          hidden performance together - is no form of its own:
+          `policies = policy.expand(P, -1, -1).contiguous()` serves.  P equal rows give the bits of
+          the shared `reward=` call.
       want_q: also return 'q'.
       out: a dict from `population_sweep_buffers(P, sweeps, want_q)`, overwritten; the call then
           allocates nothing and is capturable in a HIP graph ('scratch' is needed on path 2 only,
@@ -1014,7 +1051,65 @@ class WideGame(fused.FusedGame):
     """
     P = self._check_population(policies, split=False)
     self._check_members(P)
-    return self._sweeps(P, policies.detach(), gamma, sweeps, values, reward, want_q, None, 32, out, path)
+    return self._sweeps(P, policies.detach(), gamma, sweeps, values, reward, want_q, None, 32, out, path,
+                        rewards=rewards)
+
+  def value_iteration_population(self, gamma, sweeps, rewards=None, P=None, values=None, want_q=False,
+                                 out=None, path=0):
+    """`value_iteration()` for a POPULATION of P rewards or gammas in one launch: member m of every
+    result is, bit for bit, `value_iteration(gamma[m], sweeps, values=values[m], reward=rewards[m])`
+    - 'values', 'q', 'greedy' and every 'residual' - without a launch per member (csrc/k_plan.hip,
+    `campx::wide_population_solve`).  It is what a reward-design question asks: which of P rewards
+    - a sweep of `r + lambda * perf`, shaping terms, the candidates of an inverse-RL step - or
+    which of P gammas makes the reward-optimal policy good.  The rule is `evaluate_policy()`'s with
+    the greedy reduction; no result depends on P, on the order of the members, on how members are
+    packed into workgroups or on the path.
+
+    Args:
+      gamma: a finite number for every member, or a contiguous float32 `[P]` tensor on the game's
+          device.  A tensor is NEVER read on the host, as in `evaluate_population()`.
+      sweeps: how many sweeps to run, 1 .. 2^20.  There is no `tol`, for `evaluate_population()`'s
+          reason.
+      rewards: contiguous float32 `[P, n_states, 5]` on the game's device, a reward table per
+          member (NaN counts as 0), or None: the table's own rewards for every member.
+      P: the members, where neither `rewards` nor a `gamma` tensor says it.  What is given must
+          agree; `P * n_states * 5 <= 2^31 - 1`.  With none of the three there is no population:
+          ValueError, `value_iteration()` is the call.
+      values: float32 `[P, n_states]` to start from, or None for zeros.  n sweeps and then m more
+          from the returned 'values' equal n + m sweeps, bit for bit.
+      want_q: also return 'q'.
+      out: a dict from `population_sweep_buffers(P, sweeps, want_q, greedy=True)`, overwritten; the
+          call then allocates nothing and is capturable in a HIP graph ('scratch' is needed on path
+          2 only, 'gamma' and 'rewards' never).
+      path: as `evaluate_population()`'s; whether one member fits LDS depends on the form - its
+          rewards take 20 bytes a state there.  Both give the same bits.
+
+    Returns a dict: 'values' float32 `[P, n_states]`; 'greedy' int8 `[P, n_states]`, per member and
+    state the lowest action that attains the maximum of the returned q; 'residual' float32
+    `[sweeps, P]`; 'sweeps'; with `want_q` 'q' float32 `[P, n_states, 5]`.  Argument errors raise
+    ValueError before anything is launched.
+    """
+    said = []
+    if rewards is not None:
+      if not torch.is_tensor(rewards) or rewards.dim() != 3 or rewards.shape[0] < 1:
+        raise ValueError('rewards must be a contiguous float32 [P, {}, {}] tensor (members x n_states x '
+                         'actions) on {}, or None'.format(self.n_states, gamespec.N_ACTIONS, self.device))
+      said.append(('rewards', int(rewards.shape[0])))
+    if torch.is_tensor(gamma) and gamma.dim() == 1:
+      said.append(('gamma', int(gamma.shape[0])))
+    if P is not None:
+      if isinstance(P, bool) or not isinstance(P, int):
+        raise ValueError('P must be an int >= 1 or None, got {!r}'.format(P))
+      said.append(('P', P))
+    if not said:
+      raise ValueError('value_iteration_population(): nothing says how many members there are (rewards, '
+                       'a gamma tensor or P); value_iteration() is the call for one reward and one gamma')
+    if any(n != said[0][1] for _, n in said[1:]):
+      raise ValueError('value_iteration_population(): the members disagree: {}'.format(
+          ', '.join('{} says {}'.format(k, n) for k, n in said)))
+    P = said[0][1]
+    self._check_members(P, call='value_iteration_population', verb='solve')
+    return self._sweeps(P, None, gamma, sweeps, values, None, want_q, None, 32, out, path, rewards=rewards)
 
   # ------------------------------------------------------------ exact visitation on the table
 

@@ -1435,6 +1435,48 @@ int32_t campx_wide_population_sweeps_launch(const CampxWideSpec* spec_host, cons
                                             int32_t* bad_rows, int32_t* bad_flag, int32_t n_sweeps,
                                             int32_t path, void* stream);
 /*
+ * ---- A population of rewards and gammas: either reduction, a reward table per member -----------
+ * campx_wide_population_solve_launch() is the launch above with two things more.  (1) `policies`
+ * may be NULL: every member then takes the GREEDY reduction - value iteration for `members`
+ * rewards or gammas in one launch - and `greedy` (DEVICE int8 [members][n_states], may be NULL;
+ * refused beside `policies`) receives each member's greedy action of its q_n.  (2) `rewards`
+ * (DEVICE float32 [members][n_states][5], or NULL) gives member m a reward table of its own: r of
+ * the rule is rewards[m][s][a], NaN counted as 0, in place of the table's reward and of
+ * `reward_override`, which must then be NULL.  The rule.  Member m IS campx_wide_sweeps_launch()
+ * with policy = policies[m] (or NULL), reward_override = rewards[m] (or the shared one), gamma =
+ * gammas[m]: `v_out`, `q`, `greedy` and every residual[k][m], bit for bit - whatever `members` is,
+ * however members are packed, on either path.  Every other argument, the two paths and the grid
+ * are the population launch's; `members * n_states * 5 <= 2^31 - 1` as there.
+ * Path 1 with `rewards`: the staged entries keep the shared next / done / discount-code word, and
+ * a workgroup stages its G members' rewards - NaN resolved once, there - as [5][G * n_states]
+ * floats, flat over the (member, state) pairs like the weights: 20 bytes per pair on top of a
+ * greedy member's 8 and a policy member's 32.  Path 2 with `rewards`: a lane reads its five
+ * rewards at (m * n_states + s) * 5 + a.  The largest table whose one member fits wide_lds_max so
+ * differs between the four forms (policy or greedy by shared or own rewards).
+ * Without `rewards`, with `policies`: the kernels of campx_wide_population_sweeps_launch(),
+ * chosen as it chooses them.  A greedy population or `rewards` always run instances compiled
+ * with the members, members = 1 included.
+ *
+ * campx_wide_population_solve_plan() is the choice as host-only arithmetic, plan_out[5] as
+ * campx_wide_population_sweeps_plan() gives it; `policy` 1 / 0 for the reduction,
+ * `per_member_rewards` 1 / 0.  G is that function's rule TAKEN OVER - its three bounds, with this
+ * form's LDS bytes in the first - and NOT tuned for these forms.  CAMPX_EINVAL as there (either
+ * flag not 0 / 1).  The launch returns CAMPX_EINVAL for the same, for what the population launch
+ * refuses, and for: `rewards` beside `reward_override`, `greedy` beside `policies`, a `rewards`
+ * that is not 4-byte aligned.  Every refusal of an argument is decided before the device is
+ * asked anything.  Asynchronous on `stream`, no synchronisation, no allocation, no library state.
+ */
+int32_t campx_wide_population_solve_plan(int64_t n_states, int64_t members, int32_t policy,
+                                         int32_t per_member_rewards, int64_t wide_lds_max,
+                                         int64_t n_cus, int32_t path, int64_t* plan_out);
+int32_t campx_wide_population_solve_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                           const float* policies, const float* rewards,
+                                           int64_t members, const float* reward_override,
+                                           float gamma, const float* gammas, const float* v_in,
+                                           float* v_out, float* scratch, float* q, int8_t* greedy,
+                                           float* residual, int32_t* bad_rows, int32_t* bad_flag,
+                                           int32_t n_sweeps, int32_t path, void* stream);
+/*
  * ---- Exact state visitation of a policy on the state table ------------------------------------
  * The forward half of the same MDP: given the weights campx_wide_policy_update_launch() samples
  * from, how much probability sits in each state at each frame and how often each (state, action)
