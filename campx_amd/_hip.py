@@ -35,6 +35,7 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_policy_population_launch', 'campx_wide_population_plan',
            'campx_wide_learn_plan', 'campx_wide_learn_launch',
            'campx_wide_shared_plan', 'campx_wide_shared_scratch_bytes', 'campx_wide_shared_launch',
+           'campx_wide_traces_plan', 'campx_wide_traces_launch',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
@@ -180,7 +181,20 @@ class CampxSharedLearner(ctypes.Structure):
               ('reset_first', ctypes.c_int32)]
 
 
+class CampxTraceLearner(ctypes.Structure):
+  """include/campx_hip.h: one campx_wide_traces_launch() call."""
+  _fields_ = [('q', ctypes.c_void_p), ('traces', ctypes.c_void_p), ('alpha', ctypes.c_void_p),
+              ('gamma', ctypes.c_void_p), ('epsilon', ctypes.c_void_p), ('lam', ctypes.c_void_p),
+              ('reward_sum', ctypes.c_void_p), ('perf_sum', ctypes.c_void_p),
+              ('episodes', ctypes.c_void_p), ('bad_count', ctypes.c_void_p),
+              ('bad_flag', ctypes.c_void_p), ('seed', ctypes.c_uint64),
+              ('first_frame', ctypes.c_int64), ('window', ctypes.c_int32), ('rule', ctypes.c_int32),
+              ('path', ctypes.c_int32), ('reset_first', ctypes.c_int32), ('trace', ctypes.c_int32),
+              ('team', ctypes.c_int32)]
+
+
 LEARN_RULES = {'q': 0, 'expected_sarsa': 1}
+TRACE_KINDS = {'accumulating': 0, 'replacing': 1}
 
 # second word of a state-table entry (csrc/wide_table.hip.h): next state | done << 24 | discount code << 25
 ENTRY_NEXT_MASK, ENTRY_DONE_SHIFT, ENTRY_DCODE_SHIFT, ENTRY_DCODE_MASK = 0xffffff, 24, 25, 15
@@ -289,6 +303,11 @@ def _load():
   lib.campx_wide_shared_launch.restype = i32
   lib.campx_wide_shared_launch.argtypes = [wide_p, vp, CampxState, ctypes.POINTER(CampxSharedLearner), i64,
                                            i32, vp]
+  lib.campx_wide_traces_plan.restype = i32
+  lib.campx_wide_traces_plan.argtypes = [i64, i32, i64, i64, i32, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_traces_launch.restype = i32
+  lib.campx_wide_traces_launch.argtypes = [wide_p, vp, CampxState, ctypes.POINTER(CampxTraceLearner), i64,
+                                           i32, vp]
   lib.campx_render_gather_launch.restype = i32
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
@@ -389,7 +408,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'wide_learn_shared', 'render_gather', 'wide_render_gather', 'wide_render_states',
+            'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'wide_learn_shared', 'wide_learn_traces', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'vtrace', 'state_sums', 'table_lookup', 'wide_sweeps',
             'wide_population_sweeps', 'wide_population_solve', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
 

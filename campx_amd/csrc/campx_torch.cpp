@@ -19,6 +19,7 @@
 //   campx::wide_policy_population   wide_policy_update for P policies, each over its block of environments
 //   campx::wide_learn               online tabular learners: a Q-table per environment, T frames per launch
 //   campx::wide_learn_shared        shared learners: n environments feed one Q-table, T frames per launch
+//   campx::wide_learn_traces        learners with eligibility traces: Q(lambda), expected SARSA(lambda)
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -914,6 +915,40 @@ void wide_learn_shared(const Tensor& spec_host, const Tensor& tables, Tensor& st
            "campx_wide_shared_launch");
 }
 
+// Online learners with eligibility traces (campx_wide_traces_launch): campx::wide_learn's arguments
+// and `traces` float32 [B, n_states, 5] (updated in place, as q), `lam` float32 [B], `trace`: 0
+// accumulating, 1 replacing, `team`: 0 chosen by arithmetic, else the lanes of a learner.
+void wide_learn_traces(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                       const OptTensor& ret, Tensor& q, Tensor& traces, const Tensor& alpha,
+                       const Tensor& gamma, const Tensor& epsilon, const Tensor& lam, int64_t rule,
+                       int64_t trace, int64_t seed, int64_t first_frame, int64_t frames, int64_t window,
+                       Tensor& reward_sum, const OptTensor& perf_sum, Tensor& episodes,
+                       const OptTensor& bad_count, const OptTensor& bad_flag, bool reset_first,
+                       int64_t path, int64_t team) {
+  const char* what = "campx::wide_learn_traces";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  TORCH_CHECK(g.B * g.hs->n_states * CAMPX_N_ACTIONS < (1ll << 31), what,
+              ": B * n_states * 5 must be below 2^31");
+  CampxTraceLearner l = learner_fields<CampxTraceLearner>(
+      what, g, g.B, q, alpha, gamma, epsilon, rule, seed, first_frame, frames, window, reward_sum,
+      perf_sum, episodes, bad_count, bad_flag, reset_first, path);
+  want(traces, "traces", at::kFloat, g.dev, {g.B, g.hs->n_states, CAMPX_N_ACTIONS});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(traces.data_ptr()) & 15) == 0, what,
+              ": traces must be 16-byte aligned");
+  want(lam, "lam", at::kFloat, g.dev, {g.B});
+  TORCH_CHECK(trace == CAMPX_TRACE_ACCUMULATING || trace == CAMPX_TRACE_REPLACING, what,
+              ": trace must be 0 (accumulating) or 1 (replacing)");
+  TORCH_CHECK(team >= 0 && team <= 256 && (team & (team - 1)) == 0, what,
+              ": team must be 0 or a power of two up to 256");
+  l.traces = reinterpret_cast<float*>(traces.data_ptr());
+  l.lam = reinterpret_cast<const float*>(lam.data_ptr());
+  l.trace = (int32_t)trace;
+  l.team = (int32_t)team;
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_traces_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
+           "campx_wide_traces_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1555,7 +1590,7 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
-    "wide_learn", "wide_learn_shared", "render_gather",
+    "wide_learn", "wide_learn_shared", "wide_learn_traces", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_population_solve", "wide_visit",
     "wide_visit_population",
@@ -1638,6 +1673,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(g!) episodes, Tensor(h!) clamped, Tensor(i!)? scratch, Tensor(j!)? bad_count, "
       "Tensor(k!)? bad_flag, bool reset_first, int path=0) -> ()");
   m.def(
+      "wide_learn_traces(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) q, Tensor(e!) traces, Tensor alpha, Tensor gamma, Tensor epsilon, "
+      "Tensor lam, int rule, int trace, int seed, int first_frame, int frames, int window, "
+      "Tensor(f!) reward_sum, Tensor(g!)? perf_sum, Tensor(h!) episodes, Tensor(i!)? bad_count, "
+      "Tensor(j!)? bad_flag, bool reset_first, int path=0, int team=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1709,6 +1750,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_policy_population", &wide_policy_population);
   m.impl("wide_learn", &wide_learn);
   m.impl("wide_learn_shared", &wide_learn_shared);
+  m.impl("wide_learn_traces", &wide_learn_traces);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

@@ -1,11 +1,13 @@
 // k_learn.hip - online tabular learners of the state-table tier: Q-learning and expected SARSA,
 // a whole run of T frames in ONE launch, reproducible bit for bit (include/campx_hip.h has the
 // rules in full; tests/learner_reference.py and tests/shared_learner_reference.py restate them in
-// numpy).  Two kernels, two schedules, each with its own account below: wide_learn_kernel, a table
-// per environment, updated after every single frame, nothing shared between lanes; and
-// wide_learn_shared_kernel, n environments feeding one table, two barriers a frame.
+// numpy).  Three kernels, three schedules, each with its own account below: wide_learn_kernel, a
+// table per environment, updated after every single frame, nothing shared between lanes;
+// wide_learn_shared_kernel, n environments feeding one table, two barriers a frame; and
+// wide_learn_traces_kernel, a table and an eligibility trace per environment, a team of lanes
+// sweeping the whole table every frame (tests/trace_learner_reference.py).
 //
-// What they have in common is written ONCE and called by both - a change of the rule is made
+// What they have in common is written ONCE and called by all - a change of the rule is made
 // there.  "The frame step": stage_table() (entries and perf bytes into LDS), Hyper (alpha, gamma,
 // epsilon, `keep`, the `good` test), Carried (a lane's state / done / ret), Chunks (the Philox
 // blocks of four ABSOLUTE frames), frame_action() (rule step 3), decode_entry() (step 4),
@@ -605,6 +607,209 @@ __global__ __launch_bounds__(kSharedMaxThreads) void wide_learn_shared_kernel(
 using SharedKernel = decltype(&wide_learn_shared_kernel<false, false, false, false>);
 static const SharedKernel kSharedKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_shared_kernel);
 
+// ---------------------------------------------------------------------------------------------
+// Eligibility traces: Q(lambda) and expected SARSA(lambda), a table AND a trace per (state, action)
+// per environment (include/campx_hip.h, "Online learners with eligibility traces", has the frame;
+// tests/trace_learner_reference.py restates it in numpy).  The one learner whose frame touches the
+// whole table: a learner is a TEAM of L lanes (a power of two), a workgroup 256 threads holding
+// G = 256 / L learners, thread tid being lane tid % L of learner blockIdx.x * G + tid / L.  A frame is
+//   (A) EVERY lane of the team computes the scalar part - row, action, entry, bootstrap row, delta,
+//       step, c - from the same words: broadcast reads, no communication;
+//   barrier (L > 1): all lanes have read row / nrow / old;
+//   (B) lane l's pass over the entries i = l (mod L): cut, bump, sweep and decay fused - one read of
+//       z, one read-modify-write of q where z != 0, one write of z;
+//   barrier (L > 1): the table is whole again before the next frame's rows are read.
+// EVERY lane of the workgroup reaches both barriers of every frame: the loop bounds depend on the
+// kernel's arguments alone (L is one), and what an absent lane (a team past B in the last workgroup)
+// or the lanes of a bad learner skip lies BETWEEN the barriers, never around one - the discipline of
+// wide_learn_shared_kernel.  L = 1 has no barrier: a lane reads what it wrote itself.
+// Two barriers, not one: (B) of frame t writes what (A) of frame t reads and (A) of frame t + 1
+// reads what (B) of frame t wrote, so both orders need a barrier unless (B) writes another copy than
+// (A) reads - 16 bytes of LDS per entry where the plan counts 8.  Not taken; DESIGN.md says so.
+//
+// Path 1: the entries, the perf bytes, the workgroup's q and its z in LDS.  L = 1: lane-innermost,
+// i * 256 + learner, as in wide_learn_kernel (conflict-free).  L > 1: entry-innermost,
+// learner * n_entries + i, so that a team's lanes hit consecutive banks.  Path 2: q and z as they
+// lie in global memory, through the L1 / L2 the workgroup's waves share; the entries in LDS when
+// they alone fit.  Either way entry i of learner `who` is cell who * sw + i * si of Q and of Z.
+
+constexpr int kTraceMaxTeam = kLearnThreads;
+
+// campx_wide_traces_plan()'s five words, in their order.
+struct TracePlan { int64_t path, team, lds_bytes, threads, table_in_lds; };
+
+inline int32_t plan_traces(int64_t S, int32_t has_perf, int64_t B, int64_t lds_max, int32_t path,
+                           int32_t team, TracePlan* p, int64_t* plan_out) {
+  if (!plan_args_ok(S, has_perf, B, B, lds_max, path) || team < 0 || team > kTraceMaxTeam ||
+      (team & (team - 1)))
+    return CAMPX_EINVAL;
+  const int64_t table = table_bytes(S, has_perf);
+  const int64_t per = S * CAMPX_N_ACTIONS * 2 * (int64_t)sizeof(float);      // q and z of a learner
+  // the smallest team whose learners fit beside the table (a forced team: that one or none)
+  int64_t L = team ? team : 1;
+  while (table + (kLearnThreads / L) * per > lds_max && !team && L < kTraceMaxTeam) L *= 2;
+  const bool fits = table + (kLearnThreads / L) * per <= lds_max;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
+  p->team = (p->path == 1 || team) ? L : kTraceMaxTeam;
+  p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
+  p->lds_bytes = p->path == 1 ? table + (kLearnThreads / L) * per : (p->table_in_lds ? table : 0);
+  p->threads = kLearnThreads;
+  if (plan_out) memcpy(plan_out, p, sizeof(*p));
+  return CAMPX_OK;
+}
+
+// Path 1's q or z between global memory - element i of the workgroup's piece `g` is learner
+// i / n_entries, entry i % n_entries - and its cells in LDS (kIn: into it, else back out).  `g + head`
+// is 16-byte aligned: the elements from there go four at a time, one 16-byte global access and one
+// division per group (move_q()'s walk), the at most three before and three after one by one.
+template <bool kIn>
+__device__ __forceinline__ void move_cells(float* cells, float* g, int n, int n_entries, int si, int sw,
+                                           int head, int tid) {
+  head = head < n ? head : n;
+  const int whole = (n - head) & ~3;
+  for (int i = head + tid * 4; i < head + whole; i += kLearnThreads * 4) {
+    u32x4* piece = reinterpret_cast<u32x4*>(g + i);
+    u32x4 v = kIn ? *piece : u32x4{};
+    int who = i / n_entries, k = i - who * n_entries;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float& cell = cells[who * sw + k * si];
+      if (kIn) cell = __uint_as_float(v[j]);
+      else v[j] = __float_as_uint(cell);
+      if (++k == n_entries) {
+        k = 0;
+        ++who;
+      }
+    }
+    if (!kIn) *piece = v;
+  }
+  for (int j = tid; j < n - whole; j += kLearnThreads) {
+    const int i = j < head ? j : j + whole;
+    float& cell = cells[(i / n_entries) * sw + (i % n_entries) * si];
+    if (kIn) cell = g[i];
+    else g[i] = cell;
+  }
+}
+
+// kQLds: path 1.  kTableLds, kPerf, kSarsa: as in wide_learn_kernel.  `L`: lanes of a team, a power
+// of two, blockDim.x == 256 == G * L.  `replacing`: the trace kind.
+template <bool kQLds, bool kTableLds, bool kPerf, bool kSarsa>
+__global__ __launch_bounds__(kLearnThreads) void wide_learn_traces_kernel(
+    LearnParams pp, const uint2* __restrict__ g_entries, const int8_t* __restrict__ g_perf, float* q,
+    float* traces, const float* __restrict__ alphas, const float* __restrict__ gammas,
+    const float* __restrict__ epsilons, const float* __restrict__ lams, int32_t* __restrict__ state,
+    CampxState st, float* __restrict__ reward_sum, int32_t* __restrict__ perf_sum,
+    int32_t* __restrict__ episodes, int32_t* bad_count, int32_t* bad_flag, int64_t B, int32_t T,
+    int32_t reset_first, int32_t L, int32_t replacing) {
+  static_assert(kTableLds || !kQLds, "path 1 stages the table");
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_tables[];
+  __shared__ float discounts[16];
+  const int S = pp.n_states, n_entries = S * CAMPX_N_ACTIONS;
+  const int tid = threadIdx.x;
+  const int G = kLearnThreads / L;
+  const int who = tid / L, part = tid - who * L;             // learner of the workgroup, lane of the team
+  const int64_t first_learner = (int64_t)blockIdx.x * G;
+  const int n_here = (int)(B - first_learner < G ? B - first_learner : G);   // learners present
+  const bool active = who < n_here;                          // (an absent team: last workgroup only)
+  const int64_t learner = first_learner + who;
+  const int n_own = n_here * n_entries;                      // floats: B * S * 5 < 2^31
+  float* q_block = q + first_learner * n_entries;
+  float* z_block = traces + first_learner * n_entries;
+  const int head = (int)((0 - first_learner * n_entries) & 3);     // floats up to 16 bytes (q, traces are)
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, tid, kLearnThreads);
+  float* l_q = reinterpret_cast<float*>(tab.free);
+  float* Q = kQLds ? l_q : q_block;
+  float* Z = kQLds ? l_q + G * n_entries : z_block;
+  const int si = (kQLds && L == 1) ? kLearnThreads : 1;      // entry i of learner `who`:
+  const int sw = (kQLds && L == 1) ? 1 : n_entries;          //   cell who * sw + i * si
+  if (kQLds) {
+    move_cells<true>(Q, q_block, n_own, n_entries, si, sw, head, tid);
+    move_cells<true>(Z, z_block, n_own, n_entries, si, sw, head, tid);
+  }
+  if (tid < 16) discounts[tid] = pp.discounts[tid];
+  __syncthreads();
+
+  // What stays in registers for the run.  An absent lane keeps these values - no learner, a new
+  // episode - and does nothing between the barriers below.
+  Hyper h;
+  float lam = 0.0f;
+  Carried c;
+  WindowSums<kPerf> win{reward_sum, perf_sum, episodes, learner};
+  if (active) {
+    h.load(alphas, gammas, epsilons, learner);
+    lam = lams[learner];
+    h.good = h.good && lam >= 0.0f && lam <= 1.0f;           // (a NaN is in no interval)
+    c.load(state, st, learner, S, reset_first);
+  }
+  const bool lead = part == 0;                               // writes the sums and the final state
+  float* own_q = Q + who * sw;
+  float* own_z = Z + who * sw;
+  const Chunks chunks(pp.first_frame);
+  for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
+    uint32_t x[2 * kLearnChunk];
+    if (active) chunks.words(pp, learner, t0, x);
+#pragma unroll
+    for (int j = 0; j < kLearnChunk; ++j) {
+      if (t0 + j < 0 || t0 + j >= T) continue;               // (uniform: kernel arguments alone)
+      bool sweep = false, cut = false, ends = false;
+      int idx = 0;
+      float step = 0.0f, decay = 0.0f;
+      if (active) {                                          // ---- (A)
+        float row[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) row[k] = own_q[(c.from * CAMPX_N_ACTIONS + k) * si];
+        const uint32_t a = frame_action(row, x[2 * j], x[2 * j + 1], h.epsilon, h.good);
+        idx = (int)(c.from * CAMPX_N_ACTIONS + a);
+        const Entry e = decode_entry(tab.entries[idx], S, discounts);
+        if (h.good) {
+          float nrow[5];
+#pragma unroll
+          for (int k = 0; k < 5; ++k) nrow[k] = own_q[(e.next * CAMPX_N_ACTIONS + k) * si];
+          float old = row[0], best;
+#pragma unroll
+          for (int k = 1; k < 5; ++k) old = a == (uint32_t)k ? row[k] : old;
+          uint32_t unused;
+          greedy_of(row, best, unused);
+          const float delta = td_error<kSarsa>(old, nrow, e, h.gamma, h.keep, h.epsilon);
+          step = h.alpha * delta;
+          decay = (h.gamma * e.D) * lam;
+          cut = (!kSarsa && !(old == best)) || (reset_first && t0 + j == 0);
+          ends = e.done != 0u;
+          sweep = true;
+        }
+        c.advance(e);
+        if (lead) win.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
+      }
+      if (L > 1) __syncthreads();
+      if (sweep) {                                           // ---- (B)
+        for (int i = part; i < n_entries; i += L) {
+          float z = own_z[i * si];
+          z = cut ? 0.0f : z;
+          if (i == idx) z = replacing ? 1.0f : z + 1.0f;
+          if (z != 0.0f) own_q[i * si] = own_q[i * si] + step * z;
+          own_z[i * si] = ends ? 0.0f : decay * z;
+        }
+      }
+      if (L > 1) __syncthreads();
+    }
+  }
+  if (active && lead) {
+    win.flush_short();
+    c.store(state, st, learner);
+    report_bad(bad_count, bad_flag, h.good ? 0 : 1);         // bad LEARNERS, once per launch
+  }
+  if (kQLds) {
+    __syncthreads();
+    move_cells<false>(Q, q_block, n_own, n_entries, si, sw, head, tid);
+    move_cells<false>(Z, z_block, n_own, n_entries, si, sw, head, tid);
+  }
+}
+
+using TraceKernel = decltype(&wide_learn_traces_kernel<false, false, false, false>);
+static const TraceKernel kTraceKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_traces_kernel);
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -679,6 +884,36 @@ int32_t campx_wide_shared_launch(const CampxWideSpec* s, const void* tables_dev,
                      l->reward_sum, l->perf_sum, l->episodes, reinterpret_cast<long long*>(l->clamped),
                      acc_sum, acc_count, l->bad_count, l->bad_flag, B, P, (int32_t)(B / P), (int32_t)G,
                      T, l->reset_first);
+  return launch_status();
+}
+
+int32_t campx_wide_traces_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                               int32_t path, int32_t team, int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  TracePlan plan;
+  return plan_traces(n_states, has_perf, B, wide_lds_max, path, team, &plan, plan_out);
+}
+
+int32_t campx_wide_traces_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
+                                 const CampxTraceLearner* l, int64_t B, int32_t T, void* stream) {
+  const bool own_ok = l && l->traces && l->lam && aligned_to(l->traces, 16) && aligned_to(l->lam, 4) &&
+                      (l->trace == CAMPX_TRACE_ACCUMULATING || l->trace == CAMPX_TRACE_REPLACING);
+  const int32_t screened = screen_learner(s, tables_dev, st, l, B, T, own_ok);
+  if (screened != CAMPX_OK) return screened;
+  TracePlan plan;      // (refuses B * n_states * 5 >= 2^31, a bad team, a forced shape that does not fit)
+  const int32_t planned = plan_traces(s->n_states, l->perf_sum ? 1 : 0, B, knob(K_WIDE_LDS_MAX),
+                                      l->path, l->team, &plan, nullptr);
+  if (planned != CAMPX_OK) return planned;
+  const WideTables t = wide_tables(*s, tables_dev);
+  const size_t lds = (size_t)plan.lds_bytes;
+  const TraceKernel kernel = pick_kernel(kTraceKernels, plan, *l);
+  CAMPX_ALLOW_LDS(kernel, lds);
+  const int64_t G = kLearnThreads / plan.team;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((B + G - 1) / G)), dim3(kLearnThreads), lds,
+                     static_cast<hipStream_t>(stream), learn_params(*s, *l), t.entries, t.perf, l->q,
+                     l->traces, l->alpha, l->gamma, l->epsilon, l->lam,
+                     reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
+                     l->bad_count, l->bad_flag, B, T, l->reset_first, (int32_t)plan.team, l->trace);
   return launch_status();
 }
 

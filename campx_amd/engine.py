@@ -497,6 +497,16 @@ class Engine(object):
     """State-table tier only: the dict of `learn_tabular(out=...)`, allocated once."""
     return self._batched('learner_buffers').learner_buffers(T, window=window)
 
+  def learn_traces(self, T, q=None, traces=None, *args, **kwargs):
+    """State-table tier only: T frames of online tabular learning with ELIGIBILITY TRACES -
+    Watkins's Q(lambda) (`rule='q'`) or expected SARSA(lambda), accumulating or replacing traces -
+    for B independent learners in one launch, environment e learning on its own table `q[e]` and
+    its own `traces[e]`, float32 `[B, n_states, 5]` each (None: zeros, else updated in place).
+    `lam=0` is `learn_tabular()` bit for bit.  Returns a dict: 'q', 'traces', and
+    `learn_tabular()`'s window sums.  See `wide.WideGame.learn_traces`; the other batched tiers
+    raise NotImplementedError (`use_state_table()` selects this one)."""
+    return self._batched('learn_traces').learn_traces(T, q, traces, *args, **kwargs)
+
   def learn_shared(self, T, q, *args, **kwargs):
     """State-table tier only: T frames of online tabular learning for P SHARED learners in one
     launch, learner m owning `q[m]` of `q` float32 `[P, n_states, 5]` (updated in place) and fed by

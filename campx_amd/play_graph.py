@@ -26,7 +26,26 @@ to and from ordinary `play()` / `rollout()` calls in between.  Bit-exact against
 pointed at row t of the graph's buffers.
 """
 
+import gc
+
 import torch
+
+
+class _no_collection(object):
+  """Round a stream capture: the dead cycles are collected BEFORE it, and no automatic collection
+  runs inside it.  A collection that lands inside a capture may destroy an earlier graph and its
+  memory pool, or anything else that frees device memory - calls the runtime refuses while a
+  stream is capturing, from a destructor, which ends the process.  (torch.cuda.graph no longer
+  collects on entry by default.)"""
+
+  def __enter__(self):
+    gc.collect()
+    self.was_enabled = gc.isenabled()
+    gc.disable()
+
+  def __exit__(self, *exc):
+    if self.was_enabled:
+      gc.enable()
 
 
 class PlayGraph(object):
@@ -77,7 +96,7 @@ class PlayGraph(object):
           t.copy_(kept)
     torch.cuda.current_stream(dev).wait_stream(side)
     torch.cuda.synchronize(dev)
-    with torch.cuda.graph(self._graph):
+    with _no_collection(), torch.cuda.graph(self._graph):
       self._frames()
     f.frame = frame0
     # (the graph holds ADDRESSES: the engine's frame buffers as they were when it was captured)

@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'value_iteration_population',
     'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
@@ -140,11 +140,12 @@ class WideGame(fused.FusedGame):
     # the same two of the window calls, counted apart so that the error says where they came from
     self._bad_window_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_window_ids = torch.zeros((1,), dtype=torch.int32, device=dev)
-    # learners of learn_tabular() and of learn_shared() with bad hyper-parameters, once per launch
-    # (raised under the flag of the action ids), and the [3, learners] tensors that Python-float
-    # hyper-parameters are filled into, by (method, learners)
+    # learners of learn_tabular(), of learn_shared() and of learn_traces() with bad
+    # hyper-parameters, once per launch (raised under the flag of the action ids), and the
+    # [4, learners] tensors that Python-float hyper-parameters are filled into, by (method, learners)
     self._bad_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_shared_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_trace_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._hyper_floats = {}
     self._layer_of_cell = None        # the window kernel's scenery table
     self._window_table()
@@ -198,7 +199,11 @@ class WideGame(fused.FusedGame):
         (self._bad_shared_learners, acts,
          '{} learners of learn_shared() have bad hyper-parameters (alpha, gamma or epsilon not '
          'finite, or epsilon outside [0, 1]); their environments took action {} at every frame and '
-         'their tables were left untouched')]
+         'their tables were left untouched'),
+        (self._bad_trace_learners, acts,
+         '{} learners of learn_traces() have bad hyper-parameters (alpha, gamma, epsilon or lam not '
+         'finite, or epsilon or lam outside [0, 1]); they took action {} at every frame and their '
+         'tables and traces were left untouched')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -505,7 +510,7 @@ class WideGame(fused.FusedGame):
     return out
 
   def _hyper_parameter(self, name, value, row, call, B):
-    """float32 [B] on the device of `alpha`, `gamma` or `epsilon` for the B learners of method
+    """float32 [B] on the device of `alpha`, `gamma`, `epsilon` or `lam` for the B learners of method
     `call`: a tensor as given, a Python number checked here and filled into row `row` of a tensor
     the game keeps per (call, B) - no allocation after the first call, and a captured call of one
     method never sees the numbers of the other."""
@@ -518,12 +523,13 @@ class WideGame(fused.FusedGame):
     if isinstance(value, bool) or not isinstance(value, (int, float)):
       raise ValueError('{} must be a number or a float32 [{}] tensor, got {}'.format(
           name, B, type(value).__name__))
+    unit = name in ('epsilon', 'lam')
     if (not math.isfinite(value) or abs(value) > torch.finfo(torch.float32).max
-        or (name == 'epsilon' and not 0.0 <= value <= 1.0)):
+        or (unit and not 0.0 <= value <= 1.0)):
       raise ValueError('{} must be a finite number (as a float32){}, got {!r}'.format(
-          name, ' in [0, 1]' if name == 'epsilon' else '', value))
+          name, ' in [0, 1]' if unit else '', value))
     if (call, B) not in self._hyper_floats:
-      self._hyper_floats[call, B] = torch.zeros((3, B), dtype=torch.float32, device=self.device)
+      self._hyper_floats[call, B] = torch.zeros((4, B), dtype=torch.float32, device=self.device)
     return self._hyper_floats[call, B][row].fill_(float(value))
 
   def _learner_prologue(self, call, learners, T, window, rule, first_frame, seed, alpha, gamma,
@@ -642,6 +648,112 @@ class WideGame(fused.FusedGame):
         self._bad_learners if validate else None, self._bad_flag if validate else None,
         bool(reset_first), path)
     return self._learner_epilogue(first, T, reset_first, q, out)
+
+  # ------------------------------------------------------------ learners with eligibility traces
+
+  def _traces_plan(self, path, team):
+    """The five words of campx_wide_traces_plan() for this game - path, lanes of a learner, LDS
+    bytes, threads, entries in LDS - after the checks of `path` and `team` that have a message."""
+    S = self.n_states
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    if (isinstance(team, bool) or not isinstance(team, int) or not 0 <= team <= 256
+        or team & (team - 1)):
+      raise ValueError('team must be 0 (chosen by arithmetic) or a power of two up to 256, got {!r}'.format(team))
+    plan = (ctypes.c_int64 * 5)()
+    lds_max = _hip.config_get('wide_lds_max')
+    code = _hip.lib.campx_wide_traces_plan(S, 1 if self.has_perf else 0, self.batch, lds_max, path,
+                                           team, plan)
+    if code != 0 and path == 1:
+      raise ValueError('path=1, team={}: a table of {} states with the Q-tables and traces of a '
+                       'workgroup\'s {} do not fit the LDS of one workgroup (library setting '
+                       'wide_lds_max); use path=0 or path=2{}'.format(
+                           team, S,
+                           '256 / team = {} learners'.format(256 // team) if team else 'one learner',
+                           ', or a larger team' if team else ''))
+    if code != 0:
+      raise ValueError('path={}, team={}: the library refused the plan (code {}; library setting '
+                       'wide_lds_max = {})'.format(path, team, code, lds_max))
+    return list(plan)
+
+  def learn_traces(self, T, q=None, traces=None, lam=0.9, trace='accumulating', alpha=0.1, gamma=0.99,
+                   epsilon=0.1, rule='q', seed=0, first_frame=None, reset_first=False, window=None,
+                   out=None, path=0, team=0):
+    """T frames of online tabular learning WITH ELIGIBILITY TRACES for B independent learners in ONE
+    launch: Watkins's Q(lambda) (`rule='q'`) or expected SARSA(lambda).  Environment e is learner e,
+    as in `learn_tabular()`, with its own table `q[e]` and its own trace per (state, action),
+    `traces[e]`: every frame's TD error moves EVERY entry in proportion to its trace, so that a
+    reward reaches the whole path that led to it at once, not one state per visit
+    (csrc/k_learn.hip, `campx::wide_learn_traces`).  No reduction and no atomics: the run repeats
+    bit for bit (include/campx_hip.h has the frame; tests/trace_learner_reference.py restates it
+    in numpy).
+
+    The frame of a learner in state s: it acts on `q[e, s]` as `learn_tabular()` does (the same
+    exploration stream); for `rule='q'` an action whose value is not the row's maximum CUTS the
+    traces (all zero); the TD error `delta` is `learn_tabular()`'s; the trace of (s, a) is bumped -
+    `trace='accumulating'`: plus 1, `'replacing'`: set to 1; every entry with a trace that is not
+    zero moves by `alpha * delta * trace`; and the traces decay by `gamma * D * lam`, or are
+    zeroed when the frame ends the episode.  `lam=0` is `learn_tabular()` bit for bit.
+
+    Args:
+      q, traces: contiguous float32 `[B, n_states, 5]` on the game's device (16-byte aligned,
+          `B * n_states * 5 < 2^31`), both updated IN PLACE; None: zeros.  Pass the returned
+          'traces' on and calls of T1 and T2 frames learn what one call of T1 + T2 does.
+      lam: the trace decay, a Python number in [0, 1] (checked at once) or a float32 `[B]` tensor -
+          a tensor is a sweep of lambda.
+      trace: 'accumulating' or 'replacing'.
+      alpha, gamma, epsilon, rule, seed, first_frame, window: exactly as in `learn_tabular()`.  A
+          learner that is bad there, or whose lam is not within [0, 1], takes action 4 at every
+          frame, keeps its table AND its traces, and raises ValueError lazily, counted once.
+      reset_first: every learner starts a new episode, and its traces from zero.
+      out: a dict from `learner_buffers(T, window)`, overwritten.  With `q`, `traces` and `out`
+          (and tensors, or the same numbers as before, for the hyper-parameters) the call
+          allocates nothing and is capturable in a HIP graph.
+      path, team: a learner is a team of `team` lanes (a power of two up to 256) that share the
+          sweep over its entries; a workgroup holds 256 / team learners.  0 and 0: the smallest
+          team for which the table and the workgroup's tables and traces fit the LDS (library
+          setting wide_lds_max: one lane up to 14 states, two up to 28, ..., 256 up to about
+          1 800), else tables and traces go through L1 / L2 with a team of 256.  `path=1` / `2`
+          and `team=` force either; a forced shape that does not fit raises ValueError.  No
+          choice changes a bit of any result.
+
+    Returns a dict: 'q', 'traces', and `learn_tabular()`'s 'reward_sum', 'episodes' and
+    'perf_sum'.  `state`, `done`, `ret` and `frame` carry over exactly as `learn_tabular()` leaves
+    them.  Argument errors raise ValueError before anything is launched.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    if B * S * A >= 1 << 31:
+      raise ValueError('learn_traces(): B * n_states * 5 = {} x {} x 5 must be below 2^31; use a '
+                       'smaller batch'.format(B, S))
+    for name, t in (('q', q), ('traces', traces)):
+      if t is not None and (not self._tensor_ok(t, torch.float32, (B, S, A)) or t.data_ptr() % 16):
+        got = ('{} {} on {}'.format(t.dtype, list(t.shape), t.device) if torch.is_tensor(t)
+               else type(t).__name__)
+        raise ValueError('{} must be a contiguous, 16-byte aligned float32 [{}, {}, {}] tensor '
+                         '(learners x n_states x actions) on {}, or None for zeros; got {}'.format(
+                             name, B, S, A, dev, got))
+    if trace not in _hip.TRACE_KINDS:
+      raise ValueError('trace must be \'accumulating\' or \'replacing\', got {!r}'.format(trace))
+    self._traces_plan(path, team)
+    # (lam first: a bad number must not leave the other rows of the cache filled for nothing)
+    lams = self._hyper_parameter('lam', lam, 3, 'learn_traces', B)
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_traces', B, T, window, rule, first_frame, seed, alpha, gamma, epsilon, out, [],
+        'learner_buffers({}, window={})'.format, self.learner_buffers)
+    if q is None:
+      q = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
+    if traces is None:
+      traces = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
+    validate = self.validate_actions
+    _hip.ops.wide_learn_traces(
+        self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), traces.detach(),
+        hyper[0], hyper[1], hyper[2], lams, _hip.LEARN_RULES[rule], _hip.TRACE_KINDS[trace], seed,
+        first, T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
+        out['episodes'], self._bad_trace_learners if validate else None,
+        self._bad_flag if validate else None, bool(reset_first), path, team)
+    res = self._learner_epilogue(first, T, reset_first, q, out)
+    res['traces'] = traces
+    return res
 
   # ------------------------------------------------------------ shared online learners
 

@@ -987,6 +987,91 @@ int32_t campx_wide_shared_launch(const CampxWideSpec* spec_host, const void* tab
                                  CampxState state, const CampxSharedLearner* learner, int64_t B,
                                  int32_t T, void* stream);
 /*
+ * ---- Online learners with eligibility traces: Q(lambda) and expected SARSA(lambda) ------------
+ * The one-step learners above move a reward back one state per visit.  Here learner e (environment
+ * e, as in campx_wide_learn_launch()) also owns a trace per (state, action), `traces[e]`, of the
+ * shape and contract of `q[e]` (DEVICE float32 [B][n_states][5], 16-byte aligned, updated in
+ * place), and every frame moves EVERY entry whose trace is not zero: T frames in one launch, no
+ * reduction, no atomics, reproducible bit for bit (csrc/k_learn.hip;
+ * tests/trace_learner_reference.py restates the frame in numpy).
+ *
+ * The frame of a good learner in state s, table q, traces z, with lam[e] (DEVICE float32 [B]);
+ * f32 throughout, every operation rounded on its own.  Steps 1 - 4 and 8 of the rule of the
+ * one-step learners - the Philox words, s, the action, the entry, the sums - hold unchanged.
+ *   1. Act.  row = q[s][.]; a = the frame's action from it; old = row[a]; best = the greedy
+ *      maximum of row.
+ *   2. Cut.  CAMPX_LEARN_Q (Watkins): if !(old == best) - a NaN cuts - every z[i] = +0.
+ *      CAMPX_LEARN_EXPECTED_SARSA never cuts.
+ *   3. TD error.  The entry (s, a): n, r, d, D.  delta = target - old with the bootstrap of the
+ *      one-step rule taken from q[n][.] as the table stands now, before this frame's sweep.
+ *   4. Bump.  CAMPX_TRACE_ACCUMULATING: z[s][a] = z[s][a] + 1.  CAMPX_TRACE_REPLACING: z[s][a] = 1.
+ *   5. Sweep.  step = alpha[e] * delta; for every entry i with z[i] != 0.0f (a NaN trace counts):
+ *      q[i] = q[i] + (step * z[i]).  An entry whose trace is +-0 is NOT written: its bits stay,
+ *      whatever `step` is.
+ *   6. Decay.  d set: every z[i] = +0.  Otherwise c = (gamma[e] * D) * lam[e] and z[i] = c * z[i],
+ *      for EVERY i (so that a trace may become -0, or NaN under an infinite c).
+ *   7. Advance state / done / ret and the window sums exactly as the one-step learners do.
+ * `reset_first` also zeroes (+0) a good learner's traces before frame 0.  Consequences, each pinned
+ * by the tests: lam = 0 gives campx_wide_learn_launch()'s q, sums and state bit for bit (for finite
+ * gamma * D); launches of T1 and T2 frames equal one of T1 + T2; no `path` or `team` changes a bit.
+ * A learner is BAD as above, or when its lam is not within [0, 1] (a NaN is not): action 4 at every
+ * frame, q AND traces untouched (`reset_first` included), counted once.
+ *
+ * A learner is a TEAM of L lanes, L a power of two in 1 .. 256; a workgroup is 256 threads, 256 / L
+ * learners.  Every lane of a team computes steps 1 - 3, `step` and c redundantly, from the same
+ * words (broadcast reads); lane l owns the entries i = l (mod L) for steps 2 and 4 - 6, fused into
+ * one pass: one read of z, one read-modify-write of q where z != 0, one write of z.  For L > 1 a
+ * frame has two workgroup barriers - after the rows are read, and after the pass - that every lane
+ * of the workgroup reaches at every frame; L = 1 needs none.  The team's lane 0 writes the sums and
+ * the final state.
+ * Path 1: the entries, the perf bytes and the workgroup's q and z in LDS - lane-innermost,
+ * i * 256 + learner, for L = 1; entry-innermost, learner * n_states * 5 + i, for L > 1:
+ *     LDS bytes = table + (256 / L) * n_states * 5 * 8       (table: as for the one-step learners)
+ * Path 2: q and z through L1 / L2, the entries (and perf bytes) in LDS when they alone fit.
+ * `team` 0 and `path` 0: the SMALLEST L whose path-1 bytes are within wide_lds_max, path 1; when
+ * not even L = 256 fits, path 2 with L = 256.  A `team` forces L (path 1 if it fits, else 2); path
+ * 1 forces path 1 (the smallest L that fits, or `team`; refused when it does not fit); path 2 takes
+ * `team`, or 256.  This is arithmetic, not tuned.
+ *
+ * campx_wide_traces_plan(): plan_out[5] = path (1 / 2); L; dynamic LDS bytes; threads of a workgroup
+ * (256); 1 when the entries are staged in LDS.  CAMPX_EINVAL: what campx_wide_learn_plan() refuses,
+ * a `team` that is neither 0 nor a power of two up to 256, a forced shape that does not fit.
+ * campx_wide_traces_launch() returns CAMPX_EINVAL, before anything touches a device, for the same,
+ * for what campx_wide_learn_launch() refuses, for `traces` or `lam` that are NULL or misaligned
+ * (16 and 4 bytes), and for a `trace` that is neither kind.  Asynchronous on `stream`, no
+ * synchronisation, no allocation, no library state.
+ */
+#define CAMPX_TRACE_ACCUMULATING 0
+#define CAMPX_TRACE_REPLACING 1
+
+typedef struct CampxTraceLearner {
+  float* q;               /* DEVICE [B][n_states][5], 16-byte aligned; updated in place */
+  float* traces;          /* DEVICE [B][n_states][5], 16-byte aligned; updated in place */
+  const float* alpha;     /* DEVICE [B] each */
+  const float* gamma;
+  const float* epsilon;
+  const float* lam;
+  float* reward_sum;      /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;      /* DEVICE [W][B], or NULL */
+  int32_t* episodes;      /* DEVICE [W][B] */
+  int32_t* bad_count;     /* optional device int32: += bad learners */
+  int32_t* bad_flag;      /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;    /* absolute number of the launch's frame 0 */
+  int32_t window;         /* frames per window, >= 1 (may exceed T) */
+  int32_t rule;           /* CAMPX_LEARN_Q / CAMPX_LEARN_EXPECTED_SARSA */
+  int32_t path;           /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+  int32_t trace;          /* CAMPX_TRACE_ACCUMULATING / CAMPX_TRACE_REPLACING */
+  int32_t team;           /* 0 chosen by arithmetic, else L */
+} CampxTraceLearner;
+
+int32_t campx_wide_traces_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                               int32_t path, int32_t team, int64_t* plan_out);
+int32_t campx_wide_traces_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                 CampxState state, const CampxTraceLearner* learner, int64_t B,
+                                 int32_t T, void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
