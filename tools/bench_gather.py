@@ -11,33 +11,19 @@ Settled clocks (warm-up launches first), event pairs, median of 25 runs.
 
     python tools/bench_gather.py [out.txt]        # default: profiles/r07_gather.txt
 """
-import os
-import statistics
+import functools
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 import torch  # noqa: E402
 
 from campx_amd import fused  # noqa: E402
 from campx_amd.games import boat_race, sokoban  # noqa: E402
 
 RUNS, WARM = 25, 10
-
-
-def median_ms(fn):
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+median = functools.partial(benchlib.median_ms, runs=RUNS, warm=WARM)
 
 
 def rollouts(lines):
@@ -49,8 +35,8 @@ def rollouts(lines):
     T = 100
     acts = torch.randint(0, 5, (T, B), dtype=torch.int8, device='cuda')
     full, lean = f.rollout_buffers(T), f.rollout_trace_buffers(T)
-    a = median_ms(lambda: f.rollout(acts, out=full, reset_first=True))
-    b = median_ms(lambda: f.rollout_trace(acts, out=lean, reset_first=True))
+    a = median(lambda: f.rollout(acts, out=full, reset_first=True))
+    b = median(lambda: f.rollout_trace(acts, out=lean, reset_first=True))
     row = f.n_layers * f.rows * f.cols
     lines.append('%-10s B=%-7d T=100  rollout() %.4f ms (%.1f MB obs)   rollout_trace() %.4f ms (%.1f MB trace)' % (
         name, B, a, row * B * T / 1e6, b, f.n_dyn * B * T / 1e6))
@@ -80,12 +66,12 @@ def gathers(lines):
       try:
         for streaming in (False, True):
           fused.GATHER_STREAMING = streaming
-          got[streaming] = median_ms(lambda: f.render_frames(out['trace'], t, e, out=dst))
+          got[streaming] = median(lambda: f.render_frames(out['trace'], t, e, out=dst))
       finally:
         fused.GATHER_STREAMING = shipped
       assert torch.equal(dst.view(N, row), flat_obs.index_select(0, flat))
-      sel_ms = median_ms(lambda: torch.index_select(flat_obs, 0, flat, out=sel))
-      fill_ms = median_ms(lambda: dst.fill_(1))
+      sel_ms = median(lambda: torch.index_select(flat_obs, 0, flat, out=sel))
+      fill_ms = median(lambda: dst.fill_(1))
       nbytes = N * row * dst.element_size()
       lines.append('boat_race %-8s N=%-8d %7.1f MB  render_frames plain %.4f ms (%.2f TB/s)  streaming %.4f ms (%.2f TB/s)'
                    '  index_select %.4f ms (%.2f TB/s)  fill_ %.4f ms (%.2f TB/s)' % (
@@ -96,7 +82,7 @@ def gathers(lines):
 
 
 def main():
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r07_gather.txt')
+  path = benchlib.out_path(sys.argv[1:], 'r07_gather.txt')
   lines = ['# tools/bench_gather.py on %s: median of %d runs after %d warm-up ones, event pairs' % (
       torch.cuda.get_device_name(0), RUNS, WARM)]
   rollouts(lines)

@@ -18,42 +18,29 @@ actions over S = 1 940 and S = 4 400 000 at B = 65 536.
 GATE: form (3) is no slower than form (1) at every size (exit status 1 otherwise; the table says
 where it is missed).  Form (1) is measured in the same run.
 
-Settled clocks (warm-up runs first), event pairs, median of 25 runs, a fresh process per row.
+Settled clocks (warm-up runs first), event pairs, median of 25 runs.  Rows, failures and exit
+statuses: tools/benchlib.py.
 
     python tools/bench_learner.py [out.txt]        # default: profiles/r10_learner.txt
 """
-import json
-import os
-import statistics
-import subprocess
+import functools
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, T = 25, 10, 100
 ROWS = (('boat_race', 8, 4096), ('boat_race', 8, 65536), ('uniform', 1940, 65536),
         ('uniform', 4400000, 65536))
-
-
-def median_ms(fn):
-  import torch
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+ROW_SECONDS = 900
+median = functools.partial(benchlib.median_ms, runs=RUNS, warm=WARM)
 
 
 def row(kind, S, B):
-  """One row, in this process: a dict of medians in ms."""
+  """One row, in this process: `kind`, `S`, `B`, `plan`, `device`, `max_diff_2`, `max_diff_3`, and
+  the medians in ms `form1` .. `form3`, `sums_path0` .. `sums_path2` (None where the path does not
+  fit), `sums_k0` and `lookup`."""
   import ctypes
   import torch
   from campx_amd import _hip
@@ -104,9 +91,9 @@ def row(kind, S, B):
   scale = float(g1.abs().max())
   res['max_diff_2'] = float((g2 - g1).abs().max()) / scale
   res['max_diff_3'] = float((g3 - g1).abs().max()) / scale
-  res['form1'] = median_ms(form1)
-  res['form2'] = median_ms(form2)
-  res['form3'] = median_ms(form3)
+  res['form1'] = median(form1)
+  res['form2'] = median(form2)
+  res['form3'] = median(form3)
   plan = (ctypes.c_int64 * 8)()
   _hip.check(_hip.lib.campx_state_sums_plan(S, 5, K, B, T, 24, 0, plan), 'campx_state_sums_plan')
   res['plan'] = [int(v) for v in plan]
@@ -114,15 +101,15 @@ def row(kind, S, B):
     if path == 1 and S * 5 * (K + 1) * 8 > _hip.SUMS_LDS_BUDGET:
       res['sums_path1'] = None
       continue
-    res['sums_path%d' % path] = median_ms(
+    res['sums_path%d' % path] = median(
         lambda: _hip.ops.state_sums(states, actions, [w], S, 5, 24, False, path, out['raw'],
                                     out['skipped'], out['clamped']))
-  res['sums_k0'] = median_ms(
+  res['sums_k0'] = median(
       lambda: _hip.ops.state_sums(states, actions, [], S, 5, 24, False, 0, out['raw'][:1],
                                   out['skipped'], out['clamped']))
   x = torch.empty((T, B), device='cuda')
   pd = p.detach()
-  res['lookup'] = median_ms(lambda: _hip.ops.table_lookup(pd, states, actions, x, None))
+  res['lookup'] = median(lambda: _hip.ops.table_lookup(pd, states, actions, x, None))
   res['device'] = torch.cuda.get_device_name(0)
   return res
 
@@ -131,22 +118,10 @@ def fmt(v):
   return '   n/a  ' if v is None else '%8.4f' % v
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r10_learner.txt')
-  rows = []
-  for kind, S, B in ROWS:                  # a fresh process per row, one at a time
-    done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', kind, str(S), str(B)],
-                          stdout=subprocess.PIPE, text=True, timeout=900)
-    if done.returncode != 0:
-      print('row %s S=%d B=%d failed with status %d' % (kind, S, B, done.returncode))
-      return 2
-    rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
+def report(rows):
   lines = ['# tools/bench_learner.py: [T, B] streams -> gradient of the tabular loss, T = %d; median ms '
            'of %d event pairs after %d warm-up runs, a fresh process per row, %s'
-           % (T, RUNS, WARM, rows[0]['device']),
+           % (T, RUNS, WARM, benchlib.device_of(rows)),
            '# (1) .long() + advanced index + backward   (2) table_lookup() + backward   '
            '(3) sum_by_state() + loss over [S, 5] + backward',
            '%-10s %9s %6s | %8s %8s %8s | %7s | %-24s | %8s %8s %8s %8s | %8s'
@@ -165,12 +140,16 @@ def main():
     lines.append('#   gradients against (1), largest difference / largest |gradient|: (2) %.2e  (3) %.2e'
                  % (r['max_diff_2'], r['max_diff_3']))
   lines.append('gate (form (3) no slower than form (1) at every size): %s' % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r10_learner.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

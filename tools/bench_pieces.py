@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(REPO, 'examples'))
 sys.path.insert(0, os.path.join(REPO, 'tools'))
 
 import coins_batched as ex  # noqa: E402
-from bench_variants import timed  # noqa: E402
+from bench_variants import rollout_cost  # noqa: E402
 from campx import things  # noqa: E402
 from campx.ascii_art import ascii_art_to_game  # noqa: E402
 from campx_amd import gamespec, tabulate, wide  # noqa: E402
@@ -51,7 +51,7 @@ def main():
           ('a tracked thing each', road(0, 1)))
   for name, make in rows:
     game = make()
-    ms, tbs, tier, planes = timed(game, B)
+    ms, tbs, tier, planes = rollout_cost(game, B)
     spec = getattr(game.fused, 'spec', None)
     print('%-26s B=%d  %.4f ms per 100-frame rollout  %.2f TB/s of observations  (%s, %s trace planes, %d things, %d pieces, %d variants)' % (
         name, B, ms, tbs, tier, planes, game.fused.n_dyn, getattr(spec, 'n_pieces', 0), max(1, getattr(spec, 'n_variants', 1))))

@@ -19,39 +19,21 @@ GATE: path 0 is no slower per sweep than the torch restatement at every size, fo
 bytes a sweep of the global path has to move (40 per state of entries, 20 of weights for a policy,
 4 read and 4 written of values, 20 gathered) over its time, against a `fill_()` of 256 MiB.
 
-Settled clocks (warm-up runs first), event pairs around SWEEPS sweeps, median of 15 runs, a fresh
-process per row.
+Settled clocks (warm-up runs first), event pairs around SWEEPS sweeps, median of 15 runs.  Rows,
+failures and exit statuses: tools/benchlib.py.
 
     python tools/bench_planning.py [out.txt]        # default: profiles/r11_planning.txt
 """
-import json
-import os
-import statistics
-import subprocess
 import sys
 import types
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, SWEEPS, GAMMA = 15, 5, 32, 0.99
 ROWS = (('boat_race', 8), ('synthetic', 1940), ('synthetic', 4400000))
-
-
-def median_ms(fn):
-  import torch
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+ROW_SECONDS = 900
 
 
 def synthetic_table(S, seed=0):
@@ -95,7 +77,9 @@ def synthetic_table(S, seed=0):
 
 
 def row(kind, S):
-  """One row, in this process: a dict of medians in ms PER SWEEP."""
+  """One row, in this process: `kind`, `S`, `fill_gbs`, `device`, and for each reduction ('policy',
+  'greedy') `<name>_torch`, `<name>_path0` .. `_path2` (None where the path does not fit) - medians
+  in ms PER SWEEP -, `<name>_plan` and `<name>_max_diff`."""
   import ctypes
   import torch
   from campx_amd import _hip
@@ -131,7 +115,7 @@ def row(kind, S):
     want = torch_sweeps(policy)
     got = call(0)['values']
     res[name + '_max_diff'] = float((got - want).abs().max() / want.abs().max().clamp_min(1e-30))
-    res[name + '_torch'] = median_ms(lambda: torch_sweeps(policy)) / SWEEPS
+    res[name + '_torch'] = benchlib.median_ms(lambda: torch_sweeps(policy), RUNS, WARM) / SWEEPS
     plan = (ctypes.c_int64 * 4)()
     _hip.check(_hip.lib.campx_wide_sweeps_plan(S, 1 if policy else 0, 0, _hip.config_get('wide_lds_max'),
                                                0, plan), 'campx_wide_sweeps_plan')
@@ -139,10 +123,11 @@ def row(kind, S):
     for path in (0, 1, 2):
       fits = _hip.lib.campx_wide_sweeps_plan(S, 1 if policy else 0, 0, _hip.config_get('wide_lds_max'),
                                              path, plan) == 0
-      res['%s_path%d' % (name, path)] = median_ms(lambda: call(path)) / SWEEPS if fits else None
+      res['%s_path%d' % (name, path)] = (benchlib.median_ms(lambda: call(path), RUNS, WARM) / SWEEPS
+                                         if fits else None)
   game.check_actions()
   big = torch.empty((256 << 20,), dtype=torch.uint8, device='cuda')
-  res['fill_gbs'] = big.numel() / (median_ms(lambda: big.fill_(1)) * 1e-3) / 1e9
+  res['fill_gbs'] = big.numel() / (benchlib.median_ms(lambda: big.fill_(1), RUNS, WARM) * 1e-3) / 1e9
   res['device'] = torch.cuda.get_device_name(0)
   return res
 
@@ -151,21 +136,10 @@ def fmt(v):
   return '    n/a   ' if v is None else '%10.5f' % v
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r11_planning.txt')
-  rows = []
-  for kind, S in ROWS:                     # a fresh process per row, one at a time
-    done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', kind, str(S)],
-                          stdout=subprocess.PIPE, text=True, timeout=900)
-    if done.returncode != 0:
-      print('row %s S=%d failed with status %d' % (kind, S, done.returncode))
-      return 2
-    rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
+def report(rows):
   lines = ['# tools/bench_planning.py: ms PER SWEEP (%d sweeps a call, gamma %.2f); median of %d event pairs '
-           'after %d warm-up runs, a fresh process per row, %s' % (SWEEPS, GAMMA, RUNS, WARM, rows[0]['device']),
+           'after %d warm-up runs, a fresh process per row, %s'
+           % (SWEEPS, GAMMA, RUNS, WARM, benchlib.device_of(rows)),
            '%-10s %8s %-7s | %10s | %10s %10s %10s | %4s | %8s | %9s %9s'
            % ('table', 'S', 'reduce', 'torch', 'path 0', 'LDS (1)', 'global (2)', 'auto', 'torch/0',
               'glb GB/s', 'fill GB/s')]
@@ -184,12 +158,16 @@ def main():
                    % r[name + '_max_diff'])
   lines.append('gate (path 0 no slower per sweep than the torch restatement at every size): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r11_planning.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -16,57 +16,30 @@ Settled clocks (warm-up launches first), event pairs, median of 25 runs.
 
     python tools/bench_policy.py [out.txt]        # default: profiles/r08_policy.txt
 """
-import os
-import statistics
+import functools
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 import torch  # noqa: E402
 
-from campx_amd.games import boat_race, maze  # noqa: E402
-
 RUNS, WARM, T = 25, 10, 100
-
-
-def median_ms(fn):
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
-
-
-def build(name, B):
-  if name == 'boat_race':
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=B, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game
+median = functools.partial(benchlib.median_ms, runs=RUNS, warm=WARM)
 
 
 def point(name, B, lines):
-  game = build(name, B)
+  game = benchlib.state_table_game(name, B)
   f = game.fused
   gen = torch.Generator(device='cuda').manual_seed(1)
   weights = torch.rand((f.n_states, 5), generator=gen, device='cuda') + 0.05
   bufs = f.rollout_policy_buffers(T)
-  closed = median_ms(lambda: f.rollout_policy(weights, T, seed=1, reset_first=True, out=bufs))
+  closed = median(lambda: f.rollout_policy(weights, T, seed=1, reset_first=True, out=bufs))
   acts = bufs['actions'].contiguous()
   lean = f.rollout_trace_buffers(T)
-  floor = median_ms(lambda: f.rollout_trace(acts, reset_first=True, out=lean))
+  floor = median(lambda: f.rollout_trace(acts, reset_first=True, out=lean))
   lean_ns = f.rollout_policy_buffers(T, want_states=False)
-  no_states = median_ms(lambda: f.rollout_policy(weights, T, seed=1, reset_first=True, out=lean_ns,
+  no_states = median(lambda: f.rollout_policy(weights, T, seed=1, reset_first=True, out=lean_ns,
                                                  want_states=False))
 
   def act(observation, t):       # the frame starts from row 0 when the last one ended the episode
@@ -74,7 +47,7 @@ def point(name, B, lines):
     return torch.multinomial(weights[row], 1).squeeze(1)
   f.reset()
   graph = game.capture_play(T, policy=act)
-  replay = median_ms(graph.replay)
+  replay = median(graph.replay)
   lines.append('%-10s S=%-4d B=%-6d T=%d  rollout_policy() %.4f ms (without states %.4f)   '
                'rollout_trace() on its actions %.4f ms (x%.2f)   capture_play graph replay %.4f ms (x%.1f)'
                % (name, f.n_states, B, T, closed, no_states, floor, closed / floor, replay, replay / closed))
@@ -84,7 +57,7 @@ def point(name, B, lines):
 
 
 def main():
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r08_policy.txt')
+  path = benchlib.out_path(sys.argv[1:], 'r08_policy.txt')
   lines = ['# tools/bench_policy.py: median of %d event pairs after %d warm-up runs, %s'
            % (RUNS, WARM, torch.cuda.get_device_name(0))]
   ok = True

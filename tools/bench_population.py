@@ -10,67 +10,35 @@ same loop (the three alternate, so that a drifting clock meets them alike):
   (b) one `rollout_policy()` on a game of n environments, times P: P launches on P small games,
       which is what a population costs without this call.
 
-GATE: population time <= (b) for every P >= 16 (exit status 1 otherwise): the one-launch claim is
-the feature.  A row that fails or outlasts its time limit ends the run (exit status 2): nothing
-more is started on the device, and what was collected is written.  The ratio to (a) is reported, with the path each row took (1 = table and thresholds
-in LDS, 2 = through L1 / L2) and the members one workgroup stages, and is not gated.
+GATE: population time <= (b) for every P >= 16: the one-launch claim is the feature.  The ratio to
+(a) is reported, with the path each row took (1 = table and thresholds in LDS, 2 = through L1 / L2)
+and the members one workgroup stages, and is not gated.  Rows, failures and exit statuses:
+tools/benchlib.py.
 
-A fresh process per row; settled clocks (warm-up launches first), event pairs, median of 25.
+Settled clocks (warm-up launches first), event pairs, median of 25.
 
     python tools/bench_population.py [out.txt]      # default: profiles/r14_population.txt
 """
 import ctypes
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, T, B = 25, 10, 100, 65536
 MEMBERS = (1, 16, 256, 65536)
 GAMES = ('boat_race', 'maze16')
-GATE_MISSED = 3            # exit status of a row that ran and missed the gate
 ROW_SECONDS = 300          # a row builds two games and times 35 rounds of three launches: seconds
 
 
-def build(name, batch):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(batch, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=batch, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game
-
-
-def medians_ms(fns):
-  """The median time of each of `fns`, run in turn: every round times each once."""
-  import torch
-  for _ in range(WARM):
-    for fn in fns:
-      fn()
-  torch.cuda.synchronize()
-  times = [[] for _ in fns]
-  for _ in range(RUNS):
-    for i, fn in enumerate(fns):
-      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      e0.record()
-      fn()
-      e1.record()
-      e1.synchronize()
-      times[i].append(e0.elapsed_time(e1))
-  return [statistics.median(t) for t in times]
-
-
 def row(name, P):
-  """One row, in this process: prints it; exit status GATE_MISSED when the gate is missed."""
+  """One row, in this process: `name`, `S`, `P`, `plan` (path, LDS bytes, -, members staged), the
+  medians `pop`, `same_b` (a) and `one_member` (one launch of (b)) in ms, `device`; the outcome is
+  the row's gate."""
   import torch
   from campx_amd import _hip
-  big, small = build(name, B).fused, build(name, B // P).fused
+  big, small = benchlib.state_table_game(name, B).fused, benchlib.state_table_game(name, B // P).fused
   S = big.n_states
   gen = torch.Generator(device='cuda').manual_seed(1)
   policies = torch.rand((P, S, 5), generator=gen, device='cuda') + 0.05
@@ -81,54 +49,42 @@ def row(name, P):
              'campx_wide_population_plan')
   pop_bufs, big_bufs = big.rollout_population_buffers(T), big.rollout_policy_buffers(T)
   small_bufs = small.rollout_policy_buffers(T)
-  pop, same_b, one_member = medians_ms([
-      lambda: big.rollout_population(policies, T, seed=1, reset_first=True, out=pop_bufs),
-      lambda: big.rollout_policy(one, T, seed=1, reset_first=True, out=big_bufs),
-      lambda: small.rollout_policy(one, T, seed=1, reset_first=True, out=small_bufs)])
-  today = one_member * P
-  ok = P < 16 or pop <= today
-  print('%-10s S=%-4d B=%d T=%d  P=%-6d n=%-6d path %d, %3d members staged (%6d B LDS)   '
-        'rollout_population() %.4f ms   (a) rollout_policy() at B %.4f ms (x%.2f)   '
-        '(b) P x rollout_policy() at n: %d x %.4f = %.3f ms (x%.1f)%s'
-        % (name, S, B, T, P, B // P, plan[0], plan[3], plan[1], pop, same_b, pop / same_b, P,
-           one_member, today, today / pop, '' if ok else '   GATE MISSED'))
-  return 0 if ok else GATE_MISSED
+  ms = benchlib.alternating_ms({
+      'pop': lambda: big.rollout_population(policies, T, seed=1, reset_first=True, out=pop_bufs),
+      'same_b': lambda: big.rollout_policy(one, T, seed=1, reset_first=True, out=big_bufs),
+      'one_member': lambda: small.rollout_policy(one, T, seed=1, reset_first=True, out=small_bufs)}, RUNS, WARM)
+  res = {'name': name, 'S': S, 'P': P, 'plan': list(plan), 'device': torch.cuda.get_device_name(0)}
+  res.update((key, ms[key][0]) for key in ms)
+  res['outcome'] = 'ok' if P < 16 or res['pop'] <= res['one_member'] * P else 'gate_missed'
+  return res
 
 
-def main():
-  if len(sys.argv) == 4 and sys.argv[1] == '--row':
-    return row(sys.argv[2], int(sys.argv[3]))
-  import torch
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r14_population.txt')
+def report(records):
   lines = ['# tools/bench_population.py: a process per row; median of %d event pairs after %d warm-up '
-           'rounds, the three calls of a row alternating; %s' % (RUNS, WARM, torch.cuda.get_device_name(0))]
-  ok, broke = True, False
-  for name, P in [(name, P) for name in GAMES for P in MEMBERS]:
-    try:
-      done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(P)],
-                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                            timeout=ROW_SECONDS)
-    except subprocess.TimeoutExpired as late:
-      lines.append('%s P=%d  ROW TIMED OUT after %d s\n%s' % (name, P, ROW_SECONDS, (late.stderr or '')[-2000:]))
-      ok, broke = False, True
-      break                      # nothing more is started on the device after a failure
-    lines.append(done.stdout.rstrip('\n'))
-    if done.returncode not in (0, GATE_MISSED):
-      lines.append('  ROW FAILED (exit status %d)\n%s' % (done.returncode, done.stderr.rstrip('\n')))
-      ok, broke = False, True
-      break                      # nothing more is started on the device after a failure
-    if done.returncode == GATE_MISSED:
-      ok = False
-  if broke:
-    lines.append('the run ended at the row above; the rows after it were not started')
+           'rounds, the three calls of a row alternating; %s' % (RUNS, WARM, benchlib.device_of(records))]
+  ok = True
+  for r in records:
+    met = r['outcome'] == 'ok'
+    ok = ok and met
+    P, plan, pop = r['P'], r['plan'], r['pop']
+    today = r['one_member'] * P
+    lines.append('%-10s S=%-4d B=%d T=%d  P=%-6d n=%-6d path %d, %3d members staged (%6d B LDS)   '
+                 'rollout_population() %.4f ms   (a) rollout_policy() at B %.4f ms (x%.2f)   '
+                 '(b) P x rollout_policy() at n: %d x %.4f = %.3f ms (x%.1f)%s'
+                 % (r['name'], r['S'], B, T, P, B // P, plan[0], plan[3], plan[1], pop, r['same_b'],
+                    pop / r['same_b'], P, r['one_member'], today, today / pop, '' if met else '   GATE MISSED'))
   lines.append('gate (rollout_population() no slower than P launches of rollout_policy() on n environments, '
                'every P >= 16): %s' % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 2 if broke else (0 if ok else 1)
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, [(name, P) for name in GAMES for P in MEMBERS], ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r14_population.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -13,60 +13,32 @@ GATE: at P = 16 on the boat race the one launch (path 0) takes no longer than th
 `evaluate_policy()` calls (exit status 1 otherwise).  Sixteen launches against one leave no doubt
 about the direction, so there is no margin.  Every other figure is recorded, not gated.
 
-Settled clocks (warm-up runs first), an event pair around each call, median of 25, a fresh process
-per row.
+Settled clocks (warm-up runs first), an event pair around each call, median of 25.  Rows, failures
+and exit statuses: tools/benchlib.py.
 
     python tools/bench_population_planning.py [out.txt]     # default: profiles/r16_population_planning.txt
 """
 import ctypes
-import json
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, SWEEPS, GAMMA = 25, 5, 64, 0.99
 GAMES = ('boat_race', 'maze16')
 MEMBERS = (1, 16, 256, 4096, 65536)
 LOOP_UP_TO = 256
-
-
-def median_ms(fn):
-  import torch
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
-
-
-def build(name):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(1, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=1, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game.fused
+ROW_SECONDS = 600
 
 
 def row(name, P):
-  """One row, in this process: medians in ms per call of SWEEPS sweeps."""
+  """One row, in this process: `game`, `S`, `P`, `plan`, `device`, and medians in ms per call of
+  SWEEPS sweeps: `path0` .. `path2` (None where the path does not fit) and `loop` (None above
+  LOOP_UP_TO, else with `same_bits`: its last member agrees with the launch's)."""
   import torch
   from campx_amd import _hip
-  game = build(name)
+  game = benchlib.state_table_game(name, 1).fused
   S = game.n_states
   torch.manual_seed(P)
   policies = torch.rand((P, S, 5), device='cuda').add_(0.5)
@@ -80,8 +52,8 @@ def row(name, P):
   res['plan'] = list(plan)
   for path in (0, 1, 2):
     fits = _hip.lib.campx_wide_population_sweeps_plan(S, P, 0, lds_max, cus, path, plan) == 0
-    res['path%d' % path] = (median_ms(lambda: game.evaluate_population(policies, GAMMA, SWEEPS, out=out, path=path))
-                            if fits else None)
+    launch = lambda: game.evaluate_population(policies, GAMMA, SWEEPS, out=out, path=path)
+    res['path%d' % path] = benchlib.median_ms(launch, RUNS, WARM) if fits else None
   res['loop'] = None
   if P <= LOOP_UP_TO:
     single = game.sweep_buffers(SWEEPS, want_q=False, greedy=False)
@@ -90,7 +62,7 @@ def row(name, P):
       for m in range(P):
         game.evaluate_policy(policies[m], GAMMA, SWEEPS, want_q=False, out=single)
 
-    res['loop'] = median_ms(loop)
+    res['loop'] = benchlib.median_ms(loop, RUNS, WARM)
     # the two agree: the last member of the loop against the population's
     got = game.evaluate_population(policies, GAMMA, SWEEPS, out=out)['values'][P - 1]
     res['same_bits'] = bool(torch.equal(got.view(torch.int32), single['values'].view(torch.int32)))
@@ -101,23 +73,10 @@ def fmt(v):
   return '      n/a' if v is None else '%9.4f' % v
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r16_population_planning.txt')
-  rows = []
-  for name in GAMES:
-    for P in MEMBERS:                      # a fresh process per row, one at a time
-      done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(P)],
-                            stdout=subprocess.PIPE, text=True, timeout=600)
-      if done.returncode != 0:
-        print('row %s P=%d failed with status %d' % (name, P, done.returncode))
-        return 2
-      rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
+def report(rows):
   lines = ['# tools/bench_population_planning.py: ms PER CALL of %d sweeps (gamma %.2f), P policies a call; median '
            'of %d event pairs after %d warm-up runs, a fresh process per row, %s'
-           % (SWEEPS, GAMMA, RUNS, WARM, rows[0]['device']),
+           % (SWEEPS, GAMMA, RUNS, WARM, benchlib.device_of(rows)),
            '# loop: P calls of evaluate_policy(), timed for P <= %d and not extrapolated beyond' % LOOP_UP_TO,
            '%-10s %5s %6s | %9s %9s %9s | %4s %5s %8s | %9s %9s'
            % ('game', 'S', 'P', 'path 0', 'LDS (1)', 'global(2)', 'auto', 'G', 'grid', 'loop', 'loop / 0')]
@@ -134,12 +93,16 @@ def main():
                     '' if r.get('same_bits', True) else '   THE LOOP AND THE LAUNCH DIFFER'))
   lines.append('gate (boat race, P = 16: the one launch no slower than the loop of 16 evaluate_policy() calls): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, [(name, P) for name in GAMES for P in MEMBERS], ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r16_population_planning.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -18,62 +18,32 @@ the members to a workgroup or the choice of path; the forced paths are recorded 
 one and no crossover is claimed.
 
 Settled clocks (warm-up runs first), an event pair around each call, median of 25, the timed
-alternatives taking turns within every one of the 25 rounds, a fresh process per row.
+alternatives taking turns within every one of the 25 rounds.  Rows, failures and exit statuses:
+tools/benchlib.py.
 
     python tools/bench_population_rewards.py [out.txt]      # default: profiles/r20_population_rewards.txt
 """
 import ctypes
-import json
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, SWEEPS, GAMMA = 25, 3, 64, 0.99
 GAMES = ('boat_race', 'maze16')
 MEMBERS = (1, 16, 256, 4096)
 FORMS = ('greedy', 'policy')
-
-
-def medians_ms(alternatives):
-  """{name: median ms} of the callables of `alternatives`, which take turns within each round."""
-  import torch
-  for _ in range(WARM):
-    for fn in alternatives.values():
-      fn()
-  torch.cuda.synchronize()
-  times = {name: [] for name in alternatives}
-  for _ in range(RUNS):
-    for name, fn in alternatives.items():
-      e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-      e0.record()
-      fn()
-      e1.record()
-      e1.synchronize()
-      times[name].append(e0.elapsed_time(e1))
-  return {name: statistics.median(t) for name, t in times.items()}
-
-
-def build(name):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(1, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=1, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game.fused
+ROW_SECONDS = 900
 
 
 def row(name, P):
-  """One row, in this process: per form, medians in ms per call of SWEEPS sweeps."""
+  """One row, in this process: `game`, `S`, `P`, `device`, and per form ('greedy', 'policy') a dict
+  of `plan`, `same_bits` and medians in ms per call of SWEEPS sweeps: `loop`, `path0`, and `path1`,
+  `path2` where they fit."""
   import torch
   from campx_amd import _hip
-  game = build(name)
+  game = benchlib.state_table_game(name, 1).fused
   S = game.n_states
   torch.manual_seed(P)
   policies = torch.rand((P, S, 5), device='cuda').add_(0.5)
@@ -107,7 +77,7 @@ def row(name, P):
     for path in (0, 1, 2):
       if _hip.lib.campx_wide_population_solve_plan(S, P, policy, 1, lds_max, cus, path, plan) == 0:
         alternatives['path%d' % path] = (lambda path: lambda: launch(path))(path)
-    r.update(medians_ms(alternatives))
+    r.update((key, ms[0]) for key, ms in benchlib.alternating_ms(alternatives, RUNS, WARM).items())
     # the two agree: the last member of the loop against the population's
     loop()
     got = launch(0)['values'][P - 1]
@@ -120,24 +90,10 @@ def fmt(v):
   return '      n/a' if v is None else '%9.4f' % v
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r20_population_rewards.txt')
-  rows = []
-  for name in GAMES:
-    for P in MEMBERS:                      # a fresh process per row, one at a time
-      done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(P)],
-                            stdout=subprocess.PIPE, text=True, timeout=900)
-      if done.returncode != 0:
-        print('row %s P=%d failed with status %d' % (name, P, done.returncode))
-        return 2
-      rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
-      print('row %s P=%d done' % (name, P), flush=True)
+def report(rows):
   lines = ['# tools/bench_population_rewards.py: ms PER CALL of %d sweeps (gamma %.2f), P reward tables a call; '
            'median of %d event pairs after %d warm-up rounds, the alternatives taking turns within a round, '
-           'a fresh process per row, %s' % (SWEEPS, GAMMA, RUNS, WARM, rows[0]['device']),
+           'a fresh process per row, %s' % (SWEEPS, GAMMA, RUNS, WARM, benchlib.device_of(rows)),
            '# greedy: value_iteration_population(rewards=) against P calls of value_iteration(reward=); '
            'policy: evaluate_population(rewards=) against P calls of evaluate_policy(reward=)',
            '# gated: path 0 <= loop at P >= 16.  Not measured: other table sizes, other sweep counts, the '
@@ -159,12 +115,16 @@ def main():
                       '' if f['same_bits'] else '   THE LOOP AND THE LAUNCH DIFFER'))
   lines.append('gate (P >= 16, both forms, both games: the one launch no slower than the loop it replaces): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, [(name, P) for name in GAMES for P in MEMBERS], ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r20_population_rewards.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -12,57 +12,27 @@ and 1 024 actors per learner (P = B / n learners), each path forced where the pl
     bits (tests/test_shared_learner.py has those);
   * `learn_tabular()` at the same B and T - a table per environment - for information only.
 
-GATE: the launch is no slower than the torch loop, every row (exit status 1 otherwise).  A row that
-fails or outlasts its time limit ends the run (exit status 2): nothing more is started on the
-device, and what was collected is written.
+GATE: the launch is no slower than the torch loop, every row.  Rows, failures and exit statuses:
+tools/benchlib.py.
 
-A fresh process per row; warm-up first, event pairs, the median of 15 launches and of 3 torch loops.
+Warm-up first, event pairs, the median of 15 launches and of 3 torch loops.
 
     python tools/bench_shared.py [out.txt]      # default: profiles/r19_shared.txt
 """
 import ctypes
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 T, B = 1000, 65536
 RUNS, WARM = 15, 3                 # launches
 LOOP_RUNS, LOOP_WARM_FRAMES = 3, 50     # torch loops of T frames
 ACTORS = (1, 16, 256, 1024)
 ROWS = tuple((name, n, path) for name in ('boat_race', 'maze16') for n in ACTORS for path in (1, 2))
-GATE_MISSED = 3            # exit status of a row that ran and missed the gate
-SKIPPED = 4                # ... of a row whose forced path the plan refuses
 ROW_SECONDS = 240          # a row builds one game and runs 36 launches and 3 050 torch frames: seconds
 ALPHA, GAMMA, EPSILON = 0.1, 0.9, 0.1
-
-
-def build(name):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=B, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game
-
-
-def timed_ms(fn, runs):
-  import torch
-  times = []
-  for _ in range(runs):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
 
 
 def torch_frames(game, q, n, frames):
@@ -92,85 +62,68 @@ def torch_frames(game, q, n, frames):
 
 
 def row(name, n, path):
-  """One row, in this process: prints it; exit status GATE_MISSED when the gate is missed."""
+  """One row, in this process: `name`, `S`, `n`, `P`, `path`, `device`; skipped where the plan
+  refuses the forced path, else `plan` (path, G, threads, LDS bytes, entries in LDS) and the medians
+  `ours`, `loop` and `tabular` in ms, the outcome being the row's gate."""
   import torch
   from campx_amd import _hip
-  game = build(name)
+  game = benchlib.state_table_game(name, B)
   f = game.fused
   S, P = f.n_states, B // n
+  res = {'name': name, 'S': S, 'n': n, 'P': P, 'path': path, 'device': torch.cuda.get_device_name(0)}
   plan = (ctypes.c_int64 * 6)()
   if _hip.lib.campx_wide_shared_plan(S, int(f.has_perf), B, P, _hip.config_get('wide_lds_max'), path,
                                      plan) != 0:
-    print('%-10s S=%-4d n=%-4d P=%-5d  path %d does not apply (not one learner fits the LDS)'
-          % (name, S, n, P, path))
-    return SKIPPED
+    return dict(res, outcome='skipped')
   q = torch.zeros((P, S, 5), device='cuda')
   hyper = [torch.full((P,), x, device='cuda') for x in (ALPHA, GAMMA, EPSILON)]
   out = game.shared_learner_buffers(P, T, 100, path)
-  launch = lambda: game.learn_shared(T, q, *hyper, seed=1, window=100, out=out, path=path)
-  for _ in range(WARM):
-    launch()
-  torch.cuda.synchronize()
-  ours = timed_ms(launch, RUNS)
+  ours = benchlib.median_ms(lambda: game.learn_shared(T, q, *hyper, seed=1, window=100, out=out, path=path),
+                            RUNS, WARM)
   q.zero_()
   torch_frames(game, q, n, LOOP_WARM_FRAMES)
-  torch.cuda.synchronize()
-  loop = timed_ms(lambda: torch_frames(game, q, n, T), LOOP_RUNS)
+  loop = benchlib.median_ms(lambda: torch_frames(game, q, n, T), LOOP_RUNS)
   del q, out
   # for information: a table per environment, the same B and T
   q_each = torch.zeros((B, S, 5), device='cuda')
   each = [torch.full((B,), x, device='cuda') for x in (ALPHA, GAMMA, EPSILON)]
   bufs = game.learner_buffers(T, 100)
-  alone = lambda: game.learn_tabular(T, q_each, *each, seed=1, window=100, out=bufs)
-  for _ in range(WARM):
-    alone()
-  torch.cuda.synchronize()
-  tabular = timed_ms(alone, RUNS)
-  ok = ours <= loop
-  print('%-10s S=%-4d n=%-4d P=%-5d  path %d (G %d, %d threads, %6d B LDS, entries %s)   learn_shared() %.3f ms '
-        '= %.2f us / frame   torch loop %.1f ms = %.1f us / frame (x%.0f)   learn_tabular() %.3f ms%s'
-        % (name, S, n, P, plan[0], plan[1], plan[2], plan[3], 'in LDS' if plan[4] else 'through L1 / L2',
-           ours, ours * 1000 / T, loop, loop * 1000 / T, loop / ours, tabular, '' if ok else '   GATE MISSED'))
-  return 0 if ok else GATE_MISSED
+  tabular = benchlib.median_ms(lambda: game.learn_tabular(T, q_each, *each, seed=1, window=100, out=bufs),
+                               RUNS, WARM)
+  return dict(res, plan=list(plan), ours=ours, loop=loop, tabular=tabular,
+              outcome='ok' if ours <= loop else 'gate_missed')
 
 
-def main():
-  if len(sys.argv) == 5 and sys.argv[1] == '--row':
-    return row(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))
-  import torch
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r19_shared.txt')
+def report(records):
   lines = ['# tools/bench_shared.py: B = %d, T = %d; a process per row; event pairs, the median of %d '
            'launches after %d warm-up launches and of %d torch loops after %d warm-up frames; %s'
-           % (B, T, RUNS, WARM, LOOP_RUNS, LOOP_WARM_FRAMES, torch.cuda.get_device_name(0))]
-  ok, broke = True, False
-  for name, n, forced in ROWS:
-    try:
-      done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(n), str(forced)],
-                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                            timeout=ROW_SECONDS)
-    except subprocess.TimeoutExpired as late:
-      lines.append('%s n %d path %d  ROW TIMED OUT after %d s\n%s'
-                   % (name, n, forced, ROW_SECONDS, (late.stderr or '')[-2000:]))
-      ok, broke = False, True
-      break                      # nothing more is started on the device after a failure
-    lines.append(done.stdout.rstrip('\n'))
-    if done.returncode not in (0, GATE_MISSED, SKIPPED):
-      lines.append('  ROW FAILED (exit status %d)\n%s' % (done.returncode, done.stderr.rstrip('\n')))
-      ok, broke = False, True
-      break                      # nothing more is started on the device after a failure
-    if done.returncode == GATE_MISSED:
-      ok = False
-    print(lines[-1], flush=True)
-  if broke:
-    lines.append('the run ended at the row above; the rows after it were not started')
+           % (B, T, RUNS, WARM, LOOP_RUNS, LOOP_WARM_FRAMES, benchlib.device_of(records))]
+  ok = True
+  for r in records:
+    if r['outcome'] == 'skipped':
+      lines.append('%-10s S=%-4d n=%-4d P=%-5d  path %d does not apply (not one learner fits the LDS)'
+                   % (r['name'], r['S'], r['n'], r['P'], r['path']))
+      continue
+    met = r['outcome'] == 'ok'
+    ok = ok and met
+    plan, ours, loop = r['plan'], r['ours'], r['loop']
+    lines.append('%-10s S=%-4d n=%-4d P=%-5d  path %d (G %d, %d threads, %6d B LDS, entries %s)   learn_shared() %.3f ms '
+                 '= %.2f us / frame   torch loop %.1f ms = %.1f us / frame (x%.0f)   learn_tabular() %.3f ms%s'
+                 % (r['name'], r['S'], r['n'], r['P'], plan[0], plan[1], plan[2], plan[3],
+                    'in LDS' if plan[4] else 'through L1 / L2', ours, ours * 1000 / T, loop, loop * 1000 / T,
+                    loop / ours, r['tabular'], '' if met else '   GATE MISSED'))
   lines.append('gate (learn_shared() no slower than the torch loop of the same frames, every row): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 2 if broke else (0 if ok else 1)
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r19_shared.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

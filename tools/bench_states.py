@@ -20,43 +20,25 @@ Settled clocks (warm-up runs first), event pairs, median of 25 runs.
 
     python tools/bench_states.py [out.txt]        # default: profiles/r09_states.txt
 """
-import os
-import statistics
+import functools
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 import torch  # noqa: E402
 
-from campx_amd.games import boat_race, maze, sokoban  # noqa: E402
+from campx_amd.games import sokoban  # noqa: E402
 from campx_amd.returns import discounted_returns  # noqa: E402
 
 RUNS, WARM, T = 25, 10, 100
-
-
-def median_ms(fn):
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+median = functools.partial(benchlib.median_ms, runs=RUNS, warm=WARM)
 
 
 def build(name, B):
-  if name == 'boat_race':
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  elif name == 'maze16':
-    game = maze.build(16, 16, batch=B, device='cuda')
-  else:
-    game = sokoban.build(batch=B, device='cuda', level=3)
+  if name != 'sokoban16':
+    return benchlib.state_table_game(name, B)
+  game = sokoban.build(batch=B, device='cuda', level=3)
   game.its_showtime()
   game.fused.validate_actions = False
   return game
@@ -68,8 +50,8 @@ def states_point(name, lines):
   S, R = f.n_states, f.n_layers * f.rows * f.cols
   for dtype in (torch.int8, torch.bfloat16):
     out = torch.empty((S, f.n_layers, f.rows, f.cols), dtype=dtype, device='cuda')
-    render = median_ms(lambda: f.render_states(obs_dtype=dtype, out=out))
-    fill = median_ms(lambda: out.fill_(1))
+    render = median(lambda: f.render_states(obs_dtype=dtype, out=out))
+    fill = median(lambda: out.fill_(1))
     nbytes = S * R * out.element_size()
     lines.append('render_states  %-10s S=%-8d %-8s %9.3f MB  %.4f ms (%.2f TB/s)   fill_ %.4f ms   '
                  'fill_ / render_states %.2f'
@@ -90,8 +72,8 @@ def returns_point(B, lines):
   values = torch.rand((T, B), device='cuda')
   bootstrap = torch.rand((B,), device='cuda')
   out = {'returns': torch.empty((T, B), device='cuda'), 'advantages': torch.empty((T, B), device='cuda')}
-  plain = median_ms(lambda: discounted_returns(reward, done, 0.99, out={'returns': out['returns']}))
-  full = median_ms(lambda: discounted_returns(reward, done, 0.99, discount=discount, values=values,
+  plain = median(lambda: discounted_returns(reward, done, 0.99, out={'returns': out['returns']}))
+  full = median(lambda: discounted_returns(reward, done, 0.99, discount=discount, values=values,
                                               bootstrap=bootstrap, lam=0.95, out=out))
 
   def loop():
@@ -100,7 +82,7 @@ def returns_point(B, lines):
       running = r + 0.99 * running
       returns.append(running)
     return torch.stack(returns[::-1])
-  host = median_ms(loop)
+  host = median(loop)
   lines.append('discounted_returns  T=%d B=%-6d  returns %.4f ms   with discount, values, bootstrap '
                '%.4f ms   the reversed torch loop %.4f ms (x%.1f)'
                % (T, B, plain, full, host, host / plain))
@@ -110,7 +92,7 @@ def returns_point(B, lines):
 
 
 def main():
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r09_states.txt')
+  path = benchlib.out_path(sys.argv[1:], 'r09_states.txt')
   lines = ['# tools/bench_states.py: median of %d event pairs after %d warm-up runs, %s'
            % (RUNS, WARM, torch.cuda.get_device_name(0))]
   for name in ('boat_race', 'maze16', 'sokoban16'):

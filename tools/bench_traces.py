@@ -11,25 +11,21 @@ T = 1 000, B = 65 536, the boat race (8 states) and the 16x16 maze (159 states).
   - `learn_traces()` planned, and with every (path, team) forced that fits, team in TEAMS
     (`--teams all`: every power of two up to 256).
 
-GATE: every `learn_traces()` row is no slower than its game's torch loop (exit status 1 otherwise).
-A row that fails or outlasts its time limit ends the run (exit status 2): nothing more is started
-on the device, and what was collected is written.
+GATE: every `learn_traces()` row is no slower than its game's torch loop.  Rows, failures and exit
+statuses: tools/benchlib.py.
 
-A fresh process per row; warm-up first, event pairs, the median of 15 launches and of 3 torch
-loops.  A row whose first launch takes more than SLOW_MS is timed as the median of 3 launches and
-says so.
+Warm-up first, event pairs, the median of 15 launches and of 3 torch loops.  A row whose first
+launch takes more than SLOW_MS is timed as the median of 3 launches and says so.
 
     python tools/bench_traces.py [out.txt] [--teams all] [--games boat_race,maze16]
                                                 # default: profiles/r21_traces.txt
 """
 import ctypes
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 T, B = 1000, 65536
 RUNS, WARM = 15, 3                 # launches
@@ -40,39 +36,6 @@ TEAMS = (1, 2, 8, 64, 256)
 ALL_TEAMS = (1, 2, 4, 8, 16, 32, 64, 128, 256)
 ROW_SECONDS = 300
 ALPHA, GAMMA, EPSILON, LAM = 0.1, 0.9, 0.1, 0.9
-
-
-def build(name):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=B, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game
-
-
-def plan_of(f, path, team):
-  from campx_amd import _hip
-  plan = (ctypes.c_int64 * 5)()
-  code = _hip.lib.campx_wide_traces_plan(f.n_states, int(f.has_perf), B, _hip.config_get('wide_lds_max'),
-                                         path, team, plan)
-  return code, list(plan)
-
-
-def timed_ms(fn, runs):
-  import torch
-  times = []
-  for _ in range(runs):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
 
 
 def torch_frames(game, q, z, frames):
@@ -103,64 +66,97 @@ def torch_frames(game, q, z, frames):
 
 
 def row(name, what, path, team):
-  """One row, in this process: prints 'ms<TAB>text'."""
+  """One row, in this process: `name`, `S`, `what` ('torch', 'tabular' or 'traces'), the forced
+  `path` and `team` (0, 0: planned), the median `ms` of `runs` calls, `device`; for 'traces' also
+  `plan` (path, team, LDS bytes, ...)."""
   import torch
-  game = build(name)
+  from campx_amd import _hip
+  game = benchlib.state_table_game(name, B)
   f = game.fused
   S = f.n_states
   q = torch.zeros((B, S, 5), device='cuda')
   z = torch.zeros((B, S, 5), device='cuda')
-  head = '%-10s S=%-4d B=%d T=%d  ' % (name, S, B, T)
+  res = {'name': name, 'S': S, 'what': what, 'path': path, 'team': team, 'device': torch.cuda.get_device_name(0)}
   if what == 'torch':
     torch_frames(game, q, z, LOOP_WARM_FRAMES)
-    torch.cuda.synchronize()
-    ms = timed_ms(lambda: torch_frames(game, q, z, T), LOOP_RUNS)
-    print('%.6f\t%storch restatement (play() + dense q += step * z; z *= c per frame)   %.1f ms = %.1f us / frame'
-          % (ms, head, ms, ms * 1000 / T))
-    return 0
+    return dict(res, runs=LOOP_RUNS, ms=benchlib.median_ms(lambda: torch_frames(game, q, z, T), LOOP_RUNS))
   hyper = [torch.full((B,), x, device='cuda') for x in (ALPHA, GAMMA, EPSILON)]
   out = game.learner_buffers(T, 100)
   if what == 'tabular':
     launch = lambda: game.learn_tabular(T, q, *hyper, seed=1, window=100, out=out)
-    label = 'learn_tabular() planned'
   else:
     lam = torch.full((B,), LAM, device='cuda')
     launch = lambda: game.learn_traces(T, q, z, lam, 'accumulating', *hyper, seed=1, window=100, out=out,
                                        path=path, team=team)
-    plan = plan_of(f, path, team)[1]
-    label = 'learn_traces() %s -> path %d team %-3d (%6d B LDS)' % (
-        'planned        ' if (path, team) == (0, 0) else 'path=%d team=%-3d' % (path, team),
-        plan[0], plan[1], plan[2])
-  first = timed_ms(launch, 1)
-  runs, warm = (RUNS, WARM) if first <= SLOW_MS else (SLOW_RUNS, 0)
-  for _ in range(warm):
-    launch()
-  torch.cuda.synchronize()
-  ms = timed_ms(launch, runs)
-  print('%.6f\t%s%s   %.3f ms = %.2f us / frame%s'
-        % (ms, head, label, ms, ms * 1000 / T, '' if runs == RUNS else '   (median of %d: slow row)' % runs))
-  return 0
+    plan = (ctypes.c_int64 * 5)()
+    _hip.lib.campx_wide_traces_plan(S, int(f.has_perf), B, _hip.config_get('wide_lds_max'), path, team, plan)
+    res['plan'] = list(plan)
+  runs, warm = (RUNS, WARM) if benchlib.event_ms(launch) <= SLOW_MS else (SLOW_RUNS, 0)
+  return dict(res, runs=runs, ms=benchlib.median_ms(launch, runs, warm))
 
 
 def rows_of(name, teams):
   """The rows of a game; a forced shape is listed only if the plan takes it (host arithmetic)."""
   from campx_amd import _hip
   S, perf = {'boat_race': (8, 1), 'maze16': (159, 0)}[name]
-  rows = [('torch', 0, 0), ('tabular', 0, 0), ('traces', 0, 0)]
+  rows = [(name, 'torch', 0, 0), (name, 'tabular', 0, 0), (name, 'traces', 0, 0)]
   plan = (ctypes.c_int64 * 5)()
   for path in (1, 2):
     for team in teams:
       if _hip.lib.campx_wide_traces_plan(S, perf, B, _hip.config_get('wide_lds_max'), path, team, plan) == 0:
-        rows.append(('traces', path, team))
+        rows.append((name, 'traces', path, team))
   return rows
 
 
-def main():
-  args = sys.argv[1:]
-  if len(args) == 5 and args[0] == '--row':
-    return row(args[1], args[2], int(args[3]), int(args[4]))
-  import torch
-  teams, games = TEAMS, GAMES
+def report(records):
+  """A game's 'torch' and 'tabular' records come before its 'traces' ones, as `rows_of()` lists them."""
+  lines = ['# tools/bench_traces.py: a process per row; event pairs, the median of %d launches after %d '
+           'warm-up launches and of %d torch loops after %d warm-up frames; lam %.2f, accumulating, rule q; %s'
+           % (RUNS, WARM, LOOP_RUNS, LOOP_WARM_FRAMES, LAM, benchlib.device_of(records))]
+  ok = True
+  for name in dict.fromkeys(r['name'] for r in records):
+    loop = tabular = best = planned = None
+    for r in (r for r in records if r['name'] == name):
+      ms = r['ms']
+      head = '%-10s S=%-4d B=%d T=%d  ' % (name, r['S'], B, T)
+      if r['what'] == 'torch':
+        loop = ms
+        lines.append('%storch restatement (play() + dense q += step * z; z *= c per frame)   %.1f ms = %.1f us / frame'
+                     % (head, ms, ms * 1000 / T))
+        continue
+      if r['what'] == 'tabular':
+        tabular = ms
+        label = 'learn_tabular() planned'
+      else:
+        shape = (r['path'], r['team'])
+        label = 'learn_traces() %s -> path %d team %-3d (%6d B LDS)' % (
+            'planned        ' if shape == (0, 0) else 'path=%d team=%-3d' % shape, *r['plan'][:3])
+      text = '%s%s   %.3f ms = %.2f us / frame%s' % (
+          head, label, ms, ms * 1000 / T, '' if r['runs'] == RUNS else '   (median of %d: slow row)' % r['runs'])
+      if r['what'] == 'traces':
+        text += '   x%.1f learn_tabular(), torch / this = x%.1f' % (ms / tabular, loop / ms)
+        if ms > loop:
+          text += '   GATE MISSED'
+          ok = False
+        if shape == (0, 0):
+          planned = ms
+        elif best is None or ms < best[0]:
+          best = (ms,) + shape
+      lines.append(text)
+    if best is not None and planned is not None:
+      lines.append('%s: fastest forced shape path %d team %d at %.3f ms; planned %.3f ms (%s)'
+                   % (name, best[1], best[2], best[0], planned,
+                      'the planned shape is not the fastest' if best[0] < 0.95 * planned
+                      else 'within 5% of the fastest'))
+  lines.append('gate (learn_traces() no slower than the torch restatement of the same frames, every row): %s'
+               % ('met' if ok else 'MISSED'))
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  args, teams, games = list(argv), TEAMS, GAMES
   if '--teams' in args:
     i = args.index('--teams')
     teams = ALL_TEAMS if args[i + 1] == 'all' else tuple(int(x) for x in args[i + 1].split(','))
@@ -169,64 +165,10 @@ def main():
     i = args.index('--games')
     games = tuple(args[i + 1].split(','))
     del args[i:i + 2]
-  path = args[0] if args else os.path.join(REPO, 'profiles', 'r21_traces.txt')
-  lines = ['# tools/bench_traces.py: a process per row; event pairs, the median of %d launches after %d '
-           'warm-up launches and of %d torch loops after %d warm-up frames; lam %.2f, accumulating, rule q; %s'
-           % (RUNS, WARM, LOOP_RUNS, LOOP_WARM_FRAMES, LAM, torch.cuda.get_device_name(0))]
-  ok, broke = True, False
-  for name in games:
-    loop = tabular = None
-    best = None
-    planned = None
-    for what, forced, team in rows_of(name, teams):
-      cmd = [sys.executable, os.path.abspath(__file__), '--row', name, what, str(forced), str(team)]
-      try:
-        done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                              timeout=ROW_SECONDS)
-      except subprocess.TimeoutExpired as late:
-        lines.append('%s %s path %d team %d  ROW TIMED OUT after %d s\n%s'
-                     % (name, what, forced, team, ROW_SECONDS, (late.stderr or '')[-2000:]))
-        ok, broke = False, True
-        break                      # nothing more is started on the device after a failure
-      if done.returncode != 0 or '\t' not in done.stdout:
-        lines.append('%s %s path %d team %d  ROW FAILED (exit status %d)\n%s'
-                     % (name, what, forced, team, done.returncode, done.stderr.rstrip('\n')))
-        ok, broke = False, True
-        break                      # nothing more is started on the device after a failure
-      ms, text = done.stdout.rstrip('\n').split('\t', 1)
-      ms = float(ms)
-      if what == 'torch':
-        loop = ms
-      elif what == 'tabular':
-        tabular = ms
-      else:
-        text += '   x%.1f learn_tabular(), torch / this = x%.1f' % (ms / tabular, loop / ms)
-        if ms > loop:
-          text += '   GATE MISSED'
-          ok = False
-        if (forced, team) == (0, 0):
-          planned = ms
-        elif best is None or ms < best[0]:
-          best = (ms, forced, team)
-      lines.append(text)
-      print(text, flush=True)
-    if broke:
-      break
-    if best is not None and planned is not None:
-      lines.append('%s: fastest forced shape path %d team %d at %.3f ms; planned %.3f ms (%s)'
-                   % (name, best[1], best[2], best[0], planned,
-                      'the planned shape is not the fastest' if best[0] < 0.95 * planned
-                      else 'within 5% of the fastest'))
-  if broke:
-    lines.append('the run ended at the row above; the rows after it were not started')
-  lines.append('gate (learn_traces() no slower than the torch restatement of the same frames, every row): %s'
-               % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 2 if broke else (0 if ok else 1)
+  records, broke = benchlib.run_rows(__file__, [r for name in games for r in rows_of(name, teams)], ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(args, 'r21_traces.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

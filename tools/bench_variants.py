@@ -14,11 +14,12 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, 'tests'))
 import torch  # noqa: E402
 
+import benchlib  # noqa: E402
 import random_pickups  # noqa: E402
 import traced_games as tg  # noqa: E402
 
 
-def timed(game, B, T=100, n=30):
+def rollout_cost(game, B, T=100, n=30):
   game.its_showtime()
   f = game.fused
   f.validate_actions = False
@@ -27,13 +28,7 @@ def timed(game, B, T=100, n=30):
   for _ in range(10):
     f.rollout(acts, out=out, reset_first=True)
   torch.cuda.synchronize()
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  for _ in range(n):
-    f.rollout(acts, out=out, reset_first=True)
-  e1.record()
-  e1.synchronize()
-  ms = e0.elapsed_time(e1) / n
+  ms = benchlib.event_ms(lambda: [f.rollout(acts, out=out, reset_first=True) for _ in range(n)]) / n
   row = f.n_layers * f.rows * f.cols
   return ms, row * B * T / (ms / 1e3) / 1e12, type(f).__name__, getattr(f, '_n_planes', None)
 
@@ -60,7 +55,7 @@ def main():
   for name, game in (('plain backdrop', plain(batch=B, device='cuda')),
                      ('plain, state table', Forced(plain())),
                      ('tide: 2 variants', tide(batch=B, device='cuda'))):
-    ms, tbs, tier, planes = timed(game, B)
+    ms, tbs, tier, planes = rollout_cost(game, B)
     print('%-18s B=%d  %.4f ms per 100-frame rollout  %.2f TB/s of observations  (%s, %s trace planes)' % (
         name, B, ms, tbs, tier, planes))
 

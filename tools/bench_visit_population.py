@@ -13,55 +13,32 @@ P = 1 beside `state_visitation()` - it may cost more -, and every forced path 2,
 "LDS whenever a member fits" holds at that size.
 
 Settled clocks (warm-up runs first), an event pair around each call, the three ALTERNATING in each
-of 25 rounds, median and spread (min .. max) of the 25, a fresh process per row.  Every call
+of 25 rounds, median and spread (min .. max) of the 25 (rows, failures and exit statuses:
+tools/benchlib.py).  Every call
 writes into buffers made once (`out=`), starts from `start=None` and so reads nothing back; the
 times are what a caller waits for, host launch cost included.
 
     python tools/bench_visit_population.py [out.txt]     # default: profiles/r17_visit_population.txt
 """
 import ctypes
-import json
-import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, FRAMES = 25, 5, 32
 GAMES = ('boat_race', 'maze16')
 MEMBERS = (1, 16, 256, 4096)
-NAMES = ('path0', 'loop', 'path2')
-
-
-def timed_ms(fn):
-  import torch
-  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  e0.record()
-  fn()
-  e1.record()
-  e1.synchronize()
-  return e0.elapsed_time(e1)
-
-
-def build(name):
-  from campx_amd.games import boat_race, maze
-  if name == 'boat_race':
-    game = boat_race.build(1, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=1, device='cuda')
-  game.its_showtime()
-  game.fused.validate_actions = False
-  return game.fused
+ROW_SECONDS = 600
 
 
 def row(name, P):
-  """One row, in this process: ms per call of FRAMES frames for all P members."""
+  """One row, in this process: `game`, `S`, `P`, `plan`, `device`, `same_bits`, and `path0`, `loop`,
+  `path2`: (median, min, max) in ms per call of FRAMES frames for all P members."""
   import torch
   from campx_amd import _hip
-  game = build(name)
+  game = benchlib.state_table_game(name, 1).fused
   S = game.n_states
   torch.manual_seed(P)
   policies = torch.rand((P, S, 5), device='cuda').add_(0.5)
@@ -78,19 +55,10 @@ def row(name, P):
     for m in range(P):
       game.state_visitation(policies[m], FRAMES, out=single)
 
-  calls = {'path0': lambda: game.visit_population(policies, FRAMES, out=out, path=0),
-           'loop': loop,
-           'path2': lambda: game.visit_population(policies, FRAMES, out=out, path=2)}
-  for _ in range(WARM):
-    for key in NAMES:
-      calls[key]()
-  torch.cuda.synchronize()
-  times = {key: [] for key in NAMES}
-  for _ in range(RUNS):                    # alternating: each round times the three, one after the other
-    for key in NAMES:
-      times[key].append(timed_ms(calls[key]))
-  for key in NAMES:
-    res[key] = [statistics.median(times[key]), min(times[key]), max(times[key])]
+  res.update(benchlib.alternating_ms({
+      'path0': lambda: game.visit_population(policies, FRAMES, out=out, path=0),
+      'loop': loop,
+      'path2': lambda: game.visit_population(policies, FRAMES, out=out, path=2)}, RUNS, WARM))
   # the three agree: the last member of the loop against the population's, on either path
   same = True
   for path in (0, 2):
@@ -106,23 +74,10 @@ def fmt(v):
   return '%9.4f (%8.4f .. %9.4f)' % tuple(v)
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r17_visit_population.txt')
-  rows = []
-  for name in GAMES:
-    for P in MEMBERS:                      # a fresh process per row, one at a time
-      done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(P)],
-                            stdout=subprocess.PIPE, text=True, timeout=600)
-      if done.returncode != 0:
-        print('row %s P=%d failed with status %d' % (name, P, done.returncode))
-        return 2
-      rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
+def report(rows):
   lines = ['# tools/bench_visit_population.py: ms PER CALL of %d frames, P policies a call; median (min .. max) of %d '
            'event pairs after %d warm-up rounds, the three alternating in each round, a fresh process per row, %s'
-           % (FRAMES, RUNS, WARM, rows[0]['device']),
+           % (FRAMES, RUNS, WARM, benchlib.device_of(rows)),
            '# loop: P calls of state_visitation(); path 2: visit_population() with one launch per frame forced',
            '%-10s %4s %5s | %-32s | %-32s | %-32s | %4s %3s %6s | %8s %8s'
            % ('game', 'S', 'P', 'visit_population(), path 0', 'loop of state_visitation()', 'path 2 forced',
@@ -140,12 +95,16 @@ def main():
                     '' if r['same_bits'] else '   THE LOOP AND THE LAUNCH DIFFER'))
   lines.append('gate (boat race, P = 16: the one launch takes less time than the loop of 16 state_visitation() '
                'calls): %s' % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, [(name, P) for name in GAMES for P in MEMBERS], ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r17_visit_population.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

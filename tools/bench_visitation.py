@@ -21,44 +21,27 @@ global (path 2 at 4.4 M states) and LDS (path 1 at 1 940).
 GATE: path 0 is no slower per frame than the torch restatement at every size (exit status 1
 otherwise; the table says where it is missed).
 
-Settled clocks (warm-up runs first), event pairs around FRAMES frames, median of 15 runs, a fresh
-process per row.
+Settled clocks (warm-up runs first), event pairs around FRAMES frames, median of 15 runs.  Rows,
+failures and exit statuses: tools/benchlib.py.
 
     python tools/bench_visitation.py [out.txt]        # default: profiles/r12_visitation.txt
 """
-import json
-import os
-import statistics
-import subprocess
 import sys
 import types
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, 'tools'))
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, FRAMES = 15, 5, 32
 ROWS = (('boat_race', 8), ('synthetic', 1940), ('synthetic', 4400000))
-
-
-def median_ms(fn):
-  import torch
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+ROW_SECONDS = 900
 
 
 def row(kind, S):
-  """One row, in this process: a dict of medians in ms PER FRAME."""
+  """One row, in this process: `kind`, `S`, `alive` (entries that do not end the episode), `same`
+  (the torch restatement gives the same numbers), `plan`, `device`, and `torch`, `path0` .. `path2`
+  (None where the path does not fit): medians in ms PER FRAME."""
   import ctypes
   import torch
   from campx_amd import _hip
@@ -102,14 +85,14 @@ def row(kind, S):
   got = call(0)
   res['same'] = bool(torch.equal(got['visits'], want[0]) and torch.equal(got['finished'], want[1])
                      and torch.equal(got['final'], want[2]))
-  res['torch'] = median_ms(torch_frames) / FRAMES
+  res['torch'] = benchlib.median_ms(torch_frames, RUNS, WARM) / FRAMES
   plan = (ctypes.c_int64 * 4)()
   _hip.check(_hip.lib.campx_wide_visit_plan(S, _hip.config_get('wide_lds_max'), 0, plan),
              'campx_wide_visit_plan')
   res['plan'] = int(plan[0])
   for path in (0, 1, 2):
     fits = _hip.lib.campx_wide_visit_plan(S, _hip.config_get('wide_lds_max'), path, plan) == 0
-    res['path%d' % path] = median_ms(lambda: call(path)) / FRAMES if fits else None
+    res['path%d' % path] = benchlib.median_ms(lambda: call(path), RUNS, WARM) / FRAMES if fits else None
   game.check_actions()
   res['device'] = torch.cuda.get_device_name(0)
   return res
@@ -119,21 +102,10 @@ def fmt(v):
   return '    n/a   ' if v is None else '%10.5f' % v
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    print('ROW ' + json.dumps(row(sys.argv[2], int(sys.argv[3]))))
-    return 0
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r12_visitation.txt')
-  rows = []
-  for kind, S in ROWS:                     # a fresh process per row, one at a time
-    done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', kind, str(S)],
-                          stdout=subprocess.PIPE, text=True, timeout=900)
-    if done.returncode != 0:
-      print('row %s S=%d failed with status %d' % (kind, S, done.returncode))
-      return 2
-    rows.append(json.loads([l for l in done.stdout.splitlines() if l.startswith('ROW ')][-1][4:]))
+def report(rows):
   lines = ['# tools/bench_visitation.py: ms PER FRAME (%d frames a call, uniform start); median of %d event '
-           'pairs after %d warm-up runs, a fresh process per row, %s' % (FRAMES, RUNS, WARM, rows[0]['device']),
+           'pairs after %d warm-up runs, a fresh process per row, %s'
+           % (FRAMES, RUNS, WARM, benchlib.device_of(rows)),
            '%-10s %8s | %10s | %10s %10s %10s | %4s | %8s | %s'
            % ('table', 'S', 'torch', 'path 0', 'LDS (1)', 'global (2)', 'auto', 'torch/0', 'same numbers')]
   ok = True
@@ -151,12 +123,16 @@ def main():
                      'included)' % (name, r['alive'], r['alive'] / (r[key] * 1e-3)))
   lines.append('gate (path 0 no slower per frame than the torch restatement at every size, same numbers): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r12_visitation.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

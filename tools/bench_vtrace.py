@@ -16,37 +16,23 @@ T = 100 at B = 4 096 and 65 536, on the padded buffers of `rollout_population_bu
   GATE: the kernel is faster than (b) at every size and in every mode measured (exit status 1
   otherwise).
 
-Settled clocks (warm-up runs first), event pairs, median of 25 runs, a fresh process per row.
+Settled clocks (warm-up runs first), event pairs, median of 25 runs.  Rows, failures and exit
+statuses: tools/benchlib.py.
 
     python tools/bench_vtrace.py [out.txt]        # default: profiles/r18_vtrace.txt
 """
-import os
-import statistics
-import subprocess
+import functools
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
 
 RUNS, WARM, T = 25, 10, 100
 GAMMA, LAM, BARS = 0.99, 0.95, (1.0, 1.0, 1.0)
 ROWS = [(kind, B) for B in (4096, 65536) for kind in ('ratio', 'boat_race_p1', 'boat_race_p16', 'maze16')]
-
-
-def median_ms(fn):
-  import torch
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1))
-  return statistics.median(times)
+ROW_SECONDS = 120
+median = functools.partial(benchlib.median_ms, runs=RUNS, warm=WARM)
 
 
 def torch_vtrace(reward, done, discount, values, bootstrap, w):
@@ -71,18 +57,13 @@ def torch_vtrace(reward, done, discount, values, bootstrap, w):
 
 
 def row(kind, B):
+  """One row, in this process: `kind`, `B`, `S`, `P`, the medians in ms `kernel` (ratio mode: one;
+  table mode: path 1, path 2) and `loop` (b), in ratio mode also `on_policy` (a); the outcome is
+  the row's gate."""
   import torch
-  from campx_amd.games import boat_race, maze
   from campx_amd.returns import discounted_returns, table_lookup, vtrace_returns
   P = 16 if kind == 'boat_race_p16' else 1
-  if kind == 'maze16':
-    game = maze.build(16, 16, batch=B, device='cuda')
-  else:
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  game.its_showtime()
-  f = game.fused
-  f.validate_actions = False
+  f = benchlib.state_table_game('maze16' if kind == 'maze16' else 'boat_race', B).fused
   S = f.n_states
   gen = torch.Generator(device='cuda').manual_seed(1)
   policies = torch.rand((P, S, 5), device='cuda', generator=gen) + 0.1
@@ -99,59 +80,59 @@ def row(kind, B):
   out = {'vs': torch.empty((T, B), device='cuda'), 'advantages': torch.empty((T, B), device='cuda')}
   kw = dict(discount=discount, bootstrap=bootstrap, lam=LAM, rho_bar=BARS[0], c_bar=BARS[1],
             pg_rho_bar=BARS[2], out=out)
-  head = 'vtrace_returns  T=%d B=%-6d %-14s' % (T, B, kind)
+  res = {'kind': kind, 'B': B, 'S': S, 'P': P}
   if kind == 'ratio':
     ratio = table_lookup(target, states, actions) / table_lookup(behaviour, states, actions)
-    kernel = [median_ms(lambda: vtrace_returns(reward, done, GAMMA, values, ratio=ratio, **kw))]
+    kernel = [median(lambda: vtrace_returns(reward, done, GAMMA, values, ratio=ratio, **kw))]
     gae = {'returns': torch.empty((T, B), device='cuda'), 'advantages': out['advantages']}
-    on_policy = median_ms(lambda: discounted_returns(reward, done, GAMMA, discount=discount, values=values,
-                                                     bootstrap=bootstrap, lam=LAM, out=gae))
-    loop = median_ms(lambda: torch_vtrace(reward, done, discount, values, bootstrap, ratio))
-    text = ('%s ratio mode %.4f ms   (a) discounted_returns(values=...) x%.2f of it   (b) the torch loop, '
-            'ratio given %.4f ms (x%.1f)' % (head, kernel[0], on_policy / kernel[0], loop, loop / kernel[0]))
+    res['on_policy'] = median(lambda: discounted_returns(reward, done, GAMMA, discount=discount, values=values,
+                                                         bootstrap=bootstrap, lam=LAM, out=gae))
+    loop = median(lambda: torch_vtrace(reward, done, discount, values, bootstrap, ratio))
   else:
     def call(path):
       return vtrace_returns(reward, done, GAMMA, values, target=target, behaviour=behaviour, states=states,
                             actions=actions, path=path, **kw)
-    kernel = [median_ms(lambda: call(1)), median_ms(lambda: call(2))]
+    kernel = [median(lambda: call(1)), median(lambda: call(2))]
 
     def loop_with_lookups():
       own = states if P == 1 else torch.remainder(states, S)
       w = table_lookup(target, own, actions) / table_lookup(behaviour, states, actions)
       return torch_vtrace(reward, done, discount, values, bootstrap, w)
-    loop = median_ms(loop_with_lookups)
-    text = ('%s Nt=%-4d Nb=%-5d path 1 (LDS) %.4f ms   path 2 (global) %.4f ms   (b) two table_lookup(), a '
-            'division and the torch loop %.4f ms (x%.1f of the slower path)'
-            % (head, S, P * S, kernel[0], kernel[1], loop, loop / max(kernel)))
-  ok = max(kernel) < loop
-  print(text + ('' if ok else '\n  GATE MISSED: vtrace_returns() is not faster than the torch restatement'))
-  return 0 if ok else 1
+    loop = median(loop_with_lookups)
+  return dict(res, kernel=kernel, loop=loop, outcome='ok' if max(kernel) < loop else 'gate_missed')
 
 
-def main():
-  if len(sys.argv) == 4 and sys.argv[1] == '--row':
-    return row(sys.argv[2], int(sys.argv[3]))
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r18_vtrace.txt')
+def report(records):
   lines = ['# tools/bench_vtrace.py: median of %d event pairs after %d warm-up runs, a fresh process per row'
            % (RUNS, WARM)]
   ok = True
-  for kind, B in ROWS:
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', kind, str(B)],
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
-    if child.returncode not in (0, 1):               # a row that did not measure ends the run
-      sys.stderr.write(child.stdout + child.stderr)
-      return 2
-    ok = ok and child.returncode == 0
-    lines.append(child.stdout.rstrip('\n'))
+  for r in records:
+    kernel, loop = r['kernel'], r['loop']
+    head = 'vtrace_returns  T=%d B=%-6d %-14s' % (T, r['B'], r['kind'])
+    if r['kind'] == 'ratio':
+      lines.append('%s ratio mode %.4f ms   (a) discounted_returns(values=...) x%.2f of it   (b) the torch loop, '
+                   'ratio given %.4f ms (x%.1f)'
+                   % (head, kernel[0], r['on_policy'] / kernel[0], loop, loop / kernel[0]))
+    else:
+      lines.append('%s Nt=%-4d Nb=%-5d path 1 (LDS) %.4f ms   path 2 (global) %.4f ms   (b) two table_lookup(), a '
+                   'division and the torch loop %.4f ms (x%.1f of the slower path)'
+                   % (head, r['S'], r['P'] * r['S'], kernel[0], kernel[1], loop, loop / max(kernel)))
+    if r['outcome'] != 'ok':
+      ok = False
+      lines.append('  GATE MISSED: vtrace_returns() is not faster than the torch restatement')
   lines.append('gate (vtrace_returns() faster than the torch restatement at every size, in every mode): %s'
                % ('met' if ok else 'MISSED'))
   lines.append('# not measured: whether the kernel is bound by its bytes or by latency (no counters were read)')
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r18_vtrace.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -14,54 +14,36 @@ all states of the maze.  Each beside
 GATE: at N = 1 048 576 the window call is no slower than that baseline for both maze windows
 (exit status 1 otherwise).  N = 4 096 and the state rows are launch-bound: there to be read.
 
-One fresh process per row; settled clocks (warm-up runs first), event pairs, median of 25 runs.
+Settled clocks (warm-up runs first), event pairs, median of 25 runs.  Rows, failures and exit
+statuses: tools/benchlib.py.
 
     python tools/bench_windows.py [out.txt]        # default: profiles/r13_windows.txt
 """
 import os
-import statistics
-import subprocess
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-sys.path.insert(0, os.path.join(REPO, 'tests'))
+import benchlib
+
+sys.path.insert(0, benchlib.REPO)
+sys.path.insert(0, os.path.join(benchlib.REPO, 'tests'))
 
 RUNS, WARM, T, B = 25, 10, 100, 4096
 ROWS = [('maze16', 7, 7, 4096), ('maze16', 7, 7, 1048576), ('maze16', 5, 5, 4096),
         ('maze16', 5, 5, 1048576), ('boat_race', 3, 3, 4096), ('boat_race', 3, 3, 1048576),
         ('maze16', 7, 7, 0), ('maze16', 5, 5, 0)]          # N = 0: all states
 GATED = {('maze16', 7, 7, 1048576), ('maze16', 5, 5, 1048576)}
-
-
-def median_us(torch, fn):
-  for _ in range(WARM):
-    fn()
-  torch.cuda.synchronize()
-  times = []
-  for _ in range(RUNS):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    times.append(e0.elapsed_time(e1) * 1e3)
-  return statistics.median(times)
+ROW_SECONDS = 300
 
 
 def row(name, h, w, N):
+  """One row, in this process: `name`, `h`, `w`, `N` (pairs, or the states where 0 was asked for),
+  `states` (a row of all states), the bytes `mine` and `theirs` and the medians `ours` and `baseline`
+  in MICROSECONDS; a GATED row whose window call is the slower one answers gate_missed."""
   import torch
   import windows_reference as ref
-  from campx_amd.games import boat_race, maze
   from campx_amd.windows import Window
-  if name == 'boat_race':
-    game = boat_race.build(B, 'cuda')
-    game.use_state_table()
-  else:
-    game = maze.build(16, 16, batch=B, device='cuda')
-  game.its_showtime()
-  f = game.fused
-  f.validate_actions = False
+  gated = (name, h, w, N) in GATED
+  f = benchlib.state_table_game(name, B).fused
   L, H, W = f.n_layers, f.rows, f.cols
   thing = f.chars[int(f.spec.dyn_layer[0])]
   pad = f.chars[int(f.spec.static_top_layer[0])]
@@ -84,7 +66,7 @@ def row(name, h, w, N):
       f.render_frames(trace, t, e, out=full)
       r0, c0 = ref.centres(entries[t, e], W, H * W, h, w)
       return ref.crop(full, r0, c0, h, w, where.pad_layer)
-    what = 'render_frame_windows N=%-8d' % N
+    states = False
   else:
     N = f.n_states
     out = torch.empty((N, L, h, w), dtype=torch.int8, device='cuda')
@@ -99,46 +81,42 @@ def row(name, h, w, N):
       f.render_states(out=full)
       r0, c0 = ref.centres(entries, W, H * W, h, w)
       return ref.crop(full, r0, c0, h, w, where.pad_layer)
-    what = 'render_state_windows S=%-7d' % N
+    states = True
   ours()
   assert torch.equal(out, baseline())          # the same tensor, or the row means nothing
-  a = median_us(torch, ours)
-  b = median_us(torch, baseline)
-  mine, theirs = N * L * h * w, N * L * H * W
-  print('%s %-9s %dx%d  window %10.3f MB %10.1f us (%.3f TB/s)   full + pad + slice %10.3f MB '
-        '%10.1f us (%.3f TB/s)   baseline / window %.2f'
-        % (what, name, h, w, mine / 1e6, a, mine / a / 1e6, theirs / 1e6, b, theirs / b / 1e6, b / a))
-  return a <= b
+  a = benchlib.median_ms(ours, RUNS, WARM) * 1e3
+  b = benchlib.median_ms(baseline, RUNS, WARM) * 1e3
+  return {'name': name, 'h': h, 'w': w, 'N': N, 'states': states, 'mine': N * L * h * w,
+          'theirs': N * L * H * W, 'ours': a, 'baseline': b,
+          'outcome': 'gate_missed' if gated and a > b else 'ok'}
 
 
-def main():
-  if len(sys.argv) > 1 and sys.argv[1] == '--row':
-    name, h, w, N = sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
-    return 0 if row(name, h, w, N) else 3
-  path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, 'profiles', 'r13_windows.txt')
+def report(records):
   lines = ['# tools/bench_windows.py: one process per row, median of %d event pairs after %d warm-up '
            'runs; int8, traces of %d frames x %d environments' % (RUNS, WARM, T, B)]
   ok = True
-  for name, h, w, N in ROWS:
-    done = subprocess.run([sys.executable, os.path.abspath(__file__), '--row', name, str(h), str(w), str(N)],
-                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    lines.append(done.stdout.rstrip())
-    if done.returncode not in (0, 3):
-      lines.append('  ROW FAILED (exit status %d)' % done.returncode)
-      lines.append(done.stderr.rstrip())
-      ok = False
-      break                      # nothing more is started on the device after a failure
-    if done.returncode == 3 and (name, h, w, N) in GATED:
+  for r in records:
+    what = ('render_state_windows S=%-7d' if r['states'] else 'render_frame_windows N=%-8d') % r['N']
+    mine, theirs, a, b = r['mine'], r['theirs'], r['ours'], r['baseline']
+    lines.append('%s %-9s %dx%d  window %10.3f MB %10.1f us (%.3f TB/s)   full + pad + slice %10.3f MB '
+                 '%10.1f us (%.3f TB/s)   baseline / window %.2f'
+                 % (what, r['name'], r['h'], r['w'], mine / 1e6, a, mine / a / 1e6, theirs / 1e6, b,
+                    theirs / b / 1e6, b / a))
+    if r['outcome'] != 'ok':
       lines.append('  GATE MISSED: the window call is slower than render_frames() + pad + slice')
       ok = False
   lines.append('gate (window call no slower than the baseline at N = 1 048 576, both maze windows): %s'
                % ('met' if ok else 'MISSED'))
-  text = '\n'.join(lines) + '\n'
-  print(text, end='')
-  with open(path, 'w') as fh:
-    fh.write(text)
-  return 0 if ok else 1
+  return lines, ok
+
+
+def main(argv):
+  if argv[:1] == ['--row']:
+    return benchlib.row_main(row, argv[1:])
+  records, broke = benchlib.run_rows(__file__, ROWS, ROW_SECONDS)
+  lines, ok = report(records)
+  return benchlib.finish(benchlib.out_path(argv, 'r13_windows.txt'), lines, ok, broke)
 
 
 if __name__ == '__main__':
-  sys.exit(main())
+  sys.exit(main(sys.argv[1:]))

@@ -8,22 +8,26 @@ sustains, next to the 8 TB/s spec peak.
 """
 import torch
 
-def timed(fn, n=20, warm=3):
-  for _ in range(warm): fn()
+import benchlib
+
+N, WARM = 20, 3
+
+
+def seconds(fn):
+  """Per call, from ONE event pair around N calls after WARM warm-up ones."""
+  for _ in range(WARM):
+    fn()
   torch.cuda.synchronize()
-  s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-  s.record()
-  for _ in range(n): fn()
-  e.record(); torch.cuda.synchronize()
-  return s.elapsed_time(e) / n / 1e3
+  return benchlib.event_ms(lambda: [fn() for _ in range(N)]) / N / 1e3
+
 
 nbytes = 100 * 65536 * 175
 for dtype, name in ((torch.int8, 'int8'), (torch.float32, 'f32')):
   x = torch.empty(nbytes // torch.empty((), dtype=dtype).element_size(), dtype=dtype, device='cuda')
   y = torch.empty_like(x)
-  t = timed(lambda: x.fill_(1))
+  t = seconds(lambda: x.fill_(1))
   print('fill_  %-5s %.3f ms  %.0f GB/s (write only)' % (name, t * 1e3, nbytes / t / 1e9))
-  t = timed(lambda: x.zero_())
+  t = seconds(lambda: x.zero_())
   print('zero_  %-5s %.3f ms  %.0f GB/s (write only)' % (name, t * 1e3, nbytes / t / 1e9))
-  t = timed(lambda: y.copy_(x))
+  t = seconds(lambda: y.copy_(x))
   print('copy_  %-5s %.3f ms  %.0f GB/s (read+write %.0f)' % (name, t * 1e3, nbytes / t / 1e9, 2 * nbytes / t / 1e9))
