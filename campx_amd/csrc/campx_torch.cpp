@@ -20,6 +20,7 @@
 //   campx::wide_learn               online tabular learners: a Q-table per environment, T frames per launch
 //   campx::wide_learn_shared        shared learners: n environments feed one Q-table, T frames per launch
 //   campx::wide_learn_traces        learners with eligibility traces: Q(lambda), expected SARSA(lambda)
+//   campx::wide_learn_dyna          Dyna-Q learners: n planning updates of remembered pairs a frame
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -949,6 +950,40 @@ void wide_learn_traces(const Tensor& spec_host, const Tensor& tables, Tensor& st
            "campx_wide_traces_launch");
 }
 
+// Dyna-Q online learners (campx_wide_dyna_launch): campx::wide_learn's arguments and the learners'
+// model - `seen` int32 [B, n_states * 5] (16-byte aligned) and `n_seen` int32 [B], both updated in
+// place -, `planning` int32 [B], the planning updates per frame, and `marks` int32
+// [B, ceil(n_states * 5 / 32)], the global path's scratch (may be None when the launch takes the
+// LDS path).
+void wide_learn_dyna(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                     const OptTensor& ret, Tensor& q, Tensor& seen, Tensor& n_seen,
+                     const Tensor& planning, const Tensor& alpha, const Tensor& gamma,
+                     const Tensor& epsilon, int64_t rule, int64_t seed, int64_t first_frame,
+                     int64_t frames, int64_t window, Tensor& reward_sum, const OptTensor& perf_sum,
+                     Tensor& episodes, const OptTensor& marks, const OptTensor& bad_count,
+                     const OptTensor& bad_flag, bool reset_first, int64_t path) {
+  const char* what = "campx::wide_learn_dyna";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  const int64_t n_entries = g.hs->n_states * CAMPX_N_ACTIONS;
+  TORCH_CHECK(g.B * n_entries < (1ll << 31), what, ": B * n_states * 5 must be below 2^31");
+  CampxDynaLearner l = learner_fields<CampxDynaLearner>(
+      what, g, g.B, q, alpha, gamma, epsilon, rule, seed, first_frame, frames, window, reward_sum,
+      perf_sum, episodes, bad_count, bad_flag, reset_first, path);
+  want(seen, "seen", at::kInt, g.dev, {g.B, n_entries});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(seen.data_ptr()) & 15) == 0, what,
+              ": seen must be 16-byte aligned");
+  want(n_seen, "n_seen", at::kInt, g.dev, {g.B});
+  want(planning, "planning", at::kInt, g.dev, {g.B});
+  if (marks.has_value()) want(*marks, "marks", at::kInt, g.dev, {g.B, (n_entries + 31) / 32});
+  l.seen = reinterpret_cast<int32_t*>(seen.data_ptr());
+  l.n_seen = reinterpret_cast<int32_t*>(n_seen.data_ptr());
+  l.planning = reinterpret_cast<const int32_t*>(planning.data_ptr());
+  l.marks = opt_ptr<uint32_t>(marks);
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_dyna_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
+           "campx_wide_dyna_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1590,7 +1625,7 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
-    "wide_learn", "wide_learn_shared", "wide_learn_traces", "render_gather",
+    "wide_learn", "wide_learn_shared", "wide_learn_traces", "wide_learn_dyna", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_population_solve", "wide_visit",
     "wide_visit_population",
@@ -1679,6 +1714,13 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(f!) reward_sum, Tensor(g!)? perf_sum, Tensor(h!) episodes, Tensor(i!)? bad_count, "
       "Tensor(j!)? bad_flag, bool reset_first, int path=0, int team=0) -> ()");
   m.def(
+      "wide_learn_dyna(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) q, Tensor(e!) seen, Tensor(f!) n_seen, Tensor planning, "
+      "Tensor alpha, Tensor gamma, Tensor epsilon, int rule, int seed, int first_frame, int frames, "
+      "int window, Tensor(g!) reward_sum, Tensor(h!)? perf_sum, Tensor(i!) episodes, "
+      "Tensor(j!)? marks, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, bool reset_first, "
+      "int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1751,6 +1793,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_learn", &wide_learn);
   m.impl("wide_learn_shared", &wide_learn_shared);
   m.impl("wide_learn_traces", &wide_learn_traces);
+  m.impl("wide_learn_dyna", &wide_learn_dyna);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

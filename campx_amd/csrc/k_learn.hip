@@ -5,7 +5,9 @@
 // table per environment, updated after every single frame, nothing shared between lanes;
 // wide_learn_shared_kernel, n environments feeding one table, two barriers a frame; and
 // wide_learn_traces_kernel, a table and an eligibility trace per environment, a team of lanes
-// sweeping the whole table every frame (tests/trace_learner_reference.py).
+// sweeping the whole table every frame (tests/trace_learner_reference.py).  A fourth,
+// wide_learn_dyna_kernel, is the first's schedule with n planning updates of remembered pairs after
+// every frame (Dyna-Q; tests/dyna_learner_reference.py).
 //
 // What they have in common is written ONCE and called by all - a change of the rule is made
 // there.  "The frame step": stage_table() (entries and perf bytes into LDS), Hyper (alpha, gamma,
@@ -810,6 +812,213 @@ __global__ __launch_bounds__(kLearnThreads) void wide_learn_traces_kernel(
 using TraceKernel = decltype(&wide_learn_traces_kernel<false, false, false, false>);
 static const TraceKernel kTraceKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_traces_kernel);
 
+// ---------------------------------------------------------------------------------------------
+// Dyna-Q: wide_learn_kernel's frame, then `planning[e]` updates of remembered pairs (include/
+// campx_hip.h, "Dyna-Q online learners", has the frame; tests/dyna_learner_reference.py restates it
+// in numpy).  The game is deterministic and its table is what the workgroup already holds, so a
+// learner's model is the LIST of the flat entries it has met - `seen`, in order of first visit -
+// and a membership bitmap that answers "is this pair new" in one read.  A lane per learner, 256 to
+// a workgroup, nothing shared between lanes: no barrier inside the frame loop.  The chain per frame
+// is  row -> action -> entry -> bootstrap row -> write -> (bit test, append) -> n x (word -> list
+// element -> entry -> bootstrap row -> write) -> the next row, RE-READ: planning may have written
+// any element of it, so the register patch of wide_learn_kernel does not carry over - except for a
+// learner with planning[e] = 0, which keeps the patch and the one-step learner's chain.
+//
+// Path 1: entries, perf bytes, q (move_q(), lane-innermost) and, after them, the lists as 16-bit
+// elements [5S][256] and the bitmap [W][256] in LDS.  A 16-bit list that were simply lane-innermost
+// would put lanes 2j and 2j + 1 in one dword - one bank, two addresses whenever their indices
+// differ: a two-way conflict on every planning read.  dyna_slot() keeps the bytes and moves the
+// lanes: the 32 lanes of a half wave (the group a 16- or 32-bit LDS access is served in) take 32
+// different dwords, and the half waves 2h and 2h + 1 share them as low and high halves.
+// Path 2: q, seen (int32, as it lies) and the bitmap `marks` through L1 / L2.
+
+// campx_wide_dyna_plan()'s five words, in their order.
+struct DynaPlan { int64_t path, lds_bytes, threads, table_in_lds, words; };
+
+inline int32_t plan_dyna(int64_t S, int32_t has_perf, int64_t B, int64_t lds_max, int32_t path,
+                         DynaPlan* p, int64_t* plan_out) {
+  if (!plan_args_ok(S, has_perf, B, B, lds_max, path)) return CAMPX_EINVAL;
+  const int64_t n_entries = S * CAMPX_N_ACTIONS, words = (n_entries + 31) / 32;
+  const int64_t table = table_bytes(S, has_perf);
+  const int64_t want = table + kLearnThreads * (n_entries * (int64_t)(sizeof(float) + sizeof(uint16_t)) +
+                                                words * (int64_t)sizeof(uint32_t));
+  const bool fits = want <= lds_max && n_entries <= 65536;       // (a list element is 16 bits there)
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
+  p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
+  p->lds_bytes = p->path == 1 ? want : (p->table_in_lds ? table : 0);
+  p->threads = kLearnThreads;
+  p->words = words;
+  if (plan_out) memcpy(plan_out, p, sizeof(*p));
+  return CAMPX_OK;
+}
+
+// Where lane `t` sits in a row of 256 16-bit elements: dword (t & 31) + 32 * (t >> 6), half (t >> 5) & 1.
+__device__ __forceinline__ int dyna_slot(int t) {
+  return ((((t & 31) | ((t >> 6) << 5)) << 1) | ((t >> 5) & 1));
+}
+
+// One planning update of entry `i` of the lane's table: td_error() on the entry the game's table
+// has for it, the bootstrap row read before the write.
+template <bool kSarsa, int step>
+__device__ __forceinline__ void plan_update(float* own, uint32_t i, const uint2* entries, int S,
+                                            const float* discounts, const Hyper& h) {
+  const Entry e = decode_entry(entries[i], S, discounts);
+  float nrow[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) nrow[k] = own[(e.next * CAMPX_N_ACTIONS + k) * step];
+  const float old = own[i * step];
+  const float delta = td_error<kSarsa>(old, nrow, e, h.gamma, h.keep, h.epsilon);
+  own[i * step] = old + h.alpha * delta;
+}
+
+// kQLds: path 1.  kTableLds, kPerf, kSarsa: as in wide_learn_kernel.  `words`: bitmap words of a
+// learner, ceil(n_states * 5 / 32).  `marks`: path 2's bitmap, unused on path 1.
+template <bool kQLds, bool kTableLds, bool kPerf, bool kSarsa>
+__global__ __launch_bounds__(kLearnThreads) void wide_learn_dyna_kernel(
+    LearnParams pp, const uint2* __restrict__ g_entries, const int8_t* __restrict__ g_perf,
+    float* __restrict__ q, const float* __restrict__ alphas, const float* __restrict__ gammas,
+    const float* __restrict__ epsilons, int32_t* __restrict__ seen, int32_t* __restrict__ n_seen,
+    const int32_t* __restrict__ planning, uint32_t* __restrict__ marks, int32_t* __restrict__ state,
+    CampxState st, float* __restrict__ reward_sum, int32_t* __restrict__ perf_sum,
+    int32_t* __restrict__ episodes, int32_t* bad_count, int32_t* bad_flag, int64_t B, int32_t T,
+    int32_t reset_first, int32_t words) {
+  static_assert(kTableLds || !kQLds, "path 1 stages the table");
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_tables[];
+  __shared__ float discounts[16];
+  const int S = pp.n_states, n_entries = S * CAMPX_N_ACTIONS;
+  const int lane = threadIdx.x;
+  const int64_t env_lo = (int64_t)blockIdx.x * kLearnThreads;
+  const int64_t env = env_lo + lane;
+  const int n_lanes = (int)(B - env_lo < kLearnThreads ? B - env_lo : kLearnThreads);
+  const int n_q = n_lanes * n_entries;                 // floats: B * S * 5 < 2^31
+  float* q_block = q + env_lo * n_entries;
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, lane, kLearnThreads);
+  float* l_q = reinterpret_cast<float*>(tab.free);
+  if (kQLds) move_q<true>(l_q, q_block, n_q, n_entries, lane);
+  if (lane < 16) discounts[lane] = pp.discounts[lane];
+  __syncthreads();
+
+  if (env < B) {
+    Hyper h;
+    h.load(alphas, gammas, epsilons, env);
+    float* own = kQLds ? l_q + lane : q + env * n_entries;
+    constexpr int step = kQLds ? kLearnThreads : 1;
+    // the lane's list and bitmap: element k at list16[k * 256] (path 1) or list32[k] (path 2), word
+    // w at bits[w * bstep].  Nobody else touches them.
+    uint16_t* list16 = reinterpret_cast<uint16_t*>(l_q + n_entries * kLearnThreads) + dyna_slot(lane);
+    int32_t* list32 = seen + env * n_entries;
+    uint32_t* bits = kQLds ? reinterpret_cast<uint32_t*>(l_q) + n_entries * (kLearnThreads * 3 / 2) + lane
+                           : marks + env * words;
+    constexpr int bstep = kQLds ? kLearnThreads : 1;
+    // screen the list and rebuild the bitmap from it; a list that fails makes the learner bad
+    const int n_plan = planning[env];
+    const int n_old = n_seen[env];
+    bool list_ok = n_old >= 0 && n_old <= n_entries;
+    for (int w = 0; w < words; ++w) bits[w * bstep] = 0u;
+    for (int k = 0; k < (list_ok ? n_old : 0); ++k) {
+      const uint32_t i = (uint32_t)list32[k];
+      if (i < (uint32_t)n_entries) {
+        bits[(i >> 5) * bstep] |= 1u << (i & 31);
+        if (kQLds) list16[k * kLearnThreads] = (uint16_t)i;
+      } else {
+        list_ok = false;
+      }
+    }
+    h.good = h.good && list_ok && n_plan >= 0 && n_plan <= CAMPX_DYNA_MAX_PLANNING;
+    int n = n_old;                                     // (only a good learner's n is used)
+
+    Carried c;
+    c.load(state, st, env, S, reset_first);
+    float row[5];
+#pragma unroll
+    for (int a = 0; a < 5; ++a) row[a] = own[(c.from * CAMPX_N_ACTIONS + a) * step];
+    WindowSums<kPerf> sums{reward_sum, perf_sum, episodes, env};
+    const Chunks chunks(pp.first_frame);
+    for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
+      uint32_t x[2 * kLearnChunk];
+      chunks.words(pp, env, t0, x);
+#pragma unroll
+      for (int j = 0; j < kLearnChunk; ++j) {
+        if (t0 + j >= 0 && t0 + j < T) {
+          const uint32_t a = frame_action(row, x[2 * j], x[2 * j + 1], h.epsilon, h.good);
+          const uint32_t idx = c.from * CAMPX_N_ACTIONS + a;
+          const Entry e = decode_entry(tab.entries[idx], S, discounts);
+          // the next frame's row before this frame's write: the bootstrap row, as in wide_learn_kernel
+          float nrow[5];
+#pragma unroll
+          for (int k = 0; k < 5; ++k) nrow[k] = own[(e.next * CAMPX_N_ACTIONS + k) * step];
+          if (h.good) {
+            float old = row[0];
+#pragma unroll
+            for (int k = 1; k < 5; ++k) old = a == (uint32_t)k ? row[k] : old;
+            const float delta = td_error<kSarsa>(old, nrow, e, h.gamma, h.keep, h.epsilon);
+            const float fresh = old + h.alpha * delta;
+            own[idx * step] = fresh;
+            if (e.next == c.from) {
+#pragma unroll
+              for (int k = 0; k < 5; ++k) nrow[k] = a == (uint32_t)k ? fresh : nrow[k];
+            }
+            // record: n < n_entries whenever the pair is new - the bitmap holds every listed pair,
+            // so a list of n_entries elements without a repeat has no new pair left, and one WITH
+            // repeats is checked here
+            const uint32_t word = bits[(idx >> 5) * bstep], bit = 1u << (idx & 31);
+            if (!(word & bit) && n < n_entries) {
+              bits[(idx >> 5) * bstep] = word | bit;
+              if (kQLds) list16[n * kLearnThreads] = (uint16_t)idx;
+              else list32[n] = (int32_t)idx;
+              ++n;
+            }
+            // plan: n >= 1 here, the pair just met is listed
+            const uint64_t f = (uint64_t)(pp.first_frame + t0 + j);
+            for (int k0 = 0; k0 < n_plan; k0 += 4) {
+              uint32_t y[4];
+              philox4x32_10((uint32_t)env, (uint32_t)f, (uint32_t)(f >> 32), 2u + (uint32_t)(k0 >> 2),
+                            pp.key0, pp.key1, y);
+#pragma unroll
+              for (int k = 0; k < 4; ++k) {
+                if (k0 + k < n_plan) {
+                  const uint32_t at = __umulhi(y[k], (uint32_t)n);
+                  const uint32_t i = kQLds ? (uint32_t)list16[at * kLearnThreads] : (uint32_t)list32[at];
+                  plan_update<kSarsa, step>(own, i, tab.entries, S, discounts, h);
+                }
+              }
+            }
+            // the next frame's row as planning left the table: any step may have written it, so it
+            // is read again; without planning wide_learn_kernel's patch above is the whole change
+            if (n_plan > 0) {
+#pragma unroll
+              for (int k = 0; k < 5; ++k) nrow[k] = own[(e.next * CAMPX_N_ACTIONS + k) * step];
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 5; ++k) row[k] = nrow[k];
+          c.advance(e);
+          sums.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
+        }
+      }
+    }
+    sums.flush_short();
+    c.store(state, st, env);
+    if (h.good) {
+      // the elements the launch appended, and the count; nothing before n_old, nothing from n on
+      if (kQLds)
+        for (int k = n_old; k < n; ++k) list32[k] = (int32_t)list16[k * kLearnThreads];
+      n_seen[env] = n;
+    }
+    report_bad(bad_count, bad_flag, h.good ? 0 : 1);     // bad LEARNERS, once per launch
+  }
+
+  if (kQLds) {
+    __syncthreads();
+    move_q<false>(l_q, q_block, n_q, n_entries, lane);
+  }
+}
+
+using DynaKernel = decltype(&wide_learn_dyna_kernel<false, false, false, false>);
+static const DynaKernel kDynaKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_dyna_kernel);
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -914,6 +1123,37 @@ int32_t campx_wide_traces_launch(const CampxWideSpec* s, const void* tables_dev,
                      l->traces, l->alpha, l->gamma, l->epsilon, l->lam,
                      reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
                      l->bad_count, l->bad_flag, B, T, l->reset_first, (int32_t)plan.team, l->trace);
+  return launch_status();
+}
+
+int32_t campx_wide_dyna_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                             int32_t path, int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  DynaPlan plan;
+  return plan_dyna(n_states, has_perf, B, wide_lds_max, path, &plan, plan_out);
+}
+
+int32_t campx_wide_dyna_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
+                               const CampxDynaLearner* l, int64_t B, int32_t T, void* stream) {
+  const bool own_ok = l && l->seen && l->n_seen && l->planning && aligned_to(l->seen, 16) &&
+                      aligned_to(l->n_seen, 4) && aligned_to(l->planning, 4) && aligned_to(l->marks, 4);
+  const int32_t screened = screen_learner(s, tables_dev, st, l, B, T, own_ok);
+  if (screened != CAMPX_OK) return screened;
+  DynaPlan plan;       // (refuses B * n_states * 5 >= 2^31, and path 1 for what does not fit)
+  const int32_t planned = plan_dyna(s->n_states, l->perf_sum ? 1 : 0, B, knob(K_WIDE_LDS_MAX), l->path,
+                                    &plan, nullptr);
+  if (planned != CAMPX_OK) return planned;
+  if (plan.path == 2 && !l->marks) return CAMPX_EINVAL;
+  const WideTables t = wide_tables(*s, tables_dev);
+  const size_t lds = (size_t)plan.lds_bytes;
+  const DynaKernel kernel = pick_kernel(kDynaKernels, plan, *l);
+  CAMPX_ALLOW_LDS(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kLearnThreads - 1) / kLearnThreads)),
+                     dim3(kLearnThreads), lds, static_cast<hipStream_t>(stream), learn_params(*s, *l),
+                     t.entries, t.perf, l->q, l->alpha, l->gamma, l->epsilon, l->seen, l->n_seen,
+                     l->planning, l->marks, reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum,
+                     l->perf_sum, l->episodes, l->bad_count, l->bad_flag, B, T, l->reset_first,
+                     (int32_t)plan.words);
   return launch_status();
 }
 

@@ -507,6 +507,20 @@ class Engine(object):
     raise NotImplementedError (`use_state_table()` selects this one)."""
     return self._batched('learn_traces').learn_traces(T, q, traces, *args, **kwargs)
 
+  def learn_dyna(self, T, q=None, model=None, *args, **kwargs):
+    """State-table tier only: T frames of DYNA-Q for B independent learners in one launch -
+    `learn_tabular()`'s frame and, after every real step, `planning` more updates of pairs drawn
+    uniformly from those the learner has visited (its `model`, a dict of 'seen' int32
+    `[B, n_states * 5]` and 'n_seen' int32 `[B]`, updated in place; None: empty).  `planning=0` is
+    `learn_tabular()` bit for bit.  Returns `learn_tabular()`'s dict plus 'model'.  See
+    `wide.WideGame.learn_dyna`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` selects this one)."""
+    return self._batched('learn_dyna').learn_dyna(T, q, model, *args, **kwargs)
+
+  def dyna_buffers(self, T, window=None, path=0):
+    """State-table tier only: the dict of `learn_dyna(out=...)`, allocated once."""
+    return self._batched('dyna_buffers').dyna_buffers(T, window=window, path=path)
+
   def learn_shared(self, T, q, *args, **kwargs):
     """State-table tier only: T frames of online tabular learning for P SHARED learners in one
     launch, learner m owning `q[m]` of `q` float32 `[P, n_states, 5]` (updated in place) and fed by

@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'dyna_buffers', 'learn_dyna', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'value_iteration_population',
     'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
@@ -146,7 +146,9 @@ class WideGame(fused.FusedGame):
     self._bad_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_shared_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_trace_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_dyna_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._hyper_floats = {}
+    self._hyper_ints = {}             # learn_dyna()'s `planning` given as a Python int, by learners
     self._layer_of_cell = None        # the window kernel's scenery table
     self._window_table()
     self._bad_flag = torch.zeros((1,), dtype=torch.int32).pin_memory()
@@ -203,7 +205,11 @@ class WideGame(fused.FusedGame):
         (self._bad_trace_learners, acts,
          '{} learners of learn_traces() have bad hyper-parameters (alpha, gamma, epsilon or lam not '
          'finite, or epsilon or lam outside [0, 1]); they took action {} at every frame and their '
-         'tables and traces were left untouched')]
+         'tables and traces were left untouched'),
+        (self._bad_dyna_learners, acts,
+         '{} learners of learn_dyna() are bad (alpha, gamma or epsilon not finite, epsilon outside '
+         '[0, 1], planning outside 0 .. 1024, or a model whose n_seen or elements are outside the '
+         'table); they took action {} at every frame and their tables and models were left untouched')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -753,6 +759,133 @@ class WideGame(fused.FusedGame):
         self._bad_flag if validate else None, bool(reset_first), path, team)
     res = self._learner_epilogue(first, T, reset_first, q, out)
     res['traces'] = traces
+    return res
+
+  # ------------------------------------------------------------ Dyna-Q learners
+
+  def _dyna_plan(self, path):
+    """The five words of campx_wide_dyna_plan() for this game: path, LDS bytes, threads, entries in
+    LDS, bitmap words per learner."""
+    S, B = self.n_states, self.batch
+    if B * S * gamespec.N_ACTIONS >= 1 << 31:
+      raise ValueError('learn_dyna(): B * n_states * 5 = {} x {} x 5 must be below 2^31; use a '
+                       'smaller batch'.format(B, S))
+    if path not in (0, 1, 2):
+      raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
+    plan = (ctypes.c_int64 * 5)()
+    lds_max = _hip.config_get('wide_lds_max')
+    code = _hip.lib.campx_wide_dyna_plan(S, 1 if self.has_perf else 0, B, lds_max, path, plan)
+    if code != 0 and path == 1:
+      raise ValueError('path=1: a table of {} states with the Q-tables, seen lists and bitmaps of a '
+                       'workgroup\'s 256 learners does not fit the LDS of one workgroup (library '
+                       'setting wide_lds_max); use path=0 or path=2'.format(S))
+    if code != 0:
+      raise ValueError('path={}: the library refused the plan (code {}; library setting '
+                       'wide_lds_max = {})'.format(path, code, lds_max))
+    return list(plan)
+
+  def dyna_buffers(self, T, window=None, path=0):
+    """Allocate the dict of `learn_dyna(out=...)` once: `learner_buffers(T, window)`'s tensors and -
+    when a call with this `path` goes through global memory (path 2) - 'marks', its membership
+    bitmap: int32 [B, ceil(n_states * 5 / 32)], scratch whose contents mean nothing between calls."""
+    plan = self._dyna_plan(path)
+    out = self.learner_buffers(T, window)
+    if plan[0] == 2:
+      out['marks'] = torch.zeros((self.batch, plan[4]), dtype=torch.int32, device=self.device)
+    return out
+
+  def learn_dyna(self, T, q=None, model=None, planning=5, alpha=0.1, gamma=0.99, epsilon=0.1,
+                 rule='q', seed=0, first_frame=None, reset_first=False, window=None, out=None,
+                 path=0):
+    """T frames of DYNA-Q for B independent learners in ONE launch: `learn_tabular()`'s frame and,
+    after every real step, `planning` more updates of pairs the learner REMEMBERS - more learning
+    per frame of experience (Sutton & Barto ch. 8; csrc/k_learn.hip, `campx::wide_learn_dyna`).
+    Environment e is learner e, with its own table `q[e]` and its own model.  The game's table is
+    deterministic, so what a learner has to remember of a visited (s, a) is only THAT it visited
+    it: the model is the list of the flat entries `s * 5 + a` it has met, in order of first visit.
+    Nothing is shared between learners: no atomics, and the run repeats bit for bit
+    (include/campx_hip.h has the frame; tests/dyna_learner_reference.py restates it in numpy).
+
+    The frame: the real step is `learn_tabular()`'s; the pair is appended to the model if it is
+    new; then, `planning` times, one after the other: a pair is drawn UNIFORMLY FROM THE SEEN PAIRS
+    (not "a seen state, then an action taken in it": a state met with four actions is drawn four
+    times as often as one met with one), and `q` of that pair gets the one-step update from the
+    table's entry for it, each update seeing the ones before.  The next frame acts on `q` as
+    planning left it.  `planning=0` is `learn_tabular()` bit for bit, and records the model.
+
+    Args:
+      q: as in `learn_tabular()`: float32 `[B, n_states, 5]`, updated IN PLACE; None: zeros.
+      model: a dict `{'seen': int32 [B, n_states * 5], 'n_seen': int32 [B]}` of contiguous tensors
+          on the game's device ('seen' 16-byte aligned), both updated IN PLACE; None: empty.  The
+          first `n_seen[e]` elements of `seen[e]` are learner e's pairs; the rest is never read or
+          written.  Pass the returned 'model' on and calls of T1 and T2 frames learn what one call
+          of T1 + T2 does.  A learner whose `n_seen` or listed pairs are outside the table is BAD.
+          A list with repeats is used as given: a repeat is drawn as often as it is listed.
+      planning: updates per frame, a Python int in 0 .. 1024 (checked at once) or an int32 `[B]`
+          tensor - a tensor is a sweep of n; a learner whose n is outside 0 .. 1024 is BAD.
+      alpha, gamma, epsilon, rule, seed, first_frame, window: exactly as in `learn_tabular()`.
+          The planning draws come from the exploration stream's key with a counter word of their
+          own: (e, frame, 2 + k // 4).  A BAD learner - here or as in `learn_tabular()` - takes
+          action 4 at every frame, keeps its table AND its model, and raises ValueError lazily,
+          counted once per call.
+      reset_first: every learner starts a new episode; table and model stay.
+      out: a dict from `dyna_buffers(T, window, path)`, overwritten.  With `q`, `model`, `out` and
+          tensors (or the same numbers as before) for the hyper-parameters the call allocates
+          nothing and is capturable in a HIP graph.
+      path: 0 - a workgroup keeps the table and its 256 learners' Q-tables, lists (16 bits an
+          element) and bitmaps in LDS whenever they fit (library setting wide_lds_max: up to 18
+          states), else they go through L1 / L2; 1 / 2 force either (1 raises ValueError for what
+          does not fit).  Both give the same bits.
+
+    Returns `learn_tabular()`'s dict plus 'model'.  `state`, `done`, `ret` and `frame` carry over
+    exactly as `learn_tabular()` leaves them.  Argument errors raise ValueError before anything is
+    launched.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    plan = self._dyna_plan(path)
+    if q is not None and (not self._tensor_ok(q, torch.float32, (B, S, A)) or q.data_ptr() % 16):
+      got = ('{} {} on {}'.format(q.dtype, list(q.shape), q.device) if torch.is_tensor(q)
+             else type(q).__name__)
+      raise ValueError('q must be a contiguous, 16-byte aligned float32 [{}, {}, {}] tensor (learners '
+                       'x n_states x actions) on {}, or None for zeros; got {}'.format(B, S, A, dev, got))
+    if model is not None and (
+        not isinstance(model, dict) or not self._tensor_ok(model.get('seen'), torch.int32, (B, S * A))
+        or model['seen'].data_ptr() % 16 or not self._tensor_ok(model.get('n_seen'), torch.int32, (B,))):
+      raise ValueError('model must be None (empty) or a dict of contiguous int32 tensors on {}: '
+                       '\'seen\' [{}, {}], 16-byte aligned, and \'n_seen\' [{}]'.format(dev, B, S * A, B))
+    if torch.is_tensor(planning):
+      if not self._tensor_ok(planning, torch.int32, (B,)):
+        raise ValueError('planning must be an int or a contiguous int32 [{}] tensor (one per learner) '
+                         'on {}, got {} {} on {}'.format(B, dev, planning.dtype, list(planning.shape),
+                                                         planning.device))
+    elif (isinstance(planning, bool) or not isinstance(planning, int)
+          or not 0 <= planning <= _hip.DYNA_MAX_PLANNING):
+      raise ValueError('planning must be an int, 0 <= planning <= {}, or an int32 [{}] tensor, got '
+                       '{!r}'.format(_hip.DYNA_MAX_PLANNING, B, planning))
+    own = [('marks', torch.int32, (B, plan[4]))] if plan[0] == 2 else []
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_dyna', B, T, window, rule, first_frame, seed, alpha, gamma, epsilon, out, own,
+        lambda T, window: 'dyna_buffers({}, window={}, path={})'.format(T, window, path),
+        lambda T, window: self.dyna_buffers(T, window, path))
+    if not torch.is_tensor(planning):
+      if B not in self._hyper_ints:
+        self._hyper_ints[B] = torch.zeros((B,), dtype=torch.int32, device=dev)
+      planning = self._hyper_ints[B].fill_(planning)
+    if q is None:
+      q = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
+    if model is None:
+      model = {'seen': torch.zeros((B, S * A), dtype=torch.int32, device=dev),
+               'n_seen': torch.zeros((B,), dtype=torch.int32, device=dev)}
+    validate = self.validate_actions
+    _hip.ops.wide_learn_dyna(
+        self._spec_host, self._tables, self.state, self.done, self.ret, q.detach(), model['seen'],
+        model['n_seen'], planning, hyper[0], hyper[1], hyper[2], _hip.LEARN_RULES[rule], seed, first,
+        T, window, out['reward_sum'], out.get('perf_sum') if self.has_perf else None,
+        out['episodes'], out.get('marks') if plan[0] == 2 else None,
+        self._bad_dyna_learners if validate else None, self._bad_flag if validate else None,
+        bool(reset_first), path)
+    res = self._learner_epilogue(first, T, reset_first, q, out)
+    res['model'] = model
     return res
 
   # ------------------------------------------------------------ shared online learners

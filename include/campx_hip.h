@@ -1072,6 +1072,107 @@ int32_t campx_wide_traces_launch(const CampxWideSpec* spec_host, const void* tab
                                  CampxState state, const CampxTraceLearner* learner, int64_t B,
                                  int32_t T, void* stream);
 /*
+ * ---- Dyna-Q online learners: n planning updates a frame, a whole run per launch ----------------
+ * The learners above spend one table update per frame of experience.  Dyna-Q (Sutton & Barto
+ * ch. 8) also replays, after every real step, `n` transitions it REMEMBERS.  The game's table is
+ * deterministic, so the transition of a remembered (s, a) is the table's entry: the learner's
+ * private model shrinks to the list of pairs it has visited.  Learner e is environment e, as in
+ * campx_wide_learn_launch().  Besides q[e] it owns a model, two DEVICE arrays updated in place:
+ *   seen    int32 [B][n_states * 5], 16-byte aligned
+ *   n_seen  int32 [B]
+ * The first n_seen[e] elements of seen[e] are the flat entries s * 5 + a the learner has met, in
+ * order of first visit.  Elements beyond that count are never read and never written.
+ * T frames in one launch, nothing shared between learners, no atomics, reproducible bit for bit
+ * (csrc/k_learn.hip; tests/dyna_learner_reference.py restates the frame in numpy).
+ *
+ * Frame f = first_frame + t of a good learner; f32 throughout, every operation rounded on its own:
+ *   1. Real step.  Steps 1 - 7 of the rule of the one-step learners, unchanged - the same functions
+ *      of csrc/k_learn.hip, not a restatement of them.  q[e][s][a] is updated.
+ *   2. Record.  If i = s * 5 + a is not among the first n_seen[e] elements of seen[e]:
+ *      seen[e][n_seen[e]] = i; n_seen[e] += 1.  (A list that is already 5 * n_states long -
+ *      which only one given with repeats can be while a pair is still new - takes no more.)
+ *   3. Plan.  For k = 0 .. n - 1 with n = planning[e] (DEVICE int32 [B]), one after the other:
+ *        x   = output word k & 3 of the Philox4x32-10 block with key (seed & 0xffffffff,
+ *              seed >> 32) and counter (e, f & 0xffffffff, f >> 32, 2 + (k >> 2)) - the fourth
+ *              counter words 0 and 1 are taken by the closed-loop rollouts and by exploration;
+ *        idx = (uint64(x) * uint64(n_seen[e])) >> 32;   i = seen[e][idx];
+ *        entry i of the game's table gives n', r, d, D as in step 4 of the one-step rule;
+ *        the bootstrap b of step 5 from q[e][n'] as it stands BEFORE this planning step's write;
+ *        delta = (d ? r : r + (gamma[e] * D) * b) - q[e][i];   q[e][i] = q[e][i] + alpha[e] * delta.
+ *      Planning steps are SEQUENTIAL: each sees the writes of those before it, and of step 1.
+ *      Sampling is UNIFORM OVER THE SEEN PAIRS - not "a seen state first, then an action taken in
+ *      it" as in the book's pseudocode: a state met with four actions is drawn four times as often
+ *      as one met with a single action.
+ *   4. Advance.  The window sums, state, done and ret advance exactly as in the one-step learners.
+ *      The next frame acts on q as planning left it.
+ * `reset_first` starts a new episode; the model stays, as the table does.
+ *
+ * A learner is BAD when it is bad under the one-step rule; or when its planning[e] is outside
+ * 0 .. CAMPX_DYNA_MAX_PLANNING (1024: the fourth counter word stays below 258); or when its list,
+ * as screened at the start of the launch, has n_seen[e] outside 0 .. 5 * n_states or one of its
+ * first n_seen[e] elements outside 0 .. 5 * n_states - 1.  The screening is what keeps every
+ * planning read in bounds.  A BAD learner takes action 4 at every frame; its q, seen and n_seen are
+ * untouched (its sums are written); it is counted ONCE per launch into *bad_count.  A list with
+ * repeated elements is used as given: a repeat is sampled as often as it is listed.
+ * Consequences, each pinned by the tests: planning = 0 gives campx_wide_learn_launch()'s q, sums
+ * and state bit for bit, and records the model; launches of T1 and T2 frames equal one of T1 + T2;
+ * neither path changes a bit.
+ *
+ * A lane per learner, 256 to a workgroup, no barrier inside the frame loop; every loop bound is a
+ * kernel argument or the screened planning[e] <= 1024.  The next frame's row is RE-READ after the
+ * last planning step (planning may have written any element of it); a learner with planning[e] = 0
+ * keeps the one-step learners' patch of the one element written.
+ * Path 1: the workgroup stages in LDS, all lane-innermost, the entries and perf bytes; its 256
+ * learners' q as campx_wide_learn_launch() lays them out; the seen lists as 16-bit elements
+ * [5 * n_states][256]; and a membership bitmap of W = ceil(5 * n_states / 32) 32-bit words per
+ * learner, [W][256], rebuilt from the list at the start of the launch:
+ *     LDS bytes = table + 256 * (n_states * 20 + n_states * 10 + 4 * W)     (table: as above)
+ * (path 1 also needs 5 * n_states <= 65536, the 16-bit element).  Within a row of 256 16-bit
+ * elements lane t sits in dword (t & 31) + 32 * (t >> 6), half (t >> 5) & 1: the 32 lanes of a
+ * half wave fall on 32 different banks whichever elements they read.
+ * Path 2: q, seen and the bitmap go through L1 / L2; the bitmap is the caller's scratch `marks`,
+ * DEVICE uint32 [B][W], 4-byte aligned, contents ignored on entry and unspecified afterwards (may
+ * be NULL on path 1); the entries (and perf bytes) stay in LDS when they alone fit.
+ * `path` 0 takes path 1 whenever its bytes are within wide_lds_max: arithmetic, not tuned.
+ *
+ * campx_wide_dyna_plan(): plan_out[5] = path (1 / 2); dynamic LDS bytes; threads of a workgroup
+ * (256); 1 when the entries are staged in LDS; W.  CAMPX_EINVAL: what campx_wide_learn_plan()
+ * refuses.  campx_wide_dyna_launch() returns CAMPX_EINVAL, before anything touches a device, for
+ * the same, for what campx_wide_learn_launch() refuses, for `seen` (16 bytes), `n_seen` or
+ * `planning` (4 bytes) that are NULL or misaligned, and - on path 2 - for a `marks` that is NULL
+ * or not 4-byte aligned.  Asynchronous on `stream`, no synchronisation, no allocation, no library
+ * state.
+ */
+#define CAMPX_DYNA_MAX_PLANNING 1024
+
+typedef struct CampxDynaLearner {
+  float* q;               /* DEVICE [B][n_states][5], 16-byte aligned; updated in place */
+  const float* alpha;     /* DEVICE [B] each */
+  const float* gamma;
+  const float* epsilon;
+  float* reward_sum;      /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;      /* DEVICE [W][B], or NULL */
+  int32_t* episodes;      /* DEVICE [W][B] */
+  int32_t* bad_count;     /* optional device int32: += bad learners */
+  int32_t* bad_flag;      /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;    /* absolute number of the launch's frame 0 */
+  int32_t window;         /* frames per window, >= 1 (may exceed T) */
+  int32_t rule;           /* CAMPX_LEARN_Q / CAMPX_LEARN_EXPECTED_SARSA */
+  int32_t path;           /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+  int32_t* seen;          /* DEVICE [B][n_states * 5], 16-byte aligned; updated in place */
+  int32_t* n_seen;        /* DEVICE [B]; updated in place */
+  const int32_t* planning; /* DEVICE [B]: planning updates per frame, 0 .. CAMPX_DYNA_MAX_PLANNING */
+  uint32_t* marks;        /* path 2: scratch [B][ceil(n_states * 5 / 32)]; may be NULL on path 1 */
+} CampxDynaLearner;
+
+int32_t campx_wide_dyna_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                             int32_t path, int64_t* plan_out);
+int32_t campx_wide_dyna_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                               CampxState state, const CampxDynaLearner* learner, int64_t B,
+                               int32_t T, void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
