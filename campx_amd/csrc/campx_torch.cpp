@@ -21,6 +21,7 @@
 //   campx::wide_learn_shared        shared learners: n environments feed one Q-table, T frames per launch
 //   campx::wide_learn_traces        learners with eligibility traces: Q(lambda), expected SARSA(lambda)
 //   campx::wide_learn_dyna          Dyna-Q learners: n planning updates of remembered pairs a frame
+//   campx::wide_learn_actor         actor-critic learners: a softmax policy and a critic per environment
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -984,6 +985,52 @@ void wide_learn_dyna(const Tensor& spec_host, const Tensor& tables, Tensor& stat
            "campx_wide_dyna_launch");
 }
 
+// Actor-critic online learners (campx_wide_actor_launch): environment e owns `prefs[e]` float32
+// [B, n_states, 5] and `values[e]` float32 [B, n_states], both 16-byte aligned and updated in place;
+// `alpha_actor`, `alpha_critic`, `gamma` float32 [B]; the window sums as in campx::wide_learn.
+// `bad_count` counts bad learners, `bad_rows` the environment-frames that met a bad row.
+void wide_learn_actor(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                      const OptTensor& ret, Tensor& prefs, Tensor& values, const Tensor& alpha_actor,
+                      const Tensor& alpha_critic, const Tensor& gamma, int64_t seed,
+                      int64_t first_frame, int64_t frames, int64_t window, Tensor& reward_sum,
+                      const OptTensor& perf_sum, Tensor& episodes, const OptTensor& bad_count,
+                      const OptTensor& bad_rows, const OptTensor& bad_flag, bool reset_first,
+                      int64_t path) {
+  const char* what = "campx::wide_learn_actor";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  TORCH_CHECK(g.B * g.hs->n_states * CAMPX_N_ACTIONS < (1ll << 31), what,
+              ": B * n_states * 5 must be below 2^31");
+  // the checks the one-step learners' fields get: prefs is shaped and aligned as their q, the two
+  // step sizes as their alpha and epsilon
+  const CampxLearner as = learner_fields<CampxLearner>(
+      what, g, g.B, prefs, alpha_actor, gamma, alpha_critic, CAMPX_LEARN_Q, seed, first_frame, frames,
+      window, reward_sum, perf_sum, episodes, bad_count, bad_flag, reset_first, path);
+  want(values, "values", at::kFloat, g.dev, {g.B, g.hs->n_states});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(values.data_ptr()) & 15) == 0, what,
+              ": values must be 16-byte aligned");
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, g.dev, {1});
+  CampxActorLearner l{};
+  l.prefs = as.q;
+  l.values = reinterpret_cast<float*>(values.data_ptr());
+  l.alpha_actor = as.alpha;
+  l.alpha_critic = as.epsilon;
+  l.gamma = as.gamma;
+  l.reward_sum = as.reward_sum;
+  l.perf_sum = as.perf_sum;
+  l.episodes = as.episodes;
+  l.bad_count = as.bad_count;
+  l.bad_rows = opt_ptr<int32_t>(bad_rows);
+  l.bad_flag = as.bad_flag;
+  l.seed = as.seed;
+  l.first_frame = as.first_frame;
+  l.window = as.window;
+  l.path = as.path;
+  l.reset_first = as.reset_first;
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_actor_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
+           "campx_wide_actor_launch");
+}
+
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
 // campx_wide_render_gather_launch): row i of `obs` [N, L, H, W] is the observation of frame
 // t_idx[i], environment e_idx[i] of `trace` (want_stored_trace()).  Requests past the
@@ -1625,7 +1672,8 @@ void run_then_bump_versions(const c10::OperatorHandle& op, c10::DispatchKeySet k
 const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
-    "wide_learn", "wide_learn_shared", "wide_learn_traces", "wide_learn_dyna", "render_gather",
+    "wide_learn", "wide_learn_shared", "wide_learn_traces", "wide_learn_dyna", "wide_learn_actor",
+    "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_population_solve", "wide_visit",
     "wide_visit_population",
@@ -1721,6 +1769,12 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(j!)? marks, Tensor(k!)? bad_count, Tensor(l!)? bad_flag, bool reset_first, "
       "int path=0) -> ()");
   m.def(
+      "wide_learn_actor(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) prefs, Tensor(e!) values, Tensor alpha_actor, Tensor alpha_critic, "
+      "Tensor gamma, int seed, int first_frame, int frames, int window, Tensor(f!) reward_sum, "
+      "Tensor(g!)? perf_sum, Tensor(h!) episodes, Tensor(i!)? bad_count, Tensor(j!)? bad_rows, "
+      "Tensor(k!)? bad_flag, bool reset_first, int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1794,6 +1848,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_learn_shared", &wide_learn_shared);
   m.impl("wide_learn_traces", &wide_learn_traces);
   m.impl("wide_learn_dyna", &wide_learn_dyna);
+  m.impl("wide_learn_actor", &wide_learn_actor);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

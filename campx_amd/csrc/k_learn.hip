@@ -7,7 +7,9 @@
 // wide_learn_traces_kernel, a table and an eligibility trace per environment, a team of lanes
 // sweeping the whole table every frame (tests/trace_learner_reference.py).  A fourth,
 // wide_learn_dyna_kernel, is the first's schedule with n planning updates of remembered pairs after
-// every frame (Dyna-Q; tests/dyna_learner_reference.py).
+// every frame (Dyna-Q; tests/dyna_learner_reference.py).  A fifth, wide_learn_actor_kernel, is the
+// first's schedule again with a softmax policy and a critic per learner in place of the Q-table
+// (one-step actor-critic; tests/actor_critic_reference.py).
 //
 // What they have in common is written ONCE and called by all - a change of the rule is made
 // there.  "The frame step": stage_table() (entries and perf bytes into LDS), Hyper (alpha, gamma,
@@ -1019,6 +1021,158 @@ __global__ __launch_bounds__(kLearnThreads) void wide_learn_dyna_kernel(
 using DynaKernel = decltype(&wide_learn_dyna_kernel<false, false, false, false>);
 static const DynaKernel kDynaKernels[3][2][2] = CAMPX_LEARN_INSTANCES(wide_learn_dyna_kernel);
 
+// ---------------------------------------------------------------------------------------------
+// Actor-critic: one-step actor-critic with a softmax policy per learner (include/campx_hip.h,
+// "Actor-critic online learners", has the frame; tests/actor_critic_reference.py restates it in
+// numpy).  wide_learn_kernel's schedule - a lane per learner, 256 to a workgroup, nothing shared
+// between lanes, no barrier inside the frame loop - with two tables per learner, the preferences
+// `prefs[e]` [S][5] and the critic's `values[e]` [S], and k_policy.hip's sampler in place of the
+// epsilon-greedy choice: the weights are softmax_weights() of the state's row (wide_table.hip.h: a
+// stated f32 rule, not expf()), the thresholds policy_thresholds(), the random word that of
+// rollout_policy() - word f & 3 of the block with counter (e, f >> 2, 0) - so a learner whose step
+// sizes are 0 walks exactly as rollout_population() walks its weights.  The chain per frame is
+// row -> five weights -> thresholds -> action -> entry -> values[s], values[n] -> delta -> one write
+// of values, five of prefs -> the next row, RE-READ (the frame wrote all five elements of row s,
+// and n may be s).  No epsilon and no rule: Hyper, frame_action() and td_error() are not used.
+//
+// Path 1: the entries, the perf bytes, prefs (move_q(), lane-innermost, (s * 5 + a) * 256 + lane)
+// and, after them, values (move_q() with rows of one element, s * 256 + lane) in LDS: 24 bytes a
+// state and learner.  Path 2: prefs and values through L1 / L2, the entries in LDS when they fit.
+
+// campx_wide_actor_plan()'s four words, in their order (LearnPlan's).
+inline int32_t plan_actor(int64_t S, int32_t has_perf, int64_t B, int64_t lds_max, int32_t path,
+                          LearnPlan* p, int64_t* plan_out) {
+  if (!plan_args_ok(S, has_perf, B, B, lds_max, path)) return CAMPX_EINVAL;
+  const int64_t table = table_bytes(S, has_perf);
+  const int64_t want = table + kLearnThreads * S * (CAMPX_N_ACTIONS + 1) * (int64_t)sizeof(float);
+  const bool fits = want <= lds_max;
+  if (path == 1 && !fits) return CAMPX_EINVAL;
+  p->path = (path == 1 || (path == 0 && fits)) ? 1 : 2;
+  p->table_in_lds = (p->path == 1 || table <= lds_max) ? 1 : 0;
+  p->lds_bytes = p->path == 1 ? want : (p->table_in_lds ? table : 0);
+  p->threads = kLearnThreads;
+  if (plan_out) memcpy(plan_out, p, sizeof(*p));
+  return CAMPX_OK;
+}
+
+// kQLds: path 1.  kTableLds, kPerf: as in wide_learn_kernel.  `bad_rows`: environment-frames of
+// good learners that met a row that is not good; `bad_count`: bad learners, once per launch.
+template <bool kQLds, bool kTableLds, bool kPerf>
+__global__ __launch_bounds__(kLearnThreads) void wide_learn_actor_kernel(
+    LearnParams pp, const uint2* __restrict__ g_entries, const int8_t* __restrict__ g_perf,
+    float* __restrict__ prefs, float* __restrict__ values, const float* __restrict__ alpha_actors,
+    const float* __restrict__ alpha_critics, const float* __restrict__ gammas,
+    int32_t* __restrict__ state, CampxState st, float* __restrict__ reward_sum,
+    int32_t* __restrict__ perf_sum, int32_t* __restrict__ episodes, int32_t* bad_count,
+    int32_t* bad_rows, int32_t* bad_flag, int64_t B, int32_t T, int32_t reset_first) {
+  static_assert(kTableLds || !kQLds, "path 1 stages the table");
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_tables[];
+  __shared__ float discounts[16];
+  const int S = pp.n_states, n_entries = S * CAMPX_N_ACTIONS;
+  const int lane = threadIdx.x;
+  const int64_t env_lo = (int64_t)blockIdx.x * kLearnThreads;
+  const int64_t env = env_lo + lane;
+  // this workgroup's learners and their pieces of prefs and values: contiguous, 16-byte aligned
+  // (both tensors are, and a piece starts a multiple of 256 * 4 bytes in)
+  const int n_lanes = (int)(B - env_lo < kLearnThreads ? B - env_lo : kLearnThreads);
+  float* h_block = prefs + env_lo * n_entries;         // floats: B * S * 5 < 2^31
+  float* v_block = values + env_lo * S;
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, lane, kLearnThreads);
+  float* l_h = reinterpret_cast<float*>(tab.free);
+  float* l_v = l_h + n_entries * kLearnThreads;
+  if (kQLds) {
+    move_q<true>(l_h, h_block, n_lanes * n_entries, n_entries, lane);
+    move_q<true>(l_v, v_block, n_lanes * S, S, lane);
+  }
+  if (lane < 16) discounts[lane] = pp.discounts[lane];
+  __syncthreads();
+
+  if (env < B) {
+    const float alpha_actor = alpha_actors[env], alpha_critic = alpha_critics[env], gamma = gammas[env];
+    // (x - x is 0 exactly for a finite x, NaN for an infinity or a NaN)
+    const bool good = (alpha_actor - alpha_actor) == 0.0f && (alpha_critic - alpha_critic) == 0.0f &&
+                      (gamma - gamma) == 0.0f;
+    // the lane's tables: element (s, a) of prefs at own_h[(s * 5 + a) * step], values[s] at own_v[s * step]
+    float* own_h = kQLds ? l_h + lane : prefs + env * n_entries;
+    float* own_v = kQLds ? l_v + lane : values + env * S;
+    constexpr int step = kQLds ? kLearnThreads : 1;
+    Carried c;
+    c.load(state, st, env, S, reset_first);
+    WindowSums<kPerf> sums{reward_sum, perf_sum, episodes, env};
+    const Chunks chunks(pp.first_frame);
+    int n_bad_rows = 0;
+    for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
+      // rollout_policy()'s block of the chunk's four absolute frames: fourth counter word 0
+      uint32_t x[kLearnChunk];
+      const uint64_t g = (chunks.pair0 >> 1) + (uint64_t)((t0 + chunks.lead) >> 2);
+      philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 0u, pp.key0, pp.key1, x);
+#pragma unroll
+      for (int j = 0; j < kLearnChunk; ++j) {
+        if (t0 + j >= 0 && t0 + j < T) {
+          const uint32_t base = c.from * CAMPX_N_ACTIONS;
+          float h[5], w[5], thr[5];
+#pragma unroll
+          for (int k = 0; k < 5; ++k) h[k] = own_h[(base + k) * step];
+          const bool row_good = softmax_weights(h, w) && good;
+          if (!row_good) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) w[k] = 0.0f;   // (a bad learner: action 4 throughout)
+          }
+          policy_thresholds(w, thr);
+          const float u = (float)(x[j] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
+          const float r = u * thr[4];
+          const uint32_t a = (uint32_t)(r >= thr[0]) + (uint32_t)(r >= thr[1]) +
+                             (uint32_t)(r >= thr[2]) + (uint32_t)(r >= thr[3]);
+          n_bad_rows += good && !row_good;
+          const uint32_t idx = base + a;
+          const Entry e = decode_entry(tab.entries[idx], S, discounts);
+          if (row_good) {
+            // both values as the frame found them
+            const float v_s = own_v[c.from * step], v_n = own_v[e.next * step];
+            const float discounted = (gamma * e.D) * v_n;
+            const float target = e.done ? e.r : e.r + discounted;
+            const float delta = target - v_s;
+            own_v[c.from * step] = v_s + alpha_critic * delta;
+            const float push = alpha_actor * delta;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+              const float pi = w[k] / thr[4];
+              const float grad = (a == (uint32_t)k ? 1.0f : 0.0f) - pi;
+              own_h[(base + k) * step] = h[k] + push * grad;
+            }
+          }
+          c.advance(e);
+          sums.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
+        }
+      }
+    }
+    sums.flush_short();
+    c.store(state, st, env);
+    report_bad(bad_count, bad_flag, good ? 0 : 1);       // bad LEARNERS, once per launch
+    // bad ROWS, per environment-frame.  (The count is added here and not handed to report_bad():
+    // every other call of this file passes it 0 or 1, which the compiler knows and uses in the
+    // older kernels - an arbitrary count from here would change their instructions.)
+    if (n_bad_rows) {
+      if (bad_rows) atomicAdd(bad_rows, n_bad_rows);
+      report_bad(nullptr, bad_flag, 1);
+    }
+  }
+
+  if (kQLds) {
+    __syncthreads();
+    move_q<false>(l_h, h_block, n_lanes * n_entries, n_entries, lane);
+    move_q<false>(l_v, v_block, n_lanes * S, S, lane);
+  }
+}
+
+// At [where the tables are][kPerf], the first index as in CAMPX_LEARN_INSTANCES.
+using ActorKernel = decltype(&wide_learn_actor_kernel<false, false, false>);
+static const ActorKernel kActorKernels[3][2] = {
+    {wide_learn_actor_kernel<0, 0, 0>, wide_learn_actor_kernel<0, 0, 1>},
+    {wide_learn_actor_kernel<0, 1, 0>, wide_learn_actor_kernel<0, 1, 1>},
+    {wide_learn_actor_kernel<1, 1, 0>, wide_learn_actor_kernel<1, 1, 1>}};
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -1154,6 +1308,45 @@ int32_t campx_wide_dyna_launch(const CampxWideSpec* s, const void* tables_dev, C
                      l->planning, l->marks, reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum,
                      l->perf_sum, l->episodes, l->bad_count, l->bad_flag, B, T, l->reset_first,
                      (int32_t)plan.words);
+  return launch_status();
+}
+
+int32_t campx_wide_actor_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                              int32_t path, int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  LearnPlan plan;
+  return plan_actor(n_states, has_perf, B, wide_lds_max, path, &plan, plan_out);
+}
+
+int32_t campx_wide_actor_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
+                                const CampxActorLearner* l, int64_t B, int32_t T, void* stream) {
+  // the one-step learners' screening, on the fields the actor-critic shares with them: prefs stands
+  // where q does, the two step sizes where alpha and epsilon do; it has no rule
+  CampxLearner as{};
+  if (l) {
+    as.q = l->prefs, as.alpha = l->alpha_actor, as.gamma = l->gamma, as.epsilon = l->alpha_critic;
+    as.reward_sum = l->reward_sum, as.perf_sum = l->perf_sum, as.episodes = l->episodes;
+    as.bad_count = l->bad_count, as.bad_flag = l->bad_flag, as.seed = l->seed;
+    as.first_frame = l->first_frame, as.window = l->window, as.rule = CAMPX_LEARN_Q;
+    as.path = l->path, as.reset_first = l->reset_first;
+  }
+  const bool own_ok = l && l->values && aligned_to(l->values, 16) && aligned_to(l->bad_rows, 4);
+  const int32_t screened = screen_learner(s, tables_dev, st, &as, B, T, own_ok);
+  if (screened != CAMPX_OK) return screened;
+  LearnPlan plan;      // (refuses B * n_states * 5 >= 2^31, and path 1 for what does not fit)
+  const int32_t planned = plan_actor(s->n_states, l->perf_sum ? 1 : 0, B, knob(K_WIDE_LDS_MAX), l->path,
+                                     &plan, nullptr);
+  if (planned != CAMPX_OK) return planned;
+  const WideTables t = wide_tables(*s, tables_dev);
+  const size_t lds = (size_t)plan.lds_bytes;
+  const ActorKernel kernel =
+      kActorKernels[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)][l->perf_sum != nullptr];
+  CAMPX_ALLOW_LDS(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((B + kLearnThreads - 1) / kLearnThreads)),
+                     dim3(kLearnThreads), lds, static_cast<hipStream_t>(stream), learn_params(*s, as),
+                     t.entries, t.perf, l->prefs, l->values, l->alpha_actor, l->alpha_critic, l->gamma,
+                     reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
+                     l->bad_count, l->bad_rows, l->bad_flag, B, T, l->reset_first);
   return launch_status();
 }
 

@@ -63,6 +63,42 @@ __device__ __forceinline__ float policy_row_total(const float (&w)[5]) {
   return good ? c4 : 0.0f;
 }
 
+// A row of PREFERENCES h[0..4] as the sampler's weights w[0..4]: the softmax's numerators by the
+// exponent rule of include/campx_hip.h ("Actor-critic online learners", rule 1) - NOT expf(): every
+// operation below is one f32 operation rounded on its own (-ffp-contract=off), so that numpy and
+// torch restate it bit for bit.  m is the row's maximum by the greedy reduction (the lowest index
+// wins ties, NaN never wins); the row is good when (m - m) == 0 and no element is above m or NaN;
+// w = 2^k * p(f) with t = (h - m) * log2e, k = rint(t), f = t - k, p the degree-6 polynomial of
+// 2^f, and w = +0 for t < -100.  The maximum's weight is exactly 1: c4 lies in [1, 5].  A row that
+// is not good gets five zeros - policy_thresholds() then calls it bad - and `false` is returned.
+constexpr float kSoftmaxLog2e = 0x1.715476p+0f;
+constexpr float kSoftmaxCut = -100.0f;
+constexpr float kSoftmaxPoly[7] = {0x1p+0f,         0x1.62e43p-1f,   0x1.ebfbep-3f,  0x1.c6b08ep-5f,
+                                   0x1.3b2ab6p-7f,  0x1.5d87fep-10f, 0x1.430912p-13f};
+__device__ __forceinline__ bool softmax_weights(const float (&h)[5], float (&w)[5]) {
+  float m = h[0];
+#pragma unroll
+  for (int a = 1; a < 5; ++a) m = h[a] > m ? h[a] : m;
+  bool good = (m - m) == 0.0f;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) good = good && h[a] <= m;
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    const float t = (h[a] - m) * kSoftmaxLog2e;
+    const bool some = good && t >= kSoftmaxCut;
+    const float tt = some ? t : 0.0f;                  // (k stays within -100 .. 0)
+    const float k = rintf(tt);                         // ties to even
+    const float f = tt - k;
+    float p = kSoftmaxPoly[6];
+#pragma unroll
+    for (int n = 5; n >= 0; --n) p = p * f + kSoftmaxPoly[n];
+    // 2^k as a float, k in -100 .. 0: the product is exact, no result is subnormal
+    const float scale = __uint_as_float((uint32_t)((int)k + 127) << 23);
+    w[a] = some ? p * scale : 0.0f;
+  }
+  return good;
+}
+
 // One Philox4x32-10 block: the sampler of the closed-loop rollouts (k_policy.hip;
 // include/campx_hip.h has the rule).
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,

@@ -521,6 +521,18 @@ class Engine(object):
     """State-table tier only: the dict of `learn_dyna(out=...)`, allocated once."""
     return self._batched('dyna_buffers').dyna_buffers(T, window=window, path=path)
 
+  def learn_actor_critic(self, T, prefs=None, values=None, *args, **kwargs):
+    """State-table tier only: T frames of ONE-STEP ACTOR-CRITIC for B independent learners in one
+    launch - environment e owns the preferences `prefs[e]` of a softmax policy (float32
+    `[B, n_states, 5]`) and a critic `values[e]` (`[B, n_states]`), both updated in place; it samples
+    as `rollout_policy()` samples `returns.softmax_weights(prefs[e])`, and every frame moves
+    `values[e, s]` by `alpha_critic * delta` and `prefs[e, s]` by `alpha_actor * delta` along the
+    gradient of the log-probability of the action taken.  `alpha_actor`, `alpha_critic`, `gamma` are
+    numbers or `[B]` tensors.  Returns 'prefs', 'values' and `learn_tabular()`'s window rows.  See
+    `wide.WideGame.learn_actor_critic`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` selects this one)."""
+    return self._batched('learn_actor_critic').learn_actor_critic(T, prefs, values, *args, **kwargs)
+
   def learn_shared(self, T, q, *args, **kwargs):
     """State-table tier only: T frames of online tabular learning for P SHARED learners in one
     launch, learner m owning `q[m]` of `q` float32 `[P, n_states, 5]` (updated in place) and fed by

@@ -25,6 +25,10 @@ The learner's half of such an episode is here too.  Everything a tabular loss ne
 `table[states, actions]` gather without the two int64 copies of the streams, differentiable in the
 table through `sum_by_state()` (csrc/k_sums.hip, `campx::state_sums`, `campx::table_lookup`;
 tests/state_sums_reference.py restates the rule in numpy).
+
+`softmax_weights()` turns the preferences of softmax policies into the sampler's weights by the
+exponent rule of `WideGame.learn_actor_critic()` - a stated float32 rule, the same bits on the CPU,
+on the device and inside that learner's kernel (tests/actor_critic_reference.py restates it).
 """
 
 import math
@@ -415,3 +419,52 @@ def table_lookup(table, states, actions=None, bad_count=None):
   if bad_count is not None:
     _counter(bad_count, 'bad_count', device)
   return _TableLookup.apply(table, states, actions, bad_count)
+
+
+# The exponent rule of the actor-critic learners (include/campx_hip.h, "Actor-critic online
+# learners", rule 1): log2(e) and ln(2)^n / n!, each the nearest float32.
+SOFTMAX_LOG2E = float.fromhex('0x1.715476p+0')
+SOFTMAX_CUT = -100.0
+SOFTMAX_POLY = tuple(float.fromhex(c) for c in (
+    '0x1p+0', '0x1.62e43p-1', '0x1.ebfbep-3', '0x1.c6b08ep-5', '0x1.3b2ab6p-7', '0x1.5d87fep-10',
+    '0x1.430912p-13'))
+
+
+def softmax_weights(prefs):
+  """The sampler's weights of softmax policies given as preferences: float32 `[..., 5]` in,
+  float32 `[..., 5]` out, on the CPU or the device - THE SAME BITS on both, and the bits
+  `learn_actor_critic()` samples from inside its kernel.
+
+  The weights are a stated rule, not `exp`: with m the row's maximum, `w = 2^k * p(f)` for
+  `t = (h - m) * log2e`, `k = rint(t)`, `f = t - k` and p a degree-6 polynomial by Horner, every
+  multiply and add a float32 operation of its own; `w = 0` exactly for `t < -100`.  The maximum's
+  weight is exactly 1, so a row's total lies in [1, 5]; the largest relative error against float64
+  `exp(h - m)` is 3.74e-6 (include/campx_hip.h has the rule and its coefficients).  A row with a
+  NaN or a +inf, or of five -inf, is not good: it gets five zeros, which `rollout_policy()` and
+  the evaluation calls treat as a bad row by their own rule.  Elements of -inf in a good row get
+  weight 0 - an action never taken.
+
+  `rollout_population(softmax_weights(prefs), ...)`, `evaluate_population(softmax_weights(prefs),
+  ...)` and `state_visitation(softmax_weights(prefs[m]), ...)` then see exactly the probabilities
+  the learner sampled from.  Written in torch element-wise operations: no kernel of its own, not
+  differentiable (the result is detached).
+  """
+  if (not torch.is_tensor(prefs) or prefs.dtype != torch.float32 or prefs.dim() < 1
+      or prefs.shape[-1] != 5):
+    raise ValueError('prefs must be a float32 [..., 5] tensor, got {}'.format(_got(prefs)))
+  h = prefs.detach()
+  m = h[..., 0]
+  for a in range(1, 5):                       # the lowest index wins ties, NaN never wins
+    m = torch.where(h[..., a] > m, h[..., a], m)
+  m = m.unsqueeze(-1)
+  good = (torch.sub(m, m) == 0) & (h <= m).all(dim=-1, keepdim=True)
+  t = torch.mul(torch.sub(h, m), SOFTMAX_LOG2E)
+  some = good & (t >= SOFTMAX_CUT)
+  t = torch.where(some, t, torch.zeros_like(t))
+  k = torch.round(t)                          # ties to even
+  f = torch.sub(t, k)
+  p = torch.full_like(f, SOFTMAX_POLY[6])
+  for c in SOFTMAX_POLY[5::-1]:
+    p = torch.add(torch.mul(p, f), c)
+  scale = torch.bitwise_left_shift(k.to(torch.int32) + 127, 23).view(torch.float32)   # 2^k, exact
+  return torch.where(some, torch.mul(p, scale), torch.zeros_like(p))

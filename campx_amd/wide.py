@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'dyna_buffers', 'learn_dyna', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'dyna_buffers', 'learn_dyna', 'learn_actor_critic', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'value_iteration_population',
     'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
@@ -147,6 +147,8 @@ class WideGame(fused.FusedGame):
     self._bad_shared_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_trace_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_dyna_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_actor_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_actor_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._hyper_floats = {}
     self._hyper_ints = {}             # learn_dyna()'s `planning` given as a Python int, by learners
     self._layer_of_cell = None        # the window kernel's scenery table
@@ -209,7 +211,14 @@ class WideGame(fused.FusedGame):
         (self._bad_dyna_learners, acts,
          '{} learners of learn_dyna() are bad (alpha, gamma or epsilon not finite, epsilon outside '
          '[0, 1], planning outside 0 .. 1024, or a model whose n_seen or elements are outside the '
-         'table); they took action {} at every frame and their tables and models were left untouched')]
+         'table); they took action {} at every frame and their tables and models were left untouched'),
+        (self._bad_actor_learners, acts,
+         '{} learners of learn_actor_critic() have bad hyper-parameters (alpha_actor, alpha_critic or '
+         'gamma not finite); they took action {} at every frame and their preferences and values were '
+         'left untouched'),
+        (self._bad_actor_rows, acts,
+         '{} environment-frames of learn_actor_critic() met rows of preferences that are not good (a '
+         'NaN or a +inf, or five -inf); they took action {} and changed neither table')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -539,11 +548,13 @@ class WideGame(fused.FusedGame):
     return self._hyper_floats[call, B][row].fill_(float(value))
 
   def _learner_prologue(self, call, learners, T, window, rule, first_frame, seed, alpha, gamma,
-                        epsilon, out, own, made_by, make_out):
+                        epsilon, out, own, made_by, make_out, names=('alpha', 'gamma', 'epsilon')):
     """What learn_tabular() and learn_shared() do after their own checks of q and P: returns T,
     window, the first frame, the seed as the op's signed int64, the checked (or made) `out` and
     alpha, gamma, epsilon as float32 [learners].  `own`: the call's own entries of `out`;
-    `made_by(T, window)`: the call that makes `out`, for the message; `make_out(T, window)`."""
+    `made_by(T, window)`: the call that makes `out`, for the message; `make_out(T, window)`.
+    `names`: what the call names its three hyper-parameters (learn_actor_critic()'s are two step
+    sizes and gamma)."""
     B = self.batch
     T, window, W = self._windows_of(T, window)
     if rule not in _hip.LEARN_RULES:
@@ -559,9 +570,9 @@ class WideGame(fused.FusedGame):
       out = make_out(T, window)
     else:
       self._check_out(out, want, made_by(T, window))
-    hyper = (self._hyper_parameter('alpha', alpha, 0, call, learners),
-             self._hyper_parameter('gamma', gamma, 1, call, learners),
-             self._hyper_parameter('epsilon', epsilon, 2, call, learners))
+    hyper = (self._hyper_parameter(names[0], alpha, 0, call, learners),
+             self._hyper_parameter(names[1], gamma, 1, call, learners),
+             self._hyper_parameter(names[2], epsilon, 2, call, learners))
     return T, window, first, seed - (1 << 64) if seed >= 1 << 63 else seed, out, hyper
 
   def _learner_epilogue(self, first, T, reset_first, q, out, own=()):
@@ -886,6 +897,95 @@ class WideGame(fused.FusedGame):
         bool(reset_first), path)
     res = self._learner_epilogue(first, T, reset_first, q, out)
     res['model'] = model
+    return res
+
+  # ------------------------------------------------------------ actor-critic learners
+
+  def learn_actor_critic(self, T, prefs=None, values=None, alpha_actor=0.1, alpha_critic=0.1,
+                         gamma=0.99, seed=0, first_frame=None, reset_first=False, window=None,
+                         out=None, path=0):
+    """T frames of ONE-STEP ACTOR-CRITIC for B independent learners in ONE launch: environment e is
+    learner e, with a softmax policy of its own - the preferences `prefs[e]` - and a critic
+    `values[e]` (Sutton & Barto 13.5, without the gamma^t factor; csrc/k_learn.hip,
+    `campx::wide_learn_actor`).  The policy-gradient sibling of `learn_tabular()`: what
+    `examples/actor_critic_per_state.py` does from the host - a rollout, a returns pass, a
+    `sum_by_state()` and a torch step per update, for one learner - as one launch for a sweep of
+    them.  Nothing is shared between learners: no atomics, and the run repeats bit for bit
+    (include/campx_hip.h has rule and frame; tests/actor_critic_reference.py restates them in numpy).
+
+    The frame, from state s: the weights `w = returns.softmax_weights(prefs[e, s])` - a stated
+    float32 rule, NOT `exp`, so that they repeat bit for bit everywhere - and the action by
+    `rollout_policy()`'s own sampler with `rollout_policy()`'s own stream (key `seed`, counter
+    (e, frame >> 2), word frame & 3); the entry gives n, r, done, D;
+    `delta = (r if done else r + (gamma * D) * values[e, n]) - values[e, s]`;
+    `values[e, s] += alpha_critic * delta`; and, for each a', with `pi = w[a'] / sum(w)`,
+    `prefs[e, s, a'] += (alpha_actor * delta) * ((a' == a) - pi)`.
+
+    Args:
+      prefs: contiguous float32 `[B, n_states, 5]` on the game's device (16-byte aligned,
+          `B * n_states * 5 < 2^31`), updated IN PLACE; None: zeros, the uniform policy.  A
+          preference of -inf is an action never taken.  A row with a NaN or a +inf (or five -inf)
+          is NOT GOOD: an environment-frame that meets it takes action 4, changes neither table
+          and is counted; the count raises ValueError lazily, as `rollout_policy()`'s bad rows do.
+          `returns.softmax_weights(prefs)` is what `rollout_population()`,
+          `evaluate_population()` and `state_visitation()` take: exactly the probabilities the
+          learner sampled from.
+      values: contiguous float32 `[B, n_states]` (16-byte aligned), updated IN PLACE; None: zeros.
+      alpha_actor, alpha_critic, gamma: the two step sizes and the discount factor, each a Python
+          number or a float32 `[B]` tensor - a tensor is what makes a sweep.  A learner with one
+          that is not finite is BAD: it takes action 4 at every frame, both tables are left
+          untouched, and it raises ValueError - counted once per call - lazily.  Python numbers are
+          checked at once.  With both step sizes 0 the learners walk exactly as
+          `rollout_population(softmax_weights(prefs), T, seed, first_frame)` does with P = B.
+      seed, first_frame, reset_first, window: as in `learn_tabular()`, except that the stream is
+          `rollout_policy()`'s, not the exploration stream.
+      out: a dict from `learner_buffers(T, window)`, overwritten.  With `prefs`, `values`, `out`
+          and tensors (or the same numbers as before) for the hyper-parameters the call allocates
+          nothing and is capturable in a HIP graph.
+      path: 0 - a workgroup keeps the table and its 256 learners' preferences and values in LDS
+          whenever they fit (library setting wide_lds_max: 24 bytes a state and learner, up to 23
+          states), else each learner works on its rows through L1 / L2; 1 / 2 force either (1
+          raises ValueError for what does not fit).  Both give the same bits.
+
+    Returns a dict: 'prefs', 'values' and `learn_tabular()`'s window rows 'reward_sum', 'episodes'
+    and 'perf_sum'.  `state`, `done`, `ret` and `frame` carry over exactly as `learn_tabular()`
+    leaves them.  Argument errors raise ValueError before anything is launched.
+
+    NOT offered: REINFORCE with episode returns (use `rollout_policy()` and
+    `returns.discounted_returns()`), lambda-traces for the actor, an entropy bonus or a temperature,
+    and a shared form in which several actors feed one learner.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    if B * S * A >= 1 << 31:
+      raise ValueError('learn_actor_critic(): B * n_states * 5 = {} x {} x 5 must be below 2^31; use '
+                       'a smaller batch'.format(B, S))
+    for name, t, shape in (('prefs', prefs, (B, S, A)), ('values', values, (B, S))):
+      if t is not None and (not self._tensor_ok(t, torch.float32, shape) or t.data_ptr() % 16):
+        got = ('{} {} on {}'.format(t.dtype, list(t.shape), t.device) if torch.is_tensor(t)
+               else type(t).__name__)
+        raise ValueError('{} must be a contiguous, 16-byte aligned float32 {} tensor on {}, or None '
+                         'for zeros; got {}'.format(name, list(shape), dev, got))
+    self._planned_path(path, _hip.lib.campx_wide_actor_plan, 1 if self.has_perf else 0, B,
+                       what='a table of {} states with the preferences and values of a workgroup\'s '
+                            '256 learners'.format(S))
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_actor_critic', B, T, window, 'q', first_frame, seed, alpha_actor, gamma, alpha_critic,
+        out, [], 'learner_buffers({}, window={})'.format, self.learner_buffers,
+        names=('alpha_actor', 'gamma', 'alpha_critic'))
+    if prefs is None:
+      prefs = torch.zeros((B, S, A), dtype=torch.float32, device=dev)
+    if values is None:
+      values = torch.zeros((B, S), dtype=torch.float32, device=dev)
+    validate = self.validate_actions
+    _hip.ops.wide_learn_actor(
+        self._spec_host, self._tables, self.state, self.done, self.ret, prefs.detach(),
+        values.detach(), hyper[0], hyper[2], hyper[1], seed, first, T, window, out['reward_sum'],
+        out.get('perf_sum') if self.has_perf else None, out['episodes'],
+        self._bad_actor_learners if validate else None, self._bad_actor_rows if validate else None,
+        self._bad_flag if validate else None, bool(reset_first), path)
+    res = self._learner_epilogue(first, T, reset_first, prefs, out)
+    del res['q']
+    res['prefs'], res['values'] = prefs, values
     return res
 
   # ------------------------------------------------------------ shared online learners

@@ -1173,6 +1173,102 @@ int32_t campx_wide_dyna_launch(const CampxWideSpec* spec_host, const void* table
                                CampxState state, const CampxDynaLearner* learner, int64_t B,
                                int32_t T, void* stream);
 /*
+ * ---- Actor-critic online learners: a softmax policy per learner, a whole run per launch --------
+ * The learners above are value-based and act epsilon-greedily.  This one is the policy-gradient
+ * family: one-step actor-critic (Sutton & Barto 13.5, without the gamma^t factor).  Learner e is
+ * environment e, as in campx_wide_learn_launch(), and owns two DEVICE tables updated in place:
+ *   prefs   float32 [B][n_states][5], 16-byte aligned: the preferences of a softmax policy
+ *   values  float32 [B][n_states],    16-byte aligned: the critic
+ * T frames in one launch, nothing shared between learners, no atomics, reproducible bit for bit
+ * (csrc/k_learn.hip; tests/actor_critic_reference.py restates rule and frame in numpy).
+ *
+ * Rule 1, the weights of a row of preferences h[0..4].  THE WEIGHTS ARE THIS RULE, NOT exp(): no
+ * library exponent is called anywhere, every operation is one f32 operation rounded on its own.
+ *   m = h[0]; for a = 1 .. 4: if (h[a] > m) m = h[a]      (the lowest index wins ties, NaN never wins)
+ *   the row is GOOD when (m - m) == 0 and h[a] <= m for all five a: a NaN or a +inf anywhere, or
+ *   five -inf, make it bad; an element of -inf in a good row is good and gets weight 0.
+ *   For a good row, per element:
+ *     d = h[a] - m;  t = d * log2e,  log2e = 0x1.715476p+0f (the f32 nearest to log2(e));
+ *     if t < -100: w[a] = +0 exactly.  Otherwise
+ *     k = rint(t) (ties to even);  f = t - k (exact, |f| <= 0.5);
+ *     p = c6;  p = p * f + c5;  p = p * f + c4;  ...  p = p * f + c0   (Horner, 12 operations);
+ *     w[a] = ldexp(p, k)   (exact: k >= -100 and 0.7 < p < 1.5, no result is subnormal).
+ *   c0 .. c6 are ln(2)^n / n! rounded to f32:
+ *     0x1p+0f, 0x1.62e43p-1f, 0x1.ebfbep-3f, 0x1.c6b08ep-5f, 0x1.3b2ab6p-7f, 0x1.5d87fep-10f,
+ *     0x1.430912p-13f.
+ *   The maximum's weight is exactly 1 (d = 0, p = c0) and no weight is larger, so the row's total
+ *   c4 lies in [1, 5] and the row passes the sampler's own test.  A row that is not good has the
+ *   weights {0, 0, 0, 0, 0}, which the sampler calls bad.  Against float64 exp(d) the largest
+ *   relative error measured is 3.74e-6 (6 M values of d in [-69, 0]; almost all of it is the
+ *   rounding of t at large |d|; 2.4e-7 for |d| < 1).  `campx_amd.returns.softmax_weights()`
+ *   restates the rule in torch element-wise operations, the same bits on CPU and device.
+ *
+ * Frame f = first_frame + t of a good learner, from state s (state 0 after a `done`):
+ *   1. w = rule 1 of prefs[e][s]; thresholds c0 = w0, c1 = c0 + w1, ... c4 and the action by the
+ *      closed-loop rollouts' sampler, WITH THEIR STREAM: x = output word f & 3 of the Philox4x32-10
+ *      block with key (seed & 0xffffffff, seed >> 32) and counter (e, g & 0xffffffff, g >> 32, 0),
+ *      g = f >> 2;  u = (x >> 8) * 2^-24;  r = u * c4;
+ *      a = (r >= c0) + (r >= c1) + (r >= c2) + (r >= c3).  The learner samples exactly as
+ *      campx_wide_policy_population_launch() samples the weights of rule 1.
+ *   2. Entry (s, a) gives n, r, done, D as in step 4 of the one-step learners' rule.
+ *   3. delta = (done ? r : r + (gamma[e] * D) * values[e][n]) - values[e][s], both values as the
+ *      frame found them.
+ *   4. values[e][s] = values[e][s] + alpha_critic[e] * delta.
+ *   5. step = alpha_actor[e] * delta; for each a': pi = w[a'] / c4 (one f32 division);
+ *      prefs[e][s][a'] = prefs[e][s][a'] + step * ((a' == a ? 1 : 0) - pi).
+ *   6. The window sums, state, done and ret advance exactly as in the one-step learners.
+ * A frame whose row is not good takes action 4 and changes neither table; such environment-frames
+ * are counted into *bad_rows.  A learner whose alpha_actor, alpha_critic or gamma is not finite is
+ * BAD: it takes action 4 at every frame, both tables are untouched (its sums are written), and it
+ * is counted ONCE per launch into *bad_count (its frames are not counted as bad rows).
+ * Consequences, each pinned by the tests: with both step sizes 0 the walk is that of the closed-loop
+ * rollouts on softmax_weights(prefs); launches of T1 and T2 frames equal one of T1 + T2; neither
+ * path changes a bit.
+ * NOT offered: REINFORCE with episode returns, lambda-traces for the actor, an entropy bonus or a
+ * temperature, and a shared form in which several actors feed one learner.
+ *
+ * A lane per learner, 256 to a workgroup, no barrier inside the frame loop.
+ * Path 1: the workgroup stages in LDS the entries and perf bytes and its 256 learners' prefs and
+ * values, lane-innermost ((s * 5 + a) * 256 + lane, then s * 256 + lane), copied in and out with
+ * 16-byte accesses:
+ *     LDS bytes = table + 256 * n_states * 24        (table: as campx_wide_learn_plan() counts it)
+ * which wide_lds_max = 144 KiB allows up to 23 states.  Path 2: prefs and values go through
+ * L1 / L2; the entries (and perf bytes) stay in LDS when they alone fit.  `path` 0 takes path 1
+ * whenever its bytes are within wide_lds_max: arithmetic, not tuned.
+ *
+ * campx_wide_actor_plan(): plan_out[4] = path (1 / 2); dynamic LDS bytes; threads of a workgroup
+ * (256); 1 when the entries are staged in LDS.  CAMPX_EINVAL: what campx_wide_learn_plan() refuses.
+ * campx_wide_actor_launch() returns CAMPX_EINVAL, before anything touches a device, for the same,
+ * for what campx_wide_learn_launch() refuses (prefs where it says q, the step sizes where it says
+ * alpha and epsilon; there is no rule), for a `values` that is NULL or not 16-byte aligned and a
+ * `bad_rows` that is not 4-byte aligned.  Asynchronous on `stream`, no synchronisation, no
+ * allocation, no library state.
+ */
+typedef struct CampxActorLearner {
+  float* prefs;              /* DEVICE [B][n_states][5], 16-byte aligned; updated in place */
+  float* values;             /* DEVICE [B][n_states], 16-byte aligned; updated in place */
+  const float* alpha_actor;  /* DEVICE [B] each */
+  const float* alpha_critic;
+  const float* gamma;
+  float* reward_sum;         /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;         /* DEVICE [W][B], or NULL */
+  int32_t* episodes;         /* DEVICE [W][B] */
+  int32_t* bad_count;        /* optional device int32: += bad learners */
+  int32_t* bad_rows;         /* optional device int32: += environment-frames that met a bad row */
+  int32_t* bad_flag;         /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;       /* absolute number of the launch's frame 0 */
+  int32_t window;            /* frames per window, >= 1 (may exceed T) */
+  int32_t path;              /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+} CampxActorLearner;
+
+int32_t campx_wide_actor_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t wide_lds_max,
+                              int32_t path, int64_t* plan_out);
+int32_t campx_wide_actor_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                CampxState state, const CampxActorLearner* learner, int64_t B,
+                                int32_t T, void* stream);
+/*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
  * `obs_format` says) is, bit for bit, the observation a rollout shows for an environment that is
