@@ -38,6 +38,8 @@ EXPORTS = ('campx_spec_size', 'campx_flow_scratch_bytes', 'campx_spec_validate',
            'campx_wide_traces_plan', 'campx_wide_traces_launch',
            'campx_wide_dyna_plan', 'campx_wide_dyna_launch',
            'campx_wide_actor_plan', 'campx_wide_actor_launch',
+           'campx_wide_actor_shared_plan', 'campx_wide_actor_shared_scratch_bytes',
+           'campx_wide_actor_shared_launch',
            'campx_render_gather_launch',
            'campx_wide_render_gather_launch', 'campx_render_gather_plan',
            'campx_wide_render_states_scratch_bytes', 'campx_wide_render_states_launch',
@@ -217,6 +219,18 @@ class CampxActorLearner(ctypes.Structure):
               ('reset_first', ctypes.c_int32)]
 
 
+class CampxSharedActorLearner(ctypes.Structure):
+  """include/campx_hip.h: one campx_wide_actor_shared_launch() call."""
+  _fields_ = [('prefs', ctypes.c_void_p), ('values', ctypes.c_void_p), ('alpha_actor', ctypes.c_void_p),
+              ('alpha_critic', ctypes.c_void_p), ('gamma', ctypes.c_void_p),
+              ('reward_sum', ctypes.c_void_p), ('perf_sum', ctypes.c_void_p),
+              ('episodes', ctypes.c_void_p), ('clamped', ctypes.c_void_p), ('scratch', ctypes.c_void_p),
+              ('scratch_bytes', ctypes.c_int64), ('bad_count', ctypes.c_void_p),
+              ('bad_rows', ctypes.c_void_p), ('bad_flag', ctypes.c_void_p), ('seed', ctypes.c_uint64),
+              ('first_frame', ctypes.c_int64), ('n_learners', ctypes.c_int64),
+              ('window', ctypes.c_int32), ('path', ctypes.c_int32), ('reset_first', ctypes.c_int32)]
+
+
 LEARN_RULES = {'q': 0, 'expected_sarsa': 1}
 DYNA_MAX_PLANNING = 1024          # include/campx_hip.h: CAMPX_DYNA_MAX_PLANNING
 TRACE_KINDS = {'accumulating': 0, 'replacing': 1}
@@ -343,6 +357,13 @@ def _load():
   lib.campx_wide_actor_launch.restype = i32
   lib.campx_wide_actor_launch.argtypes = [wide_p, vp, CampxState, ctypes.POINTER(CampxActorLearner), i64,
                                           i32, vp]
+  lib.campx_wide_actor_shared_plan.restype = i32
+  lib.campx_wide_actor_shared_plan.argtypes = [i64, i32, i64, i64, i64, i32, ctypes.POINTER(i64)]
+  lib.campx_wide_actor_shared_scratch_bytes.restype = i64
+  lib.campx_wide_actor_shared_scratch_bytes.argtypes = [i64, i64]
+  lib.campx_wide_actor_shared_launch.restype = i32
+  lib.campx_wide_actor_shared_launch.argtypes = [wide_p, vp, CampxState,
+                                                 ctypes.POINTER(CampxSharedActorLearner), i64, i32, vp]
   lib.campx_render_gather_launch.restype = i32
   lib.campx_render_gather_launch.argtypes = [spec_p, vp, gather_p, i64, vp]
   lib.campx_wide_render_gather_launch.restype = i32
@@ -443,7 +464,7 @@ def _load_ops():
 
 ops = _load_ops()
 OP_NAMES = ('reset', 'step', 'rollout', 'update', 'render', 'rollout_pipelined', 'update_render', 'shape_rollout', 'wide_rollout',
-            'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'wide_learn_shared', 'wide_learn_traces', 'wide_learn_dyna', 'wide_learn_actor', 'render_gather', 'wide_render_gather', 'wide_render_states',
+            'wide_update', 'wide_policy_update', 'wide_policy_population', 'wide_learn', 'wide_learn_shared', 'wide_learn_traces', 'wide_learn_dyna', 'wide_learn_actor', 'wide_learn_actor_shared', 'render_gather', 'wide_render_gather', 'wide_render_states',
             'wide_render_windows', 'returns', 'vtrace', 'state_sums', 'table_lookup', 'wide_sweeps',
             'wide_population_sweeps', 'wide_population_solve', 'wide_visit', 'wide_visit_population', 'onehot_to_ids', 'check_actions')
 

@@ -22,6 +22,7 @@
 //   campx::wide_learn_traces        learners with eligibility traces: Q(lambda), expected SARSA(lambda)
 //   campx::wide_learn_dyna          Dyna-Q learners: n planning updates of remembered pairs a frame
 //   campx::wide_learn_actor         actor-critic learners: a softmax policy and a critic per environment
+//   campx::wide_learn_actor_shared  shared actor-critic learners: n environments feed one policy and critic
 //   campx::render_gather / campx::wide_render_gather   sampled frames of a stored trace -> a minibatch
 //   campx::wide_render_states       the observations of given states of a state-table game
 //   campx::wide_render_windows      egocentric / fixed windows of them, from a trace or state ids
@@ -820,17 +821,21 @@ void wide_policy_population(const Tensor& spec_host, const Tensor& tables, Tenso
 // (`n` = P) share - the checks of `q` float32 [n, n_states, 5], of `alpha`, `gamma`, `epsilon`
 // float32 [n], of the scalars and of the window sums [ceil(frames / window), B] - and the fields
 // that CampxLearner and CampxSharedLearner have in common, which carry the same names.
+// `names`: what the op calls q, alpha, gamma and epsilon in its messages.
+constexpr const char* kLearnerNames[4] = {"q", "alpha", "gamma", "epsilon"};
 template <typename Learner>
 Learner learner_fields(const char* what, const WideGame& g, int64_t n, Tensor& q, const Tensor& alpha,
                        const Tensor& gamma, const Tensor& epsilon, int64_t rule, int64_t seed,
                        int64_t first_frame, int64_t frames, int64_t window, Tensor& reward_sum,
                        const OptTensor& perf_sum, Tensor& episodes, const OptTensor& bad_count,
-                       const OptTensor& bad_flag, bool reset_first, int64_t path) {
-  want(q, "q", at::kFloat, g.dev, {n, g.hs->n_states, CAMPX_N_ACTIONS});
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": q must be 16-byte aligned");
-  want(alpha, "alpha", at::kFloat, g.dev, {n});
-  want(gamma, "gamma", at::kFloat, g.dev, {n});
-  want(epsilon, "epsilon", at::kFloat, g.dev, {n});
+                       const OptTensor& bad_flag, bool reset_first, int64_t path,
+                       const char* const (&names)[4] = kLearnerNames) {
+  want(q, names[0], at::kFloat, g.dev, {n, g.hs->n_states, CAMPX_N_ACTIONS});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(q.data_ptr()) & 15) == 0, what, ": ", names[0],
+              " must be 16-byte aligned");
+  want(alpha, names[1], at::kFloat, g.dev, {n});
+  want(gamma, names[2], at::kFloat, g.dev, {n});
+  want(epsilon, names[3], at::kFloat, g.dev, {n});
   TORCH_CHECK(rule == CAMPX_LEARN_Q || rule == CAMPX_LEARN_EXPECTED_SARSA, what,
               ": rule must be 0 (Q-learning) or 1 (expected SARSA)");
   TORCH_CHECK(first_frame >= 0, what, ": first_frame must be >= 0");
@@ -1029,6 +1034,69 @@ void wide_learn_actor(const Tensor& spec_host, const Tensor& tables, Tensor& sta
   const DeviceGuard guard(g.dev);
   check_ok(campx_wide_actor_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames, current_stream()),
            "campx_wide_actor_launch");
+}
+
+// Shared actor-critic learners (campx_wide_actor_shared_launch): the P = prefs.size(0) learners are
+// each fed by B / P consecutive environments; `prefs` float32 [P, n_states, 5] and `values` float32
+// [P, n_states], both 16-byte aligned and updated in place; `alpha_actor`, `alpha_critic`, `gamma`
+// float32 [P]; `clamped` int64 [P] (written); the window sums [ceil(frames / window), B] per
+// environment.  `scratch` int32 [11 * P * n_states], zero on entry and left zero: the global path's
+// accumulators (may be None when the launch takes the LDS path).
+void wide_learn_actor_shared(const Tensor& spec_host, const Tensor& tables, Tensor& state, Tensor& done,
+                             const OptTensor& ret, Tensor& prefs, Tensor& values,
+                             const Tensor& alpha_actor, const Tensor& alpha_critic, const Tensor& gamma,
+                             int64_t seed, int64_t first_frame, int64_t frames, int64_t window,
+                             Tensor& reward_sum, const OptTensor& perf_sum, Tensor& episodes,
+                             Tensor& clamped, const OptTensor& scratch, const OptTensor& bad_count,
+                             const OptTensor& bad_rows, const OptTensor& bad_flag, bool reset_first,
+                             int64_t path) {
+  const char* what = "campx::wide_learn_actor_shared";
+  const WideGame g = unpack_wide(what, spec_host, tables, state, done, ret);
+  const int64_t S = g.hs->n_states, A = CAMPX_N_ACTIONS;
+  TORCH_CHECK(prefs.dim() == 3 && prefs.size(0) >= 1, what,
+              ": prefs must be float32 [P, n_states, 5] with P >= 1");
+  const int64_t P = prefs.size(0);
+  TORCH_CHECK(g.B % P == 0, what, ": the ", g.B, " environments do not split into ", P, " equal blocks");
+  TORCH_CHECK(g.B / P <= 1024, what, ": ", g.B / P, " environments per learner are more than one "
+              "workgroup holds (1024)");
+  TORCH_CHECK(P * S * A < (1ll << 31), what, ": P * n_states * 5 must be below 2^31");
+  // the checks the shared learners' fields get: prefs is shaped and aligned as their q, the two step
+  // sizes as their alpha and epsilon
+  static constexpr const char* names[4] = {"prefs", "alpha_actor", "gamma", "alpha_critic"};
+  const CampxSharedLearner as = learner_fields<CampxSharedLearner>(
+      what, g, P, prefs, alpha_actor, gamma, alpha_critic, CAMPX_LEARN_Q, seed, first_frame, frames,
+      window, reward_sum, perf_sum, episodes, bad_count, bad_flag, reset_first, path, names);
+  want(values, "values", at::kFloat, g.dev, {P, S});
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(values.data_ptr()) & 15) == 0, what,
+              ": values must be 16-byte aligned");
+  want(clamped, "clamped", at::kLong, g.dev, {P});
+  if (scratch.has_value()) want(*scratch, "scratch", at::kInt, g.dev, {11 * P * S});
+  if (bad_rows.has_value()) want(*bad_rows, "bad_rows", at::kInt, g.dev, {1});
+  CampxSharedActorLearner l{};
+  l.prefs = as.q;
+  l.values = reinterpret_cast<float*>(values.data_ptr());
+  l.alpha_actor = as.alpha;
+  l.alpha_critic = as.epsilon;
+  l.gamma = as.gamma;
+  l.reward_sum = as.reward_sum;
+  l.perf_sum = as.perf_sum;
+  l.episodes = as.episodes;
+  l.clamped = reinterpret_cast<int64_t*>(clamped.data_ptr());
+  l.scratch = scratch.has_value() ? scratch->data_ptr() : nullptr;
+  l.scratch_bytes = scratch.has_value() ? 44 * P * S : 0;
+  l.bad_count = as.bad_count;
+  l.bad_rows = opt_ptr<int32_t>(bad_rows);
+  l.bad_flag = as.bad_flag;
+  l.seed = as.seed;
+  l.first_frame = as.first_frame;
+  l.n_learners = P;
+  l.window = as.window;
+  l.path = as.path;
+  l.reset_first = as.reset_first;
+  const DeviceGuard guard(g.dev);
+  check_ok(campx_wide_actor_shared_launch(g.hs, g.tables, g.state, &l, g.B, (int32_t)frames,
+                                          current_stream()),
+           "campx_wide_actor_shared_launch");
 }
 
 // Sampled frames of a stored trace rendered into a minibatch (campx_render_gather_launch /
@@ -1673,7 +1741,7 @@ const char* const kOps[] = {
     "reset", "step", "rollout", "update", "render", "rollout_pipelined", "update_render",
     "shape_rollout", "wide_rollout", "wide_update", "wide_policy_update", "wide_policy_population",
     "wide_learn", "wide_learn_shared", "wide_learn_traces", "wide_learn_dyna", "wide_learn_actor",
-    "render_gather",
+    "wide_learn_actor_shared", "render_gather",
     "wide_render_gather", "wide_render_states", "wide_render_windows", "returns", "vtrace", "state_sums",
     "table_lookup", "wide_sweeps", "wide_population_sweeps", "wide_population_solve", "wide_visit",
     "wide_visit_population",
@@ -1775,6 +1843,13 @@ TORCH_LIBRARY(campx, m) {
       "Tensor(g!)? perf_sum, Tensor(h!) episodes, Tensor(i!)? bad_count, Tensor(j!)? bad_rows, "
       "Tensor(k!)? bad_flag, bool reset_first, int path=0) -> ()");
   m.def(
+      "wide_learn_actor_shared(Tensor spec_host, Tensor tables, Tensor(a!) state, Tensor(b!) done, "
+      "Tensor(c!)? ret, Tensor(d!) prefs, Tensor(e!) values, Tensor alpha_actor, Tensor alpha_critic, "
+      "Tensor gamma, int seed, int first_frame, int frames, int window, Tensor(f!) reward_sum, "
+      "Tensor(g!)? perf_sum, Tensor(h!) episodes, Tensor(i!) clamped, Tensor(j!)? scratch, "
+      "Tensor(k!)? bad_count, Tensor(l!)? bad_rows, Tensor(m!)? bad_flag, bool reset_first, "
+      "int path=0) -> ()");
+  m.def(
       "render_gather(Tensor spec_host, Tensor spec_dev, Tensor trace, Tensor t_idx, Tensor e_idx, "
       "Tensor(a!) obs, Tensor(b!)? bad_count, Tensor(c!)? bad_flag, bool streaming=False) -> ()");
   m.def(
@@ -1849,6 +1924,7 @@ TORCH_LIBRARY_IMPL(campx, CUDA, m) {
   m.impl("wide_learn_traces", &wide_learn_traces);
   m.impl("wide_learn_dyna", &wide_learn_dyna);
   m.impl("wide_learn_actor", &wide_learn_actor);
+  m.impl("wide_learn_actor_shared", &wide_learn_actor_shared);
   m.impl("render_gather", &render_gather);
   m.impl("wide_render_gather", &wide_render_gather);
   m.impl("wide_render_states", &wide_render_states);

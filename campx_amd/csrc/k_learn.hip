@@ -9,7 +9,9 @@
 // wide_learn_dyna_kernel, is the first's schedule with n planning updates of remembered pairs after
 // every frame (Dyna-Q; tests/dyna_learner_reference.py).  A fifth, wide_learn_actor_kernel, is the
 // first's schedule again with a softmax policy and a critic per learner in place of the Q-table
-// (one-step actor-critic; tests/actor_critic_reference.py).
+// (one-step actor-critic; tests/actor_critic_reference.py).  A sixth,
+// wide_learn_actor_shared_kernel, is the second's schedule with the fifth's frame: n environments
+// feeding one policy and one critic (tests/shared_actor_reference.py).
 //
 // What they have in common is written ONCE and called by all - a change of the rule is made
 // there.  "The frame step": stage_table() (entries and perf bytes into LDS), Hyper (alpha, gamma,
@@ -457,14 +459,15 @@ constexpr long long kSharedLimitQ = 1ll << 52;
 // accumulators per bin - 1, the adds are not privatised.
 struct SharedPlan { int64_t path, learners, threads, lds_bytes, table_in_lds, copies; };
 
-inline int32_t plan_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
-                           int32_t path, SharedPlan* p, int64_t* plan_out) {
+// The plan rule of both shared kernels; `per_state`: path 1's LDS bytes per state and learner.
+inline int32_t plan_shared_rule(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
+                                int32_t path, int64_t per_state, SharedPlan* p, int64_t* plan_out) {
   if (P < 1 || P > B || !plan_args_ok(S, has_perf, B, P, lds_max, path) || B % P != 0 ||
       B / P > kSharedMaxThreads)
     return CAMPX_EINVAL;
   const int64_t n = B / P;
   const int64_t table = table_bytes(S, has_perf);
-  const int64_t per = S * CAMPX_N_ACTIONS * kSharedBytesPerEntry;
+  const int64_t per = S * per_state;
   int64_t most = n <= kSharedPack ? kSharedPack / n : 1;       // what a workgroup would hold
   if (most > P) most = P;
   const int64_t room = lds_max >= table ? (lds_max - table) / per : 0;
@@ -481,6 +484,12 @@ inline int32_t plan_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, in
   p->copies = 1;
   if (plan_out) memcpy(plan_out, p, sizeof(*p));
   return CAMPX_OK;
+}
+
+inline int32_t plan_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
+                           int32_t path, SharedPlan* p, int64_t* plan_out) {
+  return plan_shared_rule(S, has_perf, B, P, lds_max, path, CAMPX_N_ACTIONS * kSharedBytesPerEntry, p,
+                          plan_out);
 }
 
 // kQLds: path 1.  kTableLds, kPerf, kSarsa: as in wide_learn_kernel.  `n`: environments per
@@ -1173,6 +1182,222 @@ static const ActorKernel kActorKernels[3][2] = {
     {wide_learn_actor_kernel<0, 1, 0>, wide_learn_actor_kernel<0, 1, 1>},
     {wide_learn_actor_kernel<1, 1, 0>, wide_learn_actor_kernel<1, 1, 1>}};
 
+// ---------------------------------------------------------------------------------------------
+// Shared actor-critic: P softmax policies and critics, each fed by the n = B / P consecutive
+// environments of its block - synchronous advantage actor-critic (include/campx_hip.h, "Shared
+// actor-critic learners", has the frame; tests/shared_actor_reference.py restates it in numpy).
+// wide_learn_shared_kernel's schedule and arithmetic - G whole learners per workgroup, two barriers
+// a frame, the errors quantised to 64-bit fixed point and added as INTEGERS, the owner by the first
+// add - with wide_learn_actor_kernel's frame: softmax_weights(), policy_thresholds(),
+// rollout_policy()'s sampler and stream, the bad-row rule.  A frame is
+//   (A) row, weights, action, entry, values[s] and values[n] as the frame found them, delta;
+//       sum[s][a] += z and visitors[s] += 1 (workgroup-scope atomics) - the lane whose visitor-add
+//       returned 0 owns STATE s;
+//   barrier;
+//   (B) the owner exchanges the state's five sums and its visitor count for 0 and writes values[s]
+//       and the five preferences of row s, from the row, the weights and the value it still holds
+//       in registers (it is in s itself);
+//   barrier.
+// EVERY lane of the workgroup reaches both barriers of every frame: the loop bounds depend on the
+// kernel's arguments alone, and what an absent lane, a lane of a bad learner or a lane on a bad row
+// skips lies BETWEEN the barriers, never around one.
+//
+// Path 1: the entries, the perf bytes and per learner the sums, prefs, values and visitor counts in
+// LDS - 40 + 20 + 4 + 4 = 68 bytes a state; prefs and values are copied straight in and out.
+// Path 2: prefs, values and the accumulators - `scratch`, zero on entry and left zero by the
+// exchanges of (B) - in global memory; the entries in LDS when they alone fit.
+
+constexpr int64_t kSharedActorBytesPerState = 68;    // path 1, per (learner, state)
+constexpr int64_t kSharedActorScratchPerState = 44;  // path 2, per (learner, state): sums 40, visitors 4
+
+// campx_wide_actor_shared_plan()'s six words: SharedPlan's, by plan_shared()'s rule.
+inline int32_t plan_actor_shared(int64_t S, int32_t has_perf, int64_t B, int64_t P, int64_t lds_max,
+                                 int32_t path, SharedPlan* p, int64_t* plan_out) {
+  return plan_shared_rule(S, has_perf, B, P, lds_max, path, kSharedActorBytesPerState, p, plan_out);
+}
+
+// double(Z) / double(N) * 2^-32 as a float: the mean of N quantised errors that sum to Z.
+__device__ __forceinline__ float shared_mean(long long Z, double visitors) {
+  return (float)(((double)Z / visitors) * (1.0 / kSharedScale));
+}
+
+// kQLds: path 1.  kTableLds, kPerf: as in wide_learn_kernel.  `n`: environments per learner; `G`:
+// learners per workgroup, blockDim.x == G * n.  `acc_sum` [P][S][5] / `acc_visits` [P][S]: path 2's
+// accumulators.  `bad_rows`, `bad_count`: as in wide_learn_actor_kernel, the latter per LEARNER.
+template <bool kQLds, bool kTableLds, bool kPerf>
+__global__ __launch_bounds__(kSharedMaxThreads) void wide_learn_actor_shared_kernel(
+    LearnParams pp, const uint2* __restrict__ g_entries, const int8_t* __restrict__ g_perf,
+    float* prefs, float* values, const float* __restrict__ alpha_actors,
+    const float* __restrict__ alpha_critics, const float* __restrict__ gammas,
+    int32_t* __restrict__ state, CampxState st, float* __restrict__ reward_sum,
+    int32_t* __restrict__ perf_sum, int32_t* __restrict__ episodes, long long* __restrict__ clamped,
+    long long* acc_sum, uint32_t* acc_visits, int32_t* bad_count, int32_t* bad_rows, int32_t* bad_flag,
+    int64_t B, int64_t P, int32_t n, int32_t G, int32_t T, int32_t reset_first) {
+  static_assert(kTableLds || !kQLds, "path 1 stages the table");
+  extern __shared__ __attribute__((aligned(16))) uint2 lds_tables[];
+  __shared__ float discounts[16];
+  __shared__ unsigned long long l_clamped[kSharedPack];      // per learner of the workgroup
+  const int S = pp.n_states, n_entries = S * CAMPX_N_ACTIONS;
+  const int tid = threadIdx.x, threads = blockDim.x;
+  const int64_t first_learner = (int64_t)blockIdx.x * G;
+  const int n_here = (int)(P - first_learner < G ? P - first_learner : G);   // learners present
+  const int64_t env = first_learner * n + tid;
+  const int who = tid / n;                                   // learner of the workgroup
+  const bool active = who < n_here;                          // (an absent lane: last workgroup only)
+  const int64_t m = first_learner + who;
+  float* h_block = prefs + first_learner * n_entries;        // floats: P * S * 5 < 2^31
+  float* v_block = values + first_learner * S;
+  float *h_tab = h_block, *v_tab = v_block;                  // [learner][s][a], [learner][s], wherever they are
+  long long* sums = kQLds ? nullptr : acc_sum + first_learner * n_entries;
+  uint32_t* visits = kQLds ? nullptr : acc_visits + first_learner * S;
+  const StagedTable tab =
+      stage_table<kTableLds, kPerf>(lds_tables, g_entries, g_perf, n_entries, tid, threads);
+  if (kQLds) {
+    // [sums G x S x 5 x 8][prefs G x S x 5 x 4][values G x S x 4][visitors G x S x 4], 16-byte aligned
+    sums = reinterpret_cast<long long*>(tab.free);
+    h_tab = reinterpret_cast<float*>(sums + (int64_t)G * n_entries);
+    v_tab = h_tab + (int64_t)G * n_entries;
+    visits = reinterpret_cast<uint32_t*>(v_tab + (int64_t)G * S);
+    for (int i = tid; i < n_here * n_entries; i += threads) {
+      h_tab[i] = h_block[i];
+      sums[i] = 0;
+    }
+    for (int i = tid; i < n_here * S; i += threads) {
+      v_tab[i] = v_block[i];
+      visits[i] = 0u;
+    }
+  }
+  // (strided: a workgroup of G * n threads may have fewer than 16, down to one)
+  for (int i = tid; i < 16; i += threads) discounts[i] = pp.discounts[i];
+  for (int i = tid; i < kSharedPack; i += threads) l_clamped[i] = 0ull;
+  __syncthreads();
+
+  // What stays in registers for the run.  An absent lane keeps these values - no learner, a new
+  // episode, empty sums - and does nothing between the barriers below.
+  float alpha_actor = 0.0f, alpha_critic = 0.0f, gamma = 0.0f;
+  bool good = false;
+  Carried c;
+  WindowSums<kPerf> win{reward_sum, perf_sum, episodes, env};
+  unsigned long long n_clamped = 0ull;
+  int n_bad_rows = 0;
+  const int own_h = who * n_entries, own_v = who * S;        // the learner's rows start here
+  if (active) {
+    alpha_actor = alpha_actors[m], alpha_critic = alpha_critics[m], gamma = gammas[m];
+    // (x - x is 0 exactly for a finite x, NaN for an infinity or a NaN)
+    good = (alpha_actor - alpha_actor) == 0.0f && (alpha_critic - alpha_critic) == 0.0f &&
+           (gamma - gamma) == 0.0f;
+    c.load(state, st, env, S, reset_first);
+  }
+  const Chunks chunks(pp.first_frame);
+  for (int t0 = -chunks.lead; t0 < T; t0 += kLearnChunk) {
+    // rollout_policy()'s block of the chunk's four absolute frames: fourth counter word 0
+    uint32_t x[kLearnChunk] = {0u, 0u, 0u, 0u};
+    if (active) {
+      const uint64_t g = (chunks.pair0 >> 1) + (uint64_t)((t0 + chunks.lead) >> 2);
+      philox4x32_10((uint32_t)env, (uint32_t)g, (uint32_t)(g >> 32), 0u, pp.key0, pp.key1, x);
+    }
+#pragma unroll
+    for (int j = 0; j < kLearnChunk; ++j) {
+      if (t0 + j < 0 || t0 + j >= T) continue;               // (uniform: kernel arguments alone)
+      bool owner = false;
+      int row_at = 0, cell = 0;                              // own_h + s * 5, own_v + s
+      float h[5], w[5], total = 0.0f, v_s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) h[k] = w[k] = 0.0f;
+      if (active) {                                          // ---- (A)
+        const uint32_t base = c.from * CAMPX_N_ACTIONS;
+        row_at = own_h + (int)base;
+        cell = own_v + (int)c.from;
+        float thr[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) h[k] = h_tab[row_at + k];
+        const bool row_good = softmax_weights(h, w) && good;
+        if (!row_good) {
+#pragma unroll
+          for (int k = 0; k < 5; ++k) w[k] = 0.0f;           // (a bad learner: action 4 throughout)
+        }
+        policy_thresholds(w, thr);
+        total = thr[4];
+        const float u = (float)(x[j] >> 8) * 5.9604644775390625e-8f;     // 2^-24: exact
+        const float r = u * thr[4];
+        const uint32_t a = (uint32_t)(r >= thr[0]) + (uint32_t)(r >= thr[1]) +
+                           (uint32_t)(r >= thr[2]) + (uint32_t)(r >= thr[3]);
+        n_bad_rows += good && !row_good;
+        const uint32_t idx = base + a;
+        const Entry e = decode_entry(tab.entries[idx], S, discounts);
+        if (row_good) {
+          // both values as the frame found them, for every lane of the learner
+          v_s = v_tab[cell];
+          const float v_n = v_tab[own_v + (int)e.next];
+          const float discounted = (gamma * e.D) * v_n;
+          const float target = e.done ? e.r : e.r + discounted;
+          const float delta = target - v_s;
+          const double d = (double)delta * kSharedScale;
+          long long z;
+          if (!(fabs(d) <= kSharedLimit)) {                  // NaN, +-Inf, past the limit
+            ++n_clamped;
+            z = d != d ? 0ll : (d > 0.0 ? kSharedLimitQ : -kSharedLimitQ);
+          } else {
+            z = __double2ll_rn(d);
+          }
+          owner = __hip_atomic_fetch_add(&visits[cell], 1u, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_WORKGROUP) == 0u;
+          __hip_atomic_fetch_add(&sums[own_h + (int)idx], z, __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        c.advance(e);
+        win.add(pp, e.r, kPerf ? tab.perf_tab[idx] : 0, e.done, B);
+      }
+      __syncthreads();
+      if (owner) {                                           // ---- (B)
+        long long Z[5], Zall = 0ll;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+          Z[k] = __hip_atomic_exchange(&sums[row_at + k], 0ll, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+          Zall += Z[k];                                      // (1 024 values of at most 2^52: no overflow)
+        }
+        const double visitors = (double)__hip_atomic_exchange(&visits[cell], 0u, __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_WORKGROUP);
+        const float mean_all = shared_mean(Zall, visitors);
+        v_tab[cell] = v_s + alpha_critic * mean_all;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+          const float pi = w[k] / total;
+          const float grad = shared_mean(Z[k], visitors) - pi * mean_all;
+          h_tab[row_at + k] = h[k] + alpha_actor * grad;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (active) {
+    win.flush_short();
+    c.store(state, st, env);
+    if (n_clamped)
+      __hip_atomic_fetch_add(&l_clamped[who], n_clamped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (tid == who * n) report_bad(bad_count, bad_flag, good ? 0 : 1);       // bad LEARNERS, once
+    // bad ROWS, per environment-frame (added here, as in wide_learn_actor_kernel)
+    if (n_bad_rows) {
+      if (bad_rows) atomicAdd(bad_rows, n_bad_rows);
+      report_bad(nullptr, bad_flag, 1);
+    }
+  }
+  __syncthreads();
+  if (active && tid == who * n) clamped[m] = (long long)l_clamped[who];
+  if (kQLds) {
+    for (int i = tid; i < n_here * n_entries; i += threads) h_block[i] = h_tab[i];
+    for (int i = tid; i < n_here * S; i += threads) v_block[i] = v_tab[i];
+  }
+}
+
+// At [where the tables are][kPerf], the first index as in CAMPX_LEARN_INSTANCES.
+using SharedActorKernel = decltype(&wide_learn_actor_shared_kernel<false, false, false>);
+static const SharedActorKernel kSharedActorKernels[3][2] = {
+    {wide_learn_actor_shared_kernel<0, 0, 0>, wide_learn_actor_shared_kernel<0, 0, 1>},
+    {wide_learn_actor_shared_kernel<0, 1, 0>, wide_learn_actor_shared_kernel<0, 1, 1>},
+    {wide_learn_actor_shared_kernel<1, 1, 0>, wide_learn_actor_shared_kernel<1, 1, 1>}};
+
 }  // namespace campx_impl
 
 using namespace campx_impl;
@@ -1347,6 +1572,65 @@ int32_t campx_wide_actor_launch(const CampxWideSpec* s, const void* tables_dev, 
                      t.entries, t.perf, l->prefs, l->values, l->alpha_actor, l->alpha_critic, l->gamma,
                      reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
                      l->bad_count, l->bad_rows, l->bad_flag, B, T, l->reset_first);
+  return launch_status();
+}
+
+int32_t campx_wide_actor_shared_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t P,
+                                     int64_t wide_lds_max, int32_t path, int64_t* plan_out) {
+  if (!plan_out) return CAMPX_EINVAL;
+  SharedPlan plan;
+  return plan_actor_shared(n_states, has_perf, B, P, wide_lds_max, path, &plan, plan_out);
+}
+
+int64_t campx_wide_actor_shared_scratch_bytes(int64_t n_states, int64_t P) {
+  if (n_states < 1 || n_states > CAMPX_WIDE_MAX_STATES || P < 1 || P > 0xffffffffll ||
+      P * n_states * CAMPX_N_ACTIONS >= (1ll << 31))
+    return 0;
+  return P * n_states * kSharedActorScratchPerState;
+}
+
+int32_t campx_wide_actor_shared_launch(const CampxWideSpec* s, const void* tables_dev, CampxState st,
+                                       const CampxSharedActorLearner* l, int64_t B, int32_t T,
+                                       void* stream) {
+  // screened as campx_wide_actor_launch() screens: prefs stands where q does, the two step sizes
+  // where alpha and epsilon do; there is no rule
+  CampxLearner as{};
+  if (l) {
+    as.q = l->prefs, as.alpha = l->alpha_actor, as.gamma = l->gamma, as.epsilon = l->alpha_critic;
+    as.reward_sum = l->reward_sum, as.perf_sum = l->perf_sum, as.episodes = l->episodes;
+    as.bad_count = l->bad_count, as.bad_flag = l->bad_flag, as.seed = l->seed;
+    as.first_frame = l->first_frame, as.window = l->window, as.rule = CAMPX_LEARN_Q;
+    as.path = l->path, as.reset_first = l->reset_first;
+  }
+  const bool own_ok = l && l->values && aligned_to(l->values, 16) && aligned_to(l->bad_rows, 4) &&
+                      l->clamped && aligned_to(l->clamped, 8) && aligned_to(l->scratch, 8) &&
+                      l->n_learners >= 1 && l->scratch_bytes >= 0;
+  const int32_t screened = screen_learner(s, tables_dev, st, &as, B, T, own_ok);
+  if (screened != CAMPX_OK) return screened;
+  const int64_t P = l->n_learners;
+  SharedPlan plan;     // (refuses a P that does not divide B, n > 1024, P * n_states * 5 >= 2^31)
+  const int32_t planned = plan_actor_shared(s->n_states, l->perf_sum ? 1 : 0, B, P,
+                                            knob(K_WIDE_LDS_MAX), l->path, &plan, nullptr);
+  if (planned != CAMPX_OK) return planned;
+  const int64_t n_bins = P * s->n_states * CAMPX_N_ACTIONS;
+  if (plan.path == 2 &&
+      (!l->scratch || l->scratch_bytes < P * s->n_states * kSharedActorScratchPerState))
+    return CAMPX_EINVAL;
+  const WideTables t = wide_tables(*s, tables_dev);
+  const size_t lds = (size_t)plan.lds_bytes;
+  const SharedActorKernel kernel =
+      kSharedActorKernels[plan.path == 1 ? 2 : (plan.table_in_lds ? 1 : 0)][l->perf_sum != nullptr];
+  CAMPX_ALLOW_LDS(kernel, lds);
+  // path 2's accumulators: [sums int64 x P x S x 5][visitors uint32 x P x S]
+  long long* acc_sum = plan.path == 2 ? static_cast<long long*>(l->scratch) : nullptr;
+  uint32_t* acc_visits = plan.path == 2 ? reinterpret_cast<uint32_t*>(acc_sum + n_bins) : nullptr;
+  const int64_t G = plan.learners;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((P + G - 1) / G)), dim3((unsigned)plan.threads), lds,
+                     static_cast<hipStream_t>(stream), learn_params(*s, as), t.entries, t.perf,
+                     l->prefs, l->values, l->alpha_actor, l->alpha_critic, l->gamma,
+                     reinterpret_cast<int32_t*>(st.pos), st, l->reward_sum, l->perf_sum, l->episodes,
+                     reinterpret_cast<long long*>(l->clamped), acc_sum, acc_visits, l->bad_count,
+                     l->bad_rows, l->bad_flag, B, P, (int32_t)(B / P), (int32_t)G, T, l->reset_first);
   return launch_status();
 }
 

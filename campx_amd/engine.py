@@ -549,6 +549,25 @@ class Engine(object):
     """State-table tier only: the dict of `learn_shared(out=...)` for P learners, allocated once."""
     return self._batched('shared_learner_buffers').shared_learner_buffers(P, T, window=window, path=path)
 
+  def learn_actor_critic_shared(self, T, prefs, values, *args, **kwargs):
+    """State-table tier only: T frames of SYNCHRONOUS ADVANTAGE ACTOR-CRITIC for P shared learners
+    in one launch, learner m owning the preferences `prefs[m]` of one softmax policy (float32
+    `[P, n_states, 5]`) and one critic `values[m]` (`[P, n_states]`), both updated in place, and fed
+    by the n = B / P environments `[m * n, (m + 1) * n)`, 1 <= n <= 1024; `alpha_actor`,
+    `alpha_critic` and `gamma` are numbers or float32 `[P]` tensors.  Reproducible bit for bit: per
+    frame the errors of a learner's actors are summed in fixed point per (state, action) and each
+    visited state moves once, by the step size times the mean one-step actor-critic update of its
+    visitors.  Returns 'prefs', 'values', the per-environment window sums and 'clamped' int64 `[P]`.
+    See `wide.WideGame.learn_actor_critic_shared`; the other batched tiers raise NotImplementedError
+    (`use_state_table()` before `its_showtime()` puts a game on this one)."""
+    return self._batched('learn_actor_critic_shared').learn_actor_critic_shared(
+        T, prefs, values, *args, **kwargs)
+
+  def shared_actor_buffers(self, P, T, window=None, path=0):
+    """State-table tier only: the dict of `learn_actor_critic_shared(out=...)` for P learners,
+    allocated once."""
+    return self._batched('shared_actor_buffers').shared_actor_buffers(P, T, window=window, path=path)
+
   def render_states(self, state_ids=None, obs_dtype=torch.int8, out=None):
     """State-table tier only: the observations `[N, L, H, W]` of the states `state_ids` of the
     game's table (None: all of them), bit for bit what `play()` / `rollout()` show for an

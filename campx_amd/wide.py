@@ -30,7 +30,7 @@ from . import tabulate
 # NotImplementedError that names it (refuse_state_table_only()), and Engine forwards each.
 STATE_TABLE_ONLY = (
     'rollout_policy_buffers', 'rollout_policy', 'rollout_population_buffers', 'rollout_population',
-    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'dyna_buffers', 'learn_dyna', 'learn_actor_critic', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
+    'learner_buffers', 'learn_tabular', 'shared_learner_buffers', 'learn_shared', 'learn_traces', 'dyna_buffers', 'learn_dyna', 'learn_actor_critic', 'shared_actor_buffers', 'learn_actor_critic_shared', 'table_arrays', 'sweep_buffers', 'evaluate_policy',
     'value_iteration', 'population_sweep_buffers', 'evaluate_population', 'value_iteration_population',
     'visitation_buffers',
     'state_visitation', 'visit_population_buffers', 'visit_population', 'render_states', 'render_frame_windows', 'render_trace_windows', 'render_state_windows')
@@ -149,6 +149,8 @@ class WideGame(fused.FusedGame):
     self._bad_dyna_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_actor_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._bad_actor_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_shared_actor_learners = torch.zeros((1,), dtype=torch.int32, device=dev)
+    self._bad_shared_actor_rows = torch.zeros((1,), dtype=torch.int32, device=dev)
     self._hyper_floats = {}
     self._hyper_ints = {}             # learn_dyna()'s `planning` given as a Python int, by learners
     self._layer_of_cell = None        # the window kernel's scenery table
@@ -218,7 +220,14 @@ class WideGame(fused.FusedGame):
          'left untouched'),
         (self._bad_actor_rows, acts,
          '{} environment-frames of learn_actor_critic() met rows of preferences that are not good (a '
-         'NaN or a +inf, or five -inf); they took action {} and changed neither table')]
+         'NaN or a +inf, or five -inf); they took action {} and changed neither table'),
+        (self._bad_shared_actor_learners, acts,
+         '{} learners of learn_actor_critic_shared() have bad hyper-parameters (alpha_actor, '
+         'alpha_critic or gamma not finite); their environments took action {} at every frame and '
+         'their preferences and values were left untouched'),
+        (self._bad_shared_actor_rows, acts,
+         '{} environment-frames of learn_actor_critic_shared() met rows of preferences that are not '
+         'good (a NaN or a +inf, or five -inf); they took action {} and contributed nothing')]
 
   def _trace_rows(self, T):
     """int16 [K, B] (one frame) or [K, T, B] trace buffer, rows padded like the other streams."""
@@ -952,8 +961,8 @@ class WideGame(fused.FusedGame):
     leaves them.  Argument errors raise ValueError before anything is launched.
 
     NOT offered: REINFORCE with episode returns (use `rollout_policy()` and
-    `returns.discounted_returns()`), lambda-traces for the actor, an entropy bonus or a temperature,
-    and a shared form in which several actors feed one learner.
+    `returns.discounted_returns()`), lambda-traces for the actor, an entropy bonus or a temperature.
+    The shared form in which several actors feed one learner is `learn_actor_critic_shared()`.
     """
     S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
     if B * S * A >= 1 << 31:
@@ -990,28 +999,31 @@ class WideGame(fused.FusedGame):
 
   # ------------------------------------------------------------ shared online learners
 
-  def _shared_plan(self, P, path):
-    """The six words of campx_wide_shared_plan() for P learners of this game - path, learners per
-    workgroup, threads, LDS bytes, entries in LDS, accumulator copies - after the checks of P that
-    have a message of their own."""
+  def _shared_plan(self, P, path, call='learn_shared()', plan_fn=None,
+                   holds='the Q-table and the accumulators'):
+    """The six words of campx_wide_shared_plan() - or of `plan_fn`, the same rule for another
+    kernel - for P learners of this game: path, learners per workgroup, threads, LDS bytes, entries
+    in LDS, accumulator copies, after the checks of P that have a message of their own.  `call`
+    names the method in them; `holds`: what path 1 keeps per learner beside the table."""
     S, A, B = self.n_states, gamespec.N_ACTIONS, self.batch
     if isinstance(P, bool) or not isinstance(P, int) or P < 1 or P > B or B % P != 0:
-      raise ValueError('learn_shared(): the {} environments do not split into P = {!r} equal blocks '
-                       '(P must divide the batch)'.format(B, P))
+      raise ValueError('{}: the {} environments do not split into P = {!r} equal blocks '
+                       '(P must divide the batch)'.format(call, B, P))
     if B // P > 1024:
-      raise ValueError('learn_shared(): {} environments per learner are more than one workgroup '
-                       'holds: n = B / P must be at most 1024'.format(B // P))
+      raise ValueError('{}: {} environments per learner are more than one workgroup '
+                       'holds: n = B / P must be at most 1024'.format(call, B // P))
     if P * S * A >= 1 << 31:
-      raise ValueError('learn_shared(): P * n_states * 5 = {} x {} x 5 must be below 2^31'.format(P, S))
+      raise ValueError('{}: P * n_states * 5 = {} x {} x 5 must be below 2^31'.format(call, P, S))
     if path not in (0, 1, 2):
       raise ValueError('path must be 0 (chosen by arithmetic), 1 (LDS) or 2 (global), got {!r}'.format(path))
     plan = (ctypes.c_int64 * 6)()
     lds_max = _hip.config_get('wide_lds_max')
-    code = _hip.lib.campx_wide_shared_plan(S, 1 if self.has_perf else 0, B, P, lds_max, path, plan)
+    plan_fn = plan_fn or _hip.lib.campx_wide_shared_plan
+    code = plan_fn(S, 1 if self.has_perf else 0, B, P, lds_max, path, plan)
     if code != 0 and path == 1:
-      raise ValueError('path=1: a table of {} states with the Q-table and the accumulators of one '
+      raise ValueError('path=1: a table of {} states with {} of one '
                        'learner does not fit the LDS of one workgroup (library setting '
-                       'wide_lds_max); use path=0 or path=2'.format(S))
+                       'wide_lds_max); use path=0 or path=2'.format(S, holds))
     if code != 0:
       raise ValueError('path={}: the library refused the plan (code {}; library setting '
                        'wide_lds_max = {})'.format(path, code, lds_max))
@@ -1101,6 +1113,124 @@ class WideGame(fused.FusedGame):
         self._bad_shared_learners if validate else None, self._bad_flag if validate else None,
         bool(reset_first), path)
     return self._learner_epilogue(first, T, reset_first, q, out, ('clamped',))
+
+  # ------------------------------------------------------------ shared actor-critic learners
+
+  def _shared_actor_plan(self, P, path):
+    """The six words of campx_wide_actor_shared_plan() for P learners of this game:
+    `_shared_plan()`'s checks and messages, under this call's name."""
+    return self._shared_plan(P, path, 'learn_actor_critic_shared()',
+                             _hip.lib.campx_wide_actor_shared_plan,
+                             'the preferences, values and accumulators')
+
+  def shared_actor_buffers(self, P, T, window=None, path=0):
+    """Allocate the dict of `learn_actor_critic_shared(out=...)` once, for P learners:
+    `learner_buffers(T, window)`'s tensors, 'clamped' int64 [P] and - when a call with this `path`
+    goes through global memory (path 2) - 'scratch', its accumulators: int32 [11 * P * n_states],
+    zero, and left zero by every call."""
+    plan = self._shared_actor_plan(P, path)
+    out = self.learner_buffers(T, window)
+    out['clamped'] = torch.zeros((P,), dtype=torch.int64, device=self.device)
+    if plan[0] == 2:
+      out['scratch'] = torch.zeros((11 * P * self.n_states,), dtype=torch.int32, device=self.device)
+    return out
+
+  def learn_actor_critic_shared(self, T, prefs, values, alpha_actor=0.1, alpha_critic=0.1, gamma=0.99,
+                                seed=0, first_frame=None, reset_first=False, window=None, out=None,
+                                path=0):
+    """T frames of SYNCHRONOUS ADVANTAGE ACTOR-CRITIC (A2C) for P shared learners in ONE launch:
+    learner m owns one softmax policy - the preferences `prefs[m]` - and one critic `values[m]`, and
+    is fed by the n = B / P environments `[m * n, (m + 1) * n)`, `learn_shared()`'s and
+    `rollout_population()`'s split of the batch (csrc/k_learn.hip,
+    `campx::wide_learn_actor_shared`).  What otherwise takes `rollout_population()`, a returns pass,
+    `sum_by_state()` and a torch step per update.
+
+    Within a frame every actor of a learner samples from the same policy and bootstraps from the
+    same critic - both as the frame found them - with `learn_actor_critic()`'s weights, sampler and
+    stream, and computes `delta = (r if done else r + (gamma * D) * values[m, n]) - values[m, s]`.
+    The errors are quantised to 64-bit fixed point (32 fractional bits) and summed per (state,
+    action) as integers.  Each visited state then moves once: with `mean_k` the sum of action k's
+    errors over the state's N visitors divided by N, and `mean_all` the same of all five,
+    `values[m, s] += alpha_critic * mean_all` and
+    `prefs[m, s, k] += alpha_actor * (mean_k - (w[k] / sum(w)) * mean_all)` - the mean over the
+    visitors of the one-step actor-critic update.  The step size does not depend on n, and the run
+    repeats bit for bit whatever the order in which environments arrive, the path or P
+    (include/campx_hip.h has the rule in full; tests/shared_actor_reference.py restates it in numpy).
+    n = 1 is NOT `learn_actor_critic()` bit for bit: the quantiser rounds the error to 2^-32 and the
+    products are taken in another order.
+
+    Args:
+      prefs: contiguous float32 `[P, n_states, 5]` on the game's device (16-byte aligned,
+          `P * n_states * 5 < 2^31`), updated IN PLACE; P is read from it.  P must divide the batch
+          and 1 <= n = B / P <= 1024, the largest workgroup.  Rows that are not good - a NaN or a
+          +inf, or five -inf - are treated as `learn_actor_critic()` treats them: an
+          environment-frame that meets one takes action 4, contributes nothing and is counted; the
+          count raises ValueError lazily.  `returns.softmax_weights(prefs)` is what
+          `rollout_population()`, `evaluate_population()` and `visit_population()` take.
+      values: contiguous float32 `[P, n_states]` (16-byte aligned), updated IN PLACE.
+      alpha_actor, alpha_critic, gamma: each a Python number or a float32 `[P]` tensor - a tensor
+          is a sweep.  A learner with one that is not finite is BAD: all its environments take
+          action 4 at every frame, nothing of it changes, and it raises ValueError - counted once
+          per learner and call - lazily.  Python numbers are checked at once.  With both step sizes
+          0 the call walks exactly as `rollout_population(softmax_weights(prefs), T, seed,
+          first_frame)` does.
+      seed, first_frame, reset_first, window: exactly as in `learn_actor_critic()`; the Philox
+          counter is (absolute environment, frame >> 2, 0), `rollout_policy()`'s stream.
+      out: a dict from `shared_actor_buffers(P, T, window, path)`, overwritten.  With `out` (and
+          tensors, or the same numbers as before, for the hyper-parameters) the call allocates
+          nothing and is capturable in a HIP graph.
+      path: 0 - a workgroup keeps the table and its learners' preferences, values and accumulators
+          in LDS (68 bytes a state and learner) whenever enough of them fit (library setting
+          wide_lds_max), else they are in global memory; 1 / 2 force either (1 raises ValueError
+          when not even one learner fits).  Both give the same bits.
+
+    Returns a dict: 'prefs', 'values'; 'reward_sum' float32, 'episodes' int32 and - games with
+    hidden performance - 'perf_sum' int32, `[W, B]` each and PER ENVIRONMENT (`.view(W, P, n)` gives
+    a learner's curves); 'clamped' int64 `[P]`, written by the call: the errors of this call that
+    were NaN (counted as 0) or beyond +-2^20 (counted as that).  `state`, `done`, `ret` and `frame`
+    carry over exactly as `learn_tabular()` leaves them.  Argument errors raise ValueError before
+    anything is launched.
+
+    NOT offered: an entropy bonus or a temperature, lambda-traces for the actor, REINFORCE with
+    episode returns, n-step targets, and privatised accumulators.
+    """
+    S, A, B, dev = self.n_states, gamespec.N_ACTIONS, self.batch, self.device
+    if (not torch.is_tensor(prefs) or prefs.dtype != torch.float32 or prefs.dim() != 3
+        or prefs.shape[0] < 1 or tuple(prefs.shape[1:]) != (S, A) or prefs.device != dev
+        or not prefs.is_contiguous() or prefs.data_ptr() % 16):
+      got = ('{} {} on {}'.format(prefs.dtype, list(prefs.shape), prefs.device) if torch.is_tensor(prefs)
+             else type(prefs).__name__)
+      raise ValueError('prefs must be a contiguous, 16-byte aligned float32 [P, {}, {}] tensor '
+                       '(learners x n_states x actions) on {}; got {}'.format(S, A, dev, got))
+    P = int(prefs.shape[0])
+    if not self._tensor_ok(values, torch.float32, (P, S)) or values.data_ptr() % 16:
+      got = ('{} {} on {}'.format(values.dtype, list(values.shape), values.device)
+             if torch.is_tensor(values) else type(values).__name__)
+      raise ValueError('values must be a contiguous, 16-byte aligned float32 [{}, {}] tensor on {}; '
+                       'got {}'.format(P, S, dev, got))
+    plan = self._shared_actor_plan(P, path)
+    own = [('clamped', torch.int64, (P,))]
+    if plan[0] == 2:
+      own.append(('scratch', torch.int32, (11 * P * S,)))
+    T, window, first, seed, out, hyper = self._learner_prologue(
+        'learn_actor_critic_shared', P, T, window, 'q', first_frame, seed, alpha_actor, gamma,
+        alpha_critic, out, own,
+        lambda T, window: 'shared_actor_buffers({}, {}, window={}, path={})'.format(P, T, window, path),
+        lambda T, window: self.shared_actor_buffers(P, T, window, path),
+        names=('alpha_actor', 'gamma', 'alpha_critic'))
+    validate = self.validate_actions
+    _hip.ops.wide_learn_actor_shared(
+        self._spec_host, self._tables, self.state, self.done, self.ret, prefs.detach(),
+        values.detach(), hyper[0], hyper[2], hyper[1], seed, first, T, window, out['reward_sum'],
+        out.get('perf_sum') if self.has_perf else None, out['episodes'], out['clamped'],
+        out.get('scratch') if plan[0] == 2 else None,
+        self._bad_shared_actor_learners if validate else None,
+        self._bad_shared_actor_rows if validate else None, self._bad_flag if validate else None,
+        bool(reset_first), path)
+    res = self._learner_epilogue(first, T, reset_first, prefs, out, ('clamped',))
+    del res['q']
+    res['prefs'], res['values'] = prefs, values
+    return res
 
   # ------------------------------------------------------------ planning on the table
 

@@ -1225,7 +1225,7 @@ int32_t campx_wide_dyna_launch(const CampxWideSpec* spec_host, const void* table
  * rollouts on softmax_weights(prefs); launches of T1 and T2 frames equal one of T1 + T2; neither
  * path changes a bit.
  * NOT offered: REINFORCE with episode returns, lambda-traces for the actor, an entropy bonus or a
- * temperature, and a shared form in which several actors feed one learner.
+ * temperature.  The shared form in which several actors feed one learner is the next section.
  *
  * A lane per learner, 256 to a workgroup, no barrier inside the frame loop.
  * Path 1: the workgroup stages in LDS the entries and perf bytes and its 256 learners' prefs and
@@ -1268,6 +1268,103 @@ int32_t campx_wide_actor_plan(int64_t n_states, int32_t has_perf, int64_t B, int
 int32_t campx_wide_actor_launch(const CampxWideSpec* spec_host, const void* tables_dev,
                                 CampxState state, const CampxActorLearner* learner, int64_t B,
                                 int32_t T, void* stream);
+/*
+ * ---- Shared actor-critic learners: n environments feed one policy, a whole run per launch ------
+ * Synchronous advantage actor-critic (A2C) on the table: P learners, learner m fed by the
+ * n = B / P consecutive environments [m * n, (m + 1) * n) - the split of
+ * campx_wide_shared_launch() - and owning two DEVICE tables updated in place:
+ *   prefs   float32 [P][n_states][5], 16-byte aligned, P * n_states * 5 < 2^31
+ *   values  float32 [P][n_states],    16-byte aligned
+ * alpha_actor / alpha_critic / gamma are DEVICE float32 [P].  P divides B and 1 <= n <= 1024, one
+ * workgroup, as for the shared Q-learners.  The learner is SYNCHRONOUS and repeats bit for bit
+ * whatever the order in which its environments arrive, the path, G or P: only integers are summed.
+ *
+ * Frame f = first_frame + t of learner m, every float32 operation one operation rounded on its own,
+ * no contraction.  Every actor reads prefs[m] and values[m] as the frame found them.
+ *  (A) Per actor (environment e of the learner), in state s (state 0 after a `done`):
+ *   1. w = rule 1 above of prefs[m][s]; thresholds c0 .. c4 as in the actor-critic learners.
+ *   2. The action by their sampler and their stream: counter (ABSOLUTE environment e,
+ *      g & 0xffffffff, g >> 32, 0) with g = f >> 2, output word f & 3.
+ *   3. A row that is not good: the actor takes action 4, contributes nothing, and is counted into
+ *      *bad_rows, once per environment-frame of a good learner.  A learner whose alpha_actor,
+ *      alpha_critic or gamma is not finite is BAD: all its environments take action 4 at every
+ *      frame, nothing of it changes, nothing is accumulated or clamped, and it is counted ONCE per
+ *      learner and launch into *bad_count (its frames are not counted as bad rows).
+ *   4. Otherwise entry (s, a) gives n, r, done, D;
+ *      discounted = (gamma[m] * D) * values[m][n];  target = done ? r : r + discounted;
+ *      delta = target - values[m][s].
+ *   5. Quantise as the shared Q-learners do: d = double(delta) * 2^32, z = llrint(d) (round half to
+ *      even); a NaN gives 0 and |d| > 2^52 (an infinity too) gives +-2^52, both counted in
+ *      clamped[m].
+ *   6. sum[m][s][a] += z (int64) and visitors[m][s] += 1 (uint32).
+ *  (B) Per state s that N >= 1 good-row actors of the learner were in, with Z[0..4] its five sums,
+ *      and w, c4, the row h = prefs[m][s] and values[m][s] as (A) read them:
+ *   1. Zall = Z0 + Z1 + Z2 + Z3 + Z4 in int64 (n <= 1024 and |z| <= 2^52: no overflow).
+ *   2. mean_k = float32((double(Z[k]) / double(N)) * 2^-32), mean_all the same from Zall.
+ *   3. values[m][s] = values[m][s] + alpha_critic[m] * mean_all.
+ *   4. for k = 0 .. 4: pi = w[k] / c4; grad = mean_k - pi * mean_all;
+ *      prefs[m][s][k] = h[k] + alpha_actor[m] * grad.
+ *      Sums and visitors are zero again.  States nobody was in are not touched.
+ *  The next frame starts from the updated tables.  reward_sum / perf_sum / episodes [W][B], `ret`,
+ *  state and done are PER ENVIRONMENT, exactly as campx_wide_learn_launch() writes them.
+ * A visited row so moves by the step size times the MEAN, over its visitors, of the one-step
+ * actor-critic update (mean_k is the mean of delta * (a == k), mean_all that of delta): the step
+ * size does not depend on n.  With both step sizes 0 the walk is that of
+ * campx_wide_policy_population_launch() on the weights of rule 1.  n = 1 is NOT
+ * campx_wide_actor_launch() bit for bit - the quantiser rounds delta to 2^-32 and the products are
+ * taken in another order; nothing is claimed there.  clamped DEVICE int64 [P] is WRITTEN, not added
+ * to.  NOT offered: an entropy bonus or a temperature, lambda-traces for the actor, REINFORCE with
+ * episode returns, n-step targets, privatised accumulators.
+ *
+ * A workgroup holds G consecutive whole learners, G * n threads, and a frame is (A), a barrier,
+ * (B), a barrier; the actor whose visitor-add returned 0 owns state s in (B) - it holds the row,
+ * the weights and the value in registers already - and exchanges the six accumulators for 0.
+ * Path 1: the entries, the perf bytes and the G learners' sums, prefs, values and visitors in LDS:
+ *     table = as campx_wide_shared_plan() counts it
+ *     most  = min(P, n <= 256 ? 256 / n : 1)       G = min(most, (wide_lds_max - table) / (n_states * 68))
+ *     LDS bytes = table + G * n_states * 68        (per state: sums 40, prefs 20, value 4, visitors 4)
+ * Path 2: prefs, values and the accumulators in global memory, G = most; `scratch` (DEVICE, 8-byte
+ * aligned, at least campx_wide_actor_shared_scratch_bytes() = P * n_states * 44 bytes: int64
+ * [P][n_states][5] sums, then uint32 [P][n_states] visitors) must be ZERO on entry and is left
+ * zero; the entries (and perf bytes) are in LDS when `table` alone is within wide_lds_max.  `path`
+ * 0 / 1 / 2: as in campx_wide_shared_plan().
+ *
+ * campx_wide_actor_shared_plan(): plan_out[6] as campx_wide_shared_plan() writes it, and
+ * CAMPX_EINVAL for what that refuses.  campx_wide_actor_shared_scratch_bytes(): 0 for arguments out
+ * of range.  campx_wide_actor_shared_launch() returns CAMPX_EINVAL, before anything touches a
+ * device, for the same, for what campx_wide_actor_launch() refuses, a clamped that is NULL or not
+ * 8-byte aligned, and - on path 2 - a scratch that is NULL, misaligned or too small.  Asynchronous
+ * on `stream`, no synchronisation, no allocation, no library state.
+ */
+typedef struct CampxSharedActorLearner {
+  float* prefs;              /* DEVICE [P][n_states][5], 16-byte aligned; updated in place */
+  float* values;             /* DEVICE [P][n_states], 16-byte aligned; updated in place */
+  const float* alpha_actor;  /* DEVICE [P] each */
+  const float* alpha_critic;
+  const float* gamma;
+  float* reward_sum;         /* DEVICE [W][B], W = ceil(T / window) */
+  int32_t* perf_sum;         /* DEVICE [W][B], or NULL */
+  int32_t* episodes;         /* DEVICE [W][B] */
+  int64_t* clamped;          /* DEVICE [P]: written */
+  void* scratch;             /* path 2: zero on entry, left zero; may be NULL on path 1 */
+  int64_t scratch_bytes;
+  int32_t* bad_count;        /* optional device int32: += bad learners */
+  int32_t* bad_rows;         /* optional device int32: += environment-frames that met a bad row */
+  int32_t* bad_flag;         /* optional, as CampxOutputs.bad_flag */
+  uint64_t seed;
+  int64_t first_frame;       /* absolute number of the launch's frame 0 */
+  int64_t n_learners;        /* P */
+  int32_t window;            /* frames per window, >= 1 (may exceed T) */
+  int32_t path;              /* 0 chosen by arithmetic, 1 LDS, 2 global */
+  int32_t reset_first;
+} CampxSharedActorLearner;
+
+int32_t campx_wide_actor_shared_plan(int64_t n_states, int32_t has_perf, int64_t B, int64_t P,
+                                     int64_t wide_lds_max, int32_t path, int64_t* plan_out);
+int64_t campx_wide_actor_shared_scratch_bytes(int64_t n_states, int64_t P);
+int32_t campx_wide_actor_shared_launch(const CampxWideSpec* spec_host, const void* tables_dev,
+                                       CampxState state, const CampxSharedActorLearner* learner,
+                                       int64_t B, int32_t T, void* stream);
 /*
  * ---- Observations by state index --------------------------------------------------------------
  * Row i of `obs` DEVICE [N][L][H][W] (16-byte aligned; int8 0 / 1, or f16 / bf16 0.0 / 1.0 as
